@@ -2,7 +2,10 @@
 """bench.py -- VGICP linearize() throughput on MI355X (BASELINE.json metric; default workload = configs[1]).
 
 Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N > 1 launched through torch.distributed.run, one
-rank per GPU over RCCL.  Prints ONE JSON line on rank 0.
+rank per GPU over RCCL.  Prints ONE JSON line on rank 0.  Such a plain run sets up, warms up and times the K steps of the headline
+loop and nothing else; `--full` adds every other measurement of the default line (below).  `--dump-outputs DIR` writes the records
+the headline loop returned in its last timed step as DIR/<name>.npy (float64); with the same arguments the inputs are the same in
+every run, so two builds can be compared output for output.
 
 N = 1 default workload "odometry128k" (BASELINE configs[1], metric M1): 131 072-point spinning-LiDAR scans (128 rings x 1024 azimuths, synthetic
 analytic scene), each matched against the 0.5 m Gaussian voxel map of the previous scan on a 0.5 m / 2 deg arc.
@@ -25,7 +28,8 @@ Other workloads (parity-test configurations of BASELINE.json, selectable for evi
   --workload rgbd300k    configs[4]: 307 200-pt depth frames, per frame upload -> kNN -> covariance -> 0.1 m voxel map -> one
                          unary linearise against the previous frame (sustained frames/s, p50/p99 latency)
 
-Also reported: `roofline` for the dominant kernel (HIP-event timed inside this process on the stream the kernel runs on; `frac` = MEASURED
+Also reported with --full (never in a plain run): `batched_calls_per_s`, the N = 1 line's `m2_global256` and the N > 1 line's `m1_weak`,
+`roofline` for the dominant kernel (HIP-event timed inside this process on the stream the kernel runs on; `frac` = MEASURED
 traffic of the committed PMC passes over that time over 8 TB/s, SURVEY 8d's algorithmic bytes as a ratio beside it), `cpu_baseline` (the FP64
 OpenMP oracle on the usable host cores, bounded sample, thread curve), and the parity of one factor's Gauss-Newton step against the oracle.
 """
@@ -344,6 +348,67 @@ def timed_steps(D, step, steps, warmup):
     return D.max_over_ranks(time.perf_counter() - t0)
 
 
+def dump_outputs(args, D, arrays):
+    """--dump-outputs DIR: the arrays the timed path returned to its caller in its last step, one DIR/<name>.npy each, as float64."""
+    if not args.dump_outputs or D.rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        total += a.nbytes
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (the limit is 64 MB)"
+    log(f"wrote {len(arrays)} arrays ({total} bytes) to {args.dump_outputs}")
+
+
+def sync_single_factor_loop(args, D, api, clouds, vmaps, pose_sets):
+    """The loop BASELINE configs[1] names and the headline of the single-GPU line: {set pose, linearize, read back the record} per call, one factor
+    (target map vmaps[0], source clouds[1]) issued from C (glim_amd_factor_set_linearize_repeat), `--sync-calls` calls per step, `--steps` timed
+    steps after max(--warmup, 1) warm-up steps, on a context of the kind the odometry module creates (adapters/glim/odometry_estimation_hip_create.cpp:
+    own stream pool, priority 1 -- which is also what switches the resident session on; every other context leaves it off).  Clouds and maps cross
+    contexts by design.  Writes the last step's record for --dump-outputs.  Returns (context, factor set, calls per step, timed seconds)."""
+    odo = api.Context(D.local_rank, 4, priority=1)
+    single = api.NonlinearFactorSetGPU(odo)
+    single.add(api.IntegratedVGICPFactorGPU(0, 1, vmaps[0], clouds[1]))
+    P_single = np.stack([pose_sets[k][0] for k in range(len(pose_sets))])  # the optimiser moves the pose between calls
+    sync_calls = max(1, args.sync_calls)
+    got_box = {}
+
+    def sync_step(_):
+        got_box["last"] = single.linearize_repeat(P_single, sync_calls)[0]
+
+    elapsed_sync = timed_steps(D, sync_step, args.steps, max(args.warmup, 1))
+    dump_outputs(args, D, {k: np.asarray(v) for k, v in got_box["last"].items()})  # num_inliers, error, H_tt, H_ss, H_ts, b_t, b_s of the last call
+    return odo, single, sync_calls, elapsed_sync
+
+
+def odometry128k_sync_loop(args, D, api, clouds, vmaps, pose_sets, n_pts, n_vox):
+    """The plain single-GPU line: the headline loop alone (`batched_calls_per_s`, `roofline`, the per-variant call times, the resident session's
+    cost, the device timeline, `cpu_baseline` / `parity` and `m2_global256` are measured with --full)."""
+    odo, single, sync_calls, elapsed = sync_single_factor_loop(args, D, api, clouds, vmaps, pose_sets)
+    value = sync_calls * args.steps / elapsed
+    result = {
+        "metric": "vgicp_linearize_calls_per_s", "value": value, "unit": "calls/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "headline_form": (f"`value` = the loop BASELINE configs[1] names: synchronous single-factor linearize calls (pose in, 131 072-pt factor, record "
+                          f"out, host waits) issued back to back from C, {sync_calls} per step.  The batched form, the roofline and the CPU baseline are "
+                          "measured with --full"),
+        "sync_single_factor_calls_per_s": value, "timed_region_s": elapsed,
+        "config": {
+            "workload": "configs[1] odometry128k: OdometryEstimationGPU's single-factor linearize loop, one 131072-pt spinning-LiDAR scan vs a 0.5 m voxel map per call",
+            "calls_per_step": sync_calls, "points_per_factor": int(n_pts[0]), "voxels_per_factor": int(n_vox[0]),
+            "voxel_resolution_m": args.resolution, "factor_type": "binary",
+            "context": "priority 1, 4 streams (as adapters/glim/odometry_estimation_hip_create.cpp creates it): resident session on",
+            "collective": "none", "device": odo.device_info()["name"],
+        },
+    }
+    single.close()
+    odo.close()
+    return result
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def run_odometry128k(args, D, api, ctx):
     from glim_amd import synth
@@ -359,29 +424,39 @@ def run_odometry128k(args, D, api, ctx):
     radius = 0.5 / math.radians(2.0)
     cx, cy = 1.5 * (rank % 4) - 2.0, 1.0 * (rank // 4) - 0.5
     poses = synth.arc_trajectory(F + 1, start=(cx + radius * math.sin(yaw0), cy - radius * math.cos(yaw0), 1.8), yaw0_deg=math.degrees(yaw0))
+    # a plain single-GPU run times only the headline loop, which uses factor 0 alone: it builds the first two scans and one voxel map; the
+    # batched set of F factors and every measurement on it belong to --full
+    headline_only = world == 1 and not args.full and args.sync_calls > 0
+    nf = 1 if headline_only else F
     t0 = time.time()
-    clouds = make_frames(api, ctx, poses, args.rings, args.azimuths, frame_id0=1000 * rank)
-    vmaps = [api.GaussianVoxelMapGPU(args.resolution, ctx=ctx).insert(c) for c in clouds[:F]]
-    log(f"generated {F + 1} scans of {clouds[0].size()} pts (kNN, covariances, voxel maps on the device) in {time.time() - t0:.1f}s")
-    fset = api.NonlinearFactorSetGPU(ctx)
+    clouds = make_frames(api, ctx, poses[:nf + 1], args.rings, args.azimuths, frame_id0=1000 * rank)
+    vmaps = [api.GaussianVoxelMapGPU(args.resolution, ctx=ctx).insert(c) for c in clouds[:nf]]
+    log(f"generated {nf + 1} scans of {clouds[0].size()} pts (kNN, covariances, voxel maps on the device) in {time.time() - t0:.1f}s")
+    fset = None if headline_only else api.NonlinearFactorSetGPU(ctx)
     deltas = []
-    for i in range(F):
-        fset.add(api.IntegratedVGICPFactorGPU(i, i + 1, vmaps[i], clouds[i + 1]))  # binary factor: target i, source i+1
+    for i in range(nf):
+        if fset is not None:
+            fset.add(api.IntegratedVGICPFactorGPU(i, i + 1, vmaps[i], clouds[i + 1]))  # binary factor: target i, source i+1
         deltas.append(api.pose12(synth.relative_pose(poses[i], poses[i + 1])))
     deltas = np.stack(deltas)
     n_pts = [c.size() for c in clouds[1:]]
     n_vox = [v.voxelmap_info()["num_voxels"] for v in vmaps]
 
-    # a few linearisation points per factor (the optimiser moves the poses between calls)
+    # a few linearisation points per factor (the optimiser moves the poses between calls); the draws of all F factors are taken either
+    # way, so factor 0's points are the same in a plain run and in a --full run
     rng = np.random.default_rng(1234 + rank)
     pose_sets = []
     for s in range(4):
-        P = np.empty((F, 12))
+        P = np.empty((nf, 12))
         for f in range(F):
-            Dm = np.eye(4)
-            Dm[:3, :4] = deltas[f].reshape(3, 4)
-            P[f] = api.pose12(Dm @ se3_exp(rng.normal(size=6) * [2e-3, 2e-3, 2e-3, 1e-2, 1e-2, 1e-2] * (s > 0)))
+            xi = rng.normal(size=6) * [2e-3, 2e-3, 2e-3, 1e-2, 1e-2, 1e-2] * (s > 0)
+            if f < nf:
+                Dm = np.eye(4)
+                Dm[:3, :4] = deltas[f].reshape(3, 4)
+                P[f] = api.pose12(Dm @ se3_exp(xi))
         pose_sets.append(P)
+    if headline_only:
+        return odometry128k_sync_loop(args, D, api, clouds, vmaps, pose_sets, n_pts, n_vox)
     out = torch.zeros(world * F, api._lib.COMPACT_DOUBLES, dtype=torch.float64, device="cuda")
 
     # collective mode: every rank owns F rows, so the exchange is an all-gather of equal shards; two send / receive pairs so that the
@@ -442,17 +517,7 @@ def run_odometry128k(args, D, api, ctx):
                 "batched_calls_per_s": value_batched, "config": {"workload": "configs[1] odometry128k, batched form only (profiling run)", "factors_per_gpu_batched": F,
                                                                  "points_per_factor": int(np.mean(n_pts)), "voxels_per_factor": int(np.mean(n_vox))},
                 "roofline": roofline}
-    odo = api.Context(D.local_rank, 4, priority=1)
-    single = api.NonlinearFactorSetGPU(odo)
-    single.add(api.IntegratedVGICPFactorGPU(0, 1, vmaps[0], clouds[1]))
-    P_single = np.stack([pose_sets[k][0] for k in range(len(pose_sets))])  # the optimiser moves the pose between calls
-    sync_calls = max(1, args.sync_calls)
-    got_box = {}
-
-    def sync_step(_):
-        got_box["last"] = single.linearize_repeat(P_single, sync_calls)[0]
-
-    elapsed_sync = timed_steps(D, sync_step, args.steps, max(args.warmup, 1))
+    odo, single, sync_calls, elapsed_sync = sync_single_factor_loop(args, D, api, clouds, vmaps, pose_sets)
     value_sync = world * sync_calls * args.steps / elapsed_sync
     T1 = deltas[:1]
     got = single.linearize_poses(T1)[0]
@@ -1744,7 +1809,14 @@ def main():
     ap.add_argument("--no-virtual", action="store_true", help="--native on one GPU: skip the virtual_world8 run (the N > 1 path over 8 virtual devices)")
     ap.add_argument("--native", action="store_true", help="configs[3] through the native multi-device C-ABI path (glim_amd_multi_*: ONE process drives --gpus "
                                                          "devices, ncclAllGather) instead of one torch.distributed rank per GPU; run it as a plain `python bench.py`")
+    ap.add_argument("--full", action="store_true", help="default line: also measure everything beside the headline (batched form, roofline, per-variant call "
+                                                       "times, resident-session cost, device timeline, CPU baseline and parity, m2_global256 / m1_weak); "
+                                                       "a run without it times the headline loop alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the records the timed loop returned in its last step "
+                                                                        "as DIR/<name>.npy (float64); single-GPU odometry128k headline only")
     args = ap.parse_args()
+    if args.dump_outputs and ((args.workload or "odometry128k") != "odometry128k" or args.gpus != 1 or args.native or args.sync_calls <= 0):
+        ap.error("--dump-outputs is implemented for the single-GPU odometry128k headline loop (--gpus 1, --sync-calls > 0)")
 
     # stdout carries exactly ONE JSON line: libraries that print banners to fd 1 (RCCL prints its version there at init) are
     # diverted to stderr for the whole run; the result goes to the saved descriptor at the end
@@ -1767,12 +1839,12 @@ def main():
     if args.native:
         runner = run_global256_native
     result = runner(args, D, api, ctx)
-    if args.workload is None and D.world > 1:
+    if args.workload is None and D.world > 1 and args.full:
         m1 = run_odometry128k(args, D, api, ctx)  # the weak-scaling form of M1, next to the M2 headline
         if result is not None and m1 is not None:
             result["m1_weak"] = {k: m1[k] for k in ("metric", "value", "unit", "ms_per_step", "scaling", "batched_value_cold", "sync_single_factor_calls_per_s", "config",
                                                     "roofline", "headline_form") if k in m1}
-    elif args.workload is None and not args.no_m2 and not args.native:
+    elif args.workload is None and args.full and not args.no_m2 and not args.native:
         m2 = run_global256(args, D, api, ctx, extra_only=True)
         if result is not None and m2 is not None:
             result["m2_global256"] = {k: m2[k] for k in ("metric", "value", "unit", "ms_per_step", "scaling", "config", "roofline", "parity", "predicted_scaling",

@@ -14,7 +14,7 @@ fi
 for w in "${@:-default odometry_frame}"; do
   for ww in $w; do
     if [ "$ww" = default ]; then
-      timeout 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+      timeout 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err < /dev/null
     else
       timeout 300 python bench.py --workload $ww > $OUT/bench_$ww.json 2> $OUT/bench_$ww.err < /dev/null
     fi

@@ -31,7 +31,7 @@ if [ -z "$SKIP_GLOBAL256_PMC" ]; then
   rm -rf gpurun_out/prof_${TAG}_frame
   rm -rf gpurun_out/prof_${TAG}_g
 fi
-timeout 250 python bench.py > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+timeout 250 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 for w in odometry_frame submap20 global256 rgbd300k frontend128k odometry_under_load; do
   timeout 300 python bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err < /dev/null
 done

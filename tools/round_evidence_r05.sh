@@ -23,7 +23,7 @@ mkdir -p $OUT/global256
 python tools/summarize_profile.py gpurun_out/prof_${TAG}_g $OUT/global256 32640 global256 36 2029810471 >> $OUT/summarize.log 2>&1
 cp $OUT/global256/traffic_global256.json profiles/$TAG/traffic_global256.json 2>/dev/null
 rm -rf gpurun_out/prof_${TAG}_g
-timeout 480 python bench.py > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+timeout 480 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 for w in odometry_frame odometry_under_load submap20 rgbd300k frontend128k; do
   timeout 300 python bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err < /dev/null
 done
