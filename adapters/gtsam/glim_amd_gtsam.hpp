@@ -6,6 +6,8 @@
 //       -> glim_amd::IntegratedVGICPFactorHIP            (a gtsam::NonlinearFactor: error / linearize / dim / clone + the extras GLIM calls)
 //   gtsam_points::IntegratedGICPFactor(...)                                                            sub_mapping.cpp:202, global_mapping.cpp:400
 //       -> glim_amd::IntegratedGICPFactorHIP
+//   gtsam_points::IntegratedCT_GICPFactor(X, Y, target, source, target_tree)                          odometry_estimation_ct.cpp:158-160
+//       -> glim_amd::IntegratedCT_GICPFactorHIP
 //   gtsam_points::NonlinearFactorSetGPU / create_nonlinear_factor_set_gpu()                            odometry_estimation_gpu.cpp:383-385, offline_viewer.cpp:29
 //       -> glim_amd::NonlinearFactorSetHIP / glim_amd::create_nonlinear_factor_set_hip()
 //   gtsam_points::PointCloudGPU::clone(frame), overlap_gpu(voxelmap, frame, Isometry3d)                :96, :231-326
@@ -217,6 +219,59 @@ private:
     return out;
   }
   std::shared_ptr<IntegratedGICPFactor> impl_;
+};
+
+// ---- gtsam_points::IntegratedCT_GICPFactor (continuous time, point-cloud target) -------------------------------------------
+// odometry_estimation_ct.cpp:158-195: keys {X, Y} = the poses at scan begin / end.  Its error is e = sum r^T M r as the factor returns it: the
+// VGICP error-scale switch above is not applied (no reference value of this factor was ever pinned against it).
+class IntegratedCT_GICPFactorHIP : public gtsam::NonlinearFactor {
+public:
+  using shared_ptr = std::shared_ptr<IntegratedCT_GICPFactorHIP>;
+  IntegratedCT_GICPFactorHIP(gtsam::Key source_t0_key, gtsam::Key source_t1_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
+                             NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, const double* times = nullptr /* null: the source's own */)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{source_t0_key, source_t1_key}),
+    impl_(std::make_shared<IntegratedCT_GICPFactor>((Key)source_t0_key, (Key)source_t1_key, std::move(target), std::move(source), std::move(target_tree),
+                                                    times)) {}
+
+  size_t dim() const override { return 6; }
+  // the device factor keeps correspondences between linearize and error: a clone shares them (as the reference's shared_ptr members do)
+  gtsam::NonlinearFactor::shared_ptr clone() const override { return std::make_shared<IntegratedCT_GICPFactorHIP>(*this); }
+  void set_max_correspondence_distance(double d) { impl_->set_max_correspondence_distance(d); }   // odometry_estimation_ct.cpp:161
+  void set_num_threads(int n) { impl_->set_num_threads(n); }                                       // (no-op)
+
+  gtsam::GaussianFactor::shared_ptr linearize(const gtsam::Values& values) const override {
+    const glim_amd_ct_linearized& l = impl_->linearize(to_values(values));
+    auto mat = [](const double* h) {
+      gtsam::Matrix M(6, 6);
+      for (int r = 0; r < 6; r++)
+        for (int c = 0; c < 6; c++) M(r, c) = h[6 * r + c];
+      return M;
+    };
+    auto neg = [](const double* b) {
+      gtsam::Vector v(6);
+      for (int r = 0; r < 6; r++) v(r) = -b[r];
+      return v;
+    };
+    return gtsam::GaussianFactor::shared_ptr(new gtsam::HessianFactor(keys()[0], keys()[1], mat(l.H_00), mat(l.H_01), neg(l.b_0), mat(l.H_11), neg(l.b_1), l.error));
+  }
+  double error(const gtsam::Values& values) const override { return impl_->error(to_values(values)); }
+  // odometry_estimation_ct.cpp:191: the points moved by their own interpolated pose (local: in the frame of the scan-begin pose)
+  std::vector<Eigen::Vector4d> deskewed_source_points(const gtsam::Values& values, bool local = false) const {
+    const std::vector<double> p4 = impl_->deskewed_source_points(to_values(values), local);
+    std::vector<Eigen::Vector4d> out(p4.size() / 4);
+    for (std::size_t i = 0; i < out.size(); i++)
+      for (int c = 0; c < 4; c++) out[i].data()[c] = p4[4 * i + c];
+    return out;
+  }
+  const std::shared_ptr<IntegratedCT_GICPFactor>& impl() const { return impl_; }
+
+private:
+  Values to_values(const gtsam::Values& values) const {
+    Values out;
+    for (const gtsam::Key k : keys()) out[(Key)k] = to_iso(values.at<gtsam::Pose3>(k));
+    return out;
+  }
+  std::shared_ptr<IntegratedCT_GICPFactor> impl_;
 };
 
 // ---- gtsam_points::NonlinearFactorSetGPU ---------------------------------------------------------------------------------

@@ -32,6 +32,20 @@ class Linearized6(C.Structure):
     ]
 
 
+class CtLinearized(C.Structure):
+    """glim_amd_ct_linearized: HessianFactor(X, Y, H_00, H_01, -b_0, H_11, -b_1, error) of the continuous-time GICP factor."""
+
+    _fields_ = [
+        ("num_inliers", C.c_int64),
+        ("error", C.c_double),
+        ("H_00", C.c_double * 36),
+        ("H_01", C.c_double * 36),
+        ("H_11", C.c_double * 36),
+        ("b_0", C.c_double * 6),
+        ("b_1", C.c_double * 6),
+    ]
+
+
 class PreprocessParams(C.Structure):
     """glim_amd_preprocess_params (include/glim_amd.h) == CloudPreprocessorParams (cloud_preprocessor.cpp:20-61)."""
 
@@ -124,6 +138,15 @@ SYMBOLS = {
     "glim_amd_gicp_linearize": (_i, [_vp, _vp, _dp, _d, _u32, C.POINTER(Linearized6)]),
     "glim_amd_gicp_error": (_i, [_vp, _vp, _dp, _d, _dp, _lp]),
     "glim_amd_gicp_correspondences": (_i, [_vp, _vp, _dp, _d, _ip]),
+    "glim_amd_ct_gicp_create": (_i, [_vp, _vp, _dp, _pp]),
+    "glim_amd_ct_gicp_destroy": (_i, [_vp]),
+    "glim_amd_ct_gicp_set_max_correspondence_distance": (_i, [_vp, _d]),
+    "glim_amd_ct_gicp_linearize": (_i, [_vp, _dp, _dp, C.POINTER(CtLinearized)]),
+    "glim_amd_ct_gicp_error": (_i, [_vp, _dp, _dp, _dp, _lp]),
+    "glim_amd_ct_gicp_correspondences": (_i, [_vp, _dp, _dp, _ip]),
+    "glim_amd_ct_gicp_deskewed_points": (_i, [_vp, _dp, _dp, _i32, _dp]),
+    "glim_amd_ct_gicp_deskewed_cloud": (_i, [_vp, _dp, _dp, _i32, _pp]),
+    "glim_amd_debug_ct_gicp_poses": (_i, [_vp, _dp, _dp, _ip, _i32, _dp, _dp, _dp, _dp, _ip]),
     "glim_amd_merge_frames": (_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

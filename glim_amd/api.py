@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FACTOR_BINARY, FACTOR_SURFACE_VALIDATION, GlimAmdError, Linearized6, PreprocessParams, check, lib  # noqa: F401
+from ._lib import CtLinearized, FACTOR_BINARY, FACTOR_SURFACE_VALIDATION, GlimAmdError, Linearized6, PreprocessParams, check, lib  # noqa: F401
 
 _default_ctx = None
 STREAM_LEGACY = 1  # hipStreamLegacy ((hipStream_t)1): the null stream, as an explicit handle
@@ -906,6 +906,104 @@ class IntegratedGICPFactor:
         return out
 
     def close(self):
+        if self._own_tree and self.target_tree:
+            lib().glim_amd_nn_index_destroy(self.target_tree)
+            self.target_tree = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IntegratedCT_GICPFactor:
+    """gtsam_points::IntegratedCT_GICPFactor (point-cloud target, KdTree) on the device: GLIM's continuous-time odometry cost
+    (odometry_estimation_ct.cpp:158-183).  One scan between key0 (X, the pose at scan begin) and key1 (Y, at scan end); every point moves
+    with the pose of its time bucket, T_k = X Exp(t_k Log(X^-1 Y)).  `target` / `source`: PointCloudGPU with covariances; the source also
+    needs per-point times (`times`, or the ones its preprocessing kept).  linearize() returns the HessianFactor ingredients
+    {num_inliers, error, H_00, H_01, H_11, b_0, b_1}; error() reuses the correspondences and M of the last linearize()."""
+
+    def __init__(self, key0, key1, target, source, target_tree=None, max_correspondence_distance=1.0, times=None):
+        self.keys = (int(key0), int(key1))
+        self.target, self.source = target, source
+        self._own_tree = target_tree is None
+        if target_tree is None:
+            h = C.c_void_p()
+            check(lib().glim_amd_nn_index_create(target._h, float(max_correspondence_distance), C.byref(h)), "glim_amd_nn_index_create")
+            target_tree = h
+        self.target_tree = target_tree
+        self._h = None
+        t = None if times is None else np.ascontiguousarray(times, dtype=np.float64).reshape(source.size())
+        h = C.c_void_p()
+        check(lib().glim_amd_ct_gicp_create(self.target_tree, source._h, _dp(t), C.byref(h)), "glim_amd_ct_gicp_create")
+        self._h = h
+        self.set_max_correspondence_distance(max_correspondence_distance)
+
+    def set_max_correspondence_distance(self, d):
+        check(lib().glim_amd_ct_gicp_set_max_correspondence_distance(self._h, float(d)), "glim_amd_ct_gicp_set_max_correspondence_distance")
+        self.max_correspondence_distance = float(d)
+
+    def set_num_threads(self, n):
+        """no-op: the device decides its own parallelism (kept for call-site compatibility)."""
+
+    def _xy(self, values):
+        return pose12(values[self.keys[0]]), pose12(values[self.keys[1]])
+
+    def linearize(self, values):
+        X, Y = self._xy(values)
+        L = CtLinearized()
+        check(lib().glim_amd_ct_gicp_linearize(self._h, _dp(X), _dp(Y), C.byref(L)), "glim_amd_ct_gicp_linearize")
+        a = np.frombuffer(L, dtype=np.float64, count=122).copy()
+        return {"num_inliers": int(L.num_inliers), "error": float(a[1]), "H_00": a[2:38].reshape(6, 6), "H_01": a[38:74].reshape(6, 6),
+                "H_11": a[74:110].reshape(6, 6), "b_0": a[110:116], "b_1": a[116:122]}
+
+    def error(self, values, with_inliers=False):
+        X, Y = self._xy(values)
+        e, n = C.c_double(), C.c_int64()
+        check(lib().glim_amd_ct_gicp_error(self._h, _dp(X), _dp(Y), C.byref(e), C.byref(n)), "glim_amd_ct_gicp_error")
+        return (e.value, n.value) if with_inliers else e.value
+
+    def correspondences(self, values):
+        X, Y = self._xy(values)
+        out = np.zeros(self.source.size(), dtype=np.int32)
+        check(lib().glim_amd_ct_gicp_correspondences(self._h, _dp(X), _dp(Y), _ip(out)), "glim_amd_ct_gicp_correspondences")
+        return out
+
+    def deskewed_source_points(self, values, local=False):
+        """T_k p_i per point (N x 3, FP64); local: in the frame of the first bucket's pose (odometry_estimation_ct.cpp:191)."""
+        X, Y = self._xy(values)
+        p4 = np.zeros((self.source.size(), 4))
+        check(lib().glim_amd_ct_gicp_deskewed_points(self._h, _dp(X), _dp(Y), int(bool(local)), _dp(p4)), "glim_amd_ct_gicp_deskewed_points")
+        return p4[:, :3].copy()
+
+    def deskewed_cloud(self, values, local=False):
+        """The deskewed points as a new PointCloudGPU carrying the source's neighbour lists (estimate_covariances runs on it, :194-195)."""
+        X, Y = self._xy(values)
+        h = C.c_void_p()
+        check(lib().glim_amd_ct_gicp_deskewed_cloud(self._h, _dp(X), _dp(Y), int(bool(local)), C.byref(h)), "glim_amd_ct_gicp_deskewed_cloud")
+        g = PointCloudGPU(h, self.source.ctx)
+        g._k = getattr(self.source, "_k", 0)
+        return g
+
+    def debug_poses(self, values):
+        """(time table, T_k n x 4 x 4, D0_k, D1_k n x 6 x 6, time_index) as the library evaluates them at `values`."""
+        X, Y = self._xy(values)
+        nb = C.c_int32()
+        check(lib().glim_amd_debug_ct_gicp_poses(self._h, _dp(X), _dp(Y), C.byref(nb), 0, None, None, None, None, None), "glim_amd_debug_ct_gicp_poses")
+        m = nb.value
+        tab, T, D0, D1 = np.zeros(m), np.zeros((m, 12)), np.zeros((m, 36)), np.zeros((m, 36))
+        idx = np.zeros(self.source.size(), dtype=np.int32)
+        check(lib().glim_amd_debug_ct_gicp_poses(self._h, _dp(X), _dp(Y), C.byref(nb), m, _dp(tab), _dp(T), _dp(D0), _dp(D1), _ip(idx)),
+              "glim_amd_debug_ct_gicp_poses")
+        T44 = np.tile(np.eye(4), (m, 1, 1))
+        T44[:, :3, :] = T.reshape(m, 3, 4)
+        return tab, T44, D0.reshape(m, 6, 6), D1.reshape(m, 6, 6), idx
+
+    def close(self):
+        if self._h:
+            lib().glim_amd_ct_gicp_destroy(self._h)
+            self._h = None
         if self._own_tree and self.target_tree:
             lib().glim_amd_nn_index_destroy(self.target_tree)
             self.target_tree = None

@@ -17,6 +17,10 @@
 // and stops as soon as the best distance is provably inside the scanned cube, or the cube already covers the correspondence
 // radius (nothing farther can be accepted).  One lane per source point; the per-point algebra and the block reduction are the
 // VGICP ones (source-frame form, 28 FP32 accumulators, DPP wave sums, fixed-order FP64 finalisation: bit-reproducible).
+//
+// The continuous-time factor (gtsam_points::IntegratedCT_GICPFactor with a point-cloud target, odometry_estimation_ct.cpp:158-195) runs the same
+// search and per-point algebra with one pose per time bucket, T_k = X Exp(t_k Log(X^-1 Y)); its chain rule to the keys X and Y is applied per
+// bucket in FP64 (ct_gicp_kernel, ct_bucket_kernel, ct_sum_kernel below; semantics in include/glim_amd.h, layout in DESIGN.md 4.6).
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -222,6 +226,65 @@ __device__ __forceinline__ int nearest(const GicpArgs& a, double qx, double qy, 
   return (best >= 0 && best_d <= a.max_sq) ? best : -1;
 }
 
+// per-point GICP algebra in the source frame (gicp_kernel and ct_gicp_kernel): adds the point's terms to the 28 accumulators and returns the
+// source-frame A = (R^T C_B R + C_A)^-1 (a00 a01 a02 a11 a12 a22)
+template <bool LINEARIZE>
+__device__ __forceinline__ void gicp_point(float (&acc)[NACC], float R00, float R01, float R02, float R10, float R11, float R12, float R20, float R21,
+                                           float R22, const float4 p, const float4 b, const float4 tA, const float2 tB, const float4 ca, const float2 cb,
+                                           double qx, double qy, double qz, float (&A)[6]) {
+  // residual b_j - q: formed in FP64 (|r| <= the correspondence radius), then FP32
+  const float rx = (float)((double)b.x - qx), ry = (float)((double)b.y - qy), rz = (float)((double)b.z - qz);
+  // S = R^T C_B R + C_A (source frame, symmetric)
+  const float b00 = tA.x, b01 = tA.y, b02 = tA.z, b11 = tA.w, b12 = tB.x, b22 = tB.y;
+  const float w00 = b00 * R00 + b01 * R10 + b02 * R20, w01 = b00 * R01 + b01 * R11 + b02 * R21, w02 = b00 * R02 + b01 * R12 + b02 * R22;
+  const float w10 = b01 * R00 + b11 * R10 + b12 * R20, w11 = b01 * R01 + b11 * R11 + b12 * R21, w12 = b01 * R02 + b11 * R12 + b12 * R22;
+  const float w20 = b02 * R00 + b12 * R10 + b22 * R20, w21 = b02 * R01 + b12 * R11 + b22 * R21, w22 = b02 * R02 + b12 * R12 + b22 * R22;
+  const float S00 = ca.x + R00 * w00 + R10 * w10 + R20 * w20;
+  const float S01 = ca.y + R00 * w01 + R10 * w11 + R20 * w21;
+  const float S02 = ca.z + R00 * w02 + R10 * w12 + R20 * w22;
+  const float S11 = ca.w + R01 * w01 + R11 * w11 + R21 * w21;
+  const float S12 = cb.x + R01 * w02 + R11 * w12 + R21 * w22;
+  const float S22 = cb.y + R02 * w02 + R12 * w12 + R22 * w22;
+  const float k00 = S11 * S22 - S12 * S12;
+  const float k01 = S02 * S12 - S01 * S22;
+  const float k02 = S01 * S12 - S02 * S11;
+  const float det = S00 * k00 + S01 * k01 + S02 * k02;
+  float idet = __builtin_amdgcn_rcpf(det);
+  idet = fmaf(fmaf(-det, idet, 1.0f), idet, idet);
+  const float A00 = k00 * idet, A01 = k01 * idet, A02 = k02 * idet;
+  const float A11 = (S00 * S22 - S02 * S02) * idet;
+  const float A12 = (S01 * S02 - S00 * S12) * idet;
+  const float A22 = (S00 * S11 - S01 * S01) * idet;
+  const float rsx = R00 * rx + R10 * ry + R20 * rz;
+  const float rsy = R01 * rx + R11 * ry + R21 * rz;
+  const float rsz = R02 * rx + R12 * ry + R22 * rz;
+  const float ux = A00 * rsx + A01 * rsy + A02 * rsz;
+  const float uy = A01 * rsx + A11 * rsy + A12 * rsz;
+  const float uz = A02 * rsx + A12 * rsy + A22 * rsz;
+  acc[27] += rsx * ux + rsy * uy + rsz * uz;
+  if (LINEARIZE) {
+    const float x = p.x, y = p.y, z = p.z;
+    const float g00 = y * A02 - z * A01, g01 = y * A12 - z * A11, g02 = y * A22 - z * A12;
+    const float g10 = z * A00 - x * A02, g11 = z * A01 - x * A12, g12 = z * A02 - x * A22;
+    const float g20 = x * A01 - y * A00, g21 = x * A11 - y * A01, g22 = x * A12 - y * A02;
+    acc[0] += y * g02 - z * g01;
+    acc[1] += z * g00 - x * g02;
+    acc[2] += x * g01 - y * g00;
+    acc[3] += z * g10 - x * g12;
+    acc[4] += x * g11 - y * g10;
+    acc[5] += x * g21 - y * g20;
+    acc[6] += g00; acc[7] += g01; acc[8] += g02;
+    acc[9] += g10; acc[10] += g11; acc[11] += g12;
+    acc[12] += g20; acc[13] += g21; acc[14] += g22;
+    acc[15] += A00; acc[16] += A01; acc[17] += A02; acc[18] += A11; acc[19] += A12; acc[20] += A22;
+    acc[21] += uy * z - uz * y;
+    acc[22] += uz * x - ux * z;
+    acc[23] += ux * y - uy * x;
+    acc[24] += ux; acc[25] += uy; acc[26] += uz;
+  }
+  A[0] = A00; A[1] = A01; A[2] = A02; A[3] = A11; A[4] = A12; A[5] = A22;
+}
+
 template <bool LINEARIZE>
 __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __restrict__ partials, int32_t* __restrict__ corr) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
@@ -245,61 +308,8 @@ __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __
     if (corr) corr[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
     if (j < 0) continue;
     inliers++;
-    const float4 b = a.sorted[j];
-    const float4 tA = a.tA[j];
-    const float2 tB = a.tB[j];
-    const float4 ca = a.covA[i];
-    const float2 cb = a.covB[i];
-    // residual b_j - q: formed in FP64 (|r| <= the correspondence radius), then FP32
-    const float rx = (float)((double)b.x - qx), ry = (float)((double)b.y - qy), rz = (float)((double)b.z - qz);
-    // S = R^T C_B R + C_A (source frame, symmetric)
-    const float b00 = tA.x, b01 = tA.y, b02 = tA.z, b11 = tA.w, b12 = tB.x, b22 = tB.y;
-    const float w00 = b00 * R00 + b01 * R10 + b02 * R20, w01 = b00 * R01 + b01 * R11 + b02 * R21, w02 = b00 * R02 + b01 * R12 + b02 * R22;
-    const float w10 = b01 * R00 + b11 * R10 + b12 * R20, w11 = b01 * R01 + b11 * R11 + b12 * R21, w12 = b01 * R02 + b11 * R12 + b12 * R22;
-    const float w20 = b02 * R00 + b12 * R10 + b22 * R20, w21 = b02 * R01 + b12 * R11 + b22 * R21, w22 = b02 * R02 + b12 * R12 + b22 * R22;
-    const float S00 = ca.x + R00 * w00 + R10 * w10 + R20 * w20;
-    const float S01 = ca.y + R00 * w01 + R10 * w11 + R20 * w21;
-    const float S02 = ca.z + R00 * w02 + R10 * w12 + R20 * w22;
-    const float S11 = ca.w + R01 * w01 + R11 * w11 + R21 * w21;
-    const float S12 = cb.x + R01 * w02 + R11 * w12 + R21 * w22;
-    const float S22 = cb.y + R02 * w02 + R12 * w12 + R22 * w22;
-    const float k00 = S11 * S22 - S12 * S12;
-    const float k01 = S02 * S12 - S01 * S22;
-    const float k02 = S01 * S12 - S02 * S11;
-    const float det = S00 * k00 + S01 * k01 + S02 * k02;
-    float idet = __builtin_amdgcn_rcpf(det);
-    idet = fmaf(fmaf(-det, idet, 1.0f), idet, idet);
-    const float A00 = k00 * idet, A01 = k01 * idet, A02 = k02 * idet;
-    const float A11 = (S00 * S22 - S02 * S02) * idet;
-    const float A12 = (S01 * S02 - S00 * S12) * idet;
-    const float A22 = (S00 * S11 - S01 * S01) * idet;
-    const float rsx = R00 * rx + R10 * ry + R20 * rz;
-    const float rsy = R01 * rx + R11 * ry + R21 * rz;
-    const float rsz = R02 * rx + R12 * ry + R22 * rz;
-    const float ux = A00 * rsx + A01 * rsy + A02 * rsz;
-    const float uy = A01 * rsx + A11 * rsy + A12 * rsz;
-    const float uz = A02 * rsx + A12 * rsy + A22 * rsz;
-    acc[27] += rsx * ux + rsy * uy + rsz * uz;
-    if (LINEARIZE) {
-      const float x = p.x, y = p.y, z = p.z;
-      const float g00 = y * A02 - z * A01, g01 = y * A12 - z * A11, g02 = y * A22 - z * A12;
-      const float g10 = z * A00 - x * A02, g11 = z * A01 - x * A12, g12 = z * A02 - x * A22;
-      const float g20 = x * A01 - y * A00, g21 = x * A11 - y * A01, g22 = x * A12 - y * A02;
-      acc[0] += y * g02 - z * g01;
-      acc[1] += z * g00 - x * g02;
-      acc[2] += x * g01 - y * g00;
-      acc[3] += z * g10 - x * g12;
-      acc[4] += x * g11 - y * g10;
-      acc[5] += x * g21 - y * g20;
-      acc[6] += g00; acc[7] += g01; acc[8] += g02;
-      acc[9] += g10; acc[10] += g11; acc[11] += g12;
-      acc[12] += g20; acc[13] += g21; acc[14] += g22;
-      acc[15] += A00; acc[16] += A01; acc[17] += A02; acc[18] += A11; acc[19] += A12; acc[20] += A22;
-      acc[21] += uy * z - uz * y;
-      acc[22] += uz * x - ux * z;
-      acc[23] += ux * y - uy * x;
-      acc[24] += ux; acc[25] += uy; acc[26] += uz;
-    }
+    float A[6];
+    gicp_point<LINEARIZE>(acc, R00, R01, R02, R10, R11, R12, R20, R21, R22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz, A);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   wave_sums_to_lane63<NACC>(acc);  // (step-major: device_math.hpp; the same six additions per value)
@@ -352,6 +362,233 @@ __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restr
   } else if (t >= 2 && t < COMPACT) {
     out[t] = 0.0;
   }
+}
+
+// ---- the continuous-time factor (IntegratedCT_GICPFactor): the same per-point algebra, one pose per time bucket ----
+// Layout: the points of a bucket are a contiguous index run (the time table never goes back), cut into blocks of at most BLOCK * ppt points, so
+// the pose is uniform per block.  Block b writes its 28 source-frame sums (in T_k's own tangent) to partial row b; ct_bucket_kernel adds the rows
+// of each bucket in block order and maps the bucket's 6 x 6 system through the chain rule [D0_k | D1_k] in FP64; ct_sum_kernel adds the buckets in
+// bucket order.  No atomics: the record is bit-reproducible, for any number of buckets.
+constexpr int CT_POSE_STRIDE = 84;  // doubles per bucket in the pose table: T_k (12, row-major 3x4) | D0_k (36) | D1_k (36), row-major 6x6
+constexpr int CT_ROW = 92;          // doubles per bucket row / in the record: count, error, 78 upper entries of the 12 x 12 H (row-major), 12 of b
+
+struct CtArgs {
+  const int4* blocks;    // (bucket, begin, end, -) per block
+  const double* poses;   // CT_POSE_STRIDE per bucket (the deskewing kernel reads a plain 12-double table instead)
+  int32_t* keep_corr;    // kept correspondences (position in the index's sorted order, or -1), or null
+  float4* keep_m0;       // kept M = (C_B + R_k C_A R_k^T)^-1 (target frame): m00 m01 m02 m11
+  float2* keep_m1;       //                                                      m12 m22
+  int32_t* corr_out;     // original target index or -1 per source point, or null
+};
+
+template <bool LINEARIZE>
+__global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials) {
+  __shared__ float s_red[4][PARTIAL_STRIDE];
+  const int4 blk = c.blocks[blockIdx.x];
+  const double* T = c.poses + (size_t)blk.x * CT_POSE_STRIDE;
+  const float R00 = (float)T[0], R01 = (float)T[1], R02 = (float)T[2];
+  const float R10 = (float)T[4], R11 = (float)T[5], R12 = (float)T[6];
+  const float R20 = (float)T[8], R21 = (float)T[9], R22 = (float)T[10];
+  float acc[NACC];
+#pragma unroll
+  for (int j = 0; j < NACC; j++) acc[j] = 0.f;
+  int inliers = 0;
+  for (int i = blk.y + (int)threadIdx.x; i < blk.z; i += BLOCK) {
+    const float4 p = a.pts[i];
+    double qx, qy, qz;
+    transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
+    double best_d;
+    const int j = nearest(a, qx, qy, qz, best_d);
+    if (c.corr_out) c.corr_out[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
+    if (c.keep_corr) c.keep_corr[i] = j;
+    if (j < 0) continue;
+    inliers++;
+    float A[6];
+    gicp_point<LINEARIZE>(acc, R00, R01, R02, R10, R11, R12, R20, R21, R22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz, A);
+    if (c.keep_m0) {
+      // M = R A R^T: the source-frame inverse taken back to the target frame
+      const float Rm[9] = {R00, R01, R02, R10, R11, R12, R20, R21, R22};
+      const float As[9] = {A[0], A[1], A[2], A[1], A[3], A[4], A[2], A[4], A[5]};
+      float W[9];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) W[3 * r + k] = Rm[3 * r] * As[k] + Rm[3 * r + 1] * As[3 + k] + Rm[3 * r + 2] * As[6 + k];
+      float M[6];
+      const int mr[6] = {0, 0, 0, 1, 1, 2}, mc[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+      for (int u = 0; u < 6; u++) M[u] = W[3 * mr[u]] * Rm[3 * mc[u]] + W[3 * mr[u] + 1] * Rm[3 * mc[u] + 1] + W[3 * mr[u] + 2] * Rm[3 * mc[u] + 2];
+      c.keep_m0[i] = make_float4(M[0], M[1], M[2], M[3]);
+      c.keep_m1[i] = make_float2(M[4], M[5]);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_sums_to_lane63<NACC>(acc);
+  if (lane == 63) {
+#pragma unroll
+    for (int j = 0; j < NACC; j++) s_red[wave][j] = acc[j];
+  }
+  {
+    const float v = wave_sum_to_lane63((float)inliers);
+    if (lane == 63) s_red[wave][28] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PARTIAL_STRIDE) {
+    const int j = threadIdx.x;
+    partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = j <= 28 ? (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]) : 0.f;
+  }
+}
+
+// error(): the kept correspondences and M at new poses -- e = sum r^T M r, r = b_j - T_k p_i (FP64, then FP32).  Partial rows hold e (27) and the
+// count (28) only, so gicp_finalize_kernel (linearize = 0) turns them into the record.
+__global__ __launch_bounds__(BLOCK) void ct_error_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials) {
+  __shared__ float s_red[4][2];
+  const int4 blk = c.blocks[blockIdx.x];
+  const double* T = c.poses + (size_t)blk.x * CT_POSE_STRIDE;
+  float e = 0.f;
+  int inliers = 0;
+  for (int i = blk.y + (int)threadIdx.x; i < blk.z; i += BLOCK) {
+    const int j = c.keep_corr[i];
+    if (j < 0) continue;
+    const float4 p = a.pts[i];
+    double qx, qy, qz;
+    transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
+    const float4 b = a.sorted[j];
+    const float rx = (float)((double)b.x - qx), ry = (float)((double)b.y - qy), rz = (float)((double)b.z - qz);
+    const float4 m0 = c.keep_m0[i];
+    const float2 m1 = c.keep_m1[i];
+    const float ux = m0.x * rx + m0.y * ry + m0.z * rz;
+    const float uy = m0.y * rx + m0.w * ry + m1.x * rz;
+    const float uz = m0.z * rx + m1.x * ry + m1.y * rz;
+    e += rx * ux + ry * uy + rz * uz;
+    inliers++;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float se = wave_sum_to_lane63(e);
+  const float si = wave_sum_to_lane63((float)inliers);
+  if (lane == 63) {
+    s_red[wave][0] = se;
+    s_red[wave][1] = si;
+  }
+  __syncthreads();
+  if (threadIdx.x < PARTIAL_STRIDE) {
+    const int j = threadIdx.x;
+    float v = 0.f;
+    if (j == 27) v = (s_red[0][0] + s_red[1][0]) + (s_red[2][0] + s_red[3][0]);
+    if (j == 28) v = (s_red[0][1] + s_red[1][1]) + (s_red[2][1] + s_red[3][1]);
+    partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = v;
+  }
+}
+
+// one block of 64 threads per bucket: its partial rows summed in FP64 in block order -> H_k, b_k (T_k's tangent, the compact record's convention)
+// -> [D0 | D1]^T H_k [D0 | D1] and [D0 | D1]^T b_k
+__global__ __launch_bounds__(64) void ct_bucket_kernel(const float* __restrict__ partials, const int* __restrict__ bucket_first, const double* __restrict__ poses,
+                                                       double* __restrict__ rows) {
+  __shared__ double s_sum[PARTIAL_STRIDE];
+  __shared__ double s_J[6 * 12];
+  __shared__ double s_H[36];
+  __shared__ double s_b[6];
+  __shared__ double s_W[6 * 12];
+  const int k = blockIdx.x, t = threadIdx.x;
+  const int first = bucket_first[k], last = bucket_first[k + 1];
+  if (t <= 28) {
+    double s = 0.0;
+    for (int r = first; r < last; r++) s += (double)partials[(size_t)r * PARTIAL_STRIDE + t];
+    s_sum[t] = s;
+  }
+  const double* D = poses + (size_t)k * CT_POSE_STRIDE + 12;
+  for (int u = t; u < 72; u += 64) {
+    const int m = u / 12, col = u % 12;
+    s_J[u] = col < 6 ? D[6 * m + col] : D[36 + 6 * m + col - 6];
+  }
+  __syncthreads();
+  if (t < 36) {
+    const int r = t / 6, cc = t % 6, lo = min(r, cc), hi = max(r, cc);
+    const int u = lo * 6 - lo * (lo - 1) / 2 + (hi - lo);  // row-major upper-triangle index
+    s_H[t] = s_sum[c_acc_of_upper_g[u]];
+  } else if (t < 42) {
+    const int m = t - 36;
+    s_b[m] = m < 3 ? s_sum[21 + m] : -s_sum[21 + m];
+  }
+  __syncthreads();
+  for (int u = t; u < 72; u += 64) {
+    const int m = u / 12, col = u % 12;
+    double s = 0.0;
+    for (int q = 0; q < 6; q++) s += s_H[6 * m + q] * s_J[12 * q + col];
+    s_W[u] = s;
+  }
+  __syncthreads();
+  double* row = rows + (size_t)k * CT_ROW;
+  for (int u = t; u < CT_ROW; u += 64) {
+    double v;
+    if (u == 0) {
+      v = s_sum[28];
+    } else if (u == 1) {
+      v = s_sum[27];
+    } else if (u < 80) {
+      int r = 0, idx = u - 2;
+      while (idx >= 12 - r) {
+        idx -= 12 - r;
+        r++;
+      }
+      const int cc = r + idx;
+      v = 0.0;
+      for (int m = 0; m < 6; m++) v += s_J[12 * m + r] * s_W[12 * m + cc];
+    } else {
+      const int r = u - 80;
+      v = 0.0;
+      for (int m = 0; m < 6; m++) v += s_J[12 * m + r] * s_b[m];
+    }
+    row[u] = v;
+  }
+}
+
+// one block: the bucket rows summed in a fixed order (8 strided groups, then the groups in order) -> the record
+__global__ __launch_bounds__(768) void ct_sum_kernel(const double* __restrict__ rows, int nbk, double* __restrict__ out) {
+  __shared__ double s_part[8][96];
+  const int j = threadIdx.x % 96, g = threadIdx.x / 96;
+  double s = 0.0;
+  if (j < CT_ROW) {
+    constexpr int INFLIGHT = 8;
+    for (int c = g; c < nbk; c += 8 * INFLIGHT) {
+      double v[INFLIGHT];
+#pragma unroll
+      for (int u = 0; u < INFLIGHT; u++) v[u] = rows[(size_t)min(c + 8 * u, nbk - 1) * CT_ROW + j];
+#pragma unroll
+      for (int u = 0; u < INFLIGHT; u++)
+        if (c + 8 * u < nbk) s += v[u];
+    }
+  }
+  s_part[g][j] = s;
+  __syncthreads();
+  if (threadIdx.x < CT_ROW) {
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) t += s_part[q][threadIdx.x];
+    out[threadIdx.x] = t;
+  }
+}
+
+// deskewed_source_points: T[time_index[i]] p_i in FP64 (the source's exact points where it keeps them), table of 12 doubles per bucket
+__global__ __launch_bounds__(256) void ct_deskew_kernel(int n, const double4* __restrict__ pts64, const float4* __restrict__ pts, const int* __restrict__ time_index,
+                                                        const double* __restrict__ table, double4* __restrict__ out64, float4* __restrict__ out32) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double4 p;
+  if (pts64) {
+    p = pts64[i];
+  } else {
+    const float4 f = pts[i];
+    p = make_double4((double)f.x, (double)f.y, (double)f.z, 1.0);
+  }
+  const double* T = table + 12 * (size_t)time_index[i];
+  double4 q;
+  q.x = dadd(dadd(dadd(dmul(T[0], p.x), dmul(T[1], p.y)), dmul(T[2], p.z)), T[3]);
+  q.y = dadd(dadd(dadd(dmul(T[4], p.x), dmul(T[5], p.y)), dmul(T[6], p.z)), T[7]);
+  q.z = dadd(dadd(dadd(dmul(T[8], p.x), dmul(T[9], p.y)), dmul(T[10], p.z)), T[11]);
+  q.w = 1.0;
+  out64[i] = q;
+  if (out32) out32[i] = make_float4((float)q.x, (float)q.y, (float)q.z, 1.0f);
 }
 
 inline int grid_for(int n) { return (n + 255) / 256; }
@@ -426,6 +663,350 @@ int run_gicp(const glim_amd_nn_index* ix, const glim_amd_cloud* source, const do
   return GLIM_AMD_OK;
 }
 
+
+// ---- CT factor, host side: the time table and the bucket poses with their derivatives (FP64, gtsam::Pose3 conventions) ----
+// gtsam's right-perturbation Jacobians: between(X, Y) = X^-1 Y, H_X = -Ad((X^-1 Y)^-1), H_Y = I; compose(A, B): H_A = Ad(B^-1), H_B = I;
+// Expmap(xi): ExpmapDerivative(xi) = J_r(xi); Logmap(T): LogmapDerivative = J_r(Log T)^-1.  Coefficients with a cancelling numerator switch to
+// their Taylor series below 0.02 rad (truncation < 1e-16 there).
+struct Mat6 {
+  double m[36];
+};
+constexpr double CT_SERIES = 0.02;
+
+void ct_hat(const double* w, double* W) {
+  W[0] = 0.0; W[1] = -w[2]; W[2] = w[1];
+  W[3] = w[2]; W[4] = 0.0; W[5] = -w[0];
+  W[6] = -w[1]; W[7] = w[0]; W[8] = 0.0;
+}
+void mm3(const double* A, const double* B, double* C) {
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+}
+void inv3(const double* A, double* B) {
+  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+  const double id = 1.0 / (A[0] * c00 + A[1] * c01 + A[2] * c02);
+  B[0] = c00 * id; B[1] = (A[2] * A[7] - A[1] * A[8]) * id; B[2] = (A[1] * A[5] - A[2] * A[4]) * id;
+  B[3] = c01 * id; B[4] = (A[0] * A[8] - A[2] * A[6]) * id; B[5] = (A[2] * A[3] - A[0] * A[5]) * id;
+  B[6] = c02 * id; B[7] = (A[1] * A[6] - A[0] * A[7]) * id; B[8] = (A[0] * A[4] - A[1] * A[3]) * id;
+}
+// (1 - cos th) / th^2 and (th - sin th) / th^3
+void so3_coeffs(double th, double& b, double& c) {
+  const double t2 = th * th;
+  if (th < CT_SERIES) {
+    b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+    c = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
+  } else {
+    b = (1.0 - std::cos(th)) / t2;
+    c = (th - std::sin(th)) / (t2 * th);
+  }
+}
+// Pose3::Expmap: T = [Exp(w) | V(w) v], V = I + b W + c W^2
+void se3_exp(const double* xi, double* T12) {
+  double W[9], W2[9];
+  ct_hat(xi, W);
+  mm3(W, W, W2);
+  const double th = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]);
+  const double t2 = th * th;
+  const double a = th < CT_SERIES ? 1.0 - t2 / 6.0 + t2 * t2 / 120.0 : std::sin(th) / th;
+  double b, c;
+  so3_coeffs(th, b, c);
+  for (int r = 0; r < 3; r++) {
+    double tr = 0.0;
+    for (int k = 0; k < 3; k++) {
+      const double I = r == k ? 1.0 : 0.0;
+      T12[4 * r + k] = I + a * W[3 * r + k] + b * W2[3 * r + k];
+      tr += (I + b * W[3 * r + k] + c * W2[3 * r + k]) * xi[3 + k];
+    }
+    T12[4 * r + 3] = tr;
+  }
+}
+// Pose3::Logmap: w = Log(R), v = V(w)^-1 t
+void se3_log(const double* T12, double* xi) {
+  const double R[9] = {T12[0], T12[1], T12[2], T12[4], T12[5], T12[6], T12[8], T12[9], T12[10]};
+  const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
+  const double s = std::sqrt(vx * vx + vy * vy + vz * vz), cth = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+  const double th = std::atan2(s, cth);
+  const double t2 = th * th;
+  const double f = th < CT_SERIES ? 1.0 + t2 / 6.0 + 7.0 * t2 * t2 / 360.0 : th / std::sin(th);
+  xi[0] = f * vx;
+  xi[1] = f * vy;
+  xi[2] = f * vz;
+  double W[9], W2[9], V[9], Vi[9];
+  ct_hat(xi, W);
+  mm3(W, W, W2);
+  double b, c;
+  so3_coeffs(th, b, c);
+  for (int u = 0; u < 9; u++) V[u] = (u % 4 == 0 ? 1.0 : 0.0) + b * W[u] + c * W2[u];
+  inv3(V, Vi);
+  for (int r = 0; r < 3; r++) xi[3 + r] = Vi[3 * r] * T12[3] + Vi[3 * r + 1] * T12[7] + Vi[3 * r + 2] * T12[11];
+}
+// Pose3::ExpmapDerivative: [[Jw, 0], [Q, Jw]] (Jw = Rot3::ExpmapDerivative, Q = computeQforExpmapDerivative)
+Mat6 se3_jr(const double* xi) {
+  double W[9], V[9], W2[9];
+  ct_hat(xi, W);
+  ct_hat(xi + 3, V);
+  mm3(W, W, W2);
+  const double th = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), t2 = th * th;
+  double b, c;
+  so3_coeffs(th, b, c);
+  double Jw[9];
+  for (int u = 0; u < 9; u++) Jw[u] = (u % 4 == 0 ? 1.0 : 0.0) - b * W[u] + c * W2[u];
+  double ca, cb, cc;  // (th - sin) / th^3, (1 - th^2/2 - cos) / th^4, -(cb - 3 (th - sin - th^3/6) / th^5) / 2
+  if (th < CT_SERIES) {
+    ca = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
+    cb = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0;
+    const double cd = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0;
+    cc = -0.5 * (cb - 3.0 * cd);
+  } else {
+    const double t3 = t2 * th, t4 = t2 * t2, t5 = t4 * th, sn = std::sin(th), cs = std::cos(th);
+    ca = (th - sn) / t3;
+    cb = (1.0 - t2 / 2.0 - cs) / t4;
+    cc = -0.5 * (cb - 3.0 * (th - sn - t3 / 6.0) / t5);
+  }
+  double WV[9], VW[9], WVW[9], WWV[9], VWW[9], WVWW[9], WWVW[9];
+  mm3(W, V, WV);
+  mm3(V, W, VW);
+  mm3(WV, W, WVW);
+  mm3(W2, V, WWV);
+  mm3(V, W2, VWW);
+  mm3(WVW, W, WVWW);
+  mm3(W, WVW, WWVW);
+  double Q[9];
+  for (int u = 0; u < 9; u++)
+    Q[u] = -0.5 * V[u] + ca * (WV[u] + VW[u] - WVW[u]) + cb * (WWV[u] + VWW[u] - 3.0 * WVW[u]) + cc * (WVWW[u] + WWVW[u]);
+  Mat6 J{};
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) {
+      J.m[6 * r + k] = Jw[3 * r + k];
+      J.m[6 * (r + 3) + k + 3] = Jw[3 * r + k];
+      J.m[6 * (r + 3) + k] = Q[3 * r + k];
+    }
+  return J;
+}
+// Pose3::LogmapDerivative at Log = xi: the block inverse of se3_jr(xi)
+Mat6 se3_jr_inv(const double* xi) {
+  const Mat6 J = se3_jr(xi);
+  double Jw[9], Q[9], Ji[9], T[9], QJ[9];
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) {
+      Jw[3 * r + k] = J.m[6 * r + k];
+      Q[3 * r + k] = J.m[6 * (r + 3) + k];
+    }
+  inv3(Jw, Ji);
+  mm3(Q, Ji, T);
+  mm3(Ji, T, QJ);
+  Mat6 I{};
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) {
+      I.m[6 * r + k] = Ji[3 * r + k];
+      I.m[6 * (r + 3) + k + 3] = Ji[3 * r + k];
+      I.m[6 * (r + 3) + k] = -QJ[3 * r + k];
+    }
+  return I;
+}
+// Pose3::AdjointMap: [[R, 0], [hat(t) R, R]]
+Mat6 se3_ad(const double* T12) {
+  const double R[9] = {T12[0], T12[1], T12[2], T12[4], T12[5], T12[6], T12[8], T12[9], T12[10]};
+  const double t[3] = {T12[3], T12[7], T12[11]};
+  double H[9], HR[9];
+  ct_hat(t, H);
+  mm3(H, R, HR);
+  Mat6 A{};
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) {
+      A.m[6 * r + k] = R[3 * r + k];
+      A.m[6 * (r + 3) + k + 3] = R[3 * r + k];
+      A.m[6 * (r + 3) + k] = HR[3 * r + k];
+    }
+  return A;
+}
+Mat6 mm6(const Mat6& A, const Mat6& B) {
+  Mat6 C{};
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) {
+      double s = 0.0;
+      for (int k = 0; k < 6; k++) s += A.m[6 * r + k] * B.m[6 * k + c];
+      C.m[6 * r + c] = s;
+    }
+  return C;
+}
+void se3_compose(const double* A, const double* B, double* C) {
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 4; c++) C[4 * r + c] = A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c] + A[4 * r + 2] * B[8 + c];
+    C[4 * r + 3] += A[4 * r + 3];
+  }
+}
+void se3_inverse(const double* A, double* B) {
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) B[4 * r + c] = A[4 * c + r];
+    B[4 * r + 3] = -(A[r] * A[3] + A[4 + r] * A[7] + A[8 + r] * A[11]);
+  }
+}
+
+}  // namespace
+
+struct glim_amd_ct_gicp_factor {
+  CtxRef ctx;
+  const glim_amd_nn_index* ix = nullptr;  // not owned
+  const glim_amd_cloud* src = nullptr;    // not owned
+  int n = 0;
+  double max_dist = 1.0;
+  std::vector<double> table;              // normalised bucket times
+  std::vector<int> time_index;            // bucket of every point
+  int nbk = 0, nb = 0;                    // buckets, blocks
+  int4* d_blocks = nullptr;               // (bucket, begin, end, -) per block
+  int* d_bucket_first = nullptr;          // first block of every bucket, nbk + 1 entries
+  int* d_time_index = nullptr;
+  double* d_poses = nullptr;              // CT_POSE_STRIDE per bucket
+  double* h_poses = nullptr;              // pinned staging of the same
+  float* d_partials = nullptr;            // nb partial rows
+  double* d_rows = nullptr;               // nbk bucket rows
+  double* d_out = nullptr;                // CT_ROW doubles
+  int32_t* keep_corr = nullptr;           // the state linearize keeps for error
+  float4* keep_m0 = nullptr;
+  float2* keep_m1 = nullptr;
+  bool kept = false;
+};
+
+namespace {
+
+// rings of the index's walk that cover `d`, or -1 when the walk is bounded below that (the rule of run_gicp)
+int ct_rings(const glim_amd_nn_index* ix, double d) {
+  const double rings = std::ceil(d / ix->h) + 1.0;
+  return rings <= (double)GICP_MAX_RING ? (int)rings : -1;
+}
+
+// T_k, D0_k, D1_k of every bucket at (X, Y): CT_POSE_STRIDE doubles per bucket
+void ct_poses(const std::vector<double>& table, const double* X, const double* Y, double* out) {
+  double Xi[12], delta[12], vel[6], Dinv[12];
+  se3_inverse(X, Xi);
+  se3_compose(Xi, Y, delta);
+  se3_log(delta, vel);
+  se3_inverse(delta, Dinv);
+  const Mat6 Jlog = se3_jr_inv(vel);
+  Mat6 Hb1 = se3_ad(Dinv);
+  for (double& v : Hb1.m) v = -v;
+  for (size_t k = 0; k < table.size(); k++) {
+    const double tk = table[k];
+    double xi[6], E[12], Ei[12];
+    for (int u = 0; u < 6; u++) xi[u] = tk * vel[u];
+    se3_exp(xi, E);
+    se3_inverse(E, Ei);
+    double* o = out + k * CT_POSE_STRIDE;
+    se3_compose(X, E, o);
+    Mat6 G = mm6(se3_jr(xi), Jlog);  // H_compose_2 H_exp t_k H_log
+    for (double& v : G.m) v *= tk;
+    const Mat6 G0 = mm6(G, Hb1);
+    const Mat6 Ad = se3_ad(Ei);
+    for (int u = 0; u < 36; u++) {
+      o[12 + u] = Ad.m[u] + G0.m[u];
+      o[48 + u] = G.m[u];
+    }
+  }
+}
+
+GicpArgs ct_args(const glim_amd_ct_gicp_factor* f, int max_ring) {
+  GicpArgs a{};
+  const glim_amd_nn_index* ix = f->ix;
+  a.sorted = ix->sorted;
+  a.tA = ix->covA;
+  a.tB = ix->covB;
+  a.keys = ix->keys;
+  a.runs = ix->runs;
+  a.mask = ix->mask;
+  a.nt = ix->n;
+  a.h = ix->h;
+  a.inv_h = 1.0 / ix->h;
+  a.pts = f->src->pts;
+  a.covA = f->src->covA;
+  a.covB = f->src->covB;
+  a.n = f->n;
+  a.ppt = 1;
+  a.max_sq = f->max_dist * f->max_dist;
+  a.max_ring = max_ring;
+  return a;
+}
+
+enum { CT_LINEARIZE = 0, CT_ERROR = 1, CT_CORR = 2 };
+
+// one synchronous evaluation; caller has validated the arguments.  out: CT_ROW doubles (CT_LINEARIZE) or the 29-double compact record (CT_ERROR)
+int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mode, double* out, int32_t* corr_host) {
+  if (!f->src->has_covs) return GLIM_AMD_ERR_STATE;
+  if (!f->ix->covA) return GLIM_AMD_ERR_STATE;
+  const int max_ring = ct_rings(f->ix, f->max_dist);
+  if (max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
+  glim_amd_ctx* ctx = f->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  if (f->n == 0 || f->ix->n == 0) {
+    if (corr_host)
+      for (int i = 0; i < f->n; i++) corr_host[i] = -1;
+    return GLIM_AMD_OK;
+  }
+  ct_poses(f->table, X, Y, f->h_poses);
+  const GicpArgs a = ct_args(f, max_ring);
+  CtArgs c{};
+  c.blocks = f->d_blocks;
+  c.poses = f->d_poses;
+  DeviceTemp corr;
+  SyncOnExit in_flight(st);
+  GA_HIP(hipMemcpyAsync(f->d_poses, f->h_poses, (size_t)f->nbk * CT_POSE_STRIDE * sizeof(double), hipMemcpyHostToDevice, st));
+  if (mode == CT_LINEARIZE) {
+    c.keep_corr = f->keep_corr;
+    c.keep_m0 = f->keep_m0;
+    c.keep_m1 = f->keep_m1;
+    f->kept = false;
+    ct_gicp_kernel<true><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
+    ct_bucket_kernel<<<f->nbk, 64, 0, st>>>(f->d_partials, f->d_bucket_first, f->d_poses, f->d_rows);
+    ct_sum_kernel<<<1, 768, 0, st>>>(f->d_rows, f->nbk, f->d_out);
+    GA_HIP(hipGetLastError());
+    GA_HIP(read_back_sync(ctx, st, out, f->d_out, CT_ROW * sizeof(double)));
+    f->kept = true;
+  } else if (mode == CT_ERROR) {
+    if (!f->kept) {
+      CtArgs k = c;
+      k.keep_corr = f->keep_corr;
+      k.keep_m0 = f->keep_m0;
+      k.keep_m1 = f->keep_m1;
+      ct_gicp_kernel<false><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials);
+    }
+    c.keep_corr = f->keep_corr;
+    c.keep_m0 = f->keep_m0;
+    c.keep_m1 = f->keep_m1;
+    ct_error_kernel<<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
+    gicp_finalize_kernel<<<1, 256, 0, st>>>(f->d_partials, f->nb, 0, f->d_out);
+    GA_HIP(hipGetLastError());
+    GA_HIP(read_back_sync(ctx, st, out, f->d_out, COMPACT * sizeof(double)));
+    f->kept = true;
+  } else {
+    GA_HIP(pool_malloc(&corr.p, (size_t)f->n * sizeof(int32_t)));
+    c.corr_out = corr.as<int32_t>();
+    ct_gicp_kernel<false><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
+    GA_HIP(hipGetLastError());
+    GA_HIP(hipMemcpyAsync(corr_host, corr.p, (size_t)f->n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GA_HIP(hipStreamSynchronize(st));
+  }
+  in_flight.dismiss();
+  return GLIM_AMD_OK;
+}
+
+// the deskewed points into out64 (device, n double4) and, when out32 is set, their FP32 image; caller holds ctx->mu
+int run_ct_deskew(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, bool local, double4* out64, float4* out32, hipStream_t st) {
+  std::vector<double> full((size_t)f->nbk * CT_POSE_STRIDE);
+  ct_poses(f->table, X, Y, full.data());
+  double T0i[12];
+  se3_inverse(full.data(), T0i);
+  for (int k = 0; k < f->nbk; k++) {
+    double* dst = f->h_poses + 12 * (size_t)k;
+    if (local) se3_compose(T0i, full.data() + (size_t)k * CT_POSE_STRIDE, dst);
+    else memcpy(dst, full.data() + (size_t)k * CT_POSE_STRIDE, 12 * sizeof(double));
+  }
+  GA_HIP(hipMemcpyAsync(f->d_poses, f->h_poses, (size_t)f->nbk * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+  ct_deskew_kernel<<<grid_for(f->n), 256, 0, st>>>(f->n, f->src->pts64, f->src->pts, f->d_time_index, f->d_poses, out64, out32);
+  GA_HIP(hipGetLastError());
+  return GLIM_AMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -550,6 +1131,201 @@ int glim_amd_gicp_correspondences(const glim_amd_nn_index* target, const glim_am
   if (!correspondences) return GLIM_AMD_ERR_INVALID;
   double compact[COMPACT];
   return run_gicp(target, source, T_target_source12, max_correspondence_distance, false, compact, correspondences);
+}
+
+}  // extern "C"
+
+// ---- continuous-time GICP factor (IntegratedCT_GICPFactor_<PointCloud, PointCloud>) ----
+extern "C" {
+
+int glim_amd_ct_gicp_destroy(glim_amd_ct_gicp_factor* f) {
+  if (!f) return GLIM_AMD_OK;
+  if (f->ctx) (void)hipSetDevice(f->ctx->device);
+  void* dev[] = {f->d_blocks, f->d_bucket_first, f->d_time_index, f->d_poses, f->d_partials, f->d_rows, f->d_out, f->keep_corr, f->keep_m0, f->keep_m1};
+  for (void* p : dev)
+    if (p) (void)pool_free(p);
+  if (f->h_poses) (void)pinned_free(f->h_poses);
+  delete f;
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
+  if (!target || !source || !out) return GLIM_AMD_ERR_INVALID;
+  *out = nullptr;
+  if (source->ctx->device != target->ctx->device) return GLIM_AMD_ERR_INVALID;
+  if (source->n > (int64_t)(1 << 28)) return GLIM_AMD_ERR_INVALID;
+  const int n = (int)source->n;
+  if (!times && (int64_t)source->h_times.size() != source->n) return GLIM_AMD_ERR_STATE;  // no per-point times
+  if (!source->has_covs) return GLIM_AMD_ERR_STATE;
+  const double* t = times ? times : source->h_times.data();
+  std::unique_ptr<glim_amd_ct_gicp_factor, int (*)(glim_amd_ct_gicp_factor*)> f(new glim_amd_ct_gicp_factor(), glim_amd_ct_gicp_destroy);
+  glim_amd_ctx* ctx = target->ctx;
+  f->ctx = ctx;
+  f->ix = target;
+  f->src = source;
+  f->n = n;
+  // the time table (IntegratedCT_ICPFactor's constructor): a new bucket when the time moves on by more than 1e-3, entries / the last one
+  f->time_index.resize((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (f->table.empty() || t[i] - f->table.back() > 1e-3) f->table.push_back(t[i]);
+    f->time_index[i] = (int)f->table.size() - 1;
+  }
+  if (!f->table.empty()) {
+    const double last = std::max(1e-9, f->table.back());
+    for (double& v : f->table) v /= last;
+  }
+  f->nbk = (int)f->table.size();
+  // blocks: each bucket's index run cut into pieces of BLOCK * ppt points (ppt as run_gicp picks it for the whole cloud)
+  const int target_blocks = std::max(1, ctx->num_cus * 4);
+  const int ppt = std::max(1, std::min(64, (n + BLOCK * target_blocks - 1) / (BLOCK * target_blocks)));
+  std::vector<int4> blocks;
+  std::vector<int> first((size_t)f->nbk + 1, 0);
+  for (int i = 0; i < n;) {
+    const int k = f->time_index[i];
+    int e = i;
+    while (e < n && f->time_index[e] == k) e++;
+    first[k] = (int)blocks.size();
+    for (int b = i; b < e; b += BLOCK * ppt) blocks.push_back(make_int4(k, b, std::min(e, b + BLOCK * ppt), 0));
+    i = e;
+  }
+  f->nb = (int)blocks.size();
+  first[f->nbk] = f->nb;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  const size_t nn = (size_t)std::max(n, 1), nk = (size_t)std::max(f->nbk, 1), nbb = (size_t)std::max(f->nb, 1);
+  GA_HIP(pool_malloc(&f->d_blocks, nbb * sizeof(int4)));
+  GA_HIP(pool_malloc(&f->d_bucket_first, (nk + 1) * sizeof(int)));
+  GA_HIP(pool_malloc(&f->d_time_index, nn * sizeof(int)));
+  GA_HIP(pool_malloc(&f->d_poses, nk * CT_POSE_STRIDE * sizeof(double)));
+  GA_HIP(pinned_malloc(&f->h_poses, nk * CT_POSE_STRIDE * sizeof(double)));
+  GA_HIP(pool_malloc(&f->d_partials, nbb * PARTIAL_STRIDE * sizeof(float)));
+  GA_HIP(pool_malloc(&f->d_rows, nk * CT_ROW * sizeof(double)));
+  GA_HIP(pool_malloc(&f->d_out, CT_ROW * sizeof(double)));
+  GA_HIP(pool_malloc(&f->keep_corr, nn * sizeof(int32_t)));
+  GA_HIP(pool_malloc(&f->keep_m0, nn * sizeof(float4)));
+  GA_HIP(pool_malloc(&f->keep_m1, nn * sizeof(float2)));
+  if (n > 0) {
+    SyncOnExit in_flight(st);
+    GA_HIP(hipMemcpyAsync(f->d_blocks, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    GA_HIP(hipMemcpyAsync(f->d_bucket_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    GA_HIP(hipMemcpyAsync(f->d_time_index, f->time_index.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    GA_HIP(hipStreamSynchronize(st));
+    in_flight.dismiss();
+  }
+  *out = f.release();
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_set_max_correspondence_distance(glim_amd_ct_gicp_factor* f, double d) {
+  if (!f || !(d >= 0.0)) return GLIM_AMD_ERR_INVALID;
+  if (ct_rings(f->ix, d) < 0) return GLIM_AMD_ERR_UNSUPPORTED;
+  f->max_dist = d;
+  f->kept = false;
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_linearize(glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, glim_amd_ct_linearized* out) {
+  if (!f || !X12 || !Y12 || !out) return GLIM_AMD_ERR_INVALID;
+  double rec[CT_ROW] = {};
+  GA_TRY(run_ct(f, X12, Y12, CT_LINEARIZE, rec, nullptr));
+  memset(out, 0, sizeof(*out));
+  out->num_inliers = (int64_t)llround(rec[0]);
+  out->error = rec[1];
+  double H[144];
+  int u = 2;
+  for (int r = 0; r < 12; r++)
+    for (int c = r; c < 12; c++, u++) H[12 * r + c] = H[12 * c + r] = rec[u];
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) {
+      out->H_00[6 * r + c] = H[12 * r + c];
+      out->H_01[6 * r + c] = H[12 * r + c + 6];
+      out->H_11[6 * r + c] = H[12 * (r + 6) + c + 6];
+    }
+  for (int r = 0; r < 6; r++) {
+    out->b_0[r] = rec[80 + r];
+    out->b_1[r] = rec[86 + r];
+  }
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_error(glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, double* error, int64_t* num_inliers) {
+  if (!f || !X12 || !Y12 || !error) return GLIM_AMD_ERR_INVALID;
+  double rec[COMPACT] = {};
+  GA_TRY(run_ct(f, X12, Y12, CT_ERROR, rec, nullptr));
+  *error = rec[1];
+  if (num_inliers) *num_inliers = (int64_t)llround(rec[0]);
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_correspondences(glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, int32_t* correspondences) {
+  if (!f || !X12 || !Y12 || (!correspondences && f->n > 0)) return GLIM_AMD_ERR_INVALID;
+  return run_ct(f, X12, Y12, CT_CORR, nullptr, correspondences);
+}
+
+int glim_amd_ct_gicp_deskewed_points(glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, int32_t local, double* points4) {
+  if (!f || !X12 || !Y12 || (!points4 && f->n > 0)) return GLIM_AMD_ERR_INVALID;
+  if (f->n == 0) return GLIM_AMD_OK;
+  glim_amd_ctx* ctx = f->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  DeviceTemp d;
+  SyncOnExit in_flight(st);
+  GA_HIP(pool_malloc(&d.p, (size_t)f->n * sizeof(double4)));
+  GA_TRY(run_ct_deskew(f, X12, Y12, local != 0, d.as<double4>(), nullptr, st));
+  GA_HIP(hipMemcpyAsync(points4, d.p, (size_t)f->n * sizeof(double4), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_ct_gicp_deskewed_cloud(glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, int32_t local, glim_amd_cloud** out) {
+  if (!f || !X12 || !Y12 || !out) return GLIM_AMD_ERR_INVALID;
+  *out = nullptr;
+  const glim_amd_cloud* src = f->src;
+  glim_amd_ctx* ctx = f->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  std::unique_ptr<glim_amd_cloud, int (*)(glim_amd_cloud*)> c(new glim_amd_cloud(), glim_amd_cloud_destroy);
+  c->ctx = static_cast<glim_amd_ctx*>(src->ctx);
+  c->n = f->n;
+  const size_t nn = (size_t)std::max(f->n, 1);
+  GA_HIP(pool_malloc(&c->pts, nn * sizeof(float4)));
+  GA_HIP(pool_malloc(&c->pts64, nn * sizeof(double4)));
+  if (f->n > 0) {
+    SyncOnExit in_flight(st);
+    GA_TRY(run_ct_deskew(f, X12, Y12, local != 0, c->pts64, c->pts, st));
+    if (src->neighbors && src->k > 0) {
+      // the source's neighbour lists travel with the points (odometry_estimation_ct.cpp:194-195 estimates covariances from them)
+      GA_HIP(pool_malloc(&c->neighbors, (size_t)f->n * src->k * sizeof(int32_t)));
+      GA_HIP(hipMemcpyAsync(c->neighbors, src->neighbors, (size_t)f->n * src->k * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+      c->k = src->k;
+    }
+    GA_HIP(hipStreamSynchronize(st));
+    in_flight.dismiss();
+  }
+  *out = c.release();
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* f, const double* X12, const double* Y12, int32_t* num_buckets, int32_t table_cap,
+                                 double* table_out, double* T12_out, double* D0_out, double* D1_out, int32_t* time_index_out) {
+  if (!f || !X12 || !Y12 || table_cap < 0) return GLIM_AMD_ERR_INVALID;
+  if (num_buckets) *num_buckets = f->nbk;
+  std::vector<double> full((size_t)f->nbk * CT_POSE_STRIDE);
+  ct_poses(f->table, X12, Y12, full.data());
+  const int m = std::min(table_cap, f->nbk);
+  for (int k = 0; k < m; k++) {
+    const double* o = full.data() + (size_t)k * CT_POSE_STRIDE;
+    if (table_out) table_out[k] = f->table[k];
+    if (T12_out) memcpy(T12_out + 12 * (size_t)k, o, 12 * sizeof(double));
+    if (D0_out) memcpy(D0_out + 36 * (size_t)k, o + 12, 36 * sizeof(double));
+    if (D1_out) memcpy(D1_out + 36 * (size_t)k, o + 48, 36 * sizeof(double));
+  }
+  if (time_index_out) memcpy(time_index_out, f->time_index.data(), f->time_index.size() * sizeof(int32_t));
+  return GLIM_AMD_OK;
 }
 
 }  // extern "C"

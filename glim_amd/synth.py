@@ -183,3 +183,29 @@ def grid_trajectory(nx, ny, spacing=2.0, z=1.8):
 def relative_pose(T_world_a, T_world_b):
     """T_a_b (maps frame-b points into frame a)."""
     return np.linalg.inv(T_world_a) @ T_world_b
+
+
+def interpolate_pose(T_begin, T_end, s):
+    """T_begin Exp(s Log(T_begin^-1 T_end)): the constant-velocity pose at fraction s of a sweep (the continuous-time factor's model)."""
+    from .se3 import se3_exp, se3_log
+
+    return np.asarray(T_begin, dtype=np.float64) @ se3_exp(s * se3_log(np.linalg.inv(T_begin) @ T_end))
+
+
+def moving_scan(scene, T_begin, T_end, rings, azimuths, duration=0.1, frame_id=0, sigma=0.01, seed=SCENE_SEED):
+    """One sweep of a MOVING sensor: azimuth column a is captured at time duration * a / azimuths from its own pose, interpolated between
+    T_begin and T_end (world <- sensor), and its points are returned in that pose's sensor frame.  Columns are emitted in capture order, so
+    the times ascend with the index.  Returns (N x 3 float32 points, N times)."""
+    dirs = lidar_directions(rings, azimuths).reshape(rings, azimuths, 3)
+    rng = np.random.default_rng(seed + int(frame_id))
+    pts, times = [], []
+    for a in range(azimuths):
+        s = a / azimuths
+        T = interpolate_pose(T_begin, T_end, s)
+        d = dirs[:, a, :]
+        t = scene.raycast(T[:3, 3], d @ T[:3, :3].T)
+        t = t + rng.normal(0.0, sigma, size=t.shape)
+        ok = np.isfinite(t)
+        pts.append(d[ok] * t[ok, None])
+        times.append(np.full(int(ok.sum()), duration * s))
+    return np.concatenate(pts).astype(np.float32), np.concatenate(times)

@@ -188,6 +188,48 @@ int glim_amd_gicp_error(const glim_amd_nn_index* target, const glim_amd_cloud* s
 int glim_amd_gicp_correspondences(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                                   double max_correspondence_distance, int32_t* correspondences);
 
+/* ---- continuous-time GICP factor on device: gtsam_points::IntegratedCT_GICPFactor_<PointCloud, PointCloud> (KdTree target), the whole
+ * per-frame cost of GLIM's LiDAR-only CT odometry (src/glim/odometry/odometry_estimation_ct.cpp:158-183, config_odometry_ct.json).
+ * One scan, two keys: X = the pose at scan begin, Y = at scan end.  Semantics (upstream recall, gicp.hip states them in full):
+ *   time table, built once: source times in index order, a new bucket when t - table.back() > 1e-3, every entry / max(1e-9, table.back());
+ *   bucket k: T_k = X * Exp(t_k * Log(X^-1 Y)), D0_k / D1_k = d T_k / d X, d T_k / d Y (right perturbations, FP64 on the host);
+ *   point i of bucket k: q = T_k p_i, exact nearest target point within max_correspondence_distance (glim_amd_gicp_*'s search),
+ *   M = (C_B + R_k C_A R_k^T)^-1, r = q - b, J = [-R_k hat(p) | R_k]: e += r^T M r, H_00 += (J D0)^T M (J D0), ... b_1 += (J D1)^T M r.
+ * gtsam::HessianFactor(X, Y, H_00, H_01, -b_0, H_11, -b_1, error).  All H_* row-major 6x6, tangent [omega; v]. */
+typedef struct glim_amd_ct_gicp_factor glim_amd_ct_gicp_factor; /* child of the target index's context */
+typedef struct {
+  int64_t num_inliers;
+  double error;
+  double H_00[36]; /* X-X */
+  double H_01[36]; /* X-Y */
+  double H_11[36]; /* Y-Y */
+  double b_0[6];
+  double b_1[6];
+} glim_amd_ct_linearized;
+/* IntegratedCT_GICPFactor(X, Y, target, source, target_tree) -- odometry_estimation_ct.cpp:158-160.  `target` needs covariances (checked
+ * per call, as glim_amd_gicp_*); `source` needs covariances and per-point times: `times` (n, host, copied) or NULL = the times its
+ * preprocessing kept (glim_amd_preprocess).  GLIM_AMD_ERR_STATE when either is missing.  Both the index and the source must outlive the
+ * factor; max_correspondence_distance starts at 1.0. */
+int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out);
+int glim_amd_ct_gicp_destroy(glim_amd_ct_gicp_factor* factor);
+/* set_max_correspondence_distance (config_odometry_ct.json max_correspondence_distance); GLIM_AMD_ERR_UNSUPPORTED beyond what the index was
+ * sized for (the rule of glim_amd_gicp_*), the distance is then left unchanged. */
+int glim_amd_ct_gicp_set_max_correspondence_distance(glim_amd_ct_gicp_factor* factor, double max_correspondence_distance);
+/* linearize(values) -- called by LM at odometry_estimation_ct.cpp:176-183: correspondences and M are recomputed at (X, Y) and kept on the
+ * device for error(). */
+int glim_amd_ct_gicp_linearize(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, glim_amd_ct_linearized* out);
+/* error(values) -- LM's cost evaluations (same call site): the correspondences and M kept by the last linearize (computed first at (X, Y)
+ * when there was none).  num_inliers may be NULL. */
+int glim_amd_ct_gicp_error(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, double* error, int64_t* num_inliers);
+/* parity / debug: matched target index per source point at (X, Y), or -1 (the kept state is not touched). */
+int glim_amd_ct_gicp_correspondences(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t* correspondences);
+/* deskewed_source_points(values, local) -- odometry_estimation_ct.cpp:191: T_k p_i (n x Vector4d, w = 1), FP64 from the source's exact
+ * points where it keeps them; local != 0: in the frame of T_0 (T_0^-1 T_k p_i). */
+int glim_amd_ct_gicp_deskewed_points(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t local, double* points4);
+/* the same points as a new device cloud (FP64 kept beside the FP32 image) carrying the source's neighbour lists: what :194-195 hands to
+ * CloudCovarianceEstimation::estimate -- glim_amd_cloud_estimate_covariances runs on it directly. */
+int glim_amd_ct_gicp_deskewed_cloud(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t local, glim_amd_cloud** out);
+
 /* ---- submap merge on device: gtsam_points::merge_frames(poses, frames, downsample_resolution, target_num_points)
  * as called at src/glim/mapping/sub_mapping.cpp:480-497 (the reference's own GPU variant, merge_frames_gpu, is commented out at :491).
  * Frame f (sizes[f] points: points4[f] n x Vector4d, covs16[f] n x column-major Matrix4d) is moved by poses12[f] (row-major 3x4

@@ -442,6 +442,57 @@ private:
   LinearizedSystem6 linearized_{};
 };
 
+// gtsam_points::IntegratedCT_GICPFactor (point-cloud target): GLIM's continuous-time odometry cost, odometry_estimation_ct.cpp:158-195.
+// Keys {X, Y} = the poses at scan begin / end; the source needs covariances and per-point times (its preprocessing's, or `times`).
+class IntegratedCT_GICPFactor {
+public:
+  using shared_ptr = std::shared_ptr<IntegratedCT_GICPFactor>;
+  IntegratedCT_GICPFactor(Key source_t0_key, Key source_t1_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
+                          NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, const double* times = nullptr)
+      : key0_(source_t0_key), key1_(source_t1_key), source_(std::move(source)),
+        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {
+    check(glim_amd_ct_gicp_create(tree_->handle(), source_->handle(), times, &h_), "IntegratedCT_GICPFactor");
+  }
+  ~IntegratedCT_GICPFactor() { glim_amd_ct_gicp_destroy(h_); }
+  IntegratedCT_GICPFactor(const IntegratedCT_GICPFactor&) = delete;
+  IntegratedCT_GICPFactor& operator=(const IntegratedCT_GICPFactor&) = delete;
+
+  void set_max_correspondence_distance(double d) { check(glim_amd_ct_gicp_set_max_correspondence_distance(h_, d), "IntegratedCT_GICPFactor::set_max_correspondence_distance"); }
+  void set_num_threads(int) {}  // accepted for source compatibility (odometry_estimation_ct.cpp:161); the device has no thread knob
+  std::vector<Key> keys() const { return {key0_, key1_}; }
+  std::size_t dim() const { return 6; }
+  const glim_amd_ct_linearized& linearize(const Values& values) {
+    check(glim_amd_ct_gicp_linearize(h_, values.at(key0_).m.data(), values.at(key1_).m.data(), &linearized_), "IntegratedCT_GICPFactor::linearize");
+    return linearized_;
+  }
+  double error(const Values& values) const {
+    double e = 0.0;
+    check(glim_amd_ct_gicp_error(h_, values.at(key0_).m.data(), values.at(key1_).m.data(), &e, nullptr), "IntegratedCT_GICPFactor::error");
+    return e;
+  }
+  // T_k p_i as n x Vector4d (local: in the frame of the scan-begin pose, odometry_estimation_ct.cpp:191)
+  std::vector<double> deskewed_source_points(const Values& values, bool local = false) const {
+    std::vector<double> p4(source_->size() * 4);
+    check(glim_amd_ct_gicp_deskewed_points(h_, values.at(key0_).m.data(), values.at(key1_).m.data(), local ? 1 : 0, p4.data()),
+          "IntegratedCT_GICPFactor::deskewed_source_points");
+    return p4;
+  }
+  // the same as a device cloud carrying the source's neighbour lists (covariances re-estimated on it at :194-195)
+  PointCloudGPU::Ptr deskewed_cloud(const Values& values, bool local = false, Context ctx = nullptr) const {
+    glim_amd_cloud* h = nullptr;
+    check(glim_amd_ct_gicp_deskewed_cloud(h_, values.at(key0_).m.data(), values.at(key1_).m.data(), local ? 1 : 0, &h), "IntegratedCT_GICPFactor::deskewed_cloud");
+    return PointCloudGPU::adopt(h, ctx);
+  }
+  const glim_amd_ct_linearized& linearized() const { return linearized_; }
+
+private:
+  Key key0_, key1_;
+  PointCloudGPU::ConstPtr source_;
+  NearestNeighborSearchGPU::ConstPtr tree_;
+  glim_amd_ct_gicp_factor* h_ = nullptr;
+  glim_amd_ct_linearized linearized_{};
+};
+
 // gtsam_points::median_distance(frame, max_scan_count) and the resolution blend GLIM applies to it
 // (odometry_estimation_gpu.cpp:90-93, global_mapping.cpp:238-241): host-side, as in the reference.
 inline double median_distance(const double* points4, std::int64_t n, std::size_t max_scan_count = 256) {

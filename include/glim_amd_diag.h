@@ -43,6 +43,11 @@ int glim_amd_ctx_get_diag(glim_amd_ctx* ctx, char* buf, size_t len);
 int glim_amd_debug_deskew_table(int64_t n, const double* times, const double* T_imu_lidar12, int32_t n_imu, const double* imu_times, const double* imu_poses12,
                                 double stamp, const double* linear_vel3, const double* angular_vel3, int32_t* entry_out, double* table12_out, int32_t table_cap,
                                 int32_t* table_size);
+/* parity / debug only (host arithmetic, no device work): what glim_amd_ct_gicp_* evaluates at (X, Y) -- *num_buckets = size of the factor's
+ * time table; for the first table_cap buckets: table_out the normalised bucket times, T12_out row-major 3x4 T_k, D0_out / D1_out row-major
+ * 6x6 dT_k/dX, dT_k/dY; time_index_out (source size) the bucket of every point.  Any output may be NULL. */
+int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t* num_buckets, int32_t table_cap,
+                                 double* table_out, double* T12_out, double* D0_out, double* D1_out, int32_t* time_index_out);
 /* test hook: writes `value` into 32-bit word `word` (< 256) of the context's pinned scratch block -- what an earlier read-back (kNN counters, kept
  * points) may have left where the polled voxel-map builds keep their completion word (word 2; 4 * (levels - 1) + 2 for glim_amd_frame_create).
  * value = 0xffffffff stands for "the sequence number the context's NEXT polled build will wait for". */

@@ -107,6 +107,13 @@ vals.update({
  'UL_MAPPING': (f"{mt.get('loops_per_s_alone',0):.0f} loops/s alone, {mt.get('loops_per_s_beside_the_odometry',0):.0f} beside the odometry's resident session ({mt.get('slowdown',0):.2f}×), {mtl.get('loops_per_s_beside_the_odometry',0):.0f} beside its launch-per-call form ({mtl.get('slowdown',0):.2f}×)") if mt else 'n/a',
  'ABI_STABLE': str(n_stable), 'ABI_DIAG': f"{n_diag} entry points",
 })
+# ---- the continuous-time GICP factor (tools/ct_gicp_time.py) ----
+ct=json.load(open('profiles/ct_gicp/ct_gicp_time.json'))['sources']
+for tag,key in (('CT10','pre10k'),('CT131','raw131k')):
+    c=ct[key]
+    vals.update({tag+'_N':sp(c['source_points']), tag+'_LIN':f(c['ct_linearize']['p50_us'],1), tag+'_ERR':f(c['ct_error']['p50_us'],1),
+                 tag+'_GICP':f(c['gicp_linearize']['p50_us'],1), tag+'_RATIO':f(c['ct_over_gicp_linearize'],2), tag+'_FRAME':f(c['lm_frame_8_iterations']['p50_us']/1e3,2),
+                 tag+'_BUCKETS':str(c['buckets'])})
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
