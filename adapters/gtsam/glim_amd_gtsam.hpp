@@ -196,6 +196,13 @@ public:
                           NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
   : gtsam::NonlinearFactor(gtsam::KeyVector{source_key}),
     impl_(std::make_shared<IntegratedGICPFactor>(to_iso(fixed_target_pose), (Key)source_key, std::move(target), std::move(source), std::move(target_tree))) {}
+  // IntegratedGICPFactor_<iVox, PointCloud>: the target is a device iVox (glim_amd::IncrementalVoxelMap)
+  IntegratedGICPFactorHIP(gtsam::Key target_key, gtsam::Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{target_key, source_key}),
+    impl_(std::make_shared<IntegratedGICPFactor>((Key)target_key, (Key)source_key, std::move(target), std::move(source))) {}
+  IntegratedGICPFactorHIP(const gtsam::Pose3& fixed_target_pose, gtsam::Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{source_key}),
+    impl_(std::make_shared<IntegratedGICPFactor>(to_iso(fixed_target_pose), (Key)source_key, std::move(target), std::move(source))) {}
 
   size_t dim() const override { return 6; }
   gtsam::NonlinearFactor::shared_ptr clone() const override {
@@ -229,6 +236,12 @@ public:
   using shared_ptr = std::shared_ptr<IntegratedCT_GICPFactorHIP>;
   IntegratedCT_GICPFactorHIP(gtsam::Key source_t0_key, gtsam::Key source_t1_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
                              NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, const double* times = nullptr /* null: the source's own */)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{source_t0_key, source_t1_key}),
+    impl_(std::make_shared<IntegratedCT_GICPFactor>((Key)source_t0_key, (Key)source_t1_key, std::move(target), std::move(source), std::move(target_tree),
+                                                    times)) {}
+  // IntegratedCT_GICPFactor_<iVox, PointCloud>(X, Y, target_ivox, frame, target_ivox) -- odometry_estimation_ct.cpp:158-160
+  IntegratedCT_GICPFactorHIP(gtsam::Key source_t0_key, gtsam::Key source_t1_key, IncrementalVoxelMap::Ptr target, PointCloudGPU::ConstPtr source,
+                             IncrementalVoxelMap::Ptr target_tree = nullptr, const double* times = nullptr /* null: the source's own */)
   : gtsam::NonlinearFactor(gtsam::KeyVector{source_t0_key, source_t1_key}),
     impl_(std::make_shared<IntegratedCT_GICPFactor>((Key)source_t0_key, (Key)source_t1_key, std::move(target), std::move(source), std::move(target_tree),
                                                     times)) {}

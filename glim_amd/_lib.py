@@ -147,6 +147,21 @@ SYMBOLS = {
     "glim_amd_ct_gicp_deskewed_points": (_i, [_vp, _dp, _dp, _i32, _dp]),
     "glim_amd_ct_gicp_deskewed_cloud": (_i, [_vp, _dp, _dp, _i32, _pp]),
     "glim_amd_debug_ct_gicp_poses": (_i, [_vp, _dp, _dp, _ip, _i32, _dp, _dp, _dp, _dp, _ip]),
+    "glim_amd_ivox_create": (_i, [_vp, _d, _pp]),
+    "glim_amd_ivox_destroy": (_i, [_vp]),
+    "glim_amd_ivox_set_insertion": (_i, [_vp, _d, _i32]),
+    "glim_amd_ivox_set_lru": (_i, [_vp, _i32, _i32]),
+    "glim_amd_ivox_set_neighbor_voxel_mode": (_i, [_vp, _i32]),
+    "glim_amd_ivox_insert": (_i, [_vp, _vp, _dp]),
+    "glim_amd_ivox_info": (_i, [_vp, _ip, _lp, _ip, _dp]),
+    "glim_amd_ivox_download": (_i, [_vp, _ip, _ip, _fp, _fp]),
+    "glim_amd_ivox_voxel_points": (_i, [_vp, _dp]),
+    "glim_amd_ivox_gicp_linearize": (_i, [_vp, _vp, _dp, _d, _u32, C.POINTER(Linearized6)]),
+    "glim_amd_ivox_gicp_error": (_i, [_vp, _vp, _dp, _d, _dp, _lp]),
+    "glim_amd_ivox_gicp_correspondences": (_i, [_vp, _vp, _dp, _d, _lp]),
+    "glim_amd_ivox_ct_factor_create": (_i, [_vp, _vp, _dp, _pp]),
+    "glim_amd_debug_ivox_set_initial_capacity": (_i, [_vp, _i32]),
+    "glim_amd_debug_ivox_capacity": (_i, [_vp, _ip, _ip]),
     "glim_amd_merge_frames": (_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

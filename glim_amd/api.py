@@ -370,6 +370,92 @@ class GaussianVoxelMapGPU:
             pass
 
 
+class IncrementalVoxelMap:
+    """gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox) on the device: the incremental target model of the continuous-time
+    odometry (odometry_estimation_ct.cpp:56-63, :229-235).  A flat list of at most `max_points` points per voxel of edge `leaf`; the target
+    of IntegratedGICPFactor / IntegratedCT_GICPFactor (pass it as `target` / `target_tree`).  Semantics: include/glim_amd.h."""
+
+    def __init__(self, leaf, ctx=None):
+        self.ctx = ctx or default_context()
+        self._h = None
+        h = C.c_void_p()
+        check(lib().glim_amd_ivox_create(self.ctx._h, float(leaf), C.byref(h)), "glim_amd_ivox_create")
+        self._h = h
+        self.leaf = float(leaf)
+        self.min_dist, self.max_points = 0.1, 20
+        self.lru_horizon, self.lru_clear_cycle = 10, 10
+
+    def voxel_insertion_setting(self, min_dist=None, max_points=None):
+        """voxel_insertion_setting().min_sq_dist_in_cell = min_dist^2 / .max_num_points_in_cell = max_points (1..64); before the first insert."""
+        md = self.min_dist if min_dist is None else float(min_dist)
+        mp = self.max_points if max_points is None else int(max_points)
+        check(lib().glim_amd_ivox_set_insertion(self._h, md, mp), "glim_amd_ivox_set_insertion")
+        self.min_dist, self.max_points = md, mp
+        return self
+
+    def set_lru_horizon(self, horizon):
+        check(lib().glim_amd_ivox_set_lru(self._h, int(horizon), self.lru_clear_cycle), "glim_amd_ivox_set_lru")
+        self.lru_horizon = int(horizon)
+        return self
+
+    def set_lru_clear_cycle(self, cycle):
+        check(lib().glim_amd_ivox_set_lru(self._h, self.lru_horizon, int(cycle)), "glim_amd_ivox_set_lru")
+        self.lru_clear_cycle = int(cycle)
+        return self
+
+    def set_neighbor_voxel_mode(self, mode):
+        check(lib().glim_amd_ivox_set_neighbor_voxel_mode(self._h, int(mode)), "glim_amd_ivox_set_neighbor_voxel_mode")
+        return self
+
+    def insert(self, frame, T=None):
+        """insert(frame); T (4 x 4 or 12): the frame's pose in the map, applied to points and covariances on the device."""
+        t = None if T is None else pose12(T)
+        check(lib().glim_amd_ivox_insert(self._h, frame._h, _dp(t)), "glim_amd_ivox_insert")
+        return self
+
+    def info(self):
+        nv, npts, cnt, leaf = C.c_int32(), C.c_int64(), C.c_int32(), C.c_double()
+        check(lib().glim_amd_ivox_info(self._h, C.byref(nv), C.byref(npts), C.byref(cnt), C.byref(leaf)), "glim_amd_ivox_info")
+        return {"num_voxels": nv.value, "num_points": npts.value, "lru_counter": cnt.value, "leaf_size": leaf.value}
+
+    def download(self):
+        """(coords V x 3, counts V, points V x cap x 3, covs V x cap x 3 x 3) in slot order; places beyond a voxel's count are zero."""
+        v, cap = self.info()["num_voxels"], self.max_points
+        coords = np.zeros((v, 3), dtype=np.int32)
+        counts = np.zeros(v, dtype=np.int32)
+        points = np.zeros((v, cap, 3), dtype=np.float32)
+        covs = np.zeros((v, cap, 9), dtype=np.float32)
+        check(lib().glim_amd_ivox_download(self._h, _ip(coords), _ip(counts), _fp(points), _fp(covs)), "glim_amd_ivox_download")
+        return coords, counts, points, covs.reshape(v, cap, 3, 3)
+
+    def voxel_points(self):
+        """voxel_points(): every stored point (N x 3, FP64), voxels in slot order (odometry_estimation_ct.cpp:302)."""
+        p4 = np.zeros((self.info()["num_points"], 4))
+        check(lib().glim_amd_ivox_voxel_points(self._h, _dp(p4)), "glim_amd_ivox_voxel_points")
+        return p4[:, :3].copy()
+
+    def debug_set_initial_capacity(self, slots):
+        check(lib().glim_amd_debug_ivox_set_initial_capacity(self._h, int(slots)), "glim_amd_debug_ivox_set_initial_capacity")
+        return self
+
+    def debug_capacity(self):
+        a, b = C.c_int32(), C.c_int32()
+        check(lib().glim_amd_debug_ivox_capacity(self._h, C.byref(a), C.byref(b)), "glim_amd_debug_ivox_capacity")
+        return {"slots": a.value, "table": b.value}
+
+    def close(self):
+        """Destroys the map.  Refused (GlimAmdError, the map stays usable) while a continuous-time factor built on it is alive."""
+        if self._h:
+            check(lib().glim_amd_ivox_destroy(self._h), "glim_amd_ivox_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def frame_create(points4, covs16, normals4, resolutions, ctx=None):
     """glim_amd_frame_create: PointCloudGPU::clone + one GaussianVoxelMapGPU per resolution as ONE submission with one synchronise (create_frame of
     the GPU odometry).  Arrays in the reference's layout (n x Vector4d, n x column-major Matrix4d, n x Vector4d).  Returns (cloud, [maps])."""
@@ -853,7 +939,8 @@ def preprocess_params(**kw):
 class IntegratedGICPFactor:
     """gtsam_points::IntegratedGICPFactor on the device (sub_mapping.cpp:202, global_mapping.cpp:400, global_mapping_pose_graph.cpp:393).
     Unary form: IntegratedGICPFactor(fixed_target_pose, source_key, target, source); binary: (target_key, source_key, target, source).
-    `target` / `source` are PointCloudGPU with covariances; the target's search index is built once here (or passed as `target_tree`)."""
+    `target` / `source` are PointCloudGPU with covariances; the target's search index is built once here (or passed as `target_tree`).
+    An IncrementalVoxelMap as `target_frame` (or `target_tree`) gives IntegratedGICPFactor_<iVox, PointCloud>: the map's own bounded search."""
 
     def __init__(self, target, source_key, target_frame, source_frame, target_tree=None, max_correspondence_distance=1.0):
         self.binary = np.isscalar(target)
@@ -863,8 +950,11 @@ class IntegratedGICPFactor:
         self.target_frame, self.source_frame = target_frame, source_frame
         self.max_correspondence_distance = float(max_correspondence_distance)
         self._inliers = 0
-        self._own_tree = target_tree is None
-        if target_tree is None:
+        self._ivox = target_tree if isinstance(target_tree, IncrementalVoxelMap) else (target_frame if isinstance(target_frame, IncrementalVoxelMap) else None)
+        self._own_tree = target_tree is None and self._ivox is None
+        if self._ivox is not None:
+            target_tree = self._ivox
+        elif target_tree is None:
             h = C.c_void_p()
             check(lib().glim_amd_nn_index_create(target_frame._h, self.max_correspondence_distance, C.byref(h)), "glim_amd_nn_index_create")
             target_tree = h
@@ -881,8 +971,12 @@ class IntegratedGICPFactor:
     def linearize(self, values):
         L = Linearized6()
         T = pose12(self.calc_delta(values))
-        check(lib().glim_amd_gicp_linearize(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance,
-                                            FACTOR_BINARY if self.binary else 0, C.byref(L)), "glim_amd_gicp_linearize")
+        if self._ivox is not None:
+            check(lib().glim_amd_ivox_gicp_linearize(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance,
+                                                     FACTOR_BINARY if self.binary else 0, C.byref(L)), "glim_amd_ivox_gicp_linearize")
+        else:
+            check(lib().glim_amd_gicp_linearize(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance,
+                                                FACTOR_BINARY if self.binary else 0, C.byref(L)), "glim_amd_gicp_linearize")
         out = _lin_to_dict(L)
         self._inliers = out["num_inliers"]
         return out
@@ -890,8 +984,12 @@ class IntegratedGICPFactor:
     def error(self, values):
         e, n = C.c_double(), C.c_int64()
         T = pose12(self.calc_delta(values))
-        check(lib().glim_amd_gicp_error(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance, C.byref(e), C.byref(n)),
-              "glim_amd_gicp_error")
+        if self._ivox is not None:
+            check(lib().glim_amd_ivox_gicp_error(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance, C.byref(e),
+                                                 C.byref(n)), "glim_amd_ivox_gicp_error")
+        else:
+            check(lib().glim_amd_gicp_error(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance, C.byref(e),
+                                            C.byref(n)), "glim_amd_gicp_error")
         self._inliers = n.value
         return e.value
 
@@ -899,8 +997,14 @@ class IntegratedGICPFactor:
         return self._inliers / max(1, self.source_frame.size())
 
     def correspondences(self, values):
-        out = np.zeros(self.source_frame.size(), dtype=np.int32)
         T = pose12(self.calc_delta(values))
+        if self._ivox is not None:
+            # slot * max_points + place in the cell, or -1 (int64)
+            out = np.zeros(self.source_frame.size(), dtype=np.int64)
+            check(lib().glim_amd_ivox_gicp_correspondences(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance,
+                                                           out.ctypes.data_as(C.POINTER(C.c_int64))), "glim_amd_ivox_gicp_correspondences")
+            return out
+        out = np.zeros(self.source_frame.size(), dtype=np.int32)
         check(lib().glim_amd_gicp_correspondences(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance, _ip(out)),
               "glim_amd_gicp_correspondences")
         return out
@@ -922,21 +1026,29 @@ class IntegratedCT_GICPFactor:
     (odometry_estimation_ct.cpp:158-183).  One scan between key0 (X, the pose at scan begin) and key1 (Y, at scan end); every point moves
     with the pose of its time bucket, T_k = X Exp(t_k Log(X^-1 Y)).  `target` / `source`: PointCloudGPU with covariances; the source also
     needs per-point times (`times`, or the ones its preprocessing kept).  linearize() returns the HessianFactor ingredients
-    {num_inliers, error, H_00, H_01, H_11, b_0, b_1}; error() reuses the correspondences and M of the last linearize()."""
+    {num_inliers, error, H_00, H_01, H_11, b_0, b_1}; error() reuses the correspondences and M of the last linearize().
+    An IncrementalVoxelMap as `target` (or `target_tree`) gives the frame-to-model form of :158-162: the factor reads the map as it is at
+    each call, correspondences() returns slot * max_points + place, and the map cannot be closed before the factor."""
 
     def __init__(self, key0, key1, target, source, target_tree=None, max_correspondence_distance=1.0, times=None):
         self.keys = (int(key0), int(key1))
         self.target, self.source = target, source
-        self._own_tree = target_tree is None
-        if target_tree is None:
+        self._h = None
+        self._ivox = target_tree if isinstance(target_tree, IncrementalVoxelMap) else (target if isinstance(target, IncrementalVoxelMap) else None)
+        self._own_tree = target_tree is None and self._ivox is None
+        if self._ivox is not None:
+            target_tree = self._ivox
+        elif target_tree is None:
             h = C.c_void_p()
             check(lib().glim_amd_nn_index_create(target._h, float(max_correspondence_distance), C.byref(h)), "glim_amd_nn_index_create")
             target_tree = h
         self.target_tree = target_tree
-        self._h = None
         t = None if times is None else np.ascontiguousarray(times, dtype=np.float64).reshape(source.size())
         h = C.c_void_p()
-        check(lib().glim_amd_ct_gicp_create(self.target_tree, source._h, _dp(t), C.byref(h)), "glim_amd_ct_gicp_create")
+        if self._ivox is not None:
+            check(lib().glim_amd_ivox_ct_factor_create(self._ivox._h, source._h, _dp(t), C.byref(h)), "glim_amd_ivox_ct_factor_create")
+        else:
+            check(lib().glim_amd_ct_gicp_create(self.target_tree, source._h, _dp(t), C.byref(h)), "glim_amd_ct_gicp_create")
         self._h = h
         self.set_max_correspondence_distance(max_correspondence_distance)
 

@@ -21,6 +21,10 @@
 // The continuous-time factor (gtsam_points::IntegratedCT_GICPFactor with a point-cloud target, odometry_estimation_ct.cpp:158-195) runs the same
 // search and per-point algebra with one pose per time bucket, T_k = X Exp(t_k Log(X^-1 Y)); its chain rule to the keys X and Y is applied per
 // bucket in FP64 (ct_gicp_kernel, ct_bucket_kernel, ct_sum_kernel below; semantics in include/glim_amd.h, layout in DESIGN.md 4.6).
+//
+// Both factors also run over a device iVox (gtsam_points::IncrementalVoxelMap<FlatContainer>, ivox.hpp: the container and its insert): the
+// factor kernels take the target kind as a template parameter -- IndexSearch = the exact search above, IvoxSearch = the map's bounded search of
+// the voxels of its neighbour mode -- and share everything behind the correspondence.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -226,6 +230,75 @@ __device__ __forceinline__ int nearest(const GicpArgs& a, double qx, double qy, 
   return (best >= 0 && best_d <= a.max_sq) ? best : -1;
 }
 
+// the target kind of the factor kernels: where a transformed source point finds its correspondence.  IndexSearch is the exact search above.
+struct IndexSearch {
+  __device__ __forceinline__ int find(const GicpArgs& a, double qx, double qy, double qz, double& best_d) const { return nearest(a, qx, qy, qz, best_d); }
+};
+
+// Neighbour offsets of the incremental voxel map's search (gtsam_points::IncrementalVoxelMap::set_neighbor_voxel_mode): modes 1, 7 and 19 are
+// prefixes of this list (centre; the six faces +x -x +y -y +z -z; the twelve edges); mode 27 is the full cube, z outermost and x innermost.
+__constant__ int c_ivox_offsets[19][3] = {{0, 0, 0},  {1, 0, 0},  {-1, 0, 0}, {0, 1, 0},  {0, -1, 0}, {0, 0, 1},  {0, 0, -1},
+                                          {1, 1, 0},  {1, -1, 0}, {-1, 1, 0}, {-1, -1, 0}, {1, 0, 1},  {1, 0, -1}, {-1, 0, 1},
+                                          {-1, 0, -1}, {0, 1, 1},  {0, 1, -1}, {0, -1, 1}, {0, -1, -1}};
+
+// IvoxSearch: the target is a device iVox (ivox.hpp).  a.sorted / a.tA / a.tB are the map's point and covariance arrays, `cap` entries per
+// slot; position = slot * cap + place in the cell, which is also what the point's w holds.  NOT an exact nearest-neighbour search: only the
+// cells of the neighbour mode around q's own cell are visited (upstream's behaviour).  Smallest FP64 (dx^2 + dy^2) + dz^2; a later candidate
+// replaces the best only when strictly smaller; valid iff d^2 <= max_correspondence_distance^2.
+struct IvoxSearch {
+  const u64* keys;    // open-addressing table: voxel key per entry (EMPTY_KEY when free)
+  const int* slots;   // slot of the entry's voxel
+  const int* counts;  // points per slot
+  u32 mask;
+  int cap;            // max_num_points_in_cell
+  int nnb;            // 1 | 7 | 19 | 27
+  double inv_leaf;
+  __device__ __forceinline__ int find(const GicpArgs& a, double qx, double qy, double qz, double& best_d) const {
+    best_d = __longlong_as_double(0x7ff0000000000000ll);
+    const double tx = qx * inv_leaf, ty = qy * inv_leaf, tz = qz * inv_leaf;
+    if (!(tx >= -1048576.0 && tx < 1048576.0 && ty >= -1048576.0 && ty < 1048576.0 && tz >= -1048576.0 && tz < 1048576.0)) return -1;
+    const int cx = fast_floor_d(tx), cy = fast_floor_d(ty), cz = fast_floor_d(tz);
+    int best = -1;
+    for (int k = 0; k < nnb; k++) {
+      int dx, dy, dz;
+      if (nnb == 27) {
+        dx = k % 3 - 1;
+        dy = (k / 3) % 3 - 1;
+        dz = k / 9 - 1;
+      } else {
+        dx = c_ivox_offsets[k][0];
+        dy = c_ivox_offsets[k][1];
+        dz = c_ivox_offsets[k][2];
+      }
+      const u32 ux = (u32)(cx + dx + KEY_OFFSET), uy = (u32)(cy + dy + KEY_OFFSET), uz = (u32)(cz + dz + KEY_OFFSET);
+      if ((ux | uy | uz) >> KEY_BITS) continue;
+      const u64 key = (u64)ux | ((u64)uy << 21) | ((u64)uz << 42);
+      u32 s = cell_hash(key) & mask;
+      int slot = -1;
+      for (;;) {
+        const u64 kk = keys[s];
+        if (kk == key) {
+          slot = slots[s];
+          break;
+        }
+        if (kk == EMPTY_KEY) break;
+        s = (s + 1) & mask;
+      }
+      if (slot < 0) continue;
+      const int first = slot * cap, last = first + counts[slot];
+      for (int j = first; j < last; j++) {
+        const float4 c = a.sorted[j];
+        const double d = sqdist_nc(qx, qy, qz, (double)c.x, (double)c.y, (double)c.z);
+        if (d < best_d) {
+          best_d = d;
+          best = j;
+        }
+      }
+    }
+    return (best >= 0 && best_d <= a.max_sq) ? best : -1;
+  }
+};
+
 // per-point GICP algebra in the source frame (gicp_kernel and ct_gicp_kernel): adds the point's terms to the 28 accumulators and returns the
 // source-frame A = (R^T C_B R + C_A)^-1 (a00 a01 a02 a11 a12 a22)
 template <bool LINEARIZE>
@@ -285,8 +358,8 @@ __device__ __forceinline__ void gicp_point(float (&acc)[NACC], float R00, float 
   A[0] = A00; A[1] = A01; A[2] = A02; A[3] = A11; A[4] = A12; A[5] = A22;
 }
 
-template <bool LINEARIZE>
-__global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __restrict__ partials, int32_t* __restrict__ corr) {
+template <bool LINEARIZE, class NN>
+__global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __restrict__ partials, int32_t* __restrict__ corr, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
   const double* T = a.T;
   const float R00 = (float)T[0], R01 = (float)T[1], R02 = (float)T[2];
@@ -304,7 +377,7 @@ __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __
     double qx, qy, qz;
     transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
     double best_d;
-    const int j = nearest(a, qx, qy, qz, best_d);
+    const int j = nn.find(a, qx, qy, qz, best_d);
     if (corr) corr[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
     if (j < 0) continue;
     inliers++;
@@ -381,8 +454,8 @@ struct CtArgs {
   int32_t* corr_out;     // original target index or -1 per source point, or null
 };
 
-template <bool LINEARIZE>
-__global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials) {
+template <bool LINEARIZE, class NN>
+__global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
   const int4 blk = c.blocks[blockIdx.x];
   const double* T = c.poses + (size_t)blk.x * CT_POSE_STRIDE;
@@ -398,7 +471,7 @@ __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const 
     double qx, qy, qz;
     transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
     double best_d;
-    const int j = nearest(a, qx, qy, qz, best_d);
+    const int j = nn.find(a, qx, qy, qz, best_d);
     if (c.corr_out) c.corr_out[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
     if (c.keep_corr) c.keep_corr[i] = j;
     if (j < 0) continue;
@@ -652,8 +725,8 @@ int run_gicp(const glim_amd_nn_index* ix, const glim_amd_cloud* source, const do
   GA_HIP(pool_malloc(&partials.p, (size_t)nb * PARTIAL_STRIDE * sizeof(float)));
   GA_HIP(pool_malloc(&compact.p, COMPACT * sizeof(double)));
   if (corr_host) GA_HIP(pool_malloc(&corr.p, (size_t)n * sizeof(int32_t)));
-  if (linearize) gicp_kernel<true><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>());
-  else gicp_kernel<false><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>());
+  if (linearize) gicp_kernel<true, IndexSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), IndexSearch{});
+  else gicp_kernel<false, IndexSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), IndexSearch{});
   gicp_finalize_kernel<<<1, 256, 0, st>>>(partials.as<float>(), nb, linearize ? 1 : 0, compact.as<double>());
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(compact_host, compact.p, COMPACT * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -845,9 +918,13 @@ void se3_inverse(const double* A, double* B) {
 
 }  // namespace
 
+#include "ivox.hpp"  // the device iVox (container, insert, the rigid GICP entry points over it); uses the helpers above
+
 struct glim_amd_ct_gicp_factor {
   CtxRef ctx;
-  const glim_amd_nn_index* ix = nullptr;  // not owned
+  const glim_amd_nn_index* ix = nullptr;  // not owned; null when the target is a device iVox
+  glim_amd_ivox* iv = nullptr;            // not owned (counted in its live_factors: the map cannot be destroyed under the factor)
+  uint64_t kept_gen = 0;                  // the map's generation the kept correspondences were found in
   const glim_amd_cloud* src = nullptr;    // not owned
   int n = 0;
   double max_dist = 1.0;
@@ -872,6 +949,7 @@ namespace {
 
 // rings of the index's walk that cover `d`, or -1 when the walk is bounded below that (the rule of run_gicp)
 int ct_rings(const glim_amd_nn_index* ix, double d) {
+  if (!ix) return 0;  // a device iVox: the search is bounded by the neighbour mode, any distance is accepted
   const double rings = std::ceil(d / ix->h) + 1.0;
   return rings <= (double)GICP_MAX_RING ? (int)rings : -1;
 }
@@ -907,16 +985,17 @@ void ct_poses(const std::vector<double>& table, const double* X, const double* Y
 
 GicpArgs ct_args(const glim_amd_ct_gicp_factor* f, int max_ring) {
   GicpArgs a{};
-  const glim_amd_nn_index* ix = f->ix;
-  a.sorted = ix->sorted;
-  a.tA = ix->covA;
-  a.tB = ix->covB;
-  a.keys = ix->keys;
-  a.runs = ix->runs;
-  a.mask = ix->mask;
-  a.nt = ix->n;
-  a.h = ix->h;
-  a.inv_h = 1.0 / ix->h;
+  if (const glim_amd_nn_index* ix = f->ix) {
+    a.sorted = ix->sorted;
+    a.tA = ix->covA;
+    a.tB = ix->covB;
+    a.keys = ix->keys;
+    a.runs = ix->runs;
+    a.mask = ix->mask;
+    a.nt = ix->n;
+    a.h = ix->h;
+    a.inv_h = 1.0 / ix->h;
+  }
   a.pts = f->src->pts;
   a.covA = f->src->covA;
   a.covB = f->src->covB;
@@ -932,20 +1011,29 @@ enum { CT_LINEARIZE = 0, CT_ERROR = 1, CT_CORR = 2 };
 // one synchronous evaluation; caller has validated the arguments.  out: CT_ROW doubles (CT_LINEARIZE) or the 29-double compact record (CT_ERROR)
 int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mode, double* out, int32_t* corr_host) {
   if (!f->src->has_covs) return GLIM_AMD_ERR_STATE;
-  if (!f->ix->covA) return GLIM_AMD_ERR_STATE;
+  if (f->ix && !f->ix->covA) return GLIM_AMD_ERR_STATE;
   const int max_ring = ct_rings(f->ix, f->max_dist);
   if (max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
   glim_amd_ctx* ctx = f->ctx;
   std::lock_guard<std::mutex> lock(ctx->mu);
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
-  if (f->n == 0 || f->ix->n == 0) {
+  if (f->n == 0 || (f->ix ? f->ix->n == 0 : f->iv->num_slots == 0)) {
     if (corr_host)
       for (int i = 0; i < f->n; i++) corr_host[i] = -1;
     return GLIM_AMD_OK;
   }
   ct_poses(f->table, X, Y, f->h_poses);
-  const GicpArgs a = ct_args(f, max_ring);
+  GicpArgs a = ct_args(f, max_ring);
+  IvoxSearch nn{};
+  if (f->iv) {
+    // the map as it is now; correspondences kept before an insert (or a change of the neighbour mode) are positions in a map that is gone
+    const GicpArgs src = a;
+    ivox_target_args(f->iv, &a, &nn);
+    a.pts = src.pts; a.covA = src.covA; a.covB = src.covB; a.n = src.n; a.ppt = src.ppt; a.max_sq = src.max_sq;
+    if (f->kept_gen != f->iv->generation) f->kept = false;
+    f->kept_gen = f->iv->generation;
+  }
   CtArgs c{};
   c.blocks = f->d_blocks;
   c.poses = f->d_poses;
@@ -957,7 +1045,8 @@ int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mod
     c.keep_m0 = f->keep_m0;
     c.keep_m1 = f->keep_m1;
     f->kept = false;
-    ct_gicp_kernel<true><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
+    if (f->iv) ct_gicp_kernel<true, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
+    else ct_gicp_kernel<true, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, IndexSearch{});
     ct_bucket_kernel<<<f->nbk, 64, 0, st>>>(f->d_partials, f->d_bucket_first, f->d_poses, f->d_rows);
     ct_sum_kernel<<<1, 768, 0, st>>>(f->d_rows, f->nbk, f->d_out);
     GA_HIP(hipGetLastError());
@@ -969,7 +1058,8 @@ int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mod
       k.keep_corr = f->keep_corr;
       k.keep_m0 = f->keep_m0;
       k.keep_m1 = f->keep_m1;
-      ct_gicp_kernel<false><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials);
+      if (f->iv) ct_gicp_kernel<false, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials, nn);
+      else ct_gicp_kernel<false, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials, IndexSearch{});
     }
     c.keep_corr = f->keep_corr;
     c.keep_m0 = f->keep_m0;
@@ -982,7 +1072,8 @@ int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mod
   } else {
     GA_HIP(pool_malloc(&corr.p, (size_t)f->n * sizeof(int32_t)));
     c.corr_out = corr.as<int32_t>();
-    ct_gicp_kernel<false><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
+    if (f->iv) ct_gicp_kernel<false, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
+    else ct_gicp_kernel<false, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, IndexSearch{});
     GA_HIP(hipGetLastError());
     GA_HIP(hipMemcpyAsync(corr_host, corr.p, (size_t)f->n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GA_HIP(hipStreamSynchronize(st));
@@ -1145,23 +1236,32 @@ int glim_amd_ct_gicp_destroy(glim_amd_ct_gicp_factor* f) {
   for (void* p : dev)
     if (p) (void)pool_free(p);
   if (f->h_poses) (void)pinned_free(f->h_poses);
+  if (f->iv) f->iv->live_factors--;
   delete f;
   return GLIM_AMD_OK;
 }
 
-int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
-  if (!target || !source || !out) return GLIM_AMD_ERR_INVALID;
+}  // extern "C"
+
+namespace {
+// the factor over either target kind: exactly one of `target` / `map` is set
+int ct_factor_create(const glim_amd_nn_index* target, glim_amd_ivox* map, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
+  if ((!target && !map) || !source || !out) return GLIM_AMD_ERR_INVALID;
   *out = nullptr;
-  if (source->ctx->device != target->ctx->device) return GLIM_AMD_ERR_INVALID;
+  glim_amd_ctx* ctx = target ? static_cast<glim_amd_ctx*>(target->ctx) : static_cast<glim_amd_ctx*>(map->ctx);
+  if (source->ctx->device != ctx->device) return GLIM_AMD_ERR_INVALID;
   if (source->n > (int64_t)(1 << 28)) return GLIM_AMD_ERR_INVALID;
   const int n = (int)source->n;
   if (!times && (int64_t)source->h_times.size() != source->n) return GLIM_AMD_ERR_STATE;  // no per-point times
   if (!source->has_covs) return GLIM_AMD_ERR_STATE;
   const double* t = times ? times : source->h_times.data();
   std::unique_ptr<glim_amd_ct_gicp_factor, int (*)(glim_amd_ct_gicp_factor*)> f(new glim_amd_ct_gicp_factor(), glim_amd_ct_gicp_destroy);
-  glim_amd_ctx* ctx = target->ctx;
   f->ctx = ctx;
   f->ix = target;
+  if (map) {
+    f->iv = map;
+    map->live_factors++;
+  }
   f->src = source;
   f->n = n;
   // the time table (IntegratedCT_ICPFactor's constructor): a new bucket when the time moves on by more than 1e-3, entries / the last one
@@ -1215,6 +1315,19 @@ int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_clou
   }
   *out = f.release();
   return GLIM_AMD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
+  if (!target) return GLIM_AMD_ERR_INVALID;
+  return ct_factor_create(target, nullptr, source, times, out);
+}
+
+int glim_amd_ivox_ct_factor_create(glim_amd_ivox* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
+  if (!target) return GLIM_AMD_ERR_INVALID;
+  return ct_factor_create(nullptr, target, source, times, out);
 }
 
 int glim_amd_ct_gicp_set_max_correspondence_distance(glim_amd_ct_gicp_factor* f, double d) {

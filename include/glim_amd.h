@@ -15,7 +15,7 @@
  *     covariances (16 doubles, column-major, zero last row/col)   include/glim/preprocess/preprocessed_frame.hpp:31,
  *     src/glim/common/cloud_covariance_estimation.cpp:96.  Host arrays are borrowed only for the duration of a call.
  *   - all device work of a context runs on its HIP stream(s); calls are synchronous unless named *_async.
- *   - handles are owned by the caller; destroy children (clouds, voxel maps, factor sets, search indices) before their context:
+ *   - handles are owned by the caller; destroy children (clouds, voxel maps, iVox maps, factor sets, search indices) before their context:
  *     glim_amd_ctx_destroy refuses (GLIM_AMD_ERR_STATE) while any child is alive.
  */
 #ifndef GLIM_AMD_H
@@ -229,6 +229,62 @@ int glim_amd_ct_gicp_deskewed_points(glim_amd_ct_gicp_factor* factor, const doub
 /* the same points as a new device cloud (FP64 kept beside the FP32 image) carrying the source's neighbour lists: what :194-195 hands to
  * CloudCovarianceEstimation::estimate -- glim_amd_cloud_estimate_covariances runs on it directly. */
 int glim_amd_ct_gicp_deskewed_cloud(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t local, glim_amd_cloud** out);
+
+/* ---- device iVox: gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox), the incremental target model of the LiDAR-only
+ * continuous-time odometry (src/glim/odometry/odometry_estimation_ct.cpp:56-63 creates it, :158-162 builds the frame's factor on it, :229-235
+ * inserts every finished frame); also the target of the "GICP" branch of odometry_estimation_cpu.cpp, of loose_initial_state_estimation.cpp and
+ * of the manual loop-close tool.  gtsam_points is not under the reference tree: the semantics below are upstream recall (DESIGN.md lists the
+ * guesses).
+ *   voxel of a point: floor(p * (1 / leaf)) per axis, FP64, on the STORED point.
+ *   insert(cloud): points in input order.  A point whose voxel does not exist creates it (new voxels are appended in first-seen order); the
+ *     voxel's lru becomes the current counter; FlatContainer::add drops the point when the cell already holds max_points_in_cell points, or
+ *     when a point already in the cell -- one accepted earlier in the same call included -- is closer than min_dist_in_cell (squared distance
+ *     < min_dist^2, strict; FP64 (dx^2 + dy^2) + dz^2 with separate roundings); otherwise the point is appended with its covariance.  After
+ *     all points: if (++lru_counter % lru_clear_cycle == 0) every voxel with lru + lru_horizon < lru_counter is removed, survivors keep
+ *     their order.
+ *   nearest neighbour of q: from the voxel c of q visit c + offset for the offsets of the neighbour mode -- 1: {0}; 7: the centre, then +x -x
+ *     +y -y +z -z; 19: those, then the twelve edges (+-1,+-1,0), (+-1,0,+-1), (0,+-1,+-1), first sign slower; 27: the full cube, z outermost
+ *     and x innermost -- and keep the smallest FP64 squared distance (same form); a later candidate replaces the best only when strictly
+ *     smaller; valid iff d^2 <= max_correspondence_distance^2.  NOT an exact search: points outside the visited voxels are never seen.
+ *   defaults: min_dist_in_cell 0.1, max_points_in_cell 20, lru_horizon 10, lru_clear_cycle 10, neighbour mode 7.
+ * Storage (this library's choice): FP32 points and six-float covariances, like every device cloud.  Insert with a pose computes
+ * x' = ((R00 x + R01 y) + R02 z) + tx in FP64 with separate roundings (likewise y', z'), rounds to FP32, and C' = R C R^T in FP32; the voxel
+ * and the min_dist test use the stored value.  Normals are not stored.  Non-finite points and points outside the +-2^20-voxel key range are
+ * skipped.  Every call returns with the map's work finished: `num_voxels` / `num_points` are on the host and any later reader sees the map.
+ * The map is a child of its context; a map with a live continuous-time factor on it refuses to be destroyed (GLIM_AMD_ERR_STATE). */
+typedef struct glim_amd_ivox glim_amd_ivox;
+int glim_amd_ivox_create(glim_amd_ctx* ctx, double leaf_size, glim_amd_ivox** out);
+int glim_amd_ivox_destroy(glim_amd_ivox* ivox);
+/* voxel_insertion_setting(): max_points_in_cell in 1..64 (a cell never holds more than one wavefront's lanes).  GLIM_AMD_ERR_STATE once the
+ * map has been inserted into. */
+int glim_amd_ivox_set_insertion(glim_amd_ivox* ivox, double min_dist_in_cell, int32_t max_points_in_cell);
+/* set_lru_horizon / set_lru_clear_cycle (horizon >= 0, clear_cycle >= 1) */
+int glim_amd_ivox_set_lru(glim_amd_ivox* ivox, int32_t horizon, int32_t clear_cycle);
+/* set_neighbor_voxel_mode: 1 | 7 | 19 | 27 */
+int glim_amd_ivox_set_neighbor_voxel_mode(glim_amd_ivox* ivox, int32_t mode);
+/* insert(*frame) with the host transform loop of odometry_estimation_ct.cpp:230-234 fused in: T_world_cloud12 moves points and covariances
+ * (NULL = identity: values are stored as they are).  The cloud needs covariances (GLIM_AMD_ERR_STATE). */
+int glim_amd_ivox_insert(glim_amd_ivox* ivox, const glim_amd_cloud* cloud, const double* T_world_cloud12);
+int glim_amd_ivox_info(const glim_amd_ivox* ivox, int32_t* num_voxels, int64_t* num_points, int32_t* lru_counter, double* leaf_size);
+/* copy back in slot (= upstream's voxel) order; cap = max_points_in_cell.  coords V x 3, counts V, points V x cap x 3, covs V x cap x 9
+ * (places beyond a voxel's count are zero).  Any may be NULL. */
+int glim_amd_ivox_download(const glim_amd_ivox* ivox, int32_t* coords, int32_t* counts, float* points, float* covs);
+/* voxel_points() (odometry_estimation_ct.cpp:302): num_points x Vector4d, voxels in slot order, points in cell order. */
+int glim_amd_ivox_voxel_points(const glim_amd_ivox* ivox, double* points4);
+/* IntegratedGICPFactor_<iVox, PointCloud>: the glim_amd_gicp_* trio over the map.  Any finite max_correspondence_distance is accepted (the
+ * search is bounded by the neighbour mode, not by the radius).  correspondences: slot * max_points_in_cell + place in the cell, or -1. */
+int glim_amd_ivox_gicp_linearize(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
+                                 double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out);
+int glim_amd_ivox_gicp_error(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
+                             double max_correspondence_distance, double* error, int64_t* num_inliers);
+int glim_amd_ivox_gicp_correspondences(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
+                                       double max_correspondence_distance, int64_t* correspondences);
+/* IntegratedCT_GICPFactor_<iVox, PointCloud>(X, Y, target_ivox, frame, target_ivox) -- odometry_estimation_ct.cpp:158-162.  The handle is the
+ * continuous-time factor's: linearize, error, set_max_correspondence_distance (any distance), deskewed_points, deskewed_cloud and destroy
+ * above work on it unchanged, and its correspondences call writes slot * max_points_in_cell + place (always below 2^31: the map refuses to
+ * grow beyond that) or -1.  The factor reads the map as it is at each call; an insert after linearize invalidates the kept correspondences
+ * and M (error then recomputes them first).  The map must outlive the factor: glim_amd_ivox_destroy refuses while the factor lives. */
+int glim_amd_ivox_ct_factor_create(glim_amd_ivox* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out);
 
 /* ---- submap merge on device: gtsam_points::merge_frames(poses, frames, downsample_resolution, target_num_points)
  * as called at src/glim/mapping/sub_mapping.cpp:480-497 (the reference's own GPU variant, merge_frames_gpu, is commented out at :491).

@@ -390,6 +390,74 @@ private:
   glim_amd_nn_index* h_ = nullptr;
 };
 
+// gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox): the incremental target model of the continuous-time odometry
+// (odometry_estimation_ct.cpp:56-63, :229-235), on the device.  Upstream's method names; semantics in glim_amd.h ("device iVox").
+class IncrementalVoxelMap {
+public:
+  using Ptr = std::shared_ptr<IncrementalVoxelMap>;
+  using ConstPtr = std::shared_ptr<const IncrementalVoxelMap>;
+  struct InsertionSetting {  // FlatContainer::Setting, applied with set_voxel_insertion_setting before the first insert
+    double min_dist_in_cell = 0.1;
+    int max_num_points_in_cell = 20;
+  };
+  explicit IncrementalVoxelMap(double leaf_size, Context ctx = nullptr) : ctx_(ctx ? ctx : StreamTempBufferRoundRobin::default_instance()) {
+    check(glim_amd_ivox_create(ctx_->context(), leaf_size, &h_), "IncrementalVoxelMap");
+  }
+  ~IncrementalVoxelMap() { glim_amd_ivox_destroy(h_); }
+  IncrementalVoxelMap(const IncrementalVoxelMap&) = delete;
+  IncrementalVoxelMap& operator=(const IncrementalVoxelMap&) = delete;
+  // voxel_insertion_setting().set_min_dist_in_cell(d) / .max_num_points_in_cell (odometry_estimation_ct.cpp:58)
+  void set_voxel_insertion_setting(const InsertionSetting& s) {
+    check(glim_amd_ivox_set_insertion(h_, s.min_dist_in_cell, s.max_num_points_in_cell), "IncrementalVoxelMap::set_voxel_insertion_setting");
+    setting_ = s;
+  }
+  const InsertionSetting& voxel_insertion_setting() const { return setting_; }
+  void set_lru_horizon(int horizon) {  // :59
+    check(glim_amd_ivox_set_lru(h_, horizon, lru_clear_cycle_), "IncrementalVoxelMap::set_lru_horizon");
+    lru_horizon_ = horizon;
+  }
+  void set_lru_clear_cycle(int cycle) {
+    check(glim_amd_ivox_set_lru(h_, lru_horizon_, cycle), "IncrementalVoxelMap::set_lru_clear_cycle");
+    lru_clear_cycle_ = cycle;
+  }
+  void set_neighbor_voxel_mode(int mode) { check(glim_amd_ivox_set_neighbor_voxel_mode(h_, mode), "IncrementalVoxelMap::set_neighbor_voxel_mode"); }  // :60
+  // insert(*frame) (:235); with a pose, the host transform loop of :230-234 runs on the device as part of the call
+  void insert(const PointCloudGPU& frame) { check(glim_amd_ivox_insert(h_, frame.handle(), nullptr), "IncrementalVoxelMap::insert"); }
+  void insert(const PointCloudGPU& frame, const Isometry3d& T_world_frame) {
+    check(glim_amd_ivox_insert(h_, frame.handle(), T_world_frame.m.data()), "IncrementalVoxelMap::insert");
+  }
+  std::size_t num_voxels() const {
+    std::int32_t v = 0;
+    glim_amd_ivox_info(h_, &v, nullptr, nullptr, nullptr);
+    return (std::size_t)v;
+  }
+  std::size_t size() const {
+    std::int64_t n = 0;
+    glim_amd_ivox_info(h_, nullptr, &n, nullptr, nullptr);
+    return (std::size_t)n;
+  }
+  double leaf_size() const {
+    double l = 0.0;
+    glim_amd_ivox_info(h_, nullptr, nullptr, nullptr, &l);
+    return l;
+  }
+  // voxel_points() (:302): every stored point as n x Vector4d
+  std::vector<double> voxel_points() const {
+    std::vector<double> p4(size() * 4);
+    check(glim_amd_ivox_voxel_points(h_, p4.data()), "IncrementalVoxelMap::voxel_points");
+    return p4;
+  }
+  glim_amd_ivox* handle() const { return h_; }
+  const Context& context() const { return ctx_; }
+
+private:
+  Context ctx_;
+  glim_amd_ivox* h_ = nullptr;
+  InsertionSetting setting_;
+  int lru_horizon_ = 10, lru_clear_cycle_ = 10;
+};
+using iVox = IncrementalVoxelMap;
+
 // gtsam_points::IntegratedGICPFactor (sub_mapping.cpp:202, global_mapping.cpp:400-402, global_mapping_pose_graph.cpp:393-405)
 class IntegratedGICPFactor {
 public:
@@ -404,6 +472,13 @@ public:
                        NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
       : is_binary_(false), target_key_(0), source_key_(source_key), fixed_target_pose_(fixed_target_pose), source_(std::move(source)),
         tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {}
+  // IntegratedGICPFactor_<iVox, PointCloud>: the target is a device iVox, searched with its own neighbour mode (the "GICP" registration of
+  // odometry_estimation_cpu.cpp, loose_initial_state_estimation.cpp)
+  IntegratedGICPFactor(Key target_key, Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
+      : is_binary_(true), target_key_(target_key), source_key_(source_key), source_(std::move(source)), ivox_(std::move(target)) {}
+  IntegratedGICPFactor(const Isometry3d& fixed_target_pose, Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
+      : is_binary_(false), target_key_(0), source_key_(source_key), fixed_target_pose_(fixed_target_pose), source_(std::move(source)),
+        ivox_(std::move(target)) {}
 
   void set_max_correspondence_distance(double d) { max_correspondence_distance_ = d; }
   void set_num_threads(int) {}  // accepted for source compatibility (global_mapping.cpp:402); the device has no thread knob
@@ -416,16 +491,20 @@ public:
   }
   const LinearizedSystem6& linearize(const Values& values) {
     const Isometry3d d = calc_delta(values);
-    check(glim_amd_gicp_linearize(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, is_binary_ ? GLIM_AMD_FACTOR_BINARY : 0u,
-                                  &linearized_),
-          "IntegratedGICPFactor::linearize");
+    const std::uint32_t flags = is_binary_ ? GLIM_AMD_FACTOR_BINARY : 0u;
+    if (ivox_) check(glim_amd_ivox_gicp_linearize(ivox_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, flags, &linearized_),
+                     "IntegratedGICPFactor::linearize");
+    else check(glim_amd_gicp_linearize(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, flags, &linearized_),
+               "IntegratedGICPFactor::linearize");
     num_inliers_ = linearized_.num_inliers;
     return linearized_;
   }
   double error(const Values& values) {
     const Isometry3d d = calc_delta(values);
     double e = 0.0;
-    check(glim_amd_gicp_error(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_), "IntegratedGICPFactor::error");
+    if (ivox_) check(glim_amd_ivox_gicp_error(ivox_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_),
+                     "IntegratedGICPFactor::error");
+    else check(glim_amd_gicp_error(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_), "IntegratedGICPFactor::error");
     return e;
   }
   double inlier_fraction() const { return (double)num_inliers_ / (double)std::max<std::size_t>(1, source_->size()); }
@@ -437,6 +516,7 @@ private:
   Isometry3d fixed_target_pose_;
   PointCloudGPU::ConstPtr source_;
   NearestNeighborSearchGPU::ConstPtr tree_;
+  IncrementalVoxelMap::ConstPtr ivox_;        // set instead of tree_ when the target is a device iVox
   double max_correspondence_distance_ = 1.0;  // gtsam_points default: max_correspondence_distance_sq = 1.0
   std::int64_t num_inliers_ = 0;
   LinearizedSystem6 linearized_{};
@@ -452,6 +532,13 @@ public:
       : key0_(source_t0_key), key1_(source_t1_key), source_(std::move(source)),
         tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {
     check(glim_amd_ct_gicp_create(tree_->handle(), source_->handle(), times, &h_), "IntegratedCT_GICPFactor");
+  }
+  // IntegratedCT_GICPFactor_<iVox, PointCloud>(X, Y, target_ivox, frame, target_ivox) -- odometry_estimation_ct.cpp:158-160: the factor reads the
+  // map as it is at each call and keeps it alive
+  IntegratedCT_GICPFactor(Key source_t0_key, Key source_t1_key, IncrementalVoxelMap::Ptr target, PointCloudGPU::ConstPtr source,
+                          IncrementalVoxelMap::Ptr target_tree = nullptr, const double* times = nullptr)
+      : key0_(source_t0_key), key1_(source_t1_key), source_(std::move(source)), ivox_(target_tree ? std::move(target_tree) : std::move(target)) {
+    check(glim_amd_ivox_ct_factor_create(ivox_->handle(), source_->handle(), times, &h_), "IntegratedCT_GICPFactor");
   }
   ~IntegratedCT_GICPFactor() { glim_amd_ct_gicp_destroy(h_); }
   IntegratedCT_GICPFactor(const IntegratedCT_GICPFactor&) = delete;
@@ -489,6 +576,7 @@ private:
   Key key0_, key1_;
   PointCloudGPU::ConstPtr source_;
   NearestNeighborSearchGPU::ConstPtr tree_;
+  IncrementalVoxelMap::Ptr ivox_;  // set instead of tree_ when the target is a device iVox (destroyed after the factor: members die after ~h_)
   glim_amd_ct_gicp_factor* h_ = nullptr;
   glim_amd_ct_linearized linearized_{};
 };

@@ -48,6 +48,10 @@ int glim_amd_debug_deskew_table(int64_t n, const double* times, const double* T_
  * 6x6 dT_k/dX, dT_k/dY; time_index_out (source size) the bucket of every point.  Any output may be NULL. */
 int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t* num_buckets, int32_t table_cap,
                                  double* table_out, double* T12_out, double* D0_out, double* D1_out, int32_t* time_index_out);
+/* test hooks of the device iVox (glim_amd.h): the slot capacity its first insert allocates (default 1024; a tiny value forces the growth path of
+ * the slot arrays and of the table; GLIM_AMD_ERR_STATE once the map has been inserted into), and the capacities it holds now. */
+int glim_amd_debug_ivox_set_initial_capacity(glim_amd_ivox* ivox, int32_t slots);
+int glim_amd_debug_ivox_capacity(const glim_amd_ivox* ivox, int32_t* slot_capacity, int32_t* table_size);
 /* test hook: writes `value` into 32-bit word `word` (< 256) of the context's pinned scratch block -- what an earlier read-back (kNN counters, kept
  * points) may have left where the polled voxel-map builds keep their completion word (word 2; 4 * (levels - 1) + 2 for glim_amd_frame_create).
  * value = 0xffffffff stands for "the sequence number the context's NEXT polled build will wait for". */

@@ -114,6 +114,15 @@ for tag,key in (('CT10','pre10k'),('CT131','raw131k')):
     vals.update({tag+'_N':sp(c['source_points']), tag+'_LIN':f(c['ct_linearize']['p50_us'],1), tag+'_ERR':f(c['ct_error']['p50_us'],1),
                  tag+'_GICP':f(c['gicp_linearize']['p50_us'],1), tag+'_RATIO':f(c['ct_over_gicp_linearize'],2), tag+'_FRAME':f(c['lm_frame_8_iterations']['p50_us']/1e3,2),
                  tag+'_BUCKETS':str(c['buckets'])})
+# ---- the device iVox (tools/ivox_time.py) ----
+iv=json.load(open('profiles/ivox/ivox_time.json')); ivf=iv['ct_factor']
+vals.update({'IVX_MAP_POINTS':sp(iv['map']['num_points']), 'IVX_MAP_VOXELS':sp(iv['map']['num_voxels']), 'IVX_SRC':sp(iv['source_points']),
+             'IVX_INS':f(iv['insert_sweep']['p50_us'],0), 'IVX_INS_RAW':f(iv['insert_raw_131072']['p50_us'],0),
+             'IVX_IDX':f(iv['index_rebuild_accumulated_cloud']['p50_us'],0), 'IVX_INS_RATIO':f(iv['insert_over_index_rebuild'],2),
+             'IVX_LIN1':f(ivf['ivox_mode1']['linearize']['p50_us'],0), 'IVX_LIN7':f(ivf['ivox_mode7']['linearize']['p50_us'],0),
+             'IVX_LIN27':f(ivf['ivox_mode27']['linearize']['p50_us'],0), 'IVX_LIN_IDX':f(ivf['index']['linearize']['p50_us'],0),
+             'IVX_LIN_RATIO':f(iv['mode1_linearize_over_index_linearize'],2), 'IVX_ERR1':f(ivf['ivox_mode1']['error']['p50_us'],0),
+             'IVX_FRAME':f(iv['frame_8_iterations_deskew_covariances_insert']['p50_us']/1e3,2)})
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
