@@ -936,11 +936,38 @@ def preprocess_params(**kw):
     return p
 
 
+class _GicpTarget:
+    """What (target, target_tree) of a GICP-family factor resolve to: `ivox` (a borrowed IncrementalVoxelMap, or None), `tree` (what the factor
+    shows as target_tree: the map, a borrowed search index, or an index created here) and `handle` (what the C calls take: the map's handle
+    as it is at the call, None once the map is closed).  close() destroys the index only when it was created here."""
+
+    def __init__(self, target, target_tree, max_correspondence_distance):
+        self.ivox = next((t for t in (target_tree, target) if isinstance(t, IncrementalVoxelMap)), None)
+        self.owned = target_tree is None and self.ivox is None
+        if self.owned:
+            target_tree = C.c_void_p()
+            check(lib().glim_amd_nn_index_create(target._h, float(max_correspondence_distance), C.byref(target_tree)), "glim_amd_nn_index_create")
+        self.tree = self.ivox if self.ivox is not None else target_tree
+
+    @property
+    def handle(self):
+        return self.ivox._h if self.ivox is not None else self.tree
+
+    def close(self):
+        if self.owned and self.tree:
+            lib().glim_amd_nn_index_destroy(self.tree)
+            self.tree = None
+
+
 class IntegratedGICPFactor:
     """gtsam_points::IntegratedGICPFactor on the device (sub_mapping.cpp:202, global_mapping.cpp:400, global_mapping_pose_graph.cpp:393).
     Unary form: IntegratedGICPFactor(fixed_target_pose, source_key, target, source); binary: (target_key, source_key, target, source).
     `target` / `source` are PointCloudGPU with covariances; the target's search index is built once here (or passed as `target_tree`).
     An IncrementalVoxelMap as `target_frame` (or `target_tree`) gives IntegratedGICPFactor_<iVox, PointCloud>: the map's own bounded search."""
+
+    # the entry points of a target kind and the type of its correspondences (an index: original target index; a map: slot * max_points + place)
+    _OVER_INDEX = ("glim_amd_gicp_linearize", "glim_amd_gicp_error", "glim_amd_gicp_correspondences", np.int32, C.c_int32)
+    _OVER_IVOX = ("glim_amd_ivox_gicp_linearize", "glim_amd_ivox_gicp_error", "glim_amd_ivox_gicp_correspondences", np.int64, C.c_int64)
 
     def __init__(self, target, source_key, target_frame, source_frame, target_tree=None, max_correspondence_distance=1.0):
         self.binary = np.isscalar(target)
@@ -950,15 +977,10 @@ class IntegratedGICPFactor:
         self.target_frame, self.source_frame = target_frame, source_frame
         self.max_correspondence_distance = float(max_correspondence_distance)
         self._inliers = 0
-        self._ivox = target_tree if isinstance(target_tree, IncrementalVoxelMap) else (target_frame if isinstance(target_frame, IncrementalVoxelMap) else None)
-        self._own_tree = target_tree is None and self._ivox is None
-        if self._ivox is not None:
-            target_tree = self._ivox
-        elif target_tree is None:
-            h = C.c_void_p()
-            check(lib().glim_amd_nn_index_create(target_frame._h, self.max_correspondence_distance, C.byref(h)), "glim_amd_nn_index_create")
-            target_tree = h
-        self.target_tree = target_tree
+        self._target = _GicpTarget(target_frame, target_tree, self.max_correspondence_distance)
+        self.target_tree = self._target.tree
+        kind = self._OVER_IVOX if self._target.ivox is not None else self._OVER_INDEX
+        self._linearize, self._error, self._correspondences, self._corr_dtype, self._corr_ctype = kind
 
     def set_max_correspondence_distance(self, d):
         self.max_correspondence_distance = float(d)
@@ -971,12 +993,7 @@ class IntegratedGICPFactor:
     def linearize(self, values):
         L = Linearized6()
         T = pose12(self.calc_delta(values))
-        if self._ivox is not None:
-            check(lib().glim_amd_ivox_gicp_linearize(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance,
-                                                     FACTOR_BINARY if self.binary else 0, C.byref(L)), "glim_amd_ivox_gicp_linearize")
-        else:
-            check(lib().glim_amd_gicp_linearize(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance,
-                                                FACTOR_BINARY if self.binary else 0, C.byref(L)), "glim_amd_gicp_linearize")
+        self._call(self._linearize, T, FACTOR_BINARY if self.binary else 0, C.byref(L))
         out = _lin_to_dict(L)
         self._inliers = out["num_inliers"]
         return out
@@ -984,12 +1001,7 @@ class IntegratedGICPFactor:
     def error(self, values):
         e, n = C.c_double(), C.c_int64()
         T = pose12(self.calc_delta(values))
-        if self._ivox is not None:
-            check(lib().glim_amd_ivox_gicp_error(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance, C.byref(e),
-                                                 C.byref(n)), "glim_amd_ivox_gicp_error")
-        else:
-            check(lib().glim_amd_gicp_error(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance, C.byref(e),
-                                            C.byref(n)), "glim_amd_gicp_error")
+        self._call(self._error, T, C.byref(e), C.byref(n))
         self._inliers = n.value
         return e.value
 
@@ -998,21 +1010,16 @@ class IntegratedGICPFactor:
 
     def correspondences(self, values):
         T = pose12(self.calc_delta(values))
-        if self._ivox is not None:
-            # slot * max_points + place in the cell, or -1 (int64)
-            out = np.zeros(self.source_frame.size(), dtype=np.int64)
-            check(lib().glim_amd_ivox_gicp_correspondences(self._ivox._h, self.source_frame._h, _dp(T), self.max_correspondence_distance,
-                                                           out.ctypes.data_as(C.POINTER(C.c_int64))), "glim_amd_ivox_gicp_correspondences")
-            return out
-        out = np.zeros(self.source_frame.size(), dtype=np.int32)
-        check(lib().glim_amd_gicp_correspondences(self.target_tree, self.source_frame._h, _dp(T), self.max_correspondence_distance, _ip(out)),
-              "glim_amd_gicp_correspondences")
+        out = np.zeros(self.source_frame.size(), dtype=self._corr_dtype)
+        self._call(self._correspondences, T, out.ctypes.data_as(C.POINTER(self._corr_ctype)))
         return out
 
+    def _call(self, name, T, *out):
+        check(getattr(lib(), name)(self._target.handle, self.source_frame._h, _dp(T), self.max_correspondence_distance, *out), name)
+
     def close(self):
-        if self._own_tree and self.target_tree:
-            lib().glim_amd_nn_index_destroy(self.target_tree)
-            self.target_tree = None
+        self._target.close()
+        self.target_tree = self._target.tree
 
     def __del__(self):
         try:
@@ -1034,21 +1041,12 @@ class IntegratedCT_GICPFactor:
         self.keys = (int(key0), int(key1))
         self.target, self.source = target, source
         self._h = None
-        self._ivox = target_tree if isinstance(target_tree, IncrementalVoxelMap) else (target if isinstance(target, IncrementalVoxelMap) else None)
-        self._own_tree = target_tree is None and self._ivox is None
-        if self._ivox is not None:
-            target_tree = self._ivox
-        elif target_tree is None:
-            h = C.c_void_p()
-            check(lib().glim_amd_nn_index_create(target._h, float(max_correspondence_distance), C.byref(h)), "glim_amd_nn_index_create")
-            target_tree = h
-        self.target_tree = target_tree
+        self._target = _GicpTarget(target, target_tree, max_correspondence_distance)
+        self.target_tree = self._target.tree
         t = None if times is None else np.ascontiguousarray(times, dtype=np.float64).reshape(source.size())
         h = C.c_void_p()
-        if self._ivox is not None:
-            check(lib().glim_amd_ivox_ct_factor_create(self._ivox._h, source._h, _dp(t), C.byref(h)), "glim_amd_ivox_ct_factor_create")
-        else:
-            check(lib().glim_amd_ct_gicp_create(self.target_tree, source._h, _dp(t), C.byref(h)), "glim_amd_ct_gicp_create")
+        create = "glim_amd_ivox_ct_factor_create" if self._target.ivox is not None else "glim_amd_ct_gicp_create"
+        check(getattr(lib(), create)(self._target.handle, source._h, _dp(t), C.byref(h)), create)
         self._h = h
         self.set_max_correspondence_distance(max_correspondence_distance)
 
@@ -1116,9 +1114,8 @@ class IntegratedCT_GICPFactor:
         if self._h:
             lib().glim_amd_ct_gicp_destroy(self._h)
             self._h = None
-        if self._own_tree and self.target_tree:
-            lib().glim_amd_nn_index_destroy(self.target_tree)
-            self.target_tree = None
+        self._target.close()
+        self.target_tree = self._target.tree
 
     def __del__(self):
         try:

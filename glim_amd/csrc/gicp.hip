@@ -679,54 +679,106 @@ unsigned int next_pow2(unsigned long long v) {
   return (unsigned int)p;
 }
 
-int run_gicp(const glim_amd_nn_index* ix, const glim_amd_cloud* source, const double* T12, double max_dist, bool linearize, double* compact_host,
+// the search is latency-bound: spread the points over >= 4 blocks per CU when there are enough of them
+int points_per_thread(const glim_amd_ctx* ctx, int n) {
+  const int target_blocks = std::max(1, ctx->num_cus * 4);
+  return std::max(1, std::min(64, (n + BLOCK * target_blocks - 1) / (BLOCK * target_blocks)));
+}
+
+// ---- a target the factor kernels can search, as the host sees it ----
+// Everything the two kinds differ in, as data: built by gicp_target() from a search index (below) or from a device iVox (ivox.hpp), read by
+// run_gicp and run_ct, which do not ask for the kind.  A map changes under insert, so the description holds the context's mutex from the moment
+// it is taken: what it says stays true, and its arrays stay where they are, for as long as it lives.  That is also the lock of the evaluation.
+struct GicpTarget {
+  glim_amd_ctx* ctx = nullptr;  // null: no target was given
+  std::unique_lock<std::mutex> held;
+  GicpArgs args{};              // the target half filled (sorted .. inv_h), the source half zero
+  bool ivox = false;            // the search object: `nn` when set, IndexSearch otherwise (with_search)
+  IvoxSearch nn{};
+  bool usable = true;           // the target has covariances
+  bool empty = true;            // nothing to find: every point is an outlier
+  int ring_cap = 0;             // most rings the index's walk may take; 0: no walk (a map searches the cells of its neighbour mode)
+  int64_t max_source = INT64_MAX;  // source points beyond which the kind's entry points refuse the call
+  uint64_t generation = 0;      // moves when positions in the target change their meaning (never for an index)
+  // rings after which the scanned cube covers the correspondence radius `d`; the walk is bounded, so a radius far beyond what the index was
+  // sized for (cells are hint/3 .. hint wide) is refused rather than searched incompletely: -1
+  int rings(double d) const {
+    if (ring_cap == 0) return 0;
+    const double r = std::ceil(d / args.h) + 1.0;
+    return r <= (double)ring_cap ? (int)r : -1;
+  }
+};
+
+GicpTarget gicp_target(const glim_amd_nn_index* ix) {
+  GicpTarget t;
+  if (!ix) return t;
+  t.ctx = ix->ctx;
+  t.held = std::unique_lock<std::mutex>(t.ctx->mu);
+  t.args.sorted = ix->sorted;
+  t.args.tA = ix->covA;
+  t.args.tB = ix->covB;
+  t.args.keys = ix->keys;
+  t.args.runs = ix->runs;
+  t.args.mask = ix->mask;
+  t.args.nt = ix->n;
+  t.args.h = ix->h;
+  t.args.inv_h = 1.0 / ix->h;
+  t.usable = ix->covA != nullptr;
+  t.empty = ix->n == 0;
+  t.ring_cap = GICP_MAX_RING;
+  return t;
+}
+
+// the source half of the kernels' arguments
+void set_source(GicpArgs* a, const glim_amd_cloud* source, int ppt, double max_dist) {
+  a->pts = source->pts;
+  a->covA = source->covA;
+  a->covB = source->covB;
+  a->n = (int)source->n;
+  a->ppt = ppt;
+  a->max_sq = max_dist * max_dist;
+}
+
+// the one place where the target's kind becomes the NN template argument of a factor kernel: launch(search object)
+template <class Launch>
+void with_search(const GicpTarget& t, Launch&& launch) {
+  if (t.ivox) launch(t.nn);
+  else launch(IndexSearch{});
+}
+
+// one synchronous evaluation of the rigid factor over either kind of target; corr_host: n positions (original target index / the map's
+// slot * cap + place, or -1), or null
+int run_gicp(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, bool linearize, double* compact_host,
              int32_t* corr_host) {
-  if (!ix || !source || !T12 || !(max_dist >= 0.0)) return GLIM_AMD_ERR_INVALID;
-  if (source->ctx->device != ix->ctx->device) return GLIM_AMD_ERR_INVALID;
-  if (!source->has_covs || !ix->covA) return GLIM_AMD_ERR_STATE;
-  glim_amd_ctx* ctx = ix->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!t.ctx || !source || !T12 || !(max_dist >= 0.0)) return GLIM_AMD_ERR_INVALID;
+  if (source->ctx->device != t.ctx->device) return GLIM_AMD_ERR_INVALID;
+  if (source->n > t.max_source) return GLIM_AMD_ERR_INVALID;
+  if (!source->has_covs || !t.usable) return GLIM_AMD_ERR_STATE;
+  glim_amd_ctx* ctx = t.ctx;
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
   const int n = (int)source->n;
   for (int i = 0; i < COMPACT; i++) compact_host[i] = 0.0;
-  if (n == 0 || ix->n == 0) {
+  if (n == 0 || t.empty) {
     if (corr_host)
       for (int i = 0; i < n; i++) corr_host[i] = -1;
     return GLIM_AMD_OK;
   }
-  GicpArgs a;
-  a.sorted = ix->sorted;
-  a.tA = ix->covA;
-  a.tB = ix->covB;
-  a.keys = ix->keys;
-  a.runs = ix->runs;
-  a.mask = ix->mask;
-  a.nt = ix->n;
-  a.h = ix->h;
-  a.inv_h = 1.0 / ix->h;
-  a.pts = source->pts;
-  a.covA = source->covA;
-  a.covB = source->covB;
-  a.n = n;
+  GicpArgs a = t.args;
+  set_source(&a, source, points_per_thread(ctx, n), max_dist);
   memcpy(a.T, T12, sizeof(a.T));
-  a.max_sq = max_dist * max_dist;
-  // rings after which the scanned cube covers the correspondence radius; the walk is bounded, so a radius far beyond what the index was
-  // sized for (cells are hint/3 .. hint wide) is refused rather than searched incompletely
-  const double rings = std::ceil(max_dist / ix->h) + 1.0;
-  if (!(rings <= (double)GICP_MAX_RING)) return GLIM_AMD_ERR_UNSUPPORTED;
-  a.max_ring = (int)rings;
-  // the search is latency-bound: spread the points over >= 4 blocks per CU when there are enough of them
-  const int target_blocks = std::max(1, ctx->num_cus * 4);
-  a.ppt = std::max(1, std::min(64, (n + BLOCK * target_blocks - 1) / (BLOCK * target_blocks)));
+  a.max_ring = t.rings(max_dist);
+  if (a.max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
   const int nb = (n + BLOCK * a.ppt - 1) / (BLOCK * a.ppt);
   DeviceTemp partials, compact, corr;
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
   GA_HIP(pool_malloc(&partials.p, (size_t)nb * PARTIAL_STRIDE * sizeof(float)));
   GA_HIP(pool_malloc(&compact.p, COMPACT * sizeof(double)));
   if (corr_host) GA_HIP(pool_malloc(&corr.p, (size_t)n * sizeof(int32_t)));
-  if (linearize) gicp_kernel<true, IndexSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), IndexSearch{});
-  else gicp_kernel<false, IndexSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), IndexSearch{});
+  with_search(t, [&](auto nn) {
+    if (linearize) gicp_kernel<true, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
+    else gicp_kernel<false, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
+  });
   gicp_finalize_kernel<<<1, 256, 0, st>>>(partials.as<float>(), nb, linearize ? 1 : 0, compact.as<double>());
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(compact_host, compact.p, COMPACT * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -736,6 +788,21 @@ int run_gicp(const glim_amd_nn_index* ix, const glim_amd_cloud* source, const do
   return GLIM_AMD_OK;
 }
 
+// the three entry points of the rigid factor, over the description of either kind
+int gicp_linearize(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, uint32_t flags, glim_amd_linearized6* out) {
+  if (!out) return GLIM_AMD_ERR_INVALID;
+  double compact[COMPACT];
+  GA_TRY(run_gicp(t, source, T12, max_dist, true, compact, nullptr));
+  return glim_amd_expand_compact(compact, T12, flags, out);
+}
+
+int gicp_error(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, double* error, int64_t* num_inliers) {
+  double compact[COMPACT];
+  GA_TRY(run_gicp(t, source, T12, max_dist, false, compact, nullptr));
+  if (error) *error = compact[1];
+  if (num_inliers) *num_inliers = (int64_t)llround(compact[0]);
+  return GLIM_AMD_OK;
+}
 
 // ---- CT factor, host side: the time table and the bucket poses with their derivatives (FP64, gtsam::Pose3 conventions) ----
 // gtsam's right-perturbation Jacobians: between(X, Y) = X^-1 Y, H_X = -Ad((X^-1 Y)^-1), H_Y = I; compose(A, B): H_A = Ad(B^-1), H_B = I;
@@ -918,7 +985,7 @@ void se3_inverse(const double* A, double* B) {
 
 }  // namespace
 
-#include "ivox.hpp"  // the device iVox (container, insert, the rigid GICP entry points over it); uses the helpers above
+#include "ivox.hpp"  // the device iVox (container, insert, its gicp_target(), the rigid GICP entry points over it); uses the helpers above
 
 struct glim_amd_ct_gicp_factor {
   CtxRef ctx;
@@ -947,12 +1014,8 @@ struct glim_amd_ct_gicp_factor {
 
 namespace {
 
-// rings of the index's walk that cover `d`, or -1 when the walk is bounded below that (the rule of run_gicp)
-int ct_rings(const glim_amd_nn_index* ix, double d) {
-  if (!ix) return 0;  // a device iVox: the search is bounded by the neighbour mode, any distance is accepted
-  const double rings = std::ceil(d / ix->h) + 1.0;
-  return rings <= (double)GICP_MAX_RING ? (int)rings : -1;
-}
+// the factor's target as it is now (the lock of the call comes with it)
+GicpTarget ct_target(const glim_amd_ct_gicp_factor* f) { return f->ix ? gicp_target(f->ix) : gicp_target(f->iv); }
 
 // T_k, D0_k, D1_k of every bucket at (X, Y): CT_POSE_STRIDE doubles per bucket
 void ct_poses(const std::vector<double>& table, const double* X, const double* Y, double* out) {
@@ -983,87 +1046,57 @@ void ct_poses(const std::vector<double>& table, const double* X, const double* Y
   }
 }
 
-GicpArgs ct_args(const glim_amd_ct_gicp_factor* f, int max_ring) {
-  GicpArgs a{};
-  if (const glim_amd_nn_index* ix = f->ix) {
-    a.sorted = ix->sorted;
-    a.tA = ix->covA;
-    a.tB = ix->covB;
-    a.keys = ix->keys;
-    a.runs = ix->runs;
-    a.mask = ix->mask;
-    a.nt = ix->n;
-    a.h = ix->h;
-    a.inv_h = 1.0 / ix->h;
-  }
-  a.pts = f->src->pts;
-  a.covA = f->src->covA;
-  a.covB = f->src->covB;
-  a.n = f->n;
-  a.ppt = 1;
-  a.max_sq = f->max_dist * f->max_dist;
-  a.max_ring = max_ring;
-  return a;
-}
-
 enum { CT_LINEARIZE = 0, CT_ERROR = 1, CT_CORR = 2 };
+
+// the search pass of the factor: correspondences (and, with keep_* set, the M of every point) at the bucket poses
+void launch_ct_search(const GicpTarget& t, const glim_amd_ct_gicp_factor* f, const GicpArgs& a, const CtArgs& c, bool linearize, hipStream_t st) {
+  with_search(t, [&](auto nn) {
+    if (linearize) ct_gicp_kernel<true, decltype(nn)><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
+    else ct_gicp_kernel<false, decltype(nn)><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
+  });
+}
 
 // one synchronous evaluation; caller has validated the arguments.  out: CT_ROW doubles (CT_LINEARIZE) or the 29-double compact record (CT_ERROR)
 int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mode, double* out, int32_t* corr_host) {
-  if (!f->src->has_covs) return GLIM_AMD_ERR_STATE;
-  if (f->ix && !f->ix->covA) return GLIM_AMD_ERR_STATE;
-  const int max_ring = ct_rings(f->ix, f->max_dist);
-  if (max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
+  const GicpTarget t = ct_target(f);
+  if (!f->src->has_covs || !t.usable) return GLIM_AMD_ERR_STATE;
+  GicpArgs a = t.args;
+  set_source(&a, f->src, 1, f->max_dist);
+  a.max_ring = t.rings(f->max_dist);
+  if (a.max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
   glim_amd_ctx* ctx = f->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
-  if (f->n == 0 || (f->ix ? f->ix->n == 0 : f->iv->num_slots == 0)) {
+  if (f->n == 0 || t.empty) {
     if (corr_host)
       for (int i = 0; i < f->n; i++) corr_host[i] = -1;
     return GLIM_AMD_OK;
   }
   ct_poses(f->table, X, Y, f->h_poses);
-  GicpArgs a = ct_args(f, max_ring);
-  IvoxSearch nn{};
-  if (f->iv) {
-    // the map as it is now; correspondences kept before an insert (or a change of the neighbour mode) are positions in a map that is gone
-    const GicpArgs src = a;
-    ivox_target_args(f->iv, &a, &nn);
-    a.pts = src.pts; a.covA = src.covA; a.covB = src.covB; a.n = src.n; a.ppt = src.ppt; a.max_sq = src.max_sq;
-    if (f->kept_gen != f->iv->generation) f->kept = false;
-    f->kept_gen = f->iv->generation;
-  }
+  // correspondences kept before an insert into the map (or a change of its neighbour mode) are positions in a map that is gone
+  if (f->kept_gen != t.generation) f->kept = false;
+  f->kept_gen = t.generation;
   CtArgs c{};
   c.blocks = f->d_blocks;
   c.poses = f->d_poses;
+  if (mode != CT_CORR) {
+    c.keep_corr = f->keep_corr;
+    c.keep_m0 = f->keep_m0;
+    c.keep_m1 = f->keep_m1;
+  }
   DeviceTemp corr;
   SyncOnExit in_flight(st);
   GA_HIP(hipMemcpyAsync(f->d_poses, f->h_poses, (size_t)f->nbk * CT_POSE_STRIDE * sizeof(double), hipMemcpyHostToDevice, st));
   if (mode == CT_LINEARIZE) {
-    c.keep_corr = f->keep_corr;
-    c.keep_m0 = f->keep_m0;
-    c.keep_m1 = f->keep_m1;
     f->kept = false;
-    if (f->iv) ct_gicp_kernel<true, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
-    else ct_gicp_kernel<true, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, IndexSearch{});
+    launch_ct_search(t, f, a, c, true, st);
     ct_bucket_kernel<<<f->nbk, 64, 0, st>>>(f->d_partials, f->d_bucket_first, f->d_poses, f->d_rows);
     ct_sum_kernel<<<1, 768, 0, st>>>(f->d_rows, f->nbk, f->d_out);
     GA_HIP(hipGetLastError());
     GA_HIP(read_back_sync(ctx, st, out, f->d_out, CT_ROW * sizeof(double)));
     f->kept = true;
   } else if (mode == CT_ERROR) {
-    if (!f->kept) {
-      CtArgs k = c;
-      k.keep_corr = f->keep_corr;
-      k.keep_m0 = f->keep_m0;
-      k.keep_m1 = f->keep_m1;
-      if (f->iv) ct_gicp_kernel<false, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials, nn);
-      else ct_gicp_kernel<false, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, k, f->d_partials, IndexSearch{});
-    }
-    c.keep_corr = f->keep_corr;
-    c.keep_m0 = f->keep_m0;
-    c.keep_m1 = f->keep_m1;
+    if (!f->kept) launch_ct_search(t, f, a, c, false, st);
     ct_error_kernel<<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials);
     gicp_finalize_kernel<<<1, 256, 0, st>>>(f->d_partials, f->nb, 0, f->d_out);
     GA_HIP(hipGetLastError());
@@ -1072,8 +1105,7 @@ int run_ct(glim_amd_ct_gicp_factor* f, const double* X, const double* Y, int mod
   } else {
     GA_HIP(pool_malloc(&corr.p, (size_t)f->n * sizeof(int32_t)));
     c.corr_out = corr.as<int32_t>();
-    if (f->iv) ct_gicp_kernel<false, IvoxSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, nn);
-    else ct_gicp_kernel<false, IndexSearch><<<f->nb, BLOCK, 0, st>>>(a, c, f->d_partials, IndexSearch{});
+    launch_ct_search(t, f, a, c, false, st);
     GA_HIP(hipGetLastError());
     GA_HIP(hipMemcpyAsync(corr_host, corr.p, (size_t)f->n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GA_HIP(hipStreamSynchronize(st));
@@ -1202,26 +1234,19 @@ int glim_amd_nn_index_destroy(glim_amd_nn_index* ix) {
 
 int glim_amd_gicp_linearize(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                             double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out) {
-  if (!out) return GLIM_AMD_ERR_INVALID;
-  double compact[COMPACT];
-  GA_TRY(run_gicp(target, source, T_target_source12, max_correspondence_distance, true, compact, nullptr));
-  return glim_amd_expand_compact(compact, T_target_source12, flags, out);
+  return gicp_linearize(gicp_target(target), source, T_target_source12, max_correspondence_distance, flags, out);
 }
 
 int glim_amd_gicp_error(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                         double max_correspondence_distance, double* error, int64_t* num_inliers) {
-  double compact[COMPACT];
-  GA_TRY(run_gicp(target, source, T_target_source12, max_correspondence_distance, false, compact, nullptr));
-  if (error) *error = compact[1];
-  if (num_inliers) *num_inliers = (int64_t)llround(compact[0]);
-  return GLIM_AMD_OK;
+  return gicp_error(gicp_target(target), source, T_target_source12, max_correspondence_distance, error, num_inliers);
 }
 
 int glim_amd_gicp_correspondences(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                                   double max_correspondence_distance, int32_t* correspondences) {
   if (!correspondences) return GLIM_AMD_ERR_INVALID;
   double compact[COMPACT];
-  return run_gicp(target, source, T_target_source12, max_correspondence_distance, false, compact, correspondences);
+  return run_gicp(gicp_target(target), source, T_target_source12, max_correspondence_distance, false, compact, correspondences);
 }
 
 }  // extern "C"
@@ -1244,11 +1269,11 @@ int glim_amd_ct_gicp_destroy(glim_amd_ct_gicp_factor* f) {
 }  // extern "C"
 
 namespace {
-// the factor over either target kind: exactly one of `target` / `map` is set
-int ct_factor_create(const glim_amd_nn_index* target, glim_amd_ivox* map, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
-  if ((!target && !map) || !source || !out) return GLIM_AMD_ERR_INVALID;
+// the factor over either target kind: exactly one of `target` / `map` is set, `ctx` is its context
+int ct_factor_create(glim_amd_ctx* ctx, const glim_amd_nn_index* target, glim_amd_ivox* map, const glim_amd_cloud* source, const double* times,
+                     glim_amd_ct_gicp_factor** out) {
+  if (!source || !out) return GLIM_AMD_ERR_INVALID;
   *out = nullptr;
-  glim_amd_ctx* ctx = target ? static_cast<glim_amd_ctx*>(target->ctx) : static_cast<glim_amd_ctx*>(map->ctx);
   if (source->ctx->device != ctx->device) return GLIM_AMD_ERR_INVALID;
   if (source->n > (int64_t)(1 << 28)) return GLIM_AMD_ERR_INVALID;
   const int n = (int)source->n;
@@ -1276,8 +1301,7 @@ int ct_factor_create(const glim_amd_nn_index* target, glim_amd_ivox* map, const 
   }
   f->nbk = (int)f->table.size();
   // blocks: each bucket's index run cut into pieces of BLOCK * ppt points (ppt as run_gicp picks it for the whole cloud)
-  const int target_blocks = std::max(1, ctx->num_cus * 4);
-  const int ppt = std::max(1, std::min(64, (n + BLOCK * target_blocks - 1) / (BLOCK * target_blocks)));
+  const int ppt = points_per_thread(ctx, n);
   std::vector<int4> blocks;
   std::vector<int> first((size_t)f->nbk + 1, 0);
   for (int i = 0; i < n;) {
@@ -1322,17 +1346,18 @@ extern "C" {
 
 int glim_amd_ct_gicp_create(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
   if (!target) return GLIM_AMD_ERR_INVALID;
-  return ct_factor_create(target, nullptr, source, times, out);
+  return ct_factor_create(target->ctx, target, nullptr, source, times, out);
 }
 
 int glim_amd_ivox_ct_factor_create(glim_amd_ivox* target, const glim_amd_cloud* source, const double* times, glim_amd_ct_gicp_factor** out) {
   if (!target) return GLIM_AMD_ERR_INVALID;
-  return ct_factor_create(nullptr, target, source, times, out);
+  return ct_factor_create(target->ctx, nullptr, target, source, times, out);
 }
 
 int glim_amd_ct_gicp_set_max_correspondence_distance(glim_amd_ct_gicp_factor* f, double d) {
   if (!f || !(d >= 0.0)) return GLIM_AMD_ERR_INVALID;
-  if (ct_rings(f->ix, d) < 0) return GLIM_AMD_ERR_UNSUPPORTED;
+  const GicpTarget t = ct_target(f);
+  if (t.rings(d) < 0) return GLIM_AMD_ERR_UNSUPPORTED;
   f->max_dist = d;
   f->kept = false;
   return GLIM_AMD_OK;

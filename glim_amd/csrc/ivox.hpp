@@ -1,6 +1,6 @@
 // ivox.hpp -- the device iVox: gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox), the incremental target model of GLIM's
 // LiDAR-only continuous-time odometry (odometry_estimation_ct.cpp:56-63 creates it, :229-235 inserts every finished frame).  Part of gicp.hip's
-// translation unit (included there, after its search helpers): the factors over the map are gicp.hip's kernels with IvoxSearch as target kind.
+// translation unit (included there, after its search helpers and run_gicp): the factors over the map are gicp.hip's, over gicp_target(map) below.
 //
 // Semantics (upstream recall; include/glim_amd.h states them in full): a voxel is floor(p / leaf) of the STORED (FP32) point; insert takes the
 // points in input order, a new voxel is appended in first-seen order, a cell drops a point when it is full or when a point already in it is
@@ -362,77 +362,32 @@ int ivox_sweep(glim_amd_ivox* m, hipStream_t st) {
   return GLIM_AMD_OK;
 }
 
-// GicpArgs / IvoxSearch of a factor evaluation over the map
-void ivox_target_args(const glim_amd_ivox* m, GicpArgs* a, IvoxSearch* nn) {
-  a->sorted = m->pts;
-  a->tA = m->covA;
-  a->tB = m->covB;
-  a->keys = nullptr;
-  a->runs = nullptr;
-  a->mask = 0;
-  a->nt = (int)m->num_points;
-  a->h = m->leaf;
-  a->inv_h = m->inv_leaf;
-  a->max_ring = 0;
-  nn->keys = m->tkeys;
-  nn->slots = m->tslots;
-  nn->counts = m->scount;
-  nn->mask = m->tsize - 1;
-  nn->cap = m->cap;
-  nn->nnb = m->mode;
-  nn->inv_leaf = m->inv_leaf;
-}
+constexpr int64_t IVOX_MAX_SOURCE = 1 << 28;  // source points of a rigid factor over the map
 
-// run_gicp over the map: IntegratedGICPFactor_<iVox, PointCloud>
-int run_gicp_ivox(const glim_amd_ivox* m, const glim_amd_cloud* source, const double* T12, double max_dist, bool linearize, double* compact_host,
-                  int64_t* corr_host) {
-  if (!m || !source || !T12 || !(max_dist >= 0.0)) return GLIM_AMD_ERR_INVALID;
-  if (source->ctx->device != m->ctx->device) return GLIM_AMD_ERR_INVALID;
-  if (source->n > (int64_t)(1 << 28)) return GLIM_AMD_ERR_INVALID;
-  if (!source->has_covs) return GLIM_AMD_ERR_STATE;
-  glim_amd_ctx* ctx = m->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  const int n = (int)source->n;
-  for (int i = 0; i < COMPACT; i++) compact_host[i] = 0.0;
-  if (n == 0 || m->num_slots == 0) {
-    if (corr_host)
-      for (int i = 0; i < n; i++) corr_host[i] = -1;
-    return GLIM_AMD_OK;
-  }
-  GicpArgs a{};
-  IvoxSearch nn{};
-  ivox_target_args(m, &a, &nn);
-  a.pts = source->pts;
-  a.covA = source->covA;
-  a.covB = source->covB;
-  a.n = n;
-  memcpy(a.T, T12, sizeof(a.T));
-  a.max_sq = max_dist * max_dist;
-  const int target_blocks = std::max(1, ctx->num_cus * 4);
-  a.ppt = std::max(1, std::min(64, (n + BLOCK * target_blocks - 1) / (BLOCK * target_blocks)));
-  const int nb = (n + BLOCK * a.ppt - 1) / (BLOCK * a.ppt);
-  DeviceTemp partials, compact, corr;
-  SyncOnExit in_flight(st);
-  GA_HIP(pool_malloc(&partials.p, (size_t)nb * PARTIAL_STRIDE * sizeof(float)));
-  GA_HIP(pool_malloc(&compact.p, COMPACT * sizeof(double)));
-  std::vector<int32_t> corr32;
-  if (corr_host) {
-    GA_HIP(pool_malloc(&corr.p, (size_t)n * sizeof(int32_t)));
-    corr32.resize((size_t)n);
-  }
-  if (linearize) gicp_kernel<true, IvoxSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
-  else gicp_kernel<false, IvoxSearch><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
-  gicp_finalize_kernel<<<1, 256, 0, st>>>(partials.as<float>(), nb, linearize ? 1 : 0, compact.as<double>());
-  GA_HIP(hipGetLastError());
-  GA_HIP(hipMemcpyAsync(compact_host, compact.p, COMPACT * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (corr_host) GA_HIP(hipMemcpyAsync(corr32.data(), corr.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  GA_HIP(hipStreamSynchronize(st));
-  in_flight.dismiss();
-  if (corr_host)
-    for (int i = 0; i < n; i++) corr_host[i] = corr32[(size_t)i];
-  return GLIM_AMD_OK;
+// the map as a target of the factor kernels (gicp.hip, GicpTarget), as it is now
+GicpTarget gicp_target(const glim_amd_ivox* m) {
+  GicpTarget t;
+  if (!m) return t;
+  t.ctx = m->ctx;
+  t.held = std::unique_lock<std::mutex>(t.ctx->mu);
+  t.args.sorted = m->pts;
+  t.args.tA = m->covA;
+  t.args.tB = m->covB;
+  t.args.nt = (int)m->num_points;
+  t.args.h = m->leaf;
+  t.args.inv_h = m->inv_leaf;
+  t.ivox = true;
+  t.nn.keys = m->tkeys;
+  t.nn.slots = m->tslots;
+  t.nn.counts = m->scount;
+  t.nn.mask = m->tsize - 1;
+  t.nn.cap = m->cap;
+  t.nn.nnb = m->mode;
+  t.nn.inv_leaf = m->inv_leaf;
+  t.empty = m->num_slots == 0;
+  t.max_source = IVOX_MAX_SOURCE;
+  t.generation = m->generation;
+  return t;
 }
 
 }  // namespace
@@ -632,28 +587,26 @@ int glim_amd_ivox_voxel_points(const glim_amd_ivox* m, double* points4) {
   return GLIM_AMD_OK;
 }
 
+// IntegratedGICPFactor_<iVox, PointCloud>: gicp.hip's rigid factor over the map
 int glim_amd_ivox_gicp_linearize(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
                                  double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out) {
-  if (!out) return GLIM_AMD_ERR_INVALID;
-  double compact[COMPACT];
-  GA_TRY(run_gicp_ivox(target, source, T_target_source12, max_correspondence_distance, true, compact, nullptr));
-  return glim_amd_expand_compact(compact, T_target_source12, flags, out);
+  return gicp_linearize(gicp_target(target), source, T_target_source12, max_correspondence_distance, flags, out);
 }
 
 int glim_amd_ivox_gicp_error(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
                              double max_correspondence_distance, double* error, int64_t* num_inliers) {
-  double compact[COMPACT];
-  GA_TRY(run_gicp_ivox(target, source, T_target_source12, max_correspondence_distance, false, compact, nullptr));
-  if (error) *error = compact[1];
-  if (num_inliers) *num_inliers = (int64_t)llround(compact[0]);
-  return GLIM_AMD_OK;
+  return gicp_error(gicp_target(target), source, T_target_source12, max_correspondence_distance, error, num_inliers);
 }
 
 int glim_amd_ivox_gicp_correspondences(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
                                        double max_correspondence_distance, int64_t* correspondences) {
-  if (!correspondences) return GLIM_AMD_ERR_INVALID;
+  if (!correspondences || !source) return GLIM_AMD_ERR_INVALID;
+  // the kernels write 32-bit positions; this entry point owns the 64-bit buffer and widens (a longer source is refused by run_gicp)
+  std::vector<int32_t> corr32((size_t)std::min<int64_t>(source->n, IVOX_MAX_SOURCE));
   double compact[COMPACT];
-  return run_gicp_ivox(target, source, T_target_source12, max_correspondence_distance, false, compact, correspondences);
+  GA_TRY(run_gicp(gicp_target(target), source, T_target_source12, max_correspondence_distance, false, compact, corr32.data()));
+  std::copy(corr32.begin(), corr32.end(), correspondences);
+  return GLIM_AMD_OK;
 }
 
 int glim_amd_debug_ivox_set_initial_capacity(glim_amd_ivox* m, int32_t slots) {

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -466,19 +467,19 @@ public:
   IntegratedGICPFactor(Key target_key, Key source_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
                        NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
       : is_binary_(true), target_key_(target_key), source_key_(source_key), source_(std::move(source)),
-        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {}
+        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) { bind(tree_->handle()); }
   // unary: (fixed_target_pose, source_key, target frame, source frame[, target tree])
   IntegratedGICPFactor(const Isometry3d& fixed_target_pose, Key source_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
                        NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
       : is_binary_(false), target_key_(0), source_key_(source_key), fixed_target_pose_(fixed_target_pose), source_(std::move(source)),
-        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {}
+        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) { bind(tree_->handle()); }
   // IntegratedGICPFactor_<iVox, PointCloud>: the target is a device iVox, searched with its own neighbour mode (the "GICP" registration of
   // odometry_estimation_cpu.cpp, loose_initial_state_estimation.cpp)
   IntegratedGICPFactor(Key target_key, Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
-      : is_binary_(true), target_key_(target_key), source_key_(source_key), source_(std::move(source)), ivox_(std::move(target)) {}
+      : is_binary_(true), target_key_(target_key), source_key_(source_key), source_(std::move(source)), ivox_(std::move(target)) { bind(ivox_->handle()); }
   IntegratedGICPFactor(const Isometry3d& fixed_target_pose, Key source_key, IncrementalVoxelMap::ConstPtr target, PointCloudGPU::ConstPtr source)
       : is_binary_(false), target_key_(0), source_key_(source_key), fixed_target_pose_(fixed_target_pose), source_(std::move(source)),
-        ivox_(std::move(target)) {}
+        ivox_(std::move(target)) { bind(ivox_->handle()); }
 
   void set_max_correspondence_distance(double d) { max_correspondence_distance_ = d; }
   void set_num_threads(int) {}  // accepted for source compatibility (global_mapping.cpp:402); the device has no thread knob
@@ -492,31 +493,37 @@ public:
   const LinearizedSystem6& linearize(const Values& values) {
     const Isometry3d d = calc_delta(values);
     const std::uint32_t flags = is_binary_ ? GLIM_AMD_FACTOR_BINARY : 0u;
-    if (ivox_) check(glim_amd_ivox_gicp_linearize(ivox_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, flags, &linearized_),
-                     "IntegratedGICPFactor::linearize");
-    else check(glim_amd_gicp_linearize(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, flags, &linearized_),
-               "IntegratedGICPFactor::linearize");
+    check(linearize_(source_->handle(), d.m.data(), max_correspondence_distance_, flags, &linearized_), "IntegratedGICPFactor::linearize");
     num_inliers_ = linearized_.num_inliers;
     return linearized_;
   }
   double error(const Values& values) {
     const Isometry3d d = calc_delta(values);
     double e = 0.0;
-    if (ivox_) check(glim_amd_ivox_gicp_error(ivox_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_),
-                     "IntegratedGICPFactor::error");
-    else check(glim_amd_gicp_error(tree_->handle(), source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_), "IntegratedGICPFactor::error");
+    check(error_(source_->handle(), d.m.data(), max_correspondence_distance_, &e, &num_inliers_), "IntegratedGICPFactor::error");
     return e;
   }
   double inlier_fraction() const { return (double)num_inliers_ / (double)std::max<std::size_t>(1, source_->size()); }
   const LinearizedSystem6& linearized() const { return linearized_; }
 
 private:
+  // the target's kind is settled by the constructor, once: the handle bound into the kind's pair of entry points
+  void bind(const glim_amd_nn_index* h) {
+    linearize_ = [h](auto... a) { return glim_amd_gicp_linearize(h, a...); };
+    error_ = [h](auto... a) { return glim_amd_gicp_error(h, a...); };
+  }
+  void bind(const glim_amd_ivox* h) {
+    linearize_ = [h](auto... a) { return glim_amd_ivox_gicp_linearize(h, a...); };
+    error_ = [h](auto... a) { return glim_amd_ivox_gicp_error(h, a...); };
+  }
   bool is_binary_;
   Key target_key_, source_key_;
   Isometry3d fixed_target_pose_;
   PointCloudGPU::ConstPtr source_;
-  NearestNeighborSearchGPU::ConstPtr tree_;
-  IncrementalVoxelMap::ConstPtr ivox_;        // set instead of tree_ when the target is a device iVox
+  NearestNeighborSearchGPU::ConstPtr tree_;   // keeps the target alive; which of the two is set no longer matters after bind()
+  IncrementalVoxelMap::ConstPtr ivox_;
+  std::function<int(const glim_amd_cloud*, const double*, double, std::uint32_t, glim_amd_linearized6*)> linearize_;
+  std::function<int(const glim_amd_cloud*, const double*, double, double*, std::int64_t*)> error_;
   double max_correspondence_distance_ = 1.0;  // gtsam_points default: max_correspondence_distance_sq = 1.0
   std::int64_t num_inliers_ = 0;
   LinearizedSystem6 linearized_{};
@@ -529,17 +536,13 @@ public:
   using shared_ptr = std::shared_ptr<IntegratedCT_GICPFactor>;
   IntegratedCT_GICPFactor(Key source_t0_key, Key source_t1_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
                           NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, const double* times = nullptr)
-      : key0_(source_t0_key), key1_(source_t1_key), source_(std::move(source)),
-        tree_(target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target))) {
-    check(glim_amd_ct_gicp_create(tree_->handle(), source_->handle(), times, &h_), "IntegratedCT_GICPFactor");
-  }
+      : IntegratedCT_GICPFactor(source_t0_key, source_t1_key, std::move(source),
+                                target_tree ? std::move(target_tree) : std::make_shared<NearestNeighborSearchGPU>(std::move(target)), nullptr, times) {}
   // IntegratedCT_GICPFactor_<iVox, PointCloud>(X, Y, target_ivox, frame, target_ivox) -- odometry_estimation_ct.cpp:158-160: the factor reads the
   // map as it is at each call and keeps it alive
   IntegratedCT_GICPFactor(Key source_t0_key, Key source_t1_key, IncrementalVoxelMap::Ptr target, PointCloudGPU::ConstPtr source,
                           IncrementalVoxelMap::Ptr target_tree = nullptr, const double* times = nullptr)
-      : key0_(source_t0_key), key1_(source_t1_key), source_(std::move(source)), ivox_(target_tree ? std::move(target_tree) : std::move(target)) {
-    check(glim_amd_ivox_ct_factor_create(ivox_->handle(), source_->handle(), times, &h_), "IntegratedCT_GICPFactor");
-  }
+      : IntegratedCT_GICPFactor(source_t0_key, source_t1_key, std::move(source), nullptr, target_tree ? std::move(target_tree) : std::move(target), times) {}
   ~IntegratedCT_GICPFactor() { glim_amd_ct_gicp_destroy(h_); }
   IntegratedCT_GICPFactor(const IntegratedCT_GICPFactor&) = delete;
   IntegratedCT_GICPFactor& operator=(const IntegratedCT_GICPFactor&) = delete;
@@ -573,6 +576,13 @@ public:
   const glim_amd_ct_linearized& linearized() const { return linearized_; }
 
 private:
+  // where both constructors end: exactly one of `tree` / `ivox` is set (the library's ct_factor_create, mirrored)
+  IntegratedCT_GICPFactor(Key key0, Key key1, PointCloudGPU::ConstPtr source, NearestNeighborSearchGPU::ConstPtr tree, IncrementalVoxelMap::Ptr ivox,
+                          const double* times)
+      : key0_(key0), key1_(key1), source_(std::move(source)), tree_(std::move(tree)), ivox_(std::move(ivox)) {
+    const glim_amd_cloud* s = source_->handle();
+    check(ivox_ ? glim_amd_ivox_ct_factor_create(ivox_->handle(), s, times, &h_) : glim_amd_ct_gicp_create(tree_->handle(), s, times, &h_), "IntegratedCT_GICPFactor");
+  }
   Key key0_, key1_;
   PointCloudGPU::ConstPtr source_;
   NearestNeighborSearchGPU::ConstPtr tree_;
