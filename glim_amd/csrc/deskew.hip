@@ -49,6 +49,7 @@ Pose inverse(const Pose& A) {
 // (oracle/vgicp_oracle.c pose3_expmap_gtsam, itself bit-equal to the compiled reference over the stand-in Pose3.h): R = I + sin(theta) K +
 // (1 - cos(theta)) K^2, K = hat(omega) / theta, 1 - cos(theta) = 2 sin^2(theta / 2); t = (omega x v - R (omega x v) + omega (omega . v)) / theta^2.
 // The table has to carry the oracle's BITS: the deskewed FP64 points are compared bit for bit (tests/test_ref.py).
+// Not gicp.hip's se3_exp, on purpose: that one uses series coefficients near zero and owes nobody its bits.
 Pose se3_exp(const double* xi) {
   const double eps = 2.220446049250313e-16;
   const double w[3] = {xi[0], xi[1], xi[2]}, v[3] = {xi[3], xi[4], xi[5]};

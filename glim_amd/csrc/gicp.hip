@@ -358,13 +358,68 @@ __device__ __forceinline__ void gicp_point(float (&acc)[NACC], float R00, float 
   A[0] = A00; A[1] = A01; A[2] = A02; A[3] = A11; A[4] = A12; A[5] = A22;
 }
 
+// the FP32 rotation of a row-major 3 x 4 pose, entry by entry as gicp_point takes it
+struct Rot32 {
+  float r00, r01, r02, r10, r11, r12, r20, r21, r22;
+  __device__ __forceinline__ explicit Rot32(const double* T)
+      : r00((float)T[0]), r01((float)T[1]), r02((float)T[2]), r10((float)T[4]), r11((float)T[5]), r12((float)T[6]), r20((float)T[8]), r21((float)T[9]), r22((float)T[10]) {}
+};
+
+// The block epilogue of the factor kernels (BLOCK = 4 waves): the order of additions that makes a partial row bit-reproducible.  Every wave sums
+// its lanes into lane 63 (DPP, step-major: device_math.hpp; the same six additions per value) and leaves the sums in s_red[wave]; (0 + 1) + (2 + 3).
+template <int W>
+__device__ __forceinline__ float sum_of_waves(const float (&s_red)[4][W], int j) {
+  return (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]);
+}
+// the 28 accumulators to columns 0..27 of the block's partial row, the inlier count to column 28, zero above
+__device__ __forceinline__ void store_partial_row(float (&acc)[NACC], int inliers, float (&s_red)[4][PARTIAL_STRIDE], float* __restrict__ partials) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_sums_to_lane63<NACC>(acc);
+  if (lane == 63) {
+#pragma unroll
+    for (int j = 0; j < NACC; j++) s_red[wave][j] = acc[j];
+  }
+  const float v = wave_sum_to_lane63((float)inliers);
+  if (lane == 63) s_red[wave][28] = v;
+  __syncthreads();
+  if (threadIdx.x < PARTIAL_STRIDE) {
+    const int j = threadIdx.x;
+    partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = j <= 28 ? sum_of_waves(s_red, j) : 0.f;
+  }
+}
+
+// One group's share of a fixed-order column sum (same order as vgicp.hip's finalize_factor): group g of 8 adds rows g, g + 8, g + 16, ... of
+// column j in that order, with the (clamped) loads of INFLIGHT trips in flight at a time.  The caller then adds the 8 groups in order.
+template <class T, int STRIDE, int INFLIGHT>
+__device__ __forceinline__ double ordered_column_sum(const T* __restrict__ rows, int n, int j, int g) {
+  double s = 0.0;
+  for (int c = g; c < n; c += 8 * INFLIGHT) {
+    T v[INFLIGHT];
+#pragma unroll
+    for (int u = 0; u < INFLIGHT; u++) v[u] = rows[(size_t)min(c + 8 * u, n - 1) * STRIDE + j];
+#pragma unroll
+    for (int u = 0; u < INFLIGHT; u++)
+      if (c + 8 * u < n) s += (double)v[u];
+  }
+  return s;
+}
+
+// row-major upper triangle of a symmetric N x N matrix: entry (r, c), r <= c, is at upper_index<N>(r, c); upper_entry<N> is the way back
+template <int N>
+constexpr int upper_index(int r, int c) {
+  return r * N - r * (r - 1) / 2 + (c - r);
+}
+template <int N>
+constexpr void upper_entry(int u, int& r, int& c) {
+  for (r = 0; u >= N - r; r++) u -= N - r;
+  c = r + u;
+}
+
 template <bool LINEARIZE, class NN>
 __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __restrict__ partials, int32_t* __restrict__ corr, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
   const double* T = a.T;
-  const float R00 = (float)T[0], R01 = (float)T[1], R02 = (float)T[2];
-  const float R10 = (float)T[4], R11 = (float)T[5], R12 = (float)T[6];
-  const float R20 = (float)T[8], R21 = (float)T[9], R22 = (float)T[10];
+  const Rot32 R(T);
   float acc[NACC];
 #pragma unroll
   for (int j = 0; j < NACC; j++) acc[j] = 0.f;
@@ -382,41 +437,18 @@ __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __
     if (j < 0) continue;
     inliers++;
     float A[6];
-    gicp_point<LINEARIZE>(acc, R00, R01, R02, R10, R11, R12, R20, R21, R22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz, A);
+    gicp_point<LINEARIZE>(acc, R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz,
+                          A);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  wave_sums_to_lane63<NACC>(acc);  // (step-major: device_math.hpp; the same six additions per value)
-  if (lane == 63) {
-#pragma unroll
-    for (int j = 0; j < NACC; j++) s_red[wave][j] = acc[j];
-  }
-  {
-    const float v = wave_sum_to_lane63((float)inliers);
-    if (lane == 63) s_red[wave][28] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PARTIAL_STRIDE) {
-    const int j = threadIdx.x;
-    partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = j <= 28 ? (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]) : 0.f;
-  }
+  store_partial_row(acc, inliers, s_red, partials);
 }
 
-// fixed-order FP64 sum of the block partials -> compact record (one block of 256 threads; same order as vgicp.hip's finalise)
+// fixed-order FP64 sum of the block partials -> compact record (one block of 256 threads: 8 groups of ordered_column_sum, then the groups in order)
 __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restrict__ partials, int nb, int linearize, double* __restrict__ out) {
   __shared__ double s_part[8][PARTIAL_STRIDE];
   __shared__ double s_sum[PARTIAL_STRIDE];
   const int j = threadIdx.x & 31, g = threadIdx.x >> 5;
-  double s = 0.0;
-  constexpr int INFLIGHT = 16;  // loads of 16 trips in flight, additions in the same order (see vgicp.hip finalize_factor)
-  for (int c = g; c < nb; c += 8 * INFLIGHT) {
-    float v[INFLIGHT];
-#pragma unroll
-    for (int u = 0; u < INFLIGHT; u++) v[u] = partials[(size_t)min(c + 8 * u, nb - 1) * PARTIAL_STRIDE + j];
-#pragma unroll
-    for (int u = 0; u < INFLIGHT; u++)
-      if (c + 8 * u < nb) s += (double)v[u];
-  }
-  s_part[g][j] = s;
+  s_part[g][j] = ordered_column_sum<float, PARTIAL_STRIDE, 16>(partials, nb, j, g);
   __syncthreads();
   if (threadIdx.x < PARTIAL_STRIDE) {
     double t = 0.0;
@@ -459,9 +491,7 @@ __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const 
   __shared__ float s_red[4][PARTIAL_STRIDE];
   const int4 blk = c.blocks[blockIdx.x];
   const double* T = c.poses + (size_t)blk.x * CT_POSE_STRIDE;
-  const float R00 = (float)T[0], R01 = (float)T[1], R02 = (float)T[2];
-  const float R10 = (float)T[4], R11 = (float)T[5], R12 = (float)T[6];
-  const float R20 = (float)T[8], R21 = (float)T[9], R22 = (float)T[10];
+  const Rot32 R(T);
   float acc[NACC];
 #pragma unroll
   for (int j = 0; j < NACC; j++) acc[j] = 0.f;
@@ -477,10 +507,11 @@ __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const 
     if (j < 0) continue;
     inliers++;
     float A[6];
-    gicp_point<LINEARIZE>(acc, R00, R01, R02, R10, R11, R12, R20, R21, R22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz, A);
+    gicp_point<LINEARIZE>(acc, R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz,
+                          A);
     if (c.keep_m0) {
       // M = R A R^T: the source-frame inverse taken back to the target frame
-      const float Rm[9] = {R00, R01, R02, R10, R11, R12, R20, R21, R22};
+      const float Rm[9] = {R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22};
       const float As[9] = {A[0], A[1], A[2], A[1], A[3], A[4], A[2], A[4], A[5]};
       float W[9];
 #pragma unroll
@@ -495,21 +526,7 @@ __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const 
       c.keep_m1[i] = make_float2(M[4], M[5]);
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  wave_sums_to_lane63<NACC>(acc);
-  if (lane == 63) {
-#pragma unroll
-    for (int j = 0; j < NACC; j++) s_red[wave][j] = acc[j];
-  }
-  {
-    const float v = wave_sum_to_lane63((float)inliers);
-    if (lane == 63) s_red[wave][28] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PARTIAL_STRIDE) {
-    const int j = threadIdx.x;
-    partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = j <= 28 ? (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]) : 0.f;
-  }
+  store_partial_row(acc, inliers, s_red, partials);
 }
 
 // error(): the kept correspondences and M at new poses -- e = sum r^T M r, r = b_j - T_k p_i (FP64, then FP32).  Partial rows hold e (27) and the
@@ -547,8 +564,8 @@ __global__ __launch_bounds__(BLOCK) void ct_error_kernel(const GicpArgs a, const
   if (threadIdx.x < PARTIAL_STRIDE) {
     const int j = threadIdx.x;
     float v = 0.f;
-    if (j == 27) v = (s_red[0][0] + s_red[1][0]) + (s_red[2][0] + s_red[3][0]);
-    if (j == 28) v = (s_red[0][1] + s_red[1][1]) + (s_red[2][1] + s_red[3][1]);
+    if (j == 27) v = sum_of_waves(s_red, 0);
+    if (j == 28) v = sum_of_waves(s_red, 1);
     partials[(size_t)blockIdx.x * PARTIAL_STRIDE + j] = v;
   }
 }
@@ -576,9 +593,8 @@ __global__ __launch_bounds__(64) void ct_bucket_kernel(const float* __restrict__
   }
   __syncthreads();
   if (t < 36) {
-    const int r = t / 6, cc = t % 6, lo = min(r, cc), hi = max(r, cc);
-    const int u = lo * 6 - lo * (lo - 1) / 2 + (hi - lo);  // row-major upper-triangle index
-    s_H[t] = s_sum[c_acc_of_upper_g[u]];
+    const int r = t / 6, cc = t % 6;
+    s_H[t] = s_sum[c_acc_of_upper_g[upper_index<6>(min(r, cc), max(r, cc))]];
   } else if (t < 42) {
     const int m = t - 36;
     s_b[m] = m < 3 ? s_sum[21 + m] : -s_sum[21 + m];
@@ -599,12 +615,8 @@ __global__ __launch_bounds__(64) void ct_bucket_kernel(const float* __restrict__
     } else if (u == 1) {
       v = s_sum[27];
     } else if (u < 80) {
-      int r = 0, idx = u - 2;
-      while (idx >= 12 - r) {
-        idx -= 12 - r;
-        r++;
-      }
-      const int cc = r + idx;
+      int r, cc;
+      upper_entry<12>(u - 2, r, cc);
       v = 0.0;
       for (int m = 0; m < 6; m++) v += s_J[12 * m + r] * s_W[12 * m + cc];
     } else {
@@ -616,22 +628,12 @@ __global__ __launch_bounds__(64) void ct_bucket_kernel(const float* __restrict__
   }
 }
 
-// one block: the bucket rows summed in a fixed order (8 strided groups, then the groups in order) -> the record
+// one block: the bucket rows summed in a fixed order (8 groups of ordered_column_sum, then the groups in order) -> the record
 __global__ __launch_bounds__(768) void ct_sum_kernel(const double* __restrict__ rows, int nbk, double* __restrict__ out) {
   __shared__ double s_part[8][96];
   const int j = threadIdx.x % 96, g = threadIdx.x / 96;
   double s = 0.0;
-  if (j < CT_ROW) {
-    constexpr int INFLIGHT = 8;
-    for (int c = g; c < nbk; c += 8 * INFLIGHT) {
-      double v[INFLIGHT];
-#pragma unroll
-      for (int u = 0; u < INFLIGHT; u++) v[u] = rows[(size_t)min(c + 8 * u, nbk - 1) * CT_ROW + j];
-#pragma unroll
-      for (int u = 0; u < INFLIGHT; u++)
-        if (c + 8 * u < nbk) s += v[u];
-    }
-  }
+  if (j < CT_ROW) s = ordered_column_sum<double, CT_ROW, 8>(rows, nbk, j, g);
   s_part[g][j] = s;
   __syncthreads();
   if (threadIdx.x < CT_ROW) {
@@ -822,6 +824,21 @@ void mm3(const double* A, const double* B, double* C) {
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
 }
+// the rotation of a row-major 3 x 4 pose
+void rot_of(const double* T12, double* R) {
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) R[3 * r + k] = T12[4 * r + k];
+}
+// [[A, 0], [B, A]] from row-major 3 x 3 blocks: the shape of the se(3) Jacobians and of the adjoint below
+Mat6 block6(const double* A, const double* B) {
+  Mat6 M{};
+  for (int r = 0; r < 3; r++)
+    for (int k = 0; k < 3; k++) {
+      M.m[6 * r + k] = M.m[6 * (r + 3) + k + 3] = A[3 * r + k];
+      M.m[6 * (r + 3) + k] = B[3 * r + k];
+    }
+  return M;
+}
 void inv3(const double* A, double* B) {
   const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
   const double id = 1.0 / (A[0] * c00 + A[1] * c01 + A[2] * c02);
@@ -840,7 +857,8 @@ void so3_coeffs(double th, double& b, double& c) {
     c = (th - std::sin(th)) / (t2 * th);
   }
 }
-// Pose3::Expmap: T = [Exp(w) | V(w) v], V = I + b W + c W^2
+// Pose3::Expmap: T = [Exp(w) | V(w) v], V = I + b W + c W^2.  Not deskew.hip's se3_exp, on purpose: that one repeats the oracle's operation order
+// bit for bit, this one uses series coefficients near zero.
 void se3_exp(const double* xi, double* T12) {
   double W[9], W2[9];
   ct_hat(xi, W);
@@ -862,7 +880,8 @@ void se3_exp(const double* xi, double* T12) {
 }
 // Pose3::Logmap: w = Log(R), v = V(w)^-1 t
 void se3_log(const double* T12, double* xi) {
-  const double R[9] = {T12[0], T12[1], T12[2], T12[4], T12[5], T12[6], T12[8], T12[9], T12[10]};
+  double R[9];
+  rot_of(T12, R);
   const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
   const double s = std::sqrt(vx * vx + vy * vy + vz * vz), cth = 0.5 * (R[0] + R[4] + R[8] - 1.0);
   const double th = std::atan2(s, cth);
@@ -880,8 +899,8 @@ void se3_log(const double* T12, double* xi) {
   inv3(V, Vi);
   for (int r = 0; r < 3; r++) xi[3 + r] = Vi[3 * r] * T12[3] + Vi[3 * r + 1] * T12[7] + Vi[3 * r + 2] * T12[11];
 }
-// Pose3::ExpmapDerivative: [[Jw, 0], [Q, Jw]] (Jw = Rot3::ExpmapDerivative, Q = computeQforExpmapDerivative)
-Mat6 se3_jr(const double* xi) {
+// the blocks of Pose3::ExpmapDerivative, [[Jw, 0], [Q, Jw]] (Jw = Rot3::ExpmapDerivative, Q = computeQforExpmapDerivative)
+void se3_jr_blocks(const double* xi, double* Jw, double* Q) {
   double W[9], V[9], W2[9];
   ct_hat(xi, W);
   ct_hat(xi + 3, V);
@@ -889,7 +908,6 @@ Mat6 se3_jr(const double* xi) {
   const double th = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), t2 = th * th;
   double b, c;
   so3_coeffs(th, b, c);
-  double Jw[9];
   for (int u = 0; u < 9; u++) Jw[u] = (u % 4 == 0 ? 1.0 : 0.0) - b * W[u] + c * W2[u];
   double ca, cb, cc;  // (th - sin) / th^3, (1 - th^2/2 - cos) / th^4, -(cb - 3 (th - sin - th^3/6) / th^5) / 2
   if (th < CT_SERIES) {
@@ -911,54 +929,33 @@ Mat6 se3_jr(const double* xi) {
   mm3(V, W2, VWW);
   mm3(WVW, W, WVWW);
   mm3(W, WVW, WWVW);
-  double Q[9];
   for (int u = 0; u < 9; u++)
     Q[u] = -0.5 * V[u] + ca * (WV[u] + VW[u] - WVW[u]) + cb * (WWV[u] + VWW[u] - 3.0 * WVW[u]) + cc * (WVWW[u] + WWVW[u]);
-  Mat6 J{};
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) {
-      J.m[6 * r + k] = Jw[3 * r + k];
-      J.m[6 * (r + 3) + k + 3] = Jw[3 * r + k];
-      J.m[6 * (r + 3) + k] = Q[3 * r + k];
-    }
-  return J;
 }
-// Pose3::LogmapDerivative at Log = xi: the block inverse of se3_jr(xi)
+// Pose3::ExpmapDerivative
+Mat6 se3_jr(const double* xi) {
+  double Jw[9], Q[9];
+  se3_jr_blocks(xi, Jw, Q);
+  return block6(Jw, Q);
+}
+// Pose3::LogmapDerivative at Log = xi: the block inverse of se3_jr(xi), [[Jw^-1, 0], [-Jw^-1 Q Jw^-1, Jw^-1]]
 Mat6 se3_jr_inv(const double* xi) {
-  const Mat6 J = se3_jr(xi);
   double Jw[9], Q[9], Ji[9], T[9], QJ[9];
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) {
-      Jw[3 * r + k] = J.m[6 * r + k];
-      Q[3 * r + k] = J.m[6 * (r + 3) + k];
-    }
+  se3_jr_blocks(xi, Jw, Q);
   inv3(Jw, Ji);
   mm3(Q, Ji, T);
   mm3(Ji, T, QJ);
-  Mat6 I{};
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) {
-      I.m[6 * r + k] = Ji[3 * r + k];
-      I.m[6 * (r + 3) + k + 3] = Ji[3 * r + k];
-      I.m[6 * (r + 3) + k] = -QJ[3 * r + k];
-    }
-  return I;
+  for (double& v : QJ) v = -v;
+  return block6(Ji, QJ);
 }
 // Pose3::AdjointMap: [[R, 0], [hat(t) R, R]]
 Mat6 se3_ad(const double* T12) {
-  const double R[9] = {T12[0], T12[1], T12[2], T12[4], T12[5], T12[6], T12[8], T12[9], T12[10]};
   const double t[3] = {T12[3], T12[7], T12[11]};
-  double H[9], HR[9];
+  double R[9], H[9], HR[9];
+  rot_of(T12, R);
   ct_hat(t, H);
   mm3(H, R, HR);
-  Mat6 A{};
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) {
-      A.m[6 * r + k] = R[3 * r + k];
-      A.m[6 * (r + 3) + k + 3] = R[3 * r + k];
-      A.m[6 * (r + 3) + k] = HR[3 * r + k];
-    }
-  return A;
+  return block6(R, HR);
 }
 Mat6 mm6(const Mat6& A, const Mat6& B) {
   Mat6 C{};

@@ -6,6 +6,8 @@ Storage is the library's documented choice: FP32 points and covariances; an inse
 FP64 with separate roundings, rounds to FP32, and the voxel / the min_dist test use the stored value."""
 import numpy as np
 
+from ct_restatement import hat
+
 KEY_RANGE = 1048576.0  # voxel coordinates live in [-2^20, 2^20)
 
 OFFSETS7 = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
@@ -168,10 +170,6 @@ def search_all(ivox, q, max_d):
     return hits, fragile
 
 
-def hat(v):
-    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
-
-
 def gicp_on_hits(ivox, hits, sp, sc, T):
     """IntegratedGICPFactor_<iVox, PointCloud>::linearize at T given the correspondences: per point M = (C_B + R C_A R^T)^-1, r = b - q,
     J_s = [R hat(p) | -R]; error = sum r^T M r (no 1/2), H_ss = sum J_s^T M J_s, b_s = sum J_s^T M r."""
@@ -198,7 +196,7 @@ def gicp_on_hits(ivox, hits, sp, sc, T):
 
 def ct_on_ivox(ivox, sp, sc, idx, poses, max_d):
     """IntegratedCT_GICPFactor_<iVox, PointCloud>::linearize: point i moves with T[idx[i]]; per bucket the rigid system above, then the chain
-    rule [D0 | D1] (tests/test_ct_gicp.py np_ct_linearize, with the map's search in place of the exact one).  Returns the record, the hits and
+    rule [D0 | D1] (tests/ct_restatement.py np_ct_linearize, with the map's search in place of the exact one).  Returns the record, the hits and
     the fragile set."""
     T, D0, D1 = poses
     out = dict(num_inliers=0, error=0.0, H_00=np.zeros((6, 6)), H_01=np.zeros((6, 6)), H_11=np.zeros((6, 6)), b_0=np.zeros(6), b_1=np.zeros(6))

@@ -3,11 +3,9 @@ global_mapping.cpp:400, global_mapping_pose_graph.cpp:393.  Oracle pins on CPU, 
 import numpy as np
 import pytest
 
+from ct_restatement import gn_step
+
 POSE_TOL = 1e-4  # BASELINE.json north_star: pose delta within 1e-4 m / 1e-4 rad per Gauss-Newton iteration
-
-
-def gn_step(L, lam=0.0):
-    return np.linalg.solve(L["H_ss"] + lam * np.eye(6), -L["b_s"])
 
 
 def np_gicp(tp, tc, sp, sc, T, max_d):
@@ -188,3 +186,121 @@ def test_hip_gicp_edge_cases(orc):
         g.linearize({1: delta})
     g.set_max_correspondence_distance(5.0)  # 5 x the hint the shared index was built with: fine, and still exact
     np.testing.assert_array_equal(g.correspondences({1: delta}), orc.gicp_linearize(tp, tc, sp, sc, delta, 5.0, want_corr=True)["corr"])
+
+
+# ---- the edges of the block epilogue and of the fixed-order sums (gicp.hip store_partial_row, ordered_column_sum) ----------------------
+BLOCK, FINALISER_TRIP, CT_SUM_TRIP = 256, 8 * 16, 8 * 8  # threads per block; rows per trip of gicp_finalize_kernel / ct_sum_kernel
+CT_EDGE_POINTS = 3000
+
+
+def rigid_edge_sizes(num_cus):
+    """1 point, one thread short of a block, a full block, one block and a point, and the smallest source that makes one block more than
+    a full finaliser trip -- with the points per thread that gicp.hip's points_per_thread picks on a device of num_cus compute units"""
+    def blocks(n):
+        ppt = max(1, min(64, -(-n // (BLOCK * 4 * num_cus))))
+        return -(-n // (BLOCK * ppt))
+
+    return [1, BLOCK - 1, BLOCK, BLOCK + 1, next(n for n in range(1, 1 << 24) if blocks(n) == FINALISER_TRIP + 1)]
+
+
+def rigid_edge_subset(sp, n):
+    return np.arange(n) * (len(sp) // n)  # spread over the whole scan, so that every size but 1 gives a well-posed system
+
+
+def ct_edge_times(buckets, n=CT_EDGE_POINTS):
+    """times that make `buckets` equal time buckets of a source of n points; from 3 buckets on, the middle bucket keeps a single point and
+    hands the rest to the next one (with 2 buckets a single-point bucket would leave the 6 dof of one key to a rank-3 system)"""
+    k = (np.arange(n) * buckets) // n
+    if buckets >= 3:
+        k[np.flatnonzero(k == buckets // 2)[1:]] += 1
+    return k * 0.002
+
+
+CT_EDGE_BUCKETS = [1, 2, CT_SUM_TRIP, CT_SUM_TRIP + 1]
+CT_EDGE_X, CT_EDGE_Y = [0.001, 0.0, 0.002, 0.02, 0.01, 0.0], [0.0, -0.001, 0.0, 0.0, 0.02, -0.01]
+
+
+def test_gicp_sum_edge_cases_all_have_inliers(orc):
+    """the cases of test_gicp_sum_edges on the CPU: the correspondences need no covariances, so identity ones stand in"""
+    from glim_amd import synth
+    from ct_restatement import expmap, moving_source, np_ct_linearize, static_map, sweep_poses, time_table
+    from scipy.spatial import cKDTree
+
+    poses = synth.arc_trajectory(2, step=0.6, yaw_step_deg=3.0)
+    dirs = synth.lidar_directions(64, 1024)
+    tp, sp = (synth.scan(synth.Scene.default(), T, dirs, frame_id=i).astype(np.float64) for i, T in enumerate(poses))
+    T = np.linalg.inv(poses[0]) @ poses[1] @ orc.se3_exp([0.004, -0.003, 0.002, 0.03, 0.02, -0.01])
+    sizes = rigid_edge_sizes(256)
+    assert sizes == [1, 255, 256, 257, 128 * 256 + 1] and len(sp) >= sizes[-1]
+    tree = cKDTree(tp)
+    for n in sizes:
+        q = sp[rigid_edge_subset(sp, n)] @ T[:3, :3].T + T[:3, 3]
+        assert (tree.query(q, k=1)[0] <= 1.0).sum() > 0, n
+    tp = static_map(16, 512)
+    p, _ = moving_source(16, 256)
+    sp = p[:CT_EDGE_POINTS]
+    eye = lambda m: np.tile(np.eye(3), (m, 1, 1))
+    T0, T1 = sweep_poses()
+    for buckets in CT_EDGE_BUCKETS:
+        times = ct_edge_times(buckets)
+        table, idx = time_table(times)
+        assert len(table) == buckets and (buckets < 3 or (idx == buckets // 2).sum() == 1)
+        L = np_ct_linearize(orc, tp, eye(len(tp)), sp, eye(len(sp)), times, T0 @ expmap(CT_EDGE_X), T1 @ expmap(CT_EDGE_Y), 1.0)
+        assert L["num_inliers"] > 0 and (L["corr"][idx == buckets // 2] >= 0).any(), buckets  # the single-point bucket has its inlier too
+
+
+@pytest.mark.gpu
+def test_gicp_sum_edges(orc):
+    """Rigid and continuous-time records at the sizes where the shared block epilogue and the ordered column sum change path, against the FP64
+    restatements (np_gicp, np_ct_linearize) at the tolerances of test_hip_gicp_matches_oracle and of ct_restatement._check_record.  The GN
+    step of the rigid record is compared from BLOCK - 1 points on: one point gives a rank-3 system, whose step the regulariser decides."""
+    from ct_restatement import _check_record, _target, expmap, moving_source, np_ct_linearize, sweep_poses, time_table
+    from glim_amd import api
+
+    ctx = api.Context(0, 1)
+    ((tp, tc, tg), (sp, sc, sg)), delta = clouds(orc, api, ctx, rings=64, az=1024)
+    T = delta @ orc.se3_exp([0.004, -0.003, 0.002, 0.03, 0.02, -0.01])
+    sizes = rigid_edge_sizes(ctx.device_info()["num_cus"])
+    assert len(sp) >= sizes[-1]
+    owner = api.IntegratedGICPFactor(np.eye(4), 1, tg, sg, max_correspondence_distance=1.0)  # owns the index the cases borrow: lives to the end
+    for n in sizes:
+        sel = rigid_edge_subset(sp, n)
+        g = api.PointCloudGPU.clone(sp[sel], covs=sc[sel], ctx=ctx)
+        f = api.IntegratedGICPFactor(np.eye(4), 1, tg, g, target_tree=owner.target_tree, max_correspondence_distance=1.0)
+        got, e = f.linearize({1: T}), f.error({1: T})
+        ref = np_gicp(tp, tc, sp[sel], sc[sel], T, 1.0)
+        print(f"rigid {n} points: inliers {got['num_inliers']} / {ref['num_inliers']}, error {got['error']:.9g} / {e:.9g} / {ref['error']:.9g}")
+        assert got["num_inliers"] == ref["num_inliers"] > 0
+        scale = np.abs(ref["H_ss"]).max()
+        np.testing.assert_allclose(got["error"], ref["error"], rtol=2e-4)
+        np.testing.assert_allclose(got["H_ss"], ref["H_ss"], rtol=0, atol=2e-4 * scale)
+        np.testing.assert_allclose(got["b_s"], ref["b_s"], rtol=0, atol=2e-4 * np.abs(ref["b_s"]).max() + 1e-6 * scale)
+        assert abs(e - ref["error"]) <= 2e-4 * ref["error"]
+        if n > 1:
+            lam = 1e-6 * np.trace(ref["H_ss"]) / 6
+            assert np.abs(gn_step(got, lam) - gn_step(ref, lam)).max() < POSE_TOL
+        f.close()
+        g.close()
+    owner.close()
+    # continuous-time: 1, 2, one full trip and one trip + 1 buckets; the middle bucket of the last two holds one point
+    tp, tc, tg = _target(api, ctx, 16, 512)
+    p, _ = moving_source(16, 256)
+    g = api.PointCloudGPU.clone(p[:CT_EDGE_POINTS], ctx=ctx)
+    g.find_neighbors(10, download=False)
+    g.estimate_covariances(10)
+    sp, sc, _ = g.download(covs=True, normals=False)
+    sp, sc = sp.astype(np.float64), sc.astype(np.float64)
+    T0, T1 = sweep_poses()
+    vals = {0: T0 @ expmap(CT_EDGE_X), 1: T1 @ expmap(CT_EDGE_Y)}
+    for buckets in CT_EDGE_BUCKETS:
+        times = ct_edge_times(buckets)
+        f = api.IntegratedCT_GICPFactor(0, 1, tg, g, times=times)
+        tab, Tk, D0, D1, idx = f.debug_poses(vals)
+        assert len(tab) == buckets and (buckets < 3 or (idx == buckets // 2).sum() == 1)
+        np.testing.assert_array_equal(idx, time_table(times)[1])
+        got, e = f.linearize(vals), f.error(vals)
+        ref = np_ct_linearize(orc, tp, tc, sp, sc, times, vals[0], vals[1], 1.0, poses=(Tk, D0, D1))
+        print(f"ct {buckets} buckets: inliers {got['num_inliers']} / {ref['num_inliers']}, error {got['error']:.9g} / {e:.9g} / {ref['error']:.9g}")
+        _check_record(got, ref)
+        np.testing.assert_allclose(e, ref["error"], rtol=2e-4)
+        f.close()

@@ -9,8 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import ct_restatement as ctg
 import ivox_restatement as ivr
-import test_ct_gicp as ctg
+from ct_restatement import _prior
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POSE_TOL = 1e-4
@@ -413,12 +414,6 @@ def test_ct_factor_on_the_map_matches_the_restatement_on_a_moving_scan(gpu_ctx, 
         dev.close()
     f.close()
     dev.close()
-
-
-def _prior(T, T0, prec):
-    xi = ctg.logmap(np.linalg.inv(T0) @ T)
-    J = np.linalg.inv(ctg.expmap_derivative(xi))
-    return prec * J.T @ J, prec * J.T @ xi, prec * xi @ xi
 
 
 def _between_identity(X, Y, prec):

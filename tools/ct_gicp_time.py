@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from glim_amd import api
-    import test_ct_gicp as W  # the workload builders of the parity tests (static map, moving sweep)
+    import ct_restatement as W  # the workload builders of the parity tests (static map, moving sweep)
 
     ctx = api.Context(0, 1)
     tp = W.static_map(64, 1024)

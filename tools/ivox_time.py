@@ -36,7 +36,7 @@ def main():
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from glim_amd import api, synth
-    import test_ct_gicp as W
+    import ct_restatement as W
 
     ctx = api.Context(0, 1)
     scene = synth.Scene.default()
