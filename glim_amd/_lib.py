@@ -162,7 +162,12 @@ SYMBOLS = {
     "glim_amd_ivox_ct_factor_create": (_i, [_vp, _vp, _dp, _pp]),
     "glim_amd_debug_ivox_set_initial_capacity": (_i, [_vp, _i32]),
     "glim_amd_debug_ivox_capacity": (_i, [_vp, _ip, _ip]),
-    "glim_amd_merge_frames": (_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
+    "glim_amd_fpfh_estimate": (_i, [_vp, _d, _pp]),
+    "glim_amd_fpfh_destroy": (_i, [_vp]),
+    "glim_amd_fpfh_size": (_i, [_vp, _lp]),
+    "glim_amd_fpfh_download": (_i, [_vp, _fp]),
+    "glim_amd_fpfh_match": (_i, [_vp, _vp, _u32, _ip, _fp]),
+    "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "glim_amd_cloud_destroy": (_i, [_vp]),

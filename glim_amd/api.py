@@ -299,6 +299,12 @@ class PointCloudGPU:
         """CloudCovarianceEstimation::estimate on the device (fills covs + normals)."""
         check(lib().glim_amd_cloud_estimate_covariances(self._h, int(k_neighbors)), "glim_amd_cloud_estimate_covariances")
 
+    def estimate_fpfh(self, search_radius):
+        """gtsam_points::estimate_fpfh on the device (the cloud needs normals): FPFHFeatures, row i = point i."""
+        h = C.c_void_p()
+        check(lib().glim_amd_fpfh_estimate(self._h, float(search_radius), C.byref(h)), "glim_amd_fpfh_estimate")
+        return FPFHFeatures(h, self.ctx)
+
     def download(self, covs=True, normals=True):
         n = self.size()
         xyz = np.zeros((n, 3), dtype=np.float32)
@@ -317,6 +323,49 @@ class PointCloudGPU:
             self.close()
         except Exception:
             pass
+
+
+FPFH_DIM = 33
+FPFH_RECIPROCAL = 0x1
+
+
+class FPFHFeatures:
+    """n x 33 FP32 FPFH descriptors on the device (glim_amd_fpfh; semantics in include/glim_amd.h)."""
+
+    def __init__(self, handle, ctx):
+        self._h = handle
+        self.ctx = ctx
+
+    def size(self):
+        n = C.c_int64()
+        check(lib().glim_amd_fpfh_size(self._h, C.byref(n)), "glim_amd_fpfh_size")
+        return n.value
+
+    def download(self):
+        out = np.zeros((self.size(), FPFH_DIM), dtype=np.float32)
+        check(lib().glim_amd_fpfh_download(self._h, _fp(out)), "glim_amd_fpfh_download")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().glim_amd_fpfh_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_fpfh(target, source, reciprocal=False):
+    """Nearest target descriptor of every source descriptor (squared L2, ties to the smaller index): (nearest int32, sqdist float32), one entry
+    per source row.  reciprocal: nearest is -1 unless the source row is also the nearest source of its target (GNC's reciprocal_check)."""
+    n = source.size()
+    nearest = np.full(n, -1, dtype=np.int32)
+    sqdist = np.full(n, np.inf, dtype=np.float32)
+    check(lib().glim_amd_fpfh_match(target._h, source._h, FPFH_RECIPROCAL if reciprocal else 0, _ip(nearest), _fp(sqdist)), "glim_amd_fpfh_match")
+    return nearest, sqdist
 
 
 class GaussianVoxelMapGPU:

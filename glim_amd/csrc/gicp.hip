@@ -1464,3 +1464,6 @@ int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* f, const double*
 }
 
 }  // extern "C"
+
+// FPFH descriptors and descriptor matching (fpfh.hip): compiled as part of this translation unit, see the head of that file
+#include "fpfh.hip"

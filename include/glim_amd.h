@@ -441,6 +441,39 @@ int glim_amd_overlap(glim_amd_ctx* ctx, int32_t num_targets, const glim_amd_voxe
 int glim_amd_overlap_batch(glim_amd_ctx* ctx, int32_t num_queries, const int32_t* num_targets, const glim_amd_voxelmap* const* targets,
                            const double* T_target_source, const glim_amd_cloud* const* sources, double* overlaps);
 
+/* ---- FPFH: gtsam_points::estimate_fpfh and the nearest-descriptor queries of global registration
+ *      (viewer/interactive/manual_loop_close_modal.cpp:376-463: estimate_fpfh on both clouds, KdTreeX<FPFH_DIM> over the 33-D descriptors,
+ *      RANSAC / GNC on nearest-descriptor correspondences).  RANSAC and GNC themselves stay with the caller: they consume the correspondence
+ *      list glim_amd_fpfh_match returns.
+ * The descriptor follows PCL's FPFHEstimation, which gtsam_points follows as far as recalled; the gtsam_points source is not in the
+ * reference tree, so the points below that PCL leaves open are guesses (listed as such in DESIGN.md 4.7):
+ *   neighbours   N(i) = { j : 0 < d2_ij <= r^2 }, d2 = (dx^2 + dy^2) + dz^2 in FP64 from the cloud's FP32 coordinates (zero-distance pairs,
+ *                the point itself among them, are skipped; no cap on the neighbour count).  k = |N(i)|.
+ *   pair (i, j)  FP64 throughout.  dp = p_j - p_i, f4 = |dp|, a1 = n_i.dp / f4, a2 = n_j.dp / f4.  If |a1| < |a2| the roles swap:
+ *                n1 = n_j, n2 = n_i, dp = -dp, f3 = -a2; otherwise n1 = n_i, n2 = n_j, f3 = a1.  v = dp x n1; a pair with |v| = 0 is skipped
+ *                (it still counts in k, as in PCL); v /= |v|, w = n1 x v, f2 = v.n2, f1 = atan2(w.n2, n1.n2).
+ *                bins b1 = floor(11 (f1 + pi) / (2 pi)), b2 = floor(11 (f2 + 1) / 2), b3 = floor(11 (f3 + 1) / 2), each clamped to 0..10.
+ *   SPFH         S_i = 33 counts over N(i) (bins 0..10 by b1, 11..21 by b2, 22..32 by b3), each count * 100 / k; all zero when k = 0.
+ *   FPFH         F_i = sum over j in N(i) of S_j * (1 / d2_ij), accumulated in FP64 (the query's own SPFH is not added); each 11-bin block is
+ *                then rescaled to sum 100 unless its sum is 0; ONE rounding to FP32.
+ * A point with a non-finite coordinate has no neighbours and is nobody's neighbour: its row is all zero.
+ * Deterministic: two calls on the same cloud return the same bits (fixed candidate order, fixed reduction tree, no floating-point atomics). */
+typedef struct glim_amd_fpfh glim_amd_fpfh; /* n x 33 FP32 descriptors on the device; a child of the cloud's context */
+/* GLIM_AMD_ERR_STATE: the cloud has no normals.  GLIM_AMD_ERR_INVALID: search_radius is NaN, infinite or <= 0. */
+int glim_amd_fpfh_estimate(const glim_amd_cloud* cloud, double search_radius, glim_amd_fpfh** out);
+int glim_amd_fpfh_destroy(glim_amd_fpfh* fpfh);
+int glim_amd_fpfh_size(const glim_amd_fpfh* fpfh, int64_t* n);
+/* descriptors33: n x 33 floats, row i = point i of the cloud */
+int glim_amd_fpfh_download(const glim_amd_fpfh* fpfh, float* descriptors33);
+/* Nearest target descriptor of every source descriptor (the KdTreeX<FPFH_DIM> knn_search(k = 1) loop).  nearest[i] (source size, may be NULL)
+ * = index of the target descriptor with the smallest squared L2 distance, ties to the smaller index; sqdist[i] (may be NULL) = that distance.
+ * FP32 arithmetic: d = (|a|^2 + |b|^2) - 2 a.b, clamped at 0, every sum one FMA chain over the 33 bins in order; error bound
+ * 36 * 2^-24 * (|a|^2 + |b|^2).  GLIM_AMD_FPFH_RECIPROCAL: nearest[i] becomes -1 unless source i is also the nearest source descriptor of
+ * target nearest[i] (same rule, same arithmetic -- GNC's reciprocal_check); sqdist[i] stays the forward distance.  An empty target gives
+ * nearest = -1 and sqdist = +infinity.  Both handles must belong to one context (GLIM_AMD_ERR_INVALID otherwise). */
+#define GLIM_AMD_FPFH_RECIPROCAL 0x1
+int glim_amd_fpfh_match(const glim_amd_fpfh* target, const glim_amd_fpfh* source, uint32_t flags, int32_t* nearest, float* sqdist);
+
 #ifdef __cplusplus
 }
 #endif
