@@ -71,6 +71,31 @@ class PreprocessParams(C.Structure):
     ]
 
 
+class RansacParams(C.Structure):
+    """glim_amd_ransac_params (include/glim_amd.h "RANSAC") == gtsam_points::RANSACParams as manual_loop_close_modal.cpp:435-441 fills it."""
+
+    _fields_ = [
+        ("max_iterations", C.c_int32),
+        ("early_stop_inlier_rate", C.c_double),
+        ("poly_error_thresh", C.c_double),
+        ("inlier_voxel_resolution", C.c_double),
+        ("dof", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class RegistrationResult(C.Structure):
+    """glim_amd_registration_result"""
+
+    _fields_ = [
+        ("T_target_source", C.c_double * 12),
+        ("inlier_rate", C.c_double),
+        ("num_inliers", C.c_int64),
+        ("best_iteration", C.c_int32),
+        ("iterations_run", C.c_int32),
+    ]
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -167,6 +192,13 @@ SYMBOLS = {
     "glim_amd_fpfh_size": (_i, [_vp, _lp]),
     "glim_amd_fpfh_download": (_i, [_vp, _fp]),
     "glim_amd_fpfh_match": (_i, [_vp, _vp, _u32, _ip, _fp]),
+    "glim_amd_fpfh_create": (_i, [_vp, _i64, _fp, _pp]),
+    "glim_amd_ransac_default_params": (_i, [C.POINTER(RansacParams)]),
+    "glim_amd_ransac_align": (_i, [_vp, _vp, _ip, C.POINTER(RansacParams), C.POINTER(RegistrationResult)]),
+    "glim_amd_ransac_align_fpfh": (_i, [_vp, _vp, _vp, _vp, _u32, C.POINTER(RansacParams), C.POINTER(RegistrationResult)]),
+    "glim_amd_ransac_debug_hypotheses": (_i, [_vp, _vp, _ip, C.POINTER(RansacParams), _i32, _i32, _ip, _ip, _dp, _ip, _ip, _ip]),
+    "glim_amd_debug_ransac_max_lds_slots": (_i, [_i32]),
+    "glim_amd_ransac_profile": (_i, [_vp, _vp, _ip, C.POINTER(RansacParams), _i, _fp, _fp, _fp, _ip, _ip]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

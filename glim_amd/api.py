@@ -346,6 +346,15 @@ class FPFHFeatures:
         check(lib().glim_amd_fpfh_download(self._h, _fp(out)), "glim_amd_fpfh_download")
         return out
 
+    @classmethod
+    def from_host(cls, descriptors, ctx=None):
+        """descriptors that are already on the host (n x 33, narrowed to FP32) as a device object: glim_amd_fpfh_create"""
+        ctx = ctx or default_context()
+        d = np.ascontiguousarray(descriptors, dtype=np.float32).reshape(-1, FPFH_DIM)
+        h = C.c_void_p()
+        check(lib().glim_amd_fpfh_create(ctx._h, len(d), _fp(d), C.byref(h)), "glim_amd_fpfh_create")
+        return cls(h, ctx)
+
     def close(self):
         if self._h:
             lib().glim_amd_fpfh_destroy(self._h)
@@ -366,6 +375,79 @@ def match_fpfh(target, source, reciprocal=False):
     sqdist = np.full(n, np.inf, dtype=np.float32)
     check(lib().glim_amd_fpfh_match(target._h, source._h, FPFH_RECIPROCAL if reciprocal else 0, _ip(nearest), _fp(sqdist)), "glim_amd_fpfh_match")
     return nearest, sqdist
+
+
+class RansacParams:
+    """gtsam_points::RANSACParams (glim_amd_ransac_params); the defaults are the loop-close modal's."""
+
+    def __init__(self, max_iterations=5000, early_stop_inlier_rate=0.9, poly_error_thresh=0.5, inlier_voxel_resolution=1.0, dof=6, seed=0):
+        self.max_iterations = max_iterations
+        self.early_stop_inlier_rate = early_stop_inlier_rate
+        self.poly_error_thresh = poly_error_thresh
+        self.inlier_voxel_resolution = inlier_voxel_resolution
+        self.dof = dof
+        self.seed = seed
+
+    def _c(self):
+        return _lib.RansacParams(int(self.max_iterations), float(self.early_stop_inlier_rate), float(self.poly_error_thresh),
+                                 float(self.inlier_voxel_resolution), int(self.dof), int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class RegistrationResult:
+    """gtsam_points::RegistrationResult: T_target_source (4 x 4), inlier_rate; plus num_inliers, best_iteration (-1: none), iterations_run"""
+
+    def __init__(self, c):
+        self.T_target_source = np.eye(4)
+        self.T_target_source[:3, :4] = np.array(c.T_target_source[:], dtype=np.float64).reshape(3, 4)
+        self.inlier_rate = c.inlier_rate
+        self.num_inliers = c.num_inliers
+        self.best_iteration = c.best_iteration
+        self.iterations_run = c.iterations_run
+
+
+def ransac_align(target, source, nearest, params=None):
+    """gtsam_points::estimate_pose_ransac on the device: nearest[i] = target point matched to source point i, or -1 (match_fpfh's output)."""
+    prm = (params or RansacParams())._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    if near.shape != (source.size(),):
+        raise ValueError("nearest must hold one entry per source point")
+    out = _lib.RegistrationResult()
+    check(lib().glim_amd_ransac_align(target._h, source._h, _ip(near), C.byref(prm), C.byref(out)), "glim_amd_ransac_align")
+    return RegistrationResult(out)
+
+
+def ransac_align_fpfh(target, source, target_fpfh, source_fpfh, params=None, reciprocal=False):
+    """The same with the nearest-descriptor correspondences found on the device (they never visit the host)."""
+    prm = (params or RansacParams())._c()
+    out = _lib.RegistrationResult()
+    check(lib().glim_amd_ransac_align_fpfh(target._h, source._h, target_fpfh._h, source_fpfh._h, FPFH_RECIPROCAL if reciprocal else 0, C.byref(prm),
+                                           C.byref(out)), "glim_amd_ransac_align_fpfh")
+    return RegistrationResult(out)
+
+
+def ransac_debug_hypotheses(target, source, nearest, params, first, count):
+    """Test window (glim_amd_ransac_debug_hypotheses): every hypothesis of [first, first + count) scored, no early stop."""
+    prm = params._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    samples = np.zeros((count, 3), dtype=np.int32)
+    status = np.zeros(count, dtype=np.int32)
+    poses = np.zeros((count, 12), dtype=np.float64)
+    inliers = np.zeros(count, dtype=np.int32)
+    slots, in_lds = C.c_int32(), C.c_int32()
+    check(lib().glim_amd_ransac_debug_hypotheses(target._h, source._h, _ip(near), C.byref(prm), int(first), int(count), _ip(samples), _ip(status),
+                                                 _dp(poses), _ip(inliers), C.byref(slots), C.byref(in_lds)), "glim_amd_ransac_debug_hypotheses")
+    return {"samples": samples, "status": status, "poses": poses, "inliers": inliers, "table_slots": slots.value, "table_in_lds": in_lds.value}
+
+
+def ransac_profile(target, source, nearest, params, iters=20):
+    """microseconds of the hypothesis / scoring / fold kernels of one round (HIP events inside the library)"""
+    prm = params._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    us = [C.c_float() for _ in range(3)]
+    slots, in_lds = C.c_int32(), C.c_int32()
+    check(lib().glim_amd_ransac_profile(target._h, source._h, _ip(near), C.byref(prm), int(iters), C.byref(us[0]), C.byref(us[1]), C.byref(us[2]),
+                                        C.byref(slots), C.byref(in_lds)), "glim_amd_ransac_profile")
+    return {"hypothesis_us": us[0].value, "score_us": us[1].value, "fold_us": us[2].value, "table_slots": slots.value, "table_in_lds": in_lds.value}
 
 
 class GaussianVoxelMapGPU:

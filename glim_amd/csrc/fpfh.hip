@@ -418,6 +418,35 @@ inline void match_splits(const glim_amd_ctx* ctx, int na, int nb, int* splits, i
   *splits = (b_tiles + *tiles_per_split - 1) / *tiles_per_split;
 }
 
+// the device side of glim_amd_fpfh_match: nearest target row of every source row into b->fwd_i / b->fwd_d, the reciprocal pass when asked for.
+// Both sets are non-empty; the caller holds ctx->mu, synchronises `st` and keeps `b` until then.
+struct MatchBuffers {
+  DeviceTemp part_d, part_i, fwd_d, fwd_i, back_d, back_i;
+};
+int enqueue_match_both(glim_amd_ctx* ctx, hipStream_t st, const glim_amd_fpfh* target, const glim_amd_fpfh* source, uint32_t flags, MatchBuffers* b) {
+  const int na = (int)source->n, nb = (int)target->n;
+  const bool reciprocal = (flags & GLIM_AMD_FPFH_RECIPROCAL) != 0;
+  int splits_f = 1, tps_f = 1, splits_b = 1, tps_b = 1;
+  match_splits(ctx, na, nb, &splits_f, &tps_f);
+  if (reciprocal) match_splits(ctx, nb, na, &splits_b, &tps_b);
+  const size_t part = std::max((size_t)splits_f * na, reciprocal ? (size_t)splits_b * nb : (size_t)0);
+  GA_HIP(pool_malloc(&b->part_d.p, part * sizeof(float)));
+  GA_HIP(pool_malloc(&b->part_i.p, part * sizeof(int)));
+  GA_HIP(pool_malloc(&b->fwd_d.p, (size_t)na * sizeof(float)));
+  GA_HIP(pool_malloc(&b->fwd_i.p, (size_t)na * sizeof(int)));
+  GA_TRY(enqueue_match(ctx, st, source->desc, na, target->desc, nb, b->part_d.as<float>(), b->part_i.as<int>(), splits_f, tps_f, b->fwd_d.as<float>(),
+                       b->fwd_i.as<int>()));
+  if (reciprocal) {
+    GA_HIP(pool_malloc(&b->back_d.p, (size_t)nb * sizeof(float)));
+    GA_HIP(pool_malloc(&b->back_i.p, (size_t)nb * sizeof(int)));
+    GA_TRY(enqueue_match(ctx, st, target->desc, nb, source->desc, na, b->part_d.as<float>(), b->part_i.as<int>(), splits_b, tps_b, b->back_d.as<float>(),
+                         b->back_i.as<int>()));
+    match_reciprocal_kernel<<<(na + 255) / 256, 256, 0, st>>>(na, nb, b->back_i.as<int>(), b->fwd_i.as<int>());
+    GA_HIP(hipGetLastError());
+  }
+  return GLIM_AMD_OK;
+}
+
 }  // namespace fpfh_detail
 }  // namespace glim_amd
 
@@ -564,27 +593,11 @@ int glim_amd_fpfh_match(const glim_amd_fpfh* target, const glim_amd_fpfh* source
   std::lock_guard<std::mutex> lock(ctx->mu);
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
-  const bool reciprocal = (flags & GLIM_AMD_FPFH_RECIPROCAL) != 0;
-  int splits_f = 1, tps_f = 1, splits_b = 1, tps_b = 1;
-  match_splits(ctx, na, nb, &splits_f, &tps_f);
-  if (reciprocal) match_splits(ctx, nb, na, &splits_b, &tps_b);
-  const size_t part = std::max((size_t)splits_f * na, reciprocal ? (size_t)splits_b * nb : (size_t)0);
-  DeviceTemp part_d, part_i, fwd_d, fwd_i, back_d, back_i;
+  MatchBuffers m;
   SyncOnExit in_flight(st);
-  GA_HIP(pool_malloc(&part_d.p, part * sizeof(float)));
-  GA_HIP(pool_malloc(&part_i.p, part * sizeof(int)));
-  GA_HIP(pool_malloc(&fwd_d.p, (size_t)na * sizeof(float)));
-  GA_HIP(pool_malloc(&fwd_i.p, (size_t)na * sizeof(int)));
-  GA_TRY(enqueue_match(ctx, st, source->desc, na, target->desc, nb, part_d.as<float>(), part_i.as<int>(), splits_f, tps_f, fwd_d.as<float>(), fwd_i.as<int>()));
-  if (reciprocal) {
-    GA_HIP(pool_malloc(&back_d.p, (size_t)nb * sizeof(float)));
-    GA_HIP(pool_malloc(&back_i.p, (size_t)nb * sizeof(int)));
-    GA_TRY(enqueue_match(ctx, st, target->desc, nb, source->desc, na, part_d.as<float>(), part_i.as<int>(), splits_b, tps_b, back_d.as<float>(), back_i.as<int>()));
-    match_reciprocal_kernel<<<(na + 255) / 256, 256, 0, st>>>(na, nb, back_i.as<int>(), fwd_i.as<int>());
-    GA_HIP(hipGetLastError());
-  }
-  if (nearest) GA_HIP(hipMemcpyAsync(nearest, fwd_i.p, (size_t)na * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (sqdist) GA_HIP(hipMemcpyAsync(sqdist, fwd_d.p, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
+  GA_TRY(enqueue_match_both(ctx, st, target, source, flags, &m));
+  if (nearest) GA_HIP(hipMemcpyAsync(nearest, m.fwd_i.p, (size_t)na * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (sqdist) GA_HIP(hipMemcpyAsync(sqdist, m.fwd_d.p, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
   return GLIM_AMD_OK;

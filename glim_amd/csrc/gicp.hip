@@ -1467,3 +1467,6 @@ int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* f, const double*
 
 // FPFH descriptors and descriptor matching (fpfh.hip): compiled as part of this translation unit, see the head of that file
 #include "fpfh.hip"
+
+// RANSAC global registration over those correspondences (ransac.hip): likewise, and after fpfh.hip, whose descriptor object and matcher it uses
+#include "ransac.hip"

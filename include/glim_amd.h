@@ -443,8 +443,8 @@ int glim_amd_overlap_batch(glim_amd_ctx* ctx, int32_t num_queries, const int32_t
 
 /* ---- FPFH: gtsam_points::estimate_fpfh and the nearest-descriptor queries of global registration
  *      (viewer/interactive/manual_loop_close_modal.cpp:376-463: estimate_fpfh on both clouds, KdTreeX<FPFH_DIM> over the 33-D descriptors,
- *      RANSAC / GNC on nearest-descriptor correspondences).  RANSAC and GNC themselves stay with the caller: they consume the correspondence
- *      list glim_amd_fpfh_match returns.
+ *      RANSAC / GNC on nearest-descriptor correspondences).  RANSAC is the section after this one; GNC stays with the caller: it consumes the
+ *      correspondence list glim_amd_fpfh_match returns.
  * The descriptor follows PCL's FPFHEstimation, which gtsam_points follows as far as recalled; the gtsam_points source is not in the
  * reference tree, so the points below that PCL leaves open are guesses (listed as such in DESIGN.md 4.7):
  *   neighbours   N(i) = { j : 0 < d2_ij <= r^2 }, d2 = (dx^2 + dy^2) + dz^2 in FP64 from the cloud's FP32 coordinates (zero-distance pairs,
@@ -473,6 +473,69 @@ int glim_amd_fpfh_download(const glim_amd_fpfh* fpfh, float* descriptors33);
  * nearest = -1 and sqdist = +infinity.  Both handles must belong to one context (GLIM_AMD_ERR_INVALID otherwise). */
 #define GLIM_AMD_FPFH_RECIPROCAL 0x1
 int glim_amd_fpfh_match(const glim_amd_fpfh* target, const glim_amd_fpfh* source, uint32_t flags, int32_t* nearest, float* sqdist);
+
+/* Descriptors that are already on the host (n x 33 floats, row i = point i) as a device object of context `ctx`; the row's squared norm the
+ * matcher reads is filled in exactly as glim_amd_fpfh_estimate fills it (the same FP32 FMA chain), so matching an uploaded set and matching the
+ * set it was downloaded from give the same bits. */
+int glim_amd_fpfh_create(glim_amd_ctx* ctx, int64_t n, const float* descriptors33, glim_amd_fpfh** out);
+
+/* ---- RANSAC: gtsam_points::estimate_pose_ransac, the global registration of viewer/interactive/manual_loop_close_modal.cpp:431-443
+ *      (target, source, their FPFH descriptors, two search trees, RANSACParams{max_iterations 5000, early_stop_inlier_rate 0.9,
+ *      inlier_voxel_resolution 1.0, dof 4 | 6, seed}).  GNC (estimate_pose_gnc) is not provided.
+ * The gtsam_points source is not in the reference tree: what follows is a restatement from recall plus decisions (listed in DESIGN.md 4.7a).
+ *   inputs       target and source device clouds (points only), nearest[i] = matched target point of source point i or -1, the parameters.
+ *   occupancy    the set of voxel coordinates fast_floor(p * (1 / res)) of every target point: FP64 product of the FP32 coordinate, 21 bits per
+ *                axis, range [-2^20, 2^20).  A target point outside the range or not finite is simply absent.
+ *   hypothesis   `it` (0-based), independent of every other:
+ *     draw       s_k = splitmix64(seed, 3 it + k) mod N_source, k = 0 1 2 (the counter-based generator of glim_amd_preprocess, in place of the
+ *                reference's sequential std::mt19937); t_k = nearest[s_k].
+ *     status     the first that applies; only 0 is scored:
+ *                1  some t_k < 0
+ *                2  two equal s_k or two equal t_k
+ *                3  edge lengths: for the edges (0,1), (1,2), (2,0), d_s = |s_a - s_b| and d_t = |t_a - t_b| in FP64, (dx^2 + dy^2) + dz^2 under
+ *                   the root; rejected unless min(d_s, d_t) >= (1 - poly_error_thresh) * max(d_s, d_t).  The rule is stated for finite
+ *                   lengths: a sample with a non-finite coordinate has status 4, not 3.
+ *                4  a sampled point is not finite, or the centred source triangle is collinear: sigma_1 = 0 or sigma_2 < 1e-6 sigma_1.
+ *     pose       least-squares rigid transform of the three pairs in FP64.  dof 6: Horn's quaternion form, the eigenvector of the largest
+ *                eigenvalue of the 4 x 4 symmetric matrix by cyclic Jacobi with a fixed sweep count.  dof 4: the rotation about z by
+ *                yaw = atan2(sum(x_s y_t - y_s x_t), sum(x_s x_t + y_s y_t)) over the centred pairs (formed as (cos, sin) = (C, S) / |(C, S)|),
+ *                translation from the centroids, z included.  One function for host and device: glim_amd/csrc/ransac_pose.hpp.
+ *     score      inliers(it) = number of finite source points p whose q = R p + t, in FP64 as nine FMAs,
+ *                  q_r = fma(T[4r], p_x, fma(T[4r+1], p_y, fma(T[4r+2], p_z, T[4r+3]))),     r = 0 1 2
+ *                has fast_floor(q * (1 / res)) in the occupancy set; a q outside the key range is no inlier.
+ *   result       the sequential loop's, whatever the batching on the device: stop = the smallest `it` of status 0 with
+ *                inliers(it) >= early_stop_inlier_rate * N_source; if there is one, that hypothesis, iterations_run = stop + 1; otherwise the
+ *                status-0 hypothesis with the largest count over all max_iterations, the smallest `it` among equals, iterations_run =
+ *                max_iterations.  No status-0 hypothesis: the identity, inlier_rate 0, best_iteration -1.  inlier_rate = inliers / N_source.
+ * Deterministic: the same inputs and seed return the same bits in any context (integer counts, integer atomics only). */
+typedef struct {
+  int32_t max_iterations;
+  double early_stop_inlier_rate;
+  double poly_error_thresh;
+  double inlier_voxel_resolution;
+  int32_t dof; /* 4 or 6 */
+  uint64_t seed;
+} glim_amd_ransac_params;
+typedef struct {
+  double T_target_source[12];
+  double inlier_rate;
+  int64_t num_inliers;
+  int32_t best_iteration; /* -1: no hypothesis passed the checks */
+  int32_t iterations_run;
+} glim_amd_registration_result;
+/* the modal's defaults: 5000, 0.9, poly_error_thresh 0.5, 1.0, dof 6, seed 0 */
+int glim_amd_ransac_default_params(glim_amd_ransac_params* params);
+/* nearest: host array, one entry per source point.  GLIM_AMD_ERR_INVALID: a NULL argument, clouds of two contexts, dof not 4 or 6,
+ * max_iterations <= 0, inlier_voxel_resolution not finite or <= 0, a NaN early_stop_inlier_rate or poly_error_thresh, a nearest value < -1 or
+ * >= the target size.  A source of fewer than 3 points or an empty target is no error: the "no status-0 hypothesis" result. */
+int glim_amd_ransac_align(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_ransac_params* params,
+                          glim_amd_registration_result* result);
+/* The same with the correspondences of glim_amd_fpfh_match(target_fpfh, source_fpfh, match_flags) found on the device: `nearest` never visits
+ * the host.  match_flags: 0 or GLIM_AMD_FPFH_RECIPROCAL.  GLIM_AMD_ERR_INVALID also when a descriptor set is not the size of its cloud or
+ * belongs to another context. */
+int glim_amd_ransac_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* source, const glim_amd_fpfh* target_fpfh,
+                               const glim_amd_fpfh* source_fpfh, uint32_t match_flags, const glim_amd_ransac_params* params,
+                               glim_amd_registration_result* result);
 
 #ifdef __cplusplus
 }

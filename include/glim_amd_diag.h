@@ -60,6 +60,17 @@ int glim_amd_debug_scratch_poke(glim_amd_ctx* ctx, int32_t word, uint32_t value)
 int glim_amd_debug_sort_pairs(glim_amd_ctx* ctx, int64_t n, int32_t bits, const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out,
                               uint32_t* vals_out);
 
+/* The hypotheses [first, first + count) of glim_amd_ransac_align on the same arguments, every one scored, no early stop: samples (count x 3
+ * source indices), status (count), poses12 (count x 12; the identity where status != 0), inliers (count; 0 where status != 0); any of them may
+ * be NULL.  table_slots / table_in_lds: size of the occupancy table and whether the scoring kernel held it in LDS.  A source of 0 points is
+ * GLIM_AMD_ERR_INVALID here (nothing to draw from). */
+int glim_amd_ransac_debug_hypotheses(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest,
+                                     const glim_amd_ransac_params* params, int32_t first, int32_t count, int32_t* samples, int32_t* status,
+                                     double* poses12, int32_t* inliers, int32_t* table_slots, int32_t* table_in_lds);
+/* Largest occupancy table the RANSAC scoring kernel of THIS THREAD's calls copies into LDS, in slots (default and maximum 8192; 0: always probe
+ * global memory).  Lets a test or a timing run take both forms on one input. */
+int glim_amd_debug_ransac_max_lds_slots(int32_t slots);
+
 /* ---- timing loops measured inside the library (bench.py, tools/) -------------------------------------------------- */
 /* Timing aid used by bench.py: runs `iters` back-to-back launches bracketed by HIP events on the set's stream.
  * ms_vgicp_kernel: average duration of the fused lookup+residual+Jacobian+reduce kernel alone;
@@ -104,6 +115,11 @@ int glim_amd_cloud_profile_neighbors(glim_amd_cloud* cloud, int k, int iters, fl
 /* timing aid: `iters` back-to-back glim_amd_overlap_batch calls with these arguments; microseconds per call, measured inside the library. */
 int glim_amd_overlap_profile(glim_amd_ctx* ctx, int32_t num_queries, const int32_t* num_targets, const glim_amd_voxelmap* const* targets,
                              const double* T_target_source, const glim_amd_cloud* const* sources, int iters, float* us_per_call);
+
+/* One RANSAC round (min(1024, max_iterations) hypotheses from 0) `iters` times after two warm-up rounds: mean microseconds of the hypothesis,
+ * scoring and fold kernels by HIP events around each. */
+int glim_amd_ransac_profile(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_ransac_params* params,
+                            int iters, float* us_hypothesis, float* us_score, float* us_fold, int32_t* table_slots, int32_t* table_in_lds);
 
 /* ---- state of the resident session, the plan cache and the last frame_create ---------------------------------------- */
 /* parity / debug only: the device's resident session (repeated synchronous linearisations of a small factor list are served by a kernel that stays
