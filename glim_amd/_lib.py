@@ -71,6 +71,34 @@ class PreprocessParams(C.Structure):
     ]
 
 
+class GncParams(C.Structure):
+    """glim_amd_gnc_params (include/glim_amd.h "GNC") == gtsam_points::GNCParams as manual_loop_close_modal.cpp:449-456 fills it."""
+
+    _fields_ = [
+        ("max_init_samples", C.c_int32),
+        ("tuple_check", C.c_int32),
+        ("tuple_thresh", C.c_double),
+        ("max_num_tuples", C.c_int32),
+        ("div_factor", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("max_corr_dist", C.c_double),
+        ("inlier_voxel_resolution", C.c_double),
+        ("dof", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class GncInfo(C.Structure):
+    _fields_ = [
+        ("num_correspondences", C.c_int64),
+        ("num_tuples", C.c_int64),
+        ("list_length", C.c_int64),
+        ("mu_final", C.c_double),
+        ("weight_sum", C.c_double),
+        ("cost", C.c_double),
+    ]
+
+
 class RansacParams(C.Structure):
     """glim_amd_ransac_params (include/glim_amd.h "RANSAC") == gtsam_points::RANSACParams as manual_loop_close_modal.cpp:435-441 fills it."""
 
@@ -199,6 +227,12 @@ SYMBOLS = {
     "glim_amd_ransac_debug_hypotheses": (_i, [_vp, _vp, _ip, C.POINTER(RansacParams), _i32, _i32, _ip, _ip, _dp, _ip, _ip, _ip]),
     "glim_amd_debug_ransac_max_lds_slots": (_i, [_i32]),
     "glim_amd_ransac_profile": (_i, [_vp, _vp, _ip, C.POINTER(RansacParams), _i, _fp, _fp, _fp, _ip, _ip]),
+    "glim_amd_gnc_default_params": (_i, [C.POINTER(GncParams)]),
+    "glim_amd_gnc_align": (_i, [_vp, _vp, _ip, C.POINTER(GncParams), C.POINTER(RegistrationResult), C.POINTER(GncInfo)]),
+    "glim_amd_gnc_align_fpfh": (_i, [_vp, _vp, _vp, _vp, _u32, C.POINTER(GncParams), C.POINTER(RegistrationResult), C.POINTER(GncInfo)]),
+    "glim_amd_gnc_debug_trace": (_i, [_vp, _vp, _ip, C.POINTER(GncParams), _i64, _ip, _lp, _dp, _dp, _dp, C.POINTER(RegistrationResult),
+                                      C.POINTER(GncInfo)]),
+    "glim_amd_gnc_profile": (_i, [_vp, _vp, _ip, C.POINTER(GncParams), _i, _fp, _fp, _fp, _fp, _fp]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -450,6 +450,85 @@ def ransac_profile(target, source, nearest, params, iters=20):
     return {"hypothesis_us": us[0].value, "score_us": us[1].value, "fold_us": us[2].value, "table_slots": slots.value, "table_in_lds": in_lds.value}
 
 
+class GncParams:
+    """gtsam_points::GNCParams (glim_amd_gnc_params; include/glim_amd.h "GNC").  reciprocal_check is gnc_align_fpfh's `reciprocal` argument."""
+
+    def __init__(self, max_init_samples=5000, tuple_check=False, tuple_thresh=0.9, max_num_tuples=1000, div_factor=1.4, max_iterations=64,
+                 max_corr_dist=0.0, inlier_voxel_resolution=1.0, dof=6, seed=0):
+        self.max_init_samples = max_init_samples
+        self.tuple_check = tuple_check
+        self.tuple_thresh = tuple_thresh
+        self.max_num_tuples = max_num_tuples
+        self.div_factor = div_factor
+        self.max_iterations = max_iterations
+        self.max_corr_dist = max_corr_dist
+        self.inlier_voxel_resolution = inlier_voxel_resolution
+        self.dof = dof
+        self.seed = seed
+
+    def _c(self):
+        return _lib.GncParams(int(self.max_init_samples), 1 if self.tuple_check else 0, float(self.tuple_thresh), int(self.max_num_tuples),
+                              float(self.div_factor), int(self.max_iterations), float(self.max_corr_dist), float(self.inlier_voxel_resolution),
+                              int(self.dof), int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _gnc_result(out, info):
+    r = RegistrationResult(out)
+    r.info = {k: getattr(info, k) for k, _ in _lib.GncInfo._fields_}
+    return r
+
+
+def gnc_align(target, source, nearest, params=None):
+    """gtsam_points::estimate_pose_gnc on the device: nearest[i] = target point matched to source point i, or -1 (match_fpfh's output).
+    Returns a RegistrationResult with `info` (glim_amd_gnc_info as a dict)."""
+    prm = (params or GncParams())._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    if near.shape != (source.size(),):
+        raise ValueError("nearest must hold one entry per source point")
+    out, info = _lib.RegistrationResult(), _lib.GncInfo()
+    check(lib().glim_amd_gnc_align(target._h, source._h, _ip(near), C.byref(prm), C.byref(out), C.byref(info)), "glim_amd_gnc_align")
+    return _gnc_result(out, info)
+
+
+def gnc_align_fpfh(target, source, target_fpfh, source_fpfh, params=None, reciprocal=True):
+    """The same with the nearest-descriptor correspondences found on the device (they never visit the host); reciprocal = GNCParams::reciprocal_check."""
+    prm = (params or GncParams())._c()
+    out, info = _lib.RegistrationResult(), _lib.GncInfo()
+    check(lib().glim_amd_gnc_align_fpfh(target._h, source._h, target_fpfh._h, source_fpfh._h, FPFH_RECIPROCAL if reciprocal else 0, C.byref(prm),
+                                        C.byref(out), C.byref(info)), "glim_amd_gnc_align_fpfh")
+    return _gnc_result(out, info)
+
+
+def gnc_debug_trace(target, source, nearest, params):
+    """Test window (glim_amd_gnc_debug_trace): the final list (n x 2: source, target index), c_s, c_t, D2, per completed iteration mu / W / cost /
+    pose (3 x 4), the last iteration's weights, and the result gnc_align returns on the same arguments."""
+    prm = params._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    cap = max(source.size(), 3 * int(params.max_num_tuples) if params.tuple_check else 0, 1)
+    pairs = np.zeros((cap, 2), dtype=np.int32)
+    length = C.c_int64()
+    frame = np.zeros(7)
+    iters = np.zeros((int(params.max_iterations), 15))
+    weights = np.zeros(cap)
+    out, info = _lib.RegistrationResult(), _lib.GncInfo()
+    check(lib().glim_amd_gnc_debug_trace(target._h, source._h, _ip(near), C.byref(prm), cap, _ip(pairs), C.byref(length), _dp(frame), _dp(iters),
+                                         _dp(weights), C.byref(out), C.byref(info)), "glim_amd_gnc_debug_trace")
+    r = _gnc_result(out, info)
+    k, n = r.iterations_run, length.value
+    return {"list": pairs[:n].copy(), "c_s": frame[0:3].copy(), "c_t": frame[3:6].copy(), "D2": float(frame[6]), "mu": iters[:k, 0].copy(),
+            "W": iters[:k, 1].copy(), "cost": iters[:k, 2].copy(), "poses": iters[:k, 3:].reshape(k, 3, 4).copy(),
+            "weights": weights[:n].copy() if k > 0 else np.zeros(0), "result": r}
+
+
+def gnc_profile(target, source, nearest, params, iters=20):
+    """microseconds of the stages of one gnc_align (HIP events inside the library)"""
+    prm = params._c()
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    us = [C.c_float() for _ in range(5)]
+    check(lib().glim_amd_gnc_profile(target._h, source._h, _ip(near), C.byref(prm), int(iters), *[C.byref(u) for u in us]), "glim_amd_gnc_profile")
+    return dict(zip(("select_us", "tuples_us", "gather_and_solve_us", "table_us", "score_us"), (u.value for u in us)))
+
+
 class GaussianVoxelMapGPU:
     """gtsam_points::GaussianVoxelMapGPU(resolution, init_num_buckets, max_bucket_scan_count, target_points_drop_rate)."""
 

@@ -1470,3 +1470,7 @@ int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* f, const double*
 
 // RANSAC global registration over those correspondences (ransac.hip): likewise, and after fpfh.hip, whose descriptor object and matcher it uses
 #include "ransac.hip"
+
+// GNC global registration, the other estimator over those correspondences (gnc.hip): likewise, and after ransac.hip, whose generator, occupancy
+// table and scoring kernel it uses
+#include "gnc.hip"

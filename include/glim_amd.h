@@ -443,8 +443,8 @@ int glim_amd_overlap_batch(glim_amd_ctx* ctx, int32_t num_queries, const int32_t
 
 /* ---- FPFH: gtsam_points::estimate_fpfh and the nearest-descriptor queries of global registration
  *      (viewer/interactive/manual_loop_close_modal.cpp:376-463: estimate_fpfh on both clouds, KdTreeX<FPFH_DIM> over the 33-D descriptors,
- *      RANSAC / GNC on nearest-descriptor correspondences).  RANSAC is the section after this one; GNC stays with the caller: it consumes the
- *      correspondence list glim_amd_fpfh_match returns.
+ *      RANSAC / GNC on nearest-descriptor correspondences).  RANSAC and GNC are the two sections after this one; both consume the
+ *      correspondence list glim_amd_fpfh_match returns, on the device.
  * The descriptor follows PCL's FPFHEstimation, which gtsam_points follows as far as recalled; the gtsam_points source is not in the
  * reference tree, so the points below that PCL leaves open are guesses (listed as such in DESIGN.md 4.7):
  *   neighbours   N(i) = { j : 0 < d2_ij <= r^2 }, d2 = (dx^2 + dy^2) + dz^2 in FP64 from the cloud's FP32 coordinates (zero-distance pairs,
@@ -481,7 +481,7 @@ int glim_amd_fpfh_create(glim_amd_ctx* ctx, int64_t n, const float* descriptors3
 
 /* ---- RANSAC: gtsam_points::estimate_pose_ransac, the global registration of viewer/interactive/manual_loop_close_modal.cpp:431-443
  *      (target, source, their FPFH descriptors, two search trees, RANSACParams{max_iterations 5000, early_stop_inlier_rate 0.9,
- *      inlier_voxel_resolution 1.0, dof 4 | 6, seed}).  GNC (estimate_pose_gnc) is not provided.
+ *      inlier_voxel_resolution 1.0, dof 4 | 6, seed}).  The other estimator of that switch, GNC, is the section after this one.
  * The gtsam_points source is not in the reference tree: what follows is a restatement from recall plus decisions (listed in DESIGN.md 4.7a).
  *   inputs       target and source device clouds (points only), nearest[i] = matched target point of source point i or -1, the parameters.
  *   occupancy    the set of voxel coordinates fast_floor(p * (1 / res)) of every target point: FP64 product of the FP32 coordinate, 21 bits per
@@ -536,6 +536,74 @@ int glim_amd_ransac_align(const glim_amd_cloud* target, const glim_amd_cloud* so
 int glim_amd_ransac_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* source, const glim_amd_fpfh* target_fpfh,
                                const glim_amd_fpfh* source_fpfh, uint32_t match_flags, const glim_amd_ransac_params* params,
                                glim_amd_registration_result* result);
+
+/* ---- GNC: gtsam_points::estimate_pose_gnc, the second global registration of viewer/interactive/manual_loop_close_modal.cpp:445-458
+ *      (GNCParams{max_init_samples, reciprocal_check = true, tuple_check = false, max_num_tuples 5000, dof 4 | 6, seed}).
+ * The gtsam_points source is not in the reference tree: what follows is a restatement from recall plus decisions (listed in DESIGN.md 4.7b).  The
+ * algorithm is Fast Global Registration (Zhou, Park, Koltun 2016): optional tuple test, Geman-McClure weights, graduated mu.  FP64 throughout,
+ * contraction off, fma where written.
+ *   inputs       target and source device clouds (points only), nearest[i] = matched target point of source point i or -1, the parameters.
+ *                reciprocal_check is not a parameter: it is the match_flags argument of the *_fpfh entry.
+ *   1 selection  max_init_samples >= N_source: every source point is a candidate; otherwise the candidates are the SET
+ *                { splitmix64(seed, j) mod N_source : 0 <= j < max_init_samples } (RANSAC's generator; draws with replacement, so the set may be
+ *                smaller).  The list L holds the candidates i with nearest[i] >= 0 and both points finite, ascending in i; C = |L|.
+ *   2 tuples     only when tuple_check: trials j = 0 .. min(100 C, 2^22) - 1 draw c_k = splitmix64(seed + 1 (mod 2^64), 3 j + k) mod C, k = 0 1 2.
+ *                A trial passes when the three entries are distinct and every edge (0,1), (1,2), (2,0) has max(d_s, d_t) > 0 and
+ *                min(d_s, d_t) >= tuple_thresh * max(d_s, d_t), d = sqrt((dx^2 + dy^2) + dz^2).  The list becomes the three correspondences of
+ *                each of the first max_num_tuples passing trials, in trial order; duplicates are kept (a correspondence in several tuples weighs
+ *                more, as in FGR).
+ *   3 none       fewer than 3 list entries after 1 and 2: the identity, inlier_rate 0, best_iteration -1, iterations_run 0.  Not an error.
+ *   4 frame      c_s, c_t = unweighted centroids of the listed source / target points (sum in the tree of 5, divided by the list length);
+ *                p = s - c_s, q = t - c_t.  D^2 = the larger of the squared bounding-box diagonals (dx^2 + dy^2) + dz^2 of the listed source and
+ *                of the listed target points.  mu_0 = D^2; mu_min = max_corr_dist^2, or (0.025 sqrt(D^2))^2 when max_corr_dist <= 0.
+ *   5 loop       k = 0 .. max_iterations - 1, no data-dependent exit but the one below; the pose starts at the identity.  Per list entry:
+ *                  x = R s + t as RANSAC's nine FMAs, d = t_i - x, r^2 = (d_x^2 + d_y^2) + d_z^2, w = (mu / (mu + r^2))^2
+ *                seventeen sums over the list, each an FMA chain per lane: W = sum w, a = sum w p, b = sum w q, M = sum (w p) q^T,
+ *                cost = sum w r^2.  Tree: lane l of 512 takes the entries l, l + 512, .. in ascending order; the 64 lanes of a wavefront are
+ *                added by an xor-butterfly (offsets 32, 16, .. 1); the 8 wavefront sums are added in wavefront order.
+ *                Pose: H = M - a b^T / W; R from H as RANSAC derives it from its H (dof 6: Horn's 4 x 4 matrix by 8 cyclic Jacobi sweeps; dof 4:
+ *                (C, S) / |(C, S)|, S = H_01 - H_10, C = H_00 + H_11); t = (c_t + b / W) - R (c_s + a / W).  One function for host and device:
+ *                glim_amd/csrc/gnc_pose.hpp.  This is the closed-form minimiser for fixed weights, in place of FGR's one Gauss-Newton step.
+ *                If W or an entry of the new pose is not finite, the previous pose is kept and the loop ends: iterations_run = k.
+ *                After iteration k with k mod 4 = 3 and mu > mu_min: mu <- max(mu / div_factor, mu_min).
+ *   6 result     T_target_source = the last pose; num_inliers and inlier_rate by RANSAC's rule exactly: ALL finite source points under that pose
+ *                against the occupancy table at inlier_voxel_resolution, inlier_rate = num_inliers / N_source; best_iteration =
+ *                iterations_run - 1.  If not one iteration completed (iterations_run = 0) the result is that of 3.
+ * Deterministic: the same inputs and seed return the same bits in any context (integer selection, one fixed reduction tree, no floating-point
+ * atomics). */
+typedef struct {
+  int32_t max_init_samples;
+  int32_t tuple_check; /* 0 or 1 */
+  double tuple_thresh;
+  int32_t max_num_tuples;
+  double div_factor;
+  int32_t max_iterations;
+  double max_corr_dist; /* <= 0: 0.025 D */
+  double inlier_voxel_resolution;
+  int32_t dof; /* 4 or 6 */
+  uint64_t seed;
+} glim_amd_gnc_params;
+typedef struct {
+  int64_t num_correspondences; /* C after step 1 */
+  int64_t num_tuples;          /* passing trials kept (0 without tuple_check) */
+  int64_t list_length;         /* entries the loop ran over */
+  double mu_final;             /* the mu of the last completed iteration */
+  double weight_sum;           /* its W */
+  double cost;                 /* its sum w r^2 */
+} glim_amd_gnc_info;
+/* 5000, 0, 0.9, 1000, 1.4, 64, 0, 1.0, dof 6, seed 0 */
+int glim_amd_gnc_default_params(glim_amd_gnc_params* params);
+/* nearest: host array, one entry per source point.  info may be NULL.  GLIM_AMD_ERR_INVALID: a NULL required argument, clouds of two contexts,
+ * dof not 4 or 6, max_iterations <= 0, max_init_samples <= 0, max_num_tuples <= 0 with tuple_check, div_factor not finite or <= 1, a NaN
+ * tuple_thresh, inlier_voxel_resolution not finite or <= 0, max_corr_dist NaN or infinite, a nearest value < -1 or >= the target size. */
+int glim_amd_gnc_align(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_gnc_params* params,
+                       glim_amd_registration_result* result, glim_amd_gnc_info* info);
+/* The same with the correspondences of glim_amd_fpfh_match(target_fpfh, source_fpfh, match_flags) found on the device: `nearest` never visits
+ * the host.  match_flags: 0 or GLIM_AMD_FPFH_RECIPROCAL (GNCParams::reciprocal_check).  GLIM_AMD_ERR_INVALID also when a descriptor set is not
+ * the size of its cloud or belongs to another context. */
+int glim_amd_gnc_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* source, const glim_amd_fpfh* target_fpfh,
+                            const glim_amd_fpfh* source_fpfh, uint32_t match_flags, const glim_amd_gnc_params* params,
+                            glim_amd_registration_result* result, glim_amd_gnc_info* info);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,16 @@ int glim_amd_ransac_debug_hypotheses(const glim_amd_cloud* target, const glim_am
  * global memory).  Lets a test or a timing run take both forms on one input. */
 int glim_amd_debug_ransac_max_lds_slots(int32_t slots);
 
+/* glim_amd_gnc_align on the same arguments with every intermediate: the final list (list_pairs: source index, target index per entry, room for
+ * list_capacity entries -- N_source, or 3 max_num_tuples with tuple_check, always suffices; GLIM_AMD_ERR_INVALID when the list is longer),
+ * frame7 = c_s, c_t, D^2, iterations15 = per iteration of max_iterations the mu used, W, cost and the 12 pose doubles (only the first
+ * result->iterations_run rows are written), weights = the weights of the last completed iteration, one per list entry (an iteration that ends the
+ * loop without a finite result does not overwrite them).  Any output but result
+ * and list_length may be NULL. */
+int glim_amd_gnc_debug_trace(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_gnc_params* params,
+                             int64_t list_capacity, int32_t* list_pairs, int64_t* list_length, double* frame7, double* iterations15,
+                             double* weights, glim_amd_registration_result* result, glim_amd_gnc_info* info);
+
 /* ---- timing loops measured inside the library (bench.py, tools/) -------------------------------------------------- */
 /* Timing aid used by bench.py: runs `iters` back-to-back launches bracketed by HIP events on the set's stream.
  * ms_vgicp_kernel: average duration of the fused lookup+residual+Jacobian+reduce kernel alone;
@@ -120,6 +130,11 @@ int glim_amd_overlap_profile(glim_amd_ctx* ctx, int32_t num_queries, const int32
  * scoring and fold kernels by HIP events around each. */
 int glim_amd_ransac_profile(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_ransac_params* params,
                             int iters, float* us_hypothesis, float* us_score, float* us_fold, int32_t* table_slots, int32_t* table_in_lds);
+
+/* glim_amd_gnc_align `iters` times after one warm-up call: mean microseconds, by HIP events, of the selection (mark, scan, compaction), the tuple
+ * test (0 without tuple_check), the gather and the solve kernel, the occupancy table and the scoring of the final pose. */
+int glim_amd_gnc_profile(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_gnc_params* params,
+                         int iters, float* us_select, float* us_tuples, float* us_solve, float* us_table, float* us_score);
 
 /* ---- state of the resident session, the plan cache and the last frame_create ---------------------------------------- */
 /* parity / debug only: the device's resident session (repeated synchronous linearisations of a small factor list are served by a kernel that stays
