@@ -1,10 +1,150 @@
 // device_math.hpp -- device-side helpers shared by the gfx950 kernels.
 #pragma once
 
+// The first section ("record math") is plain C++ as well: a stand-alone host program may include this header without the HIP toolchain
+// (tests/test_record_math.py); everything after it needs hipcc.
+#if defined(__HIP__)
 #include <hip/hip_runtime.h>
 
 #include "internal.hpp"
+#define GLIM_AMD_HD __host__ __device__
+#else
+#define GLIM_AMD_HD
+#endif
 
+namespace glim_amd {
+
+// ---------------------------------------------------------------------------------------------------------------
+// Record math: the last step of a VGICP linearisation, ONE definition for every place that takes it -- the device finalisers (vgicp.hip
+// finalize_tail, finalize_short_kernel) and the host, which finishes the raw record of a small synchronous set itself (finish_raw_record).
+// All of it is contraction-free (host and device compilers would contract differently) and gives the same bits wherever it runs.
+//
+// accumulator layout:  0..5  Hww (00 01 02 11 12 22)   6..14 G = hat(p) A (row-major 3x3 = H_wv)   15..20 A (00 01 02 11 12 22)
+//                      21..23 u x p (= b_w)            24..26 u (b_v = -u)                          27 e    28 inlier count
+// compact record:      [count, error, 21 upper-triangular H_ss entries row-major, 6 b_s]
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int RECORD_ROTATED = 27;  // accumulators 0..26 go through the rotation
+constexpr int RECORD_SLOTS = 29;    // slots of a compact record = granules of a raw one (internal.hpp COMPACT)
+
+// accumulator slot of entry i of the upper triangle of H_ss -- {0, 1, 2, 6, 7, 8, 3, 4, 9, 10, 11, 5, 12, 13, 14, 15, 16, 17, 18, 19, 20} -- as two
+// immediates (5 bits per entry, entries 0..11 and 12..20): the finalisers' last step looks its slot up with two shifts instead of a load from
+// constant memory behind the last barrier of a call the host is waiting for
+GLIM_AMD_HD inline int acc_of_upper(int i) {
+  const unsigned long long lo = 0x2ad4920d0730820ull, hi = 0x149ca307b9acull;
+  return (int)(((i < 12 ? lo >> (5 * i) : hi >> (5 * (i - 12)))) & 31ull);
+}
+
+// slot t = 2..28 of the compact record from the rotated accumulators: [21 upper-triangular H_ss entries, b_w = R^T sum u x q', b_v = -R^T sum u]
+// (slot 0 is accumulator 28, the count, slot 1 accumulator 27, the error: neither is rotated)
+GLIM_AMD_HD inline double compact_from_rot(int t, const double* rot) {
+  return t < 23 ? rot[acc_of_upper(t - 2)] : (t < 26 ? rot[t - 2] : -rot[t - 2]);
+}
+
+// The kernel accumulated H' = sum J'^T M J' and b' = sum J'^T M r for J' = [hat(R p) | -I] in the target frame; with
+// J_s = J' diag(R, R):  H_ss = diag(R, R)^T H' diag(R, R), b_s = diag(R, R)^T b', i.e. every 3x3 block B' becomes R^T B' R and every
+// 3-vector R^T v.  No fma contraction.
+GLIM_AMD_HD inline void rotate_block(const double* B, const double* R, double* O) {
+#pragma clang fp contract(off)
+  double BR[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) BR[3 * r + c] = B[3 * r] * R[c] + B[3 * r + 1] * R[3 + c] + B[3 * r + 2] * R[6 + c];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) O[3 * r + c] = R[r] * BR[c] + R[3 + r] * BR[3 + c] + R[6 + r] * BR[6 + c];  // (R^T BR)[r][c]
+}
+// part 0..2: rotate block Hww / Hwv / Hvv of the summed accumulators `sum` into `rot` (accumulator layout); part 3: the two vectors.
+// T: the pose, 12 doubles (3x4 row-major)
+GLIM_AMD_HD inline void rotate_part(int part, const double* sum, const double* T, double* rot) {
+#pragma clang fp contract(off)
+  double R[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) R[3 * r + c] = T[4 * r + c];
+  if (part < 3) {
+    double B[9], O[9];
+    if (part == 0) {
+      B[0] = sum[0]; B[1] = sum[1]; B[2] = sum[2]; B[3] = sum[1]; B[4] = sum[3]; B[5] = sum[4]; B[6] = sum[2]; B[7] = sum[4]; B[8] = sum[5];
+    } else if (part == 1) {
+      for (int i = 0; i < 9; i++) B[i] = sum[6 + i];
+    } else {
+      B[0] = sum[15]; B[1] = sum[16]; B[2] = sum[17]; B[3] = sum[16]; B[4] = sum[18]; B[5] = sum[19]; B[6] = sum[17]; B[7] = sum[19]; B[8] = sum[20];
+    }
+    rotate_block(B, R, O);
+    if (part == 0) {
+      rot[0] = O[0]; rot[1] = O[1]; rot[2] = O[2]; rot[3] = O[4]; rot[4] = O[5]; rot[5] = O[8];
+    } else if (part == 1) {
+      for (int i = 0; i < 9; i++) rot[6 + i] = O[i];
+    } else {
+      rot[15] = O[0]; rot[16] = O[1]; rot[17] = O[2]; rot[18] = O[4]; rot[19] = O[5]; rot[20] = O[8];
+    }
+  } else {
+    for (int c = 0; c < 3; c++) {
+      rot[21 + c] = R[c] * sum[21] + R[3 + c] * sum[22] + R[6 + c] * sum[23];   // R^T (sum u x q')
+      rot[24 + c] = R[c] * sum[24] + R[3 + c] * sum[25] + R[6 + c] * sum[26];   // R^T (sum u)
+    }
+  }
+}
+
+// Row r and column c of accumulator slot j inside its 3x3 block, two bits per slot: the upper triangles (slots 0..5, 15..20) walk
+// (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), the full block (6..14) is row-major, a vector slot (21..26) has r = c = its component.
+constexpr unsigned long long rotate_slot_table(bool row) {
+  unsigned long long t = 0ull;
+  for (int j = 0; j < RECORD_ROTATED; j++) {
+    int r = 0, c = 0;
+    if (j >= 21) {
+      r = c = (j - 21) % 3;
+    } else if (j >= 6 && j < 15) {
+      r = (j - 6) / 3;
+      c = (j - 6) % 3;
+    } else {
+      const int u = j < 6 ? j : j - 15;
+      r = u < 3 ? 0 : (u < 5 ? 1 : 2);
+      c = u < 3 ? u : (u < 5 ? u - 2 : 2);
+    }
+    t |= (unsigned long long)(row ? r : c) << (2 * j);
+  }
+  return t;
+}
+
+// One element of rotate_part's result, for a thread of its own (the device finalisers: 27 threads instead of 4, a chain of 20 dependent FP64
+// operations instead of 72): slot j of the accumulator layout.  ONE instruction stream for all 27 slots -- no branch, no division: the slot's
+// block offset o comes from compares, its row and column from two packed immediates, and the nine entries of B are sum[o + k] with k a select
+// between the full block's and the upper triangle's offset.  A vector slot reads the triangle's offsets (in range: o + 5 <= 29), takes
+// br_k = sum[o + k] by a select and r = c, which makes the last line T[c] sum[o] + T[4 + c] sum[o + 1] + T[8 + c] sum[o + 2]: rotate_part's
+// expression.  (The three-path form this replaces -- j >= 21 / full block / triangle, with / and % -- had wave 0 walk all three in turn behind
+// the last barrier of a call the host is waiting for.)
+// The SAME expressions in the same order as rotate_block / rotate_part, no contraction: the same bits (tests/test_record_math.py on the host,
+// tests/test_gpu_edge_cases.py and tests/test_gpu_host_rotation.py across the forms of the synchronous call).
+GLIM_AMD_HD inline double rotate_element(int j, const double* sum, const double* T) {
+#pragma clang fp contract(off)
+  // (on the device sum and T are LDS arrays: every run-time index below is an address, not a register number; R[3 a + b] of rotate_part is T[4 a + b])
+  constexpr unsigned long long ROWS = rotate_slot_table(true), COLS = rotate_slot_table(false);
+  const bool vec = j >= 21, full = j >= 6 && j < 15;
+  const int o = j < 6 ? 0 : (j < 15 ? 6 : (j < 21 ? 15 : (j < 24 ? 21 : 24)));
+  const int r = (int)((ROWS >> (2 * j)) & 3ull), c = (int)((COLS >> (2 * j)) & 3ull);
+  const double B0 = sum[o], B1 = sum[o + 1], B2 = sum[o + 2];
+  const double B3 = sum[o + (full ? 3 : 1)], B4 = sum[o + (full ? 4 : 3)], B5 = sum[o + (full ? 5 : 4)];
+  const double B6 = sum[o + (full ? 6 : 2)], B7 = sum[o + (full ? 7 : 4)], B8 = sum[o + (full ? 8 : 5)];
+  const double Rc0 = T[c], Rc1 = T[4 + c], Rc2 = T[8 + c];
+  const double m0 = B0 * Rc0 + B1 * Rc1 + B2 * Rc2;
+  const double m1 = B3 * Rc0 + B4 * Rc1 + B5 * Rc2;
+  const double m2 = B6 * Rc0 + B7 * Rc1 + B8 * Rc2;
+  const double br0 = vec ? B0 : m0, br1 = vec ? B1 : m1, br2 = vec ? B2 : m2;
+  return T[r] * br0 + T[4 + r] * br1 + T[8 + r] * br2;
+}
+
+// Host side of a raw record (finalize_tail's raw branch: slot j = summed accumulator j, 29 doubles): the rotation and the slot mapping the
+// device finalisers apply, giving the compact record they would have stored.  T: the factor's linearisation pose (12 doubles).  A record
+// whose finaliser lost a row is NaN in every raw slot, so its count (compact slot 0) is NaN here as well.
+inline void finish_raw_record(const double* raw, const double* T, double* compact) {
+  double rot[RECORD_ROTATED];
+  for (int part = 0; part < 4; part++) rotate_part(part, raw, T, rot);
+  compact[0] = raw[28];
+  compact[1] = raw[27];
+  for (int t = 2; t < RECORD_SLOTS; t++) compact[t] = compact_from_rot(t, rot);
+}
+
+}  // namespace glim_amd
+
+#if defined(__HIP__)
 namespace glim_amd {
 
 // FP64 multiply / add that the compiler must NOT fuse into an FMA.  HIP compiles with -ffp-contract=fast-honor-pragmas and the
@@ -198,3 +338,4 @@ static __global__ void init_bbox_kernel(int* __restrict__ bb) {
 }
 
 }  // namespace glim_amd
+#endif  // __HIP__

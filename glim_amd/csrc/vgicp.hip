@@ -74,14 +74,6 @@ constexpr int RED_ROWS = 4;  // s_red[wavefront][16-lane row][value]
 constexpr int RED_ROWS = 1;  // s_red[wavefront][0][value]
 #endif
 typedef float RedRow[RED_ROWS][glim_amd::PARTIAL_STRIDE];
-// accumulator slot of entry i of the upper triangle of H_ss -- {0, 1, 2, 6, 7, 8, 3, 4, 9, 10, 11, 5, 12, 13, 14, 15, 16, 17, 18, 19, 20} -- as two
-// immediates (5 bits per entry, entries 0..11 and 12..20): the finalisers' last step looks its slot up with two shifts instead of a load from
-// constant memory behind the last barrier of a call the host is waiting for
-__device__ __forceinline__ int acc_of_upper(int i) {
-  const unsigned long long lo = 0x2ad4920d0730820ull, hi = 0x149ca307b9acull;
-  return (int)(((i < 12 ? lo >> (5 * i) : hi >> (5 * (i - 12)))) & 31ull);
-}
-
 __device__ __forceinline__ float4 ld16(const void* p) { return *reinterpret_cast<const float4*>(p); }
 
 enum { MODE_LINEARIZE = 0, MODE_ERROR = 1 };
@@ -151,6 +143,8 @@ struct FinalizeArgs {
   char* rows16;              // TAG_ROW_BYTES per plan row
   unsigned long long* trip_stats;  // 64 counters: skipped wavefront trips of the factors f with f % 64 == slot (null: not collected)
   char* rec16;               // host-mapped record granules (COMPACT x 16 B per factor) of the single-dispatch form, or null
+  int raw_record;            // rec16 of a linearisation: the granules carry the summed accumulators (raw slot j = accumulator j), the host rotates
+                             // (finish_raw_record) -- small sets, HOST_ROTATE_MAX_FACTORS; 0: the finished compact record
   const int* finmap;         // factor ids, plane-form segment first (null for a single-factor set: factor 0)
   // pre-cull (vgicp_kernel<..., CULL>): 4 words per row of the general segment, written by cull_kernel on the same stream just before the launch
   const unsigned long long* cull_words;
@@ -170,78 +164,9 @@ constexpr unsigned int AUX_SC1 = 16u;                    // cache policy of the 
 constexpr unsigned int AUX_SC1_VOLATILE = 16u | (1u << 31);  // ... and not to be hoisted out of / merged across the polling loop
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 
-// The last step of a linearisation, shared by the device finalise kernel and by the host-finalised single-factor call so that both give
-// the same bits: the kernel accumulated H' = sum J'^T M J' and b' = sum J'^T M r for J' = [hat(R p) | -I] in the target frame; with
-// J_s = J' diag(R, R):  H_ss = diag(R, R)^T H' diag(R, R), b_s = diag(R, R)^T b', i.e. every 3x3 block B' becomes R^T B' R and every
-// 3-vector R^T v.  No fma contraction (host and device compilers would contract differently).
-__host__ __device__ inline void rotate_block(const double* B, const double* R, double* O) {
-#pragma clang fp contract(off)
-  double BR[9];
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) BR[3 * r + c] = B[3 * r] * R[c] + B[3 * r + 1] * R[3 + c] + B[3 * r + 2] * R[6 + c];
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) O[3 * r + c] = R[r] * BR[c] + R[3 + r] * BR[3 + c] + R[6 + r] * BR[6 + c];  // (R^T BR)[r][c]
-}
-// part 0..2: rotate block Hww / Hwv / Hvv of the 32 summed accumulators `sum` into `rot` (accumulator layout); part 3: the two vectors
-__host__ __device__ inline void rotate_part(int part, const double* sum, const double* T, double* rot) {
-#pragma clang fp contract(off)
-  double R[9];
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) R[3 * r + c] = T[4 * r + c];
-  if (part < 3) {
-    double B[9], O[9];
-    if (part == 0) {
-      B[0] = sum[0]; B[1] = sum[1]; B[2] = sum[2]; B[3] = sum[1]; B[4] = sum[3]; B[5] = sum[4]; B[6] = sum[2]; B[7] = sum[4]; B[8] = sum[5];
-    } else if (part == 1) {
-      for (int i = 0; i < 9; i++) B[i] = sum[6 + i];
-    } else {
-      B[0] = sum[15]; B[1] = sum[16]; B[2] = sum[17]; B[3] = sum[16]; B[4] = sum[18]; B[5] = sum[19]; B[6] = sum[17]; B[7] = sum[19]; B[8] = sum[20];
-    }
-    rotate_block(B, R, O);
-    if (part == 0) {
-      rot[0] = O[0]; rot[1] = O[1]; rot[2] = O[2]; rot[3] = O[4]; rot[4] = O[5]; rot[5] = O[8];
-    } else if (part == 1) {
-      for (int i = 0; i < 9; i++) rot[6 + i] = O[i];
-    } else {
-      rot[15] = O[0]; rot[16] = O[1]; rot[17] = O[2]; rot[18] = O[4]; rot[19] = O[5]; rot[20] = O[8];
-    }
-  } else {
-    for (int c = 0; c < 3; c++) {
-      rot[21 + c] = R[c] * sum[21] + R[3 + c] * sum[22] + R[6 + c] * sum[23];   // R^T (sum u x q')
-      rot[24 + c] = R[c] * sum[24] + R[3 + c] * sum[25] + R[6 + c] * sum[26];   // R^T (sum u)
-    }
-  }
-}
-
-// One element of rotate_part's result, for a thread of its own (the device finalisers: 27 threads instead of 4, a chain of 20 dependent FP64
-// operations instead of 72): slot j of the accumulator layout -- 0..5 Hww (upper triangle), 6..14 Hwv, 15..20 Hvv (upper triangle), 21..23 and 24..26
-// the two vectors.  The SAME expressions in the same order as rotate_block / rotate_part, no contraction: the same bits (the host-finalised call and
-// finalize_short_kernel keep rotate_part; tests/test_gpu_edge_cases.py compares the forms bit for bit).
-__device__ __forceinline__ double rotate_element(int j, const double* sum, const double* T) {
-#pragma clang fp contract(off)
-  // (sum and T are LDS arrays: every run-time index below is an address, not a register number; R[3 a + b] of rotate_part is T[4 a + b])
-  if (j >= 21) {
-    const int c = (j - 21) % 3, o = j < 24 ? 21 : 24;
-    return T[c] * sum[o] + T[4 + c] * sum[o + 1] + T[8 + c] * sum[o + 2];
-  }
-  double B0, B1, B2, B3, B4, B5, B6, B7, B8;
-  int r, c;
-  if (j >= 6 && j < 15) {
-    B0 = sum[6]; B1 = sum[7]; B2 = sum[8]; B3 = sum[9]; B4 = sum[10]; B5 = sum[11]; B6 = sum[12]; B7 = sum[13]; B8 = sum[14];
-    r = (j - 6) / 3;
-    c = (j - 6) % 3;
-  } else {
-    const int o = j < 6 ? 0 : 15, u = j - o;  // upper-triangle index 0..5 -> (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-    B0 = sum[o]; B1 = sum[o + 1]; B2 = sum[o + 2]; B3 = B1; B4 = sum[o + 3]; B5 = sum[o + 4]; B6 = B2; B7 = B5; B8 = sum[o + 5];
-    r = u < 3 ? 0 : (u < 5 ? 1 : 2);
-    c = u < 3 ? u : (u < 5 ? u - 2 : 2);
-  }
-  const double Rc0 = T[c], Rc1 = T[4 + c], Rc2 = T[8 + c];
-  const double br0 = B0 * Rc0 + B1 * Rc1 + B2 * Rc2;
-  const double br1 = B3 * Rc0 + B4 * Rc1 + B5 * Rc2;
-  const double br2 = B6 * Rc0 + B7 * Rc1 + B8 * Rc2;
-  return T[r] * br0 + T[4 + r] * br1 + T[8 + r] * br2;
-}
+// The last step of a linearisation -- rotate_block / rotate_part / rotate_element, the slot mapping compact_from_rot and the host's
+// finish_raw_record -- is in device_math.hpp ("record math"): one definition for the device finalisers and for the host.
+static_assert(RECORD_SLOTS == COMPACT && RECORD_ROTATED == 27, "record math and the compact record agree");
 
 // Fixed-order FP64 sum of factor f's partial rows -> compact record; executed by the 256 threads of ONE block of the finalise kernel.  A
 // factor's rows are consecutive (row first_block + c belongs to its chunk c).  Thread t sums rows g, g + 32, g + 64, ... (g = t / 8) of the
@@ -293,35 +218,53 @@ __device__ __forceinline__ void finalize_factor(const FactorDesc& d, int f, cons
 // Tl: the factor's pose, 12 doubles in LDS written before this call
 // tail_stamps (device timeline of a resident session, else null): [0] the group sums are added, [1] the blocks are rotated -- s_memrealtime, kept in
 // registers and stored behind the record so that the stamps do not sit in front of a barrier
+// Raw record (fa.raw_record, a linearisation of the single-dispatch / resident form): the host rotates -- ~300 FP64 operations on 27 numbers
+// whose only other input is the pose the host itself sent (~50 ns there; here a barrier, the rotation on the one wavefront the caller waits
+// for, another barrier and the slot select: 1.3 us of the device timeline).  Thread t adds its 32 group sums -- the chain that fills s_sum[t]
+// otherwise: the same bits -- and stores the result from its register as granule t: no s_sum, no s_rot, no further barrier.
 __device__ __forceinline__ void finalize_tail(int f, const FinalizeArgs& fa, int mode, double (*s_part)[PARTIAL_STRIDE], double* s_sum, const double* Tl,
                                               unsigned long long* tail_stamps) {
   __syncthreads();
-  if (threadIdx.x < PARTIAL_STRIDE) {
-    double t = 0.0;
+  const bool raw = fa.rec16 && fa.raw_record && mode == MODE_LINEARIZE;
+  // (opaque to the optimiser: inside a resident kernel's request loop everything derived from the thread index below -- LDS addresses, the
+  //  rotation's slot constants -- would otherwise be hoisted in front of the loop and held, i.e. spilled, for the session's whole life)
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  double acc = 0.0;
+  if (t < PARTIAL_STRIDE) {
 #pragma unroll
-    for (int k = 0; k < FIN_GROUPS; k++) t += s_part[k][threadIdx.x];
-    s_sum[threadIdx.x] = t;
+    for (int k = 0; k < FIN_GROUPS; k++) acc += s_part[k][t];
+    if (!raw) s_sum[t] = acc;
   }
-  __syncthreads();
   unsigned long long st0 = 0ull, st1 = 0ull;
-  if (tail_stamps) st0 = __builtin_amdgcn_s_memrealtime();
-  const int t = threadIdx.x;
-  if (t == 29 && fa.trip_stats && s_sum[29] > 0.0) atomicAdd(&fa.trip_stats[f & 63], (unsigned long long)s_sum[29]);
-  __shared__ double s_rot[32];
-  if (mode == MODE_LINEARIZE) {
-#if GLIM_AMD_ROT27
-    if (t < 27) s_rot[t] = rotate_element(t, s_sum, Tl);  // one thread per rotated value (rotate_part's bits)
-#else
-    if (t < 4) rotate_part(t, s_sum, Tl, s_rot);  // thread k < 3 rotates block k (Hww, Hwv, Hvv), thread 3 the two vectors
-#endif
-    __syncthreads();
-  }
-  if (tail_stamps) st1 = __builtin_amdgcn_s_memrealtime();
-  // slot t of the compact record: [count, error, 21 upper-triangular H_ss entries, b_w = R^T sum u x q', b_v = -R^T sum u]
   double value = 0.0;
-  if (t == 0) value = s_sum[28];
-  else if (t == 1) value = s_sum[27];
-  else if (mode == MODE_LINEARIZE && t < COMPACT) value = t < 23 ? s_rot[acc_of_upper(t - 2)] : (t < 26 ? s_rot[t - 2] : -s_rot[t - 2]);
+  if (raw) {
+    // raw slot t = accumulator t, straight from the register that added it up
+    if (tail_stamps) {
+      __builtin_amdgcn_sched_barrier(0);  // (the stamp stays behind the add chain)
+      st0 = st1 = __builtin_amdgcn_s_memrealtime();  // (nothing is rotated here: both stamps are the end of the add chain)
+    }
+    if (t == 29 && fa.trip_stats && acc > 0.0) atomicAdd(&fa.trip_stats[f & 63], (unsigned long long)acc);
+    value = acc;
+  } else {
+    __syncthreads();
+    if (tail_stamps) st0 = __builtin_amdgcn_s_memrealtime();
+    if (t == 29 && fa.trip_stats && s_sum[29] > 0.0) atomicAdd(&fa.trip_stats[f & 63], (unsigned long long)s_sum[29]);
+    __shared__ double s_rot[32];
+    if (mode == MODE_LINEARIZE) {
+#if GLIM_AMD_ROT27
+      if (t < RECORD_ROTATED) s_rot[t] = rotate_element(t, s_sum, Tl);  // one thread per rotated value, one path for all of them (rotate_part's bits)
+#else
+      if (t < 4) rotate_part(t, s_sum, Tl, s_rot);  // thread k < 3 rotates block k (Hww, Hwv, Hvv), thread 3 the two vectors
+#endif
+      __syncthreads();
+    }
+    if (tail_stamps) st1 = __builtin_amdgcn_s_memrealtime();
+    // slot t of the compact record: [count, error, 21 upper-triangular H_ss entries, b_w = R^T sum u x q', b_v = -R^T sum u]
+    if (t == 0) value = s_sum[28];
+    else if (t == 1) value = s_sum[27];
+    else if (mode == MODE_LINEARIZE && t < COMPACT) value = compact_from_rot(t, s_rot);
+  }
   if (fa.rec16) {
     // Single-dispatch form: the record goes to host-mapped memory as 29 self-validating 16-byte granules {value, sequence number}, one
     // store each -- a PCIe write lands as a unit, so a granule whose tag is this call's carries this call's value.  The host polls the
@@ -1102,6 +1045,7 @@ struct ResidentArgs {
   int total_rows, num_factors, workers, blocks_per_round;
   char* rows16;                    // tagged partial rows (the plan's)
   char* rec16;                     // host-mapped record granules (the plan's)
+  int raw_record;                  // the finalisers store raw records, the host rotates (FinalizeArgs::raw_record): fixed for the session's life
   char* pose16;                    // device: replicas x num_factors x 12 pose granules {double, tag, 0}
   int replicas;                    // copies of the pose granules (block b watches copy b % replicas: 512 blocks polling ONE 192-byte spot is a hot
                                    // spot on one memory channel that slows everything else on the device)
@@ -1273,6 +1217,7 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       fa.rows16 = ra.rows16;
       fa.trip_stats = nullptr;
       fa.rec16 = ra.rec16;
+      fa.raw_record = ra.raw_record;
       fa.finmap = ra.finmap;
       fa.cull_words = nullptr;
       const FactorDesc d = ra.descs[f];
@@ -1404,7 +1349,7 @@ __global__ __launch_bounds__(BLOCK) void finalize_short_kernel(const FactorDesc*
   }
   if (t < 27) {  // slots 2 .. 28 of the record, by lanes 0 .. 26
     double v = 0.0;
-    if (mode == MODE_LINEARIZE) v = t < 21 ? s_rot[wave][acc_of_upper(t)] : (t < 24 ? s_rot[wave][t] : -s_rot[wave][t]);
+    if (mode == MODE_LINEARIZE) v = compact_from_rot(2 + t, s_rot[wave]);
     o[2 + t] = v;
     if (om) om[2 + t] = v;
   }
@@ -1529,6 +1474,15 @@ void resident_release(glim_amd_ctx* ctx, FactorPlan* plan);  // ends the residen
 namespace {
 
 constexpr size_t PLAN_CACHE_MAX = 16;    // idle plans kept per context
+// Linearisations of the single-dispatch / resident form with at most this many factors ship RAW records and the host rotates them
+// (finalize_tail, finish_raw_records; switch host_rotate).  Larger sets keep the device rotation: their finalisers rotate in parallel while the
+// host goes factor by factor.  Measured (profiles/r07/probe/host_rotate_threshold.json; host_rotate=0 / 1 alternating in one process, 16 x 256
+// frames): the resident call gains 0.40-0.54 us at 1, 2, 4, 8 and 16 factors and loses 1.0 us at 34; the single-dispatch form gains 0.14-0.34 us
+// up to 8 factors, nothing at 16, and loses 0.8 us at 34.  8 is the largest measured size at which both forms are faster by more than their spread.
+#ifndef GLIM_AMD_HOST_ROTATE_MAX
+#define GLIM_AMD_HOST_ROTATE_MAX 8
+#endif
+constexpr int HOST_ROTATE_MAX_FACTORS = GLIM_AMD_HOST_ROTATE_MAX;
 constexpr int RESIDENT_MAX_FACTORS = 64;  // sets a resident session may serve (vgicp.hip "resident sessions")
 constexpr int FUSED_MAX_FACTORS = 1024, FUSED_MAX_ROWS = 16384;  // sets that may take the single-dispatch form (2.6 MB of tagged rows at most)
 constexpr size_t HOST_POSES_MAX = 256;   // synchronous sets up to this many factors: poses read by the kernels from host-mapped memory (96 B per factor over PCIe)
@@ -2045,6 +1999,7 @@ FinalizeArgs finalize_args(const glim_amd_factor_set* set, double* out, long lon
   fa.rows16 = plan->d_rows16;
   fa.trip_stats = plan->d_trip_stats;
   fa.rec16 = nullptr;
+  fa.raw_record = 0;
   fa.finmap = plan->d_finmap;
   fa.cull_words = plan->cull ? plan->d_cull_words : nullptr;
   return fa;
@@ -2143,9 +2098,23 @@ bool records_lost(const FactorPlan* plan, size_t nf) {
   return false;
 }
 
+// does a synchronous linearisation of nf factors through the single-dispatch / resident form ship raw records?
+bool host_rotate_applies(const Diag& diag, size_t nf) { return diag.host_rotate && nf >= 1 && nf <= (size_t)HOST_ROTATE_MAX_FACTORS; }
+
+// host side of raw records (a producer launched with raw_record): plan->h_compact holds nf raw records after collect_tagged_records; each
+// becomes the compact record the device finalisers would have stored (same bits: device_math.hpp "record math").  T_lin: the call's poses.
+void finish_raw_records(FactorPlan* plan, size_t nf, const double* T_lin) {
+  for (size_t f = 0; f < nf; f++) {
+    double raw[COMPACT];
+    memcpy(raw, plan->h_compact + f * COMPACT, sizeof(raw));
+    finish_raw_record(raw, T_lin + 12 * f, plan->h_compact + f * COMPACT);
+  }
+}
+
 // enqueue (no sync): poses already on the device / in the inline arguments; writes compact records to `out` rows [row_offset, row_offset + n).
 // Two or three launches: the fused kernel per plan segment + the FP64 finalise.
-int enqueue(glim_amd_factor_set* set, int mode, bool frozen, double* out, long long row_offset, bool poll, bool allow_fused = true) {
+// raw_record: the single-dispatch form stores raw records (the caller finishes them: finish_raw_records)
+int enqueue(glim_amd_factor_set* set, int mode, bool frozen, double* out, long long row_offset, bool poll, bool allow_fused = true, bool raw_record = false) {
   const int nf = (int)set->entries.size();
   if (nf == 0) return GLIM_AMD_OK;
   FactorPlan* plan = set->plan;
@@ -2154,6 +2123,7 @@ int enqueue(glim_amd_factor_set* set, int mode, bool frozen, double* out, long l
   // small synchronous sets whose completion the host polls: ONE dispatch per segment, the factors are finalised inside it
   const bool fused = allow_fused && use_single_dispatch(set, poll);
   if (fused) fa.rec16 = plan->h_rec16_dev;
+  fa.raw_record = (fused && raw_record && mode == MODE_LINEARIZE) ? 1 : 0;
   launch_vgicp(set, mode, frozen, fa, plan->d_partials, fused);
   if (fused) {
     GA_HIP(hipGetLastError());
@@ -2242,6 +2212,7 @@ struct ResidentSession {
   char* d_pose16 = nullptr;
   unsigned int counter = 0, last_tag = 0;
   bool launched = false;
+  bool raw_record = false;  // what the running kernel was launched with (ResidentArgs::raw_record)
   std::atomic<bool> busy{false};
   std::chrono::steady_clock::time_point last_use;
   unsigned long long launches = 0, requests = 0;
@@ -2340,6 +2311,7 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
   ra.blocks_per_round = std::max(1, ctx->num_cus);
   ra.rows16 = plan->d_rows16;
   ra.rec16 = plan->h_rec16_dev;
+  ra.raw_record = host_rotate_applies(ctx->diag, (size_t)nf) ? 1 : 0;
   ra.pose16 = S.d_pose16;
   ra.replicas = nf <= 4 ? 8 : 1;  // (a larger set's blocks watch different factors' granules anyway)
   ra.h_lines = S.h_lines_dev;
@@ -2364,6 +2336,7 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
   else resident_kernel<false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
   GA_HIP(hipGetLastError());
   S.launched = true;
+  S.raw_record = ra.raw_record != 0;
   S.plan = plan;
   S.ctx = ctx;
   S.launches++;
@@ -2379,6 +2352,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
   const size_t nf = set->entries.size();
   FactorPlan* plan = nullptr;
   unsigned int tag = 0;
+  bool raw = false;  // the session that answers was launched with raw records
   std::chrono::steady_clock::time_point t_post;
   {
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -2398,6 +2372,8 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
       if (std::chrono::duration_cast<std::chrono::microseconds>(now - S.last_use).count() < RESIDENT_TAKEOVER_US) return GLIM_AMD_ERR_UNSUPPORTED;
       resident_stop(S);
     }
+    // the switch was flipped under a live session: its kernel keeps the form it was launched with, so it is restarted like for any other plan change
+    if (S.launched && S.raw_record != host_rotate_applies(diag, nf)) resident_stop(S);
     if (S.launched && reinterpret_cast<volatile unsigned int*>(S.h_mail)[16] == 0u) {
       (void)hipStreamSynchronize(S.stream);  // it has idled out
       S.launched = false;
@@ -2406,6 +2382,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
       // a session that cannot be started is never an error of the call: the launch-per-call path computes the same bits
       if (resident_launch(S, set, plan) != GLIM_AMD_OK) return GLIM_AMD_ERR_UNSUPPORTED;
     }
+    raw = S.raw_record;
     tag = next_session_tag(S);
     t_post = std::chrono::steady_clock::now();
     resident_post(S, T_lin, nf * 12, tag);
@@ -2425,6 +2402,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     (void)hipStreamSynchronize(S.stream);
     S.launched = false;
     int rc = resident_launch(S, set, plan);
+    raw = S.raw_record;  // (the fresh kernel answers the pending request in ITS form)
     if (rc == GLIM_AMD_OK) ok = collect_tagged_records(plan, nf, tag, nullptr);  // (the request lines still hold this request)
     if (!ok) {
       resident_stop(S);
@@ -2432,6 +2410,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
       return GLIM_AMD_ERR_STATE;
     }
   }
+  if (raw) finish_raw_records(plan, nf, T_lin);
   {
     std::lock_guard<std::mutex> slock(S.mu);
     S.last_tag = tag;
@@ -2611,7 +2590,7 @@ int run_sync(glim_amd_factor_set* set, int mode, const double* T_lin, const doub
     const int rc = run_resident(set, T_lin);
     if (rc != GLIM_AMD_ERR_UNSUPPORTED) return rc;
   }
-  bool poll = false, fused = false;
+  bool poll = false, fused = false, raw = false;
   unsigned int seq = 0;
   FactorPlan* plan = nullptr;
   {
@@ -2625,7 +2604,9 @@ int run_sync(glim_amd_factor_set* set, int mode, const double* T_lin, const doub
     poll = mapped && plan->h_flag && diag.poll;
     if (poll) seq = ++plan->poll_seq;
     fused = allow_fast && use_single_dispatch(set, poll);
-    GA_TRY(enqueue(set, mode, T_eval != nullptr, mapped ? plan->h_compact_dev : plan->d_compact, 0, poll, allow_fast));
+    // (decided here, under the lock, and kept: the record is finished the way the kernel that produces it is told to, whatever the switch reads later)
+    raw = fused && mode == MODE_LINEARIZE && host_rotate_applies(diag, nf);
+    GA_TRY(enqueue(set, mode, T_eval != nullptr, mapped ? plan->h_compact_dev : plan->d_compact, 0, poll, allow_fast, raw));
     if (!mapped) GA_HIP(hipMemcpyAsync(plan->h_compact, plan->d_compact, nf * COMPACT * sizeof(double), hipMemcpyDeviceToHost, set->stream));
   }
   if (fused) {
@@ -2636,6 +2617,7 @@ int run_sync(glim_amd_factor_set* set, int mode, const double* T_lin, const doub
       got = collect_tagged_records(plan, nf, seq);
     }
     if (!got) return GLIM_AMD_ERR_STATE;
+    if (raw) finish_raw_records(plan, nf, T_lin);
     // a lost row (the finaliser's bounded spin ran out) arrives as a NaN record under a valid tag: answer with the two-dispatch form
     if (records_lost(plan, nf)) return run_sync(set, mode, T_lin, T_eval, false);
     plan_seen_complete(set, plan);

@@ -23,7 +23,8 @@ extern "C" {
  * knn_select=0|1, plane=0|1, curve_order=0|1, ppt=<n>, poll=0|1, inline_pose=0|1, bucket_factor=<n>, plan_cache=0|1, plan_recycle=0|1, host_poses=0|1, host_pack=0|1, pull_gated=0|1, frame_fused=0|1,
  * view_fused=0|1 (a voxel map built from a plane-form cloud gets its plane view -- the (C_B + I)^-1 records the plane-form factor kernel reads --
  * from the map's own finalise kernel; 0: on the first factor that needs it),
- * fuse=0|1 (small synchronous sets in ONE dispatch), resident=0|1|auto + resident_idle_us=<n> (repeated synchronous linearisations of a small set
+ * fuse=0|1 (small synchronous sets in ONE dispatch), host_rotate=0|1 (linearisations of the smallest such sets, and of a resident session's, return
+ * raw sums and the host applies the R^T B R rotation of the record; 0: the device's finalisers do; same bits either way), resident=0|1|auto + resident_idle_us=<n> (repeated synchronous linearisations of a small set
  * served by a resident kernel that leaves after <n> us without a request; auto, the default: only in a context created with priority 1 -- the
  * session costs whatever else runs on the device 1.3-1.4x while it is alive, so it is opt-in), pp_fast=0|1 (random-grid preprocessing without sorts),
  * small_rows=<n> (partial rows ONE factor of a small synchronous set is planned into at most; 0, the default: one per compute unit -- round 5: two),
@@ -149,7 +150,7 @@ int glim_amd_debug_resident_stats(int device, uint64_t* launches, uint64_t* requ
  *   [11] finaliser of factor 0: pose seen   [12] every row of its factor summed   [13] record stored towards the host
  *   [14] worker blocks with a complete account   [15] = [13]: the device's share of [0]
  *   [16..18] worker blocks: point loop left (before the wave / block reduction), min / median / max
- *   [19] finaliser: its 32 group sums added   [20] its 3x3 blocks rotated (the record store follows)
+ *   [19] finaliser: its 32 group sums added   [20] its 3x3 blocks rotated (the record store follows; = [19] for a raw record, which the host rotates)
  *   [21] NOT a time: the shader clock the session ran at between [11] and [13], MHz (s_memtime ticks per s_memrealtime microsecond)
  * GLIM_AMD_ERR_STATE: a request is in flight, or no session has run with the stamps on. */
 #define GLIM_AMD_RESIDENT_TIMELINE_FIELDS 22
