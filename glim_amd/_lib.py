@@ -124,6 +124,50 @@ class RegistrationResult(C.Structure):
     ]
 
 
+class LMParams(C.Structure):
+    """glim_amd_lm_params (include/glim_amd.h "GICP fine registration")"""
+
+    _fields_ = [
+        ("lambda_initial", C.c_double),
+        ("lambda_factor", C.c_double),
+        ("lambda_upper_bound", C.c_double),
+        ("lambda_lower_bound", C.c_double),
+        ("relative_error_tol", C.c_double),
+        ("absolute_error_tol", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("max_trials", C.c_int32),
+        ("error_scale", C.c_double),
+    ]
+
+
+class AlignResult(C.Structure):
+    """glim_amd_align_result"""
+
+    _fields_ = [
+        ("T_target_source", C.c_double * 12),
+        ("error", C.c_double),
+        ("num_inliers", C.c_int64),
+        ("iterations", C.c_int32),
+        ("trials", C.c_int32),
+        ("status", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lam", C.c_double),
+        ("compact", C.c_double * COMPACT_DOUBLES),
+    ]
+
+
+class AlignTraceEntry(C.Structure):
+    """glim_amd_align_trace_entry (include/glim_amd_diag.h)"""
+
+    _fields_ = [
+        ("T_candidate", C.c_double * 12),
+        ("lam", C.c_double),
+        ("compact", C.c_double * COMPACT_DOUBLES),
+        ("accepted", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -233,6 +277,10 @@ SYMBOLS = {
     "glim_amd_gnc_debug_trace": (_i, [_vp, _vp, _ip, C.POINTER(GncParams), _i64, _ip, _lp, _dp, _dp, _dp, C.POINTER(RegistrationResult),
                                       C.POINTER(GncInfo)]),
     "glim_amd_gnc_profile": (_i, [_vp, _vp, _ip, C.POINTER(GncParams), _i, _fp, _fp, _fp, _fp, _fp]),
+    "glim_amd_gicp_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_gicp_align_batch": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
+    "glim_amd_gicp_align_batch_incremental": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
+    "glim_amd_debug_gicp_align_trace": (_i, [_i32, _pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry)]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -1227,6 +1227,12 @@ class IntegratedGICPFactor:
     def _call(self, name, T, *out):
         check(getattr(lib(), name)(self._target.handle, self.source_frame._h, _dp(T), self.max_correspondence_distance, *out), name)
 
+    def align(self, T_init, params=None):
+        """The fine registration of this factor's pair from T_init (4 x 4 T_target_source): gicp_align_batch with one problem."""
+        r = gicp_align_batch([self._target], [self.source_frame], [T_init], self.max_correspondence_distance, params)[0]
+        self._inliers = r.num_inliers
+        return r
+
     def close(self):
         self._target.close()
         self.target_tree = self._target.tree
@@ -1236,6 +1242,136 @@ class IntegratedGICPFactor:
             self.close()
         except Exception:
             pass
+
+
+class LMParams:
+    """glim_amd_lm_params (include/glim_amd.h "GICP fine registration"): GTSAM's LevenbergMarquardtParams fields the fine registration reads.
+    max_trials = 0: twice max_iterations."""
+
+    def __init__(self, lambda_initial=1e-5, lambda_factor=10.0, lambda_upper_bound=1e5, lambda_lower_bound=0.0, relative_error_tol=1e-5,
+                 absolute_error_tol=1e-5, max_iterations=10, max_trials=0, error_scale=1.0):
+        self.lambda_initial = lambda_initial
+        self.lambda_factor = lambda_factor
+        self.lambda_upper_bound = lambda_upper_bound
+        self.lambda_lower_bound = lambda_lower_bound
+        self.relative_error_tol = relative_error_tol
+        self.absolute_error_tol = absolute_error_tol
+        self.max_iterations = max_iterations
+        self.max_trials = max_trials
+        self.error_scale = error_scale
+
+    def resolved_max_trials(self):
+        return int(self.max_trials) if self.max_trials else 2 * int(self.max_iterations)
+
+    def _c(self):
+        return _lib.LMParams(float(self.lambda_initial), float(self.lambda_factor), float(self.lambda_upper_bound), float(self.lambda_lower_bound),
+                             float(self.relative_error_tol), float(self.absolute_error_tol), int(self.max_iterations), int(self.max_trials),
+                             float(self.error_scale))
+
+
+ALIGN_STATUS = {1: "CONVERGED", 2: "MAX_ITERATIONS", 3: "MAX_TRIALS", 4: "LAMBDA_BOUND", 5: "NO_CORRESPONDENCES", 6: "NUMERIC"}
+
+
+class AlignResult:
+    """glim_amd_align_result: the last kept pose (4 x 4), the factor's error and inliers there, the counts, the status (ALIGN_STATUS), the
+    lambda after the last trial and the compact record at the pose (expand_compact gives the linearisation at the estimate)."""
+
+    def __init__(self, c, source_size):
+        T = np.eye(4)
+        T[:3] = np.array(c.T_target_source[:]).reshape(3, 4)
+        self.T_target_source = T
+        self.error = c.error
+        self.num_inliers = c.num_inliers
+        self.inlier_fraction = c.num_inliers / max(1, source_size)
+        self.iterations = c.iterations
+        self.trials = c.trials
+        self.status = c.status
+        self.status_name = ALIGN_STATUS.get(c.status, "?")
+        self.lam = c.lam
+        self.compact = np.array(c.compact[:])
+
+    def linearized(self, flags=0):
+        return expand_compact(self.compact, self.T_target_source, flags)
+
+
+def _align_args(targets, sources, T_init, max_correspondence_distance):
+    """-> (resolved _GicpTarget per problem, is_ivox, the C arrays)"""
+    n = len(sources)
+    if len(targets) != n:
+        raise ValueError("one target per source")
+    dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_correspondence_distance, dtype=np.float64), (n,)))
+    T = np.zeros((n, 12))
+    for i, Ti in enumerate(T_init):
+        T[i] = pose12(Ti)
+    if len(T_init) != n:
+        raise ValueError("one initial pose per source")
+    resolved, owned = [], {}
+    for t, d in zip(targets, dist):
+        if isinstance(t, PointCloudGPU):  # an index of its own, one per distinct cloud of the batch
+            if id(t) not in owned:
+                owned[id(t)] = _GicpTarget(t, None, float(d))
+            resolved.append(owned[id(t)])
+        elif isinstance(t, _GicpTarget):
+            resolved.append(t)
+        else:
+            resolved.append(_GicpTarget(None, t, float(d)))
+    kinds = {r.ivox is not None for r in resolved}
+    if len(kinds) > 1:
+        for r in owned.values():
+            r.close()
+        raise GlimAmdError(-1, "gicp_align_batch", "search-index and iVox targets in one batch")
+    th = (C.c_void_p * max(n, 1))(*[r.handle for r in resolved])
+    sh = (C.c_void_p * max(n, 1))(*[s._h for s in sources])
+    return list(owned.values()), (kinds == {True}), th, sh, T, dist
+
+
+def gicp_align_batch(targets, sources, T_init, max_correspondence_distance, params=None):
+    """GICP fine registration of len(sources) independent problems in one call and one host synchronisation: Levenberg-Marquardt over one unary
+    IntegratedGICPFactor each (global_mapping_pose_graph.cpp:386-426, global_mapping.cpp:393-426, manual_loop_close_modal.cpp:470-520).
+    targets[i]: a PointCloudGPU (its index is built here), a search-index handle (IntegratedGICPFactor.target_tree) or an IncrementalVoxelMap --
+    one kind per batch; sources[i]: PointCloudGPU with covariances; T_init[i]: 4 x 4 T_target_source; max_correspondence_distance: a number or one
+    per problem.  Returns one AlignResult per problem."""
+    n = len(sources)
+    owned, ivox, th, sh, T, dist = _align_args(targets, sources, T_init, max_correspondence_distance)
+    try:
+        prm = (params or LMParams())._c()
+        out = (_lib.AlignResult * max(n, 1))()
+        name = "glim_amd_gicp_align_batch_incremental" if ivox else "glim_amd_gicp_align_batch"
+        check(getattr(lib(), name)(th, sh, _dp(T), _dp(dist), n, C.byref(prm), out), name)
+    finally:
+        for r in owned:
+            r.close()
+    return [AlignResult(out[i], sources[i].size()) for i in range(n)]
+
+
+def gicp_align_debug_trace(targets, sources, T_init, max_correspondence_distance, params=None):
+    """Test window (glim_amd_debug_gicp_align_trace): gicp_align_batch's results plus, per problem, one dict per round run -- round 0 is the
+    initial pose -- with the pose evaluated (`T`, 4 x 4), the `lam` its step was solved with, the `compact` record there, `accepted` and the
+    `status` after the round (0: still running)."""
+    n = len(sources)
+    params = params or LMParams()
+    owned, ivox, th, sh, T, dist = _align_args(targets, sources, T_init, max_correspondence_distance)
+    rounds = 1 + params.resolved_max_trials()
+    try:
+        prm = params._c()
+        out = (_lib.AlignResult * max(n, 1))()
+        trace = (_lib.AlignTraceEntry * max(n * rounds, 1))()
+        check(lib().glim_amd_debug_gicp_align_trace(1 if ivox else 0, th, sh, _dp(T), _dp(dist), n, C.byref(prm), out, trace),
+              "glim_amd_debug_gicp_align_trace")
+    finally:
+        for r in owned:
+            r.close()
+    results = [AlignResult(out[i], sources[i].size()) for i in range(n)]
+    traces = []
+    for i, r in enumerate(results):
+        rows = []
+        for k in range(min(rounds, r.trials + 1)):
+            e = trace[i * rounds + k]
+            Tk = np.eye(4)
+            Tk[:3] = np.array(e.T_candidate[:]).reshape(3, 4)
+            rows.append({"T": Tk, "lam": e.lam, "compact": np.array(e.compact[:]), "accepted": bool(e.accepted), "status": e.status})
+        traces.append(rows)
+    return results, traces
 
 
 class IntegratedCT_GICPFactor:

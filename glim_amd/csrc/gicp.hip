@@ -443,10 +443,9 @@ __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __
   store_partial_row(acc, inliers, s_red, partials);
 }
 
-// fixed-order FP64 sum of the block partials -> compact record (one block of 256 threads: 8 groups of ordered_column_sum, then the groups in order)
-__global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restrict__ partials, int nb, int linearize, double* __restrict__ out) {
-  __shared__ double s_part[8][PARTIAL_STRIDE];
-  __shared__ double s_sum[PARTIAL_STRIDE];
+// The two steps of the finaliser (a block of 256 threads), shared with the decide kernel of gicp_align.hip: the fixed-order FP64 sum of `nb`
+// partial rows -- 8 groups of ordered_column_sum, then the groups in order -- into s_sum, and entry t of the linearising compact record from it.
+__device__ __forceinline__ void sum_partial_rows(const float* __restrict__ partials, int nb, double (&s_part)[8][PARTIAL_STRIDE], double (&s_sum)[PARTIAL_STRIDE]) {
   const int j = threadIdx.x & 31, g = threadIdx.x >> 5;
   s_part[g][j] = ordered_column_sum<float, PARTIAL_STRIDE, 16>(partials, nb, j, g);
   __syncthreads();
@@ -457,16 +456,21 @@ __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restr
     s_sum[threadIdx.x] = t;
   }
   __syncthreads();
+}
+__device__ __forceinline__ double compact_entry(const double (&s_sum)[PARTIAL_STRIDE], int t) {
+  if (t == 0) return s_sum[28];
+  if (t == 1) return s_sum[27];
+  if (t < 23) return s_sum[c_acc_of_upper_g[t - 2]];
+  return t < 26 ? s_sum[t - 2] : -s_sum[t - 2];
+}
+
+// fixed-order FP64 sum of the block partials -> compact record (one block of 256 threads)
+__global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restrict__ partials, int nb, int linearize, double* __restrict__ out) {
+  __shared__ double s_part[8][PARTIAL_STRIDE];
+  __shared__ double s_sum[PARTIAL_STRIDE];
+  sum_partial_rows(partials, nb, s_part, s_sum);
   const int t = threadIdx.x;
-  if (t == 0) out[0] = s_sum[28];
-  if (t == 1) out[1] = s_sum[27];
-  if (linearize) {
-    if (t < 21) out[2 + t] = s_sum[c_acc_of_upper_g[t]];
-    if (t >= 21 && t < 24) out[2 + t] = s_sum[t];
-    if (t >= 24 && t < 27) out[2 + t] = -s_sum[t];
-  } else if (t >= 2 && t < COMPACT) {
-    out[t] = 0.0;
-  }
+  if (t < COMPACT) out[t] = (linearize || t < 2) ? compact_entry(s_sum, t) : 0.0;
 }
 
 // ---- the continuous-time factor (IntegratedCT_GICPFactor): the same per-point algebra, one pose per time bucket ----
@@ -711,11 +715,12 @@ struct GicpTarget {
   }
 };
 
-GicpTarget gicp_target(const glim_amd_nn_index* ix) {
+// (lock = false: the caller already holds the context's mutex -- a batch of targets of one context, gicp_align.hip)
+GicpTarget gicp_target(const glim_amd_nn_index* ix, bool lock = true) {
   GicpTarget t;
   if (!ix) return t;
   t.ctx = ix->ctx;
-  t.held = std::unique_lock<std::mutex>(t.ctx->mu);
+  if (lock) t.held = std::unique_lock<std::mutex>(t.ctx->mu);
   t.args.sorted = ix->sorted;
   t.args.tA = ix->covA;
   t.args.tB = ix->covB;
@@ -1474,3 +1479,6 @@ int glim_amd_debug_ct_gicp_poses(const glim_amd_ct_gicp_factor* f, const double*
 // GNC global registration, the other estimator over those correspondences (gnc.hip): likewise, and after ransac.hip, whose generator, occupancy
 // table and scoring kernel it uses
 #include "gnc.hip"
+
+// GICP fine registration, a batch of Levenberg-Marquardt loops over the rigid factor above (gicp_align.hip): likewise
+#include "gicp_align.hip"

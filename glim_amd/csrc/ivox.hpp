@@ -365,11 +365,11 @@ int ivox_sweep(glim_amd_ivox* m, hipStream_t st) {
 constexpr int64_t IVOX_MAX_SOURCE = 1 << 28;  // source points of a rigid factor over the map
 
 // the map as a target of the factor kernels (gicp.hip, GicpTarget), as it is now
-GicpTarget gicp_target(const glim_amd_ivox* m) {
+GicpTarget gicp_target(const glim_amd_ivox* m, bool lock = true) {
   GicpTarget t;
   if (!m) return t;
   t.ctx = m->ctx;
-  t.held = std::unique_lock<std::mutex>(t.ctx->mu);
+  if (lock) t.held = std::unique_lock<std::mutex>(t.ctx->mu);
   t.args.sorted = m->pts;
   t.args.tA = m->covA;
   t.args.tB = m->covB;

@@ -605,6 +605,76 @@ int glim_amd_gnc_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* 
                             const glim_amd_fpfh* source_fpfh, uint32_t match_flags, const glim_amd_gnc_params* params,
                             glim_amd_registration_result* result, glim_amd_gnc_info* info);
 
+/* ---- GICP fine registration: "a few Levenberg-Marquardt iterations over one unary IntegratedGICPFactor", the loop GLIM runs at
+ *      src/glim/mapping/global_mapping_pose_graph.cpp:386-426 (loop-candidate validation, LM <= 10, many candidates in parallel :429-438),
+ *      src/glim/mapping/global_mapping.cpp:393-426 (between-submap registration, LM <= 10, then the Hessian at the estimate :423-424),
+ *      src/glim/viewer/interactive/manual_loop_close_modal.cpp:470-520 ("run fine registration", LM <= 20, behind RANSAC / GNC) and
+ *      src/glim/odometry/loose_initial_state_estimation.cpp (iVox target) -- as a batch of B independent problems (target, source, initial
+ *      T_target_source, max_correspondence_distance) in one call with ONE host synchronisation.  The target is fixed.
+ * GTSAM's optimiser is not in the reference tree: the rule below is upstream RECALL of LevenbergMarquardtOptimizer in fixed-lambda-factor mode
+ * (diagonalDamping off), which gtsam_points' LevenbergMarquardtOptimizerExt follows.  FP64, contraction off; one function for host and device:
+ * glim_amd/csrc/lm_step.hpp.
+ *   record     "the error at a pose" is the `error` field of glim_amd_gicp_linearize (glim_amd_ivox_gicp_linearize) at that pose: a trial is one
+ *              linearising evaluation, which gives the candidate's error and, if it is accepted, the system of the next iteration.  Every trial
+ *              record is bit for bit what that entry point returns at the trial's pose.
+ *   solve      (H_ss + lambda I) delta = -b_s by 6 x 6 Cholesky; a pivot that is not > 0 is a failed solve (the trial is rejected).
+ *   retract    T' = T Exp(delta), omega first (series coefficients below 0.02 rad).  The rotation is re-orthonormalised never: the pose travels as
+ *              12 doubles.
+ *   round 0    linearise at the initial pose: always kept, neither an iteration nor a trial.  Zero inliers: NO_CORRESPONDENCES, the initial pose
+ *              is returned.
+ *   a trial    trials += 1.  Accept iff the solve succeeded, the candidate has >= 1 inlier and e_new < e_cur.
+ *     accept   T <- T', keep the record, lambda <- max(lambda / lambda_factor, lambda_lower_bound), iterations += 1; CONVERGED if
+ *              e_cur - e_new <= absolute_error_tol / error_scale or (e_cur - e_new) / e_cur <= relative_error_tol.
+ *     reject   lambda <- lambda * lambda_factor; LAMBDA_BOUND if lambda > lambda_upper_bound; pose and record unchanged, the next candidate is
+ *              solved from the kept record with the new lambda.
+ *   budgets    then MAX_ITERATIONS at iterations == max_iterations, then MAX_TRIALS at trials == max_trials.
+ *   non-finite a non-finite record or pose: NUMERIC, the last kept pose is returned.
+ * Deterministic: the same inputs return the same bits, in any batch, in any context of the same device model. */
+typedef struct {
+  double lambda_initial;     /* 1e-5 (global_mapping.cpp:414 sets 1e-12) */
+  double lambda_factor;      /* 10 */
+  double lambda_upper_bound; /* 1e5 */
+  double lambda_lower_bound; /* 0 */
+  double relative_error_tol; /* 1e-5 */
+  double absolute_error_tol; /* 1e-5 */
+  int32_t max_iterations;    /* 10 (setMaxIterations(10) at global_mapping.cpp:413, global_mapping_pose_graph.cpp:399; 20 in the modal) */
+  int32_t max_trials;        /* 0 = 2 x max_iterations; at most 4096 */
+  double error_scale;        /* 1.0: the twin of GLIM_AMD_VGICP_ERROR_SCALE; enters the absolute tolerance only */
+} glim_amd_lm_params;
+#define GLIM_AMD_ALIGN_CONVERGED 1
+#define GLIM_AMD_ALIGN_MAX_ITERATIONS 2
+#define GLIM_AMD_ALIGN_MAX_TRIALS 3
+#define GLIM_AMD_ALIGN_LAMBDA_BOUND 4
+#define GLIM_AMD_ALIGN_NO_CORRESPONDENCES 5
+#define GLIM_AMD_ALIGN_NUMERIC 6
+typedef struct {
+  double T_target_source[12]; /* the last kept pose */
+  double error;               /* IntegratedGICPFactor::error there (global_mapping_pose_graph.cpp:404) */
+  int64_t num_inliers;        /* inlier_fraction = num_inliers / source size (:405) */
+  int32_t iterations;         /* accepted trials */
+  int32_t trials;
+  int32_t status;             /* GLIM_AMD_ALIGN_* */
+  int32_t reserved;
+  double lambda;              /* after the last trial */
+  double compact[GLIM_AMD_COMPACT_DOUBLES]; /* the record at T_target_source: glim_amd_expand_compact gives the linearisation at the estimate
+                                               (what global_mapping.cpp:423-424 relinearises for) */
+} glim_amd_align_result;
+/* the values above */
+int glim_amd_gicp_align_default_params(glim_amd_lm_params* params);
+/* `count` problems: targets[i], sources[i], T_init12 + 12 i, max_correspondence_distances[i] -> out[i].  params NULL = the defaults.  All handles
+ * belong to ONE context (a target may appear in several problems).  count = 0 is OK.  Nothing is launched when an argument is refused:
+ * GLIM_AMD_ERR_INVALID: a NULL argument or handle, count < 0, a distance that is NaN or < 0, handles of two contexts, an empty source or target,
+ * a parameter that is not finite, lambda_factor <= 1, max_iterations < 0, max_trials < 0 or > 4096, error_scale <= 0;
+ * GLIM_AMD_ERR_STATE: a source or target without covariances; GLIM_AMD_ERR_UNSUPPORTED: a distance beyond the index's ring walk (see
+ * glim_amd_nn_index_create). */
+int glim_amd_gicp_align_batch(const glim_amd_nn_index* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                              const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
+                              glim_amd_align_result* out);
+/* the same over device iVox targets, glim_amd_ivox handles (loose_initial_state_estimation.cpp); the maps' neighbour modes may differ */
+int glim_amd_gicp_align_batch_incremental(const glim_amd_ivox* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                                   const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
+                                   glim_amd_align_result* out);
+
 #ifdef __cplusplus
 }
 #endif

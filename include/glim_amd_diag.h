@@ -224,6 +224,20 @@ int glim_amd_debug_multi_set_diag(glim_amd_multi* multi, const char* key_values)
 /* the DEVICE-resident gathered array of `device` after the exchange, copied back and put in factor order like glim_amd_multi_records: what a
  * device-side consumer on that device would read (tests: every device must hold every record, bit for bit) */
 int glim_amd_debug_multi_gathered_download(glim_amd_multi* multi, int32_t device, int64_t first, int64_t count, double* compact29);
+/* test window of the GICP fine registration (glim_amd.h "GICP fine registration"): the search-index entry point when ivox = 0 (targets are
+ * glim_amd_nn_index handles), the iVox one when ivox = 1 (glim_amd_ivox handles), with the same arguments and results, plus one
+ * entry per problem and round: trace[i * (1 + max_trials) + r], max_trials as resolved (0 = 2 x max_iterations).  Round 0 is the initial pose;
+ * the entries of problem i are valid for r <= out[i].trials, the rest are zero. */
+typedef struct {
+  double T_candidate[12]; /* the pose the round evaluated */
+  double lambda;          /* the lambda its step was solved with (lambda_initial in round 0) */
+  double compact[29];     /* the record there */
+  int32_t accepted;
+  int32_t status;         /* after the round; 0 = still running */
+} glim_amd_align_trace_entry;
+int glim_amd_debug_gicp_align_trace(int32_t ivox, const void* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                                    const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
+                                    glim_amd_align_result* out, glim_amd_align_trace_entry* trace);
 
 #ifdef __cplusplus
 }

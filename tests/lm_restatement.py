@@ -1,0 +1,129 @@
+"""NumPy restatement of the step rule of the GICP fine registration (glim_amd/csrc/lm_step.hpp, include/glim_amd.h "GICP fine registration"):
+Levenberg-Marquardt in fixed-lambda-factor mode over one factor, driven by a `linearize(T) -> record` callable.  A record is a dict with
+num_inliers, error, H_ss (6 x 6) and b_s (6), what the oracle and IntegratedGICPFactor.linearize return."""
+import numpy as np
+
+RUNNING, CONVERGED, MAX_ITERATIONS, MAX_TRIALS, LAMBDA_BOUND, NO_CORRESPONDENCES, NUMERIC = range(7)
+EXP_SERIES = 0.02
+EPS = 2.2e-16
+
+DEFAULTS = dict(lambda_initial=1e-5, lambda_factor=10.0, lambda_upper_bound=1e5, lambda_lower_bound=0.0, relative_error_tol=1e-5,
+                absolute_error_tol=1e-5, max_iterations=10, max_trials=0, error_scale=1.0)
+
+
+def params(**kw):
+    p = dict(DEFAULTS)
+    p.update(kw)
+    if not p["max_trials"]:
+        p["max_trials"] = 2 * p["max_iterations"]
+    return p
+
+
+def record_of_compact(c):
+    c = np.asarray(c, dtype=np.float64)
+    H = np.zeros((6, 6))
+    H[np.triu_indices(6)] = c[2:23]
+    H = H + np.triu(H, 1).T
+    return {"num_inliers": int(round(c[0])), "error": float(c[1]), "H_ss": H, "b_s": c[23:29].copy()}
+
+
+def compact_of_record(L):
+    return np.concatenate([[float(L["num_inliers"]), float(L["error"])], np.asarray(L["H_ss"])[np.triu_indices(6)], np.asarray(L["b_s"])])
+
+
+def expmap(xi):
+    """Exp of (omega, v): [R | V v], series coefficients below EXP_SERIES"""
+    w, v = np.asarray(xi[:3], dtype=np.float64), np.asarray(xi[3:], dtype=np.float64)
+    t2 = float(w @ w)
+    th = np.sqrt(t2)
+    if th < EXP_SERIES:
+        a, b, c = 1 - t2 / 6 + t2 * t2 / 120, 0.5 - t2 / 24 + t2 * t2 / 720, 1 / 6 - t2 / 120 + t2 * t2 / 5040
+    else:
+        a, b, c = np.sin(th) / th, (1 - np.cos(th)) / t2, (th - np.sin(th)) / (t2 * th)
+    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + a * W + b * W @ W
+    T[:3, 3] = (np.eye(3) + b * W + c * W @ W) @ v
+    return T
+
+
+def solve(L, lam):
+    """(H + lam I) delta = -b by Cholesky -> (ok, delta, gate): ok False when a pivot is not > 0; gate = the bound on |delta - other's delta|
+    that scales itself with the case, 100 cond(H + lam I) eps max(|delta|, 1e-12)"""
+    A = np.asarray(L["H_ss"], dtype=np.float64) + lam * np.eye(6)
+    try:
+        C = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return False, np.zeros(6), 0.0
+    if not np.all(np.isfinite(C)) or not np.all(np.diag(C) > 0):
+        return False, np.zeros(6), 0.0
+    y = np.linalg.solve(C, -np.asarray(L["b_s"], dtype=np.float64))
+    d = np.linalg.solve(C.T, y)
+    return True, d, 100.0 * np.linalg.cond(A) * EPS * max(np.abs(d).max(), 1e-12)
+
+
+def _finite(L, T):
+    return all(np.all(np.isfinite(np.asarray(x, dtype=np.float64))) for x in (L["error"], L["H_ss"], L["b_s"], T, float(L["num_inliers"])))
+
+
+def new_state(T_init, p):
+    T = np.array(T_init, dtype=np.float64)
+    return {"T": T, "rec": None, "lam": p["lambda_initial"], "cand": T.copy(), "delta": np.zeros(6), "gate": 0.0, "solve_ok": True, "started": False,
+            "iterations": 0, "trials": 0, "status": RUNNING, "accepted": False}
+
+
+def step(p, s, L):
+    """One round: L is the record evaluated at s['cand'].  Returns the new state (the argument is left alone)."""
+    s = dict(s)
+    if s["status"] != RUNNING:
+        return s
+    s["accepted"] = False
+    if not _finite(L, s["cand"]):
+        s["status"] = NUMERIC
+        return s
+    if not s["started"]:
+        s["started"], s["accepted"], s["rec"] = True, True, L
+        if not L["num_inliers"] >= 1:
+            s["status"] = NO_CORRESPONDENCES
+            return s
+    else:
+        s["trials"] += 1
+        e_cur, e_new = s["rec"]["error"], L["error"]
+        if s["solve_ok"] and L["num_inliers"] >= 1 and e_new < e_cur:
+            s["accepted"], s["T"], s["rec"] = True, s["cand"], L
+            s["lam"] = max(s["lam"] / p["lambda_factor"], p["lambda_lower_bound"])
+            s["iterations"] += 1
+            d = e_cur - e_new
+            if d <= p["absolute_error_tol"] / p["error_scale"] or d / e_cur <= p["relative_error_tol"]:
+                s["status"] = CONVERGED
+        else:
+            s["lam"] = s["lam"] * p["lambda_factor"]
+            if not s["lam"] <= p["lambda_upper_bound"]:
+                s["status"] = LAMBDA_BOUND
+    if s["status"] == RUNNING and s["iterations"] >= p["max_iterations"]:
+        s["status"] = MAX_ITERATIONS
+    if s["status"] == RUNNING and s["trials"] >= p["max_trials"]:
+        s["status"] = MAX_TRIALS
+    if s["status"] != RUNNING:
+        return s
+    s["solve_ok"], s["delta"], s["gate"] = solve(s["rec"], s["lam"])
+    s["cand"] = s["T"] @ expmap(s["delta"]) if s["solve_ok"] else s["T"]
+    if not np.all(np.isfinite(s["cand"])):
+        s["status"] = NUMERIC
+    return s
+
+
+def run(linearize, T_init, p=None):
+    """The whole loop -> (final state, trace): one trace entry per round with the pose evaluated (T), the lambda of its step (lam), the record,
+    accepted, the status after the round, and `state`, the state after it."""
+    p = p or params()
+    s = new_state(T_init, p)
+    trace = []
+    for _ in range(1 + p["max_trials"]):
+        if s["status"] != RUNNING:
+            break
+        T, lam = s["cand"], s["lam"]
+        L = linearize(T)
+        s = step(p, s, L)
+        trace.append({"T": T, "lam": lam, "record": L, "accepted": s["accepted"], "status": s["status"], "state": s})
+    return s, trace
