@@ -405,12 +405,23 @@ class RegistrationResult:
         self.iterations_run = c.iterations_run
 
 
+def _c_params(params, default):
+    """the C block of `params`, or of default() when the caller passed none"""
+    return (params or default())._c()
+
+
+def _nearest(nearest, source=None):
+    """`nearest` as contiguous int32; with `source` (the *_align functions) it must hold one entry per source point"""
+    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    if source is not None and near.shape != (source.size(),):
+        raise ValueError("nearest must hold one entry per source point")
+    return near
+
+
 def ransac_align(target, source, nearest, params=None):
     """gtsam_points::estimate_pose_ransac on the device: nearest[i] = target point matched to source point i, or -1 (match_fpfh's output)."""
-    prm = (params or RansacParams())._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
-    if near.shape != (source.size(),):
-        raise ValueError("nearest must hold one entry per source point")
+    prm = _c_params(params, RansacParams)
+    near = _nearest(nearest, source)
     out = _lib.RegistrationResult()
     check(lib().glim_amd_ransac_align(target._h, source._h, _ip(near), C.byref(prm), C.byref(out)), "glim_amd_ransac_align")
     return RegistrationResult(out)
@@ -418,7 +429,7 @@ def ransac_align(target, source, nearest, params=None):
 
 def ransac_align_fpfh(target, source, target_fpfh, source_fpfh, params=None, reciprocal=False):
     """The same with the nearest-descriptor correspondences found on the device (they never visit the host)."""
-    prm = (params or RansacParams())._c()
+    prm = _c_params(params, RansacParams)
     out = _lib.RegistrationResult()
     check(lib().glim_amd_ransac_align_fpfh(target._h, source._h, target_fpfh._h, source_fpfh._h, FPFH_RECIPROCAL if reciprocal else 0, C.byref(prm),
                                            C.byref(out)), "glim_amd_ransac_align_fpfh")
@@ -428,7 +439,7 @@ def ransac_align_fpfh(target, source, target_fpfh, source_fpfh, params=None, rec
 def ransac_debug_hypotheses(target, source, nearest, params, first, count):
     """Test window (glim_amd_ransac_debug_hypotheses): every hypothesis of [first, first + count) scored, no early stop."""
     prm = params._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    near = _nearest(nearest)
     samples = np.zeros((count, 3), dtype=np.int32)
     status = np.zeros(count, dtype=np.int32)
     poses = np.zeros((count, 12), dtype=np.float64)
@@ -442,7 +453,7 @@ def ransac_debug_hypotheses(target, source, nearest, params, first, count):
 def ransac_profile(target, source, nearest, params, iters=20):
     """microseconds of the hypothesis / scoring / fold kernels of one round (HIP events inside the library)"""
     prm = params._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    near = _nearest(nearest)
     us = [C.c_float() for _ in range(3)]
     slots, in_lds = C.c_int32(), C.c_int32()
     check(lib().glim_amd_ransac_profile(target._h, source._h, _ip(near), C.byref(prm), int(iters), C.byref(us[0]), C.byref(us[1]), C.byref(us[2]),
@@ -481,10 +492,8 @@ def _gnc_result(out, info):
 def gnc_align(target, source, nearest, params=None):
     """gtsam_points::estimate_pose_gnc on the device: nearest[i] = target point matched to source point i, or -1 (match_fpfh's output).
     Returns a RegistrationResult with `info` (glim_amd_gnc_info as a dict)."""
-    prm = (params or GncParams())._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
-    if near.shape != (source.size(),):
-        raise ValueError("nearest must hold one entry per source point")
+    prm = _c_params(params, GncParams)
+    near = _nearest(nearest, source)
     out, info = _lib.RegistrationResult(), _lib.GncInfo()
     check(lib().glim_amd_gnc_align(target._h, source._h, _ip(near), C.byref(prm), C.byref(out), C.byref(info)), "glim_amd_gnc_align")
     return _gnc_result(out, info)
@@ -492,7 +501,7 @@ def gnc_align(target, source, nearest, params=None):
 
 def gnc_align_fpfh(target, source, target_fpfh, source_fpfh, params=None, reciprocal=True):
     """The same with the nearest-descriptor correspondences found on the device (they never visit the host); reciprocal = GNCParams::reciprocal_check."""
-    prm = (params or GncParams())._c()
+    prm = _c_params(params, GncParams)
     out, info = _lib.RegistrationResult(), _lib.GncInfo()
     check(lib().glim_amd_gnc_align_fpfh(target._h, source._h, target_fpfh._h, source_fpfh._h, FPFH_RECIPROCAL if reciprocal else 0, C.byref(prm),
                                         C.byref(out), C.byref(info)), "glim_amd_gnc_align_fpfh")
@@ -503,7 +512,7 @@ def gnc_debug_trace(target, source, nearest, params):
     """Test window (glim_amd_gnc_debug_trace): the final list (n x 2: source, target index), c_s, c_t, D2, per completed iteration mu / W / cost /
     pose (3 x 4), the last iteration's weights, and the result gnc_align returns on the same arguments."""
     prm = params._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    near = _nearest(nearest)
     cap = max(source.size(), 3 * int(params.max_num_tuples) if params.tuple_check else 0, 1)
     pairs = np.zeros((cap, 2), dtype=np.int32)
     length = C.c_int64()
@@ -523,7 +532,7 @@ def gnc_debug_trace(target, source, nearest, params):
 def gnc_profile(target, source, nearest, params, iters=20):
     """microseconds of the stages of one gnc_align (HIP events inside the library)"""
     prm = params._c()
-    near = np.ascontiguousarray(nearest, dtype=np.int32)
+    near = _nearest(nearest)
     us = [C.c_float() for _ in range(5)]
     check(lib().glim_amd_gnc_profile(target._h, source._h, _ip(near), C.byref(prm), int(iters), *[C.byref(u) for u in us]), "glim_amd_gnc_profile")
     return dict(zip(("select_us", "tuples_us", "gather_and_solve_us", "table_us", "score_us"), (u.value for u in us)))

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <vector>
 
 #include "device_math.hpp"
 #include "internal.hpp"
@@ -447,6 +448,18 @@ int enqueue_match_both(glim_amd_ctx* ctx, hipStream_t st, const glim_amd_fpfh* t
   return GLIM_AMD_OK;
 }
 
+using FpfhPtr = std::unique_ptr<glim_amd_fpfh, int (*)(glim_amd_fpfh*)>;
+
+// a descriptor object of `n` rows (storage for one when n = 0), its rows not initialised.  The caller holds ctx->mu and has set the device.
+int new_fpfh(glim_amd_ctx* ctx, int64_t n, FpfhPtr* out) {
+  FpfhPtr f(new glim_amd_fpfh(), glim_amd_fpfh_destroy);
+  f->ctx = ctx;
+  f->n = n;
+  GA_HIP(pool_malloc(&f->desc, (size_t)std::max<int64_t>(n, 1) * FPFH_STRIDE * sizeof(float)));
+  *out = std::move(f);
+  return GLIM_AMD_OK;
+}
+
 }  // namespace fpfh_detail
 }  // namespace glim_amd
 
@@ -479,11 +492,9 @@ int glim_amd_fpfh_estimate(const glim_amd_cloud* cloud, double search_radius, gl
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
   const int n = (int)cloud->n;
-  std::unique_ptr<glim_amd_fpfh, int (*)(glim_amd_fpfh*)> f(new glim_amd_fpfh(), glim_amd_fpfh_destroy);
-  f->ctx = ctx;
-  f->n = n;
+  FpfhPtr f(nullptr, glim_amd_fpfh_destroy);
+  GA_TRY(new_fpfh(ctx, n, &f));
   const size_t nn = (size_t)std::max(n, 1);
-  GA_HIP(pool_malloc(&f->desc, nn * FPFH_STRIDE * sizeof(float)));
   if (n == 0) {
     *out = f.release();
     return GLIM_AMD_OK;
@@ -556,6 +567,35 @@ int glim_amd_fpfh_estimate(const glim_amd_cloud* cloud, double search_radius, gl
   }
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
+  *out = f.release();
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_fpfh_create(glim_amd_ctx* ctx, int64_t n, const float* descriptors33, glim_amd_fpfh** out) {
+  using namespace glim_amd;
+  using namespace glim_amd::fpfh_detail;
+  if (!ctx || !out) return GLIM_AMD_ERR_INVALID;
+  *out = nullptr;
+  if (n < 0 || n > (int64_t)(1 << 28) || (n > 0 && !descriptors33)) return GLIM_AMD_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  FpfhPtr f(nullptr, glim_amd_fpfh_destroy);
+  GA_TRY(new_fpfh(ctx, n, &f));
+  if (n > 0) {
+    // the device row: 33 bins | the matcher's FMA chain of the row with itself, as fpfh_kernel stores it | 0 0
+    std::vector<float> rows((size_t)n * FPFH_STRIDE, 0.0f);
+    for (int64_t i = 0; i < n; i++) {
+      float* row = &rows[(size_t)i * FPFH_STRIDE];
+      float nn2 = 0.0f;
+      for (int b = 0; b < FPFH_DIM; b++) {
+        row[b] = descriptors33[(size_t)i * FPFH_DIM + b];
+        nn2 = fmaf(row[b], row[b], nn2);
+      }
+      row[FPFH_DIM] = nn2;
+    }
+    GA_HIP(hipMemcpyAsync(f->desc, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream()));
+    GA_HIP(hipStreamSynchronize(ctx->stream()));
+  }
   *out = f.release();
   return GLIM_AMD_OK;
 }

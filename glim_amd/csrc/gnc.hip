@@ -1,8 +1,8 @@
 // gnc.hip -- GNC global registration on gfx950: gtsam_points::estimate_pose_gnc as viewer/interactive/manual_loop_close_modal.cpp:445-458 calls it,
 // the second consumer of fpfh.hip's descriptors and correspondences.  Semantics in include/glim_amd.h ("GNC"), layout in DESIGN.md 4.7b.
 //
-// Built as part of gicp.hip's translation unit, after ransac.hip (whose generator, occupancy table and scoring kernel it uses), for the reason the
-// head of fpfh.hip gives.
+// Built as part of gicp.hip's translation unit, after ransac.hip, for the reason the head of fpfh.hip gives.  It uses ransac.hip's occupancy table,
+// round buffers and scoring launch (and, through ransac.hip, the generator of sample_hash.hpp) and registration_host.hpp's host scaffold.
 //
 // select   keep[i] = candidate and matched and both points finite (the candidate marks are plain stores of one value), exclusive scan of scan.hpp,
 //          compaction into (source index, target index) pairs in ascending i.
@@ -20,6 +20,7 @@
 #include "device_math.hpp"
 #include "gnc_pose.hpp"
 #include "internal.hpp"
+#include "registration_host.hpp"
 #include "scan.hpp"
 #include "scope_sync.hpp"
 
@@ -27,6 +28,7 @@ namespace glim_amd {
 namespace gnc_detail {
 
 using ransac_detail::sample_hash;
+using reg_detail::Pair;
 using ransac_detail::u32;
 using ransac_detail::u64;
 
@@ -277,24 +279,6 @@ int check_params(const glim_amd_gnc_params* p) {
   return GLIM_AMD_OK;
 }
 
-void no_estimate(glim_amd_registration_result* r) {
-  const double I[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-  std::memcpy(r->T_target_source, I, sizeof(I));
-  r->inlier_rate = 0.0;
-  r->num_inliers = 0;
-  r->best_iteration = -1;
-  r->iterations_run = 0;
-}
-
-struct Problem {
-  glim_amd_ctx* ctx;
-  hipStream_t st;
-  int n_src, n_tgt;
-  const float4 *spts, *tpts;
-  const int* d_nearest;
-  glim_amd_gnc_params prm;
-};
-
 // what glim_amd_gnc_debug_trace hands out (host pointers, any may be null)
 struct Trace {
   int64_t list_capacity = 0;
@@ -303,32 +287,16 @@ struct Trace {
   double *frame7 = nullptr, *iterations15 = nullptr, *weights = nullptr;
 };
 
-// HIP events at the six stage boundaries (glim_amd_gnc_profile)
-struct StageClock {
-  hipEvent_t ev[6] = {};
-  bool on = false;
-  int start() {
-    for (auto& e : ev) GA_HIP(hipEventCreate(&e));
-    on = true;
-    return GLIM_AMD_OK;
-  }
-  void mark(int i, hipStream_t st) {
-    if (on) (void)hipEventRecord(ev[i], st);
-  }
-  ~StageClock() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
+using StageClock = reg_detail::StageClock<6>;  // the six boundaries of the five stages (glim_amd_gnc_profile)
 
 inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // caller holds ctx->mu, the device is set, p.d_nearest is on the device and in range; info is not null
-int run(const Problem& p, glim_amd_registration_result* result, glim_amd_gnc_info* info, const Trace* trace, StageClock* clock) {
-  const glim_amd_gnc_params& prm = p.prm;
+int run(const Pair& p, const glim_amd_gnc_params& prm, glim_amd_registration_result* result, glim_amd_gnc_info* info, const Trace* trace,
+        StageClock* clock) {
   hipStream_t st = p.st;
   *info = glim_amd_gnc_info{};
-  no_estimate(result);
+  reg_detail::identity_result(result, 0);
   if (trace && trace->list_length) *trace->list_length = 0;
   StageClock idle;
   if (!clock) clock = &idle;
@@ -417,10 +385,7 @@ int run(const Problem& p, glim_amd_registration_result* result, glim_amd_gnc_inf
   ransac_detail::Table table;
   GA_TRY(ransac_detail::build_table(p.ctx, st, p.tpts, p.n_tgt, 1.0 / prm.inlier_voxel_resolution, &table));
   clock->mark(4, st);
-  glim_amd_ransac_params rp{};
-  rp.inlier_voxel_resolution = prm.inlier_voxel_resolution;
-  const ransac_detail::Problem score{p.ctx, st, p.n_src, p.n_tgt, p.spts, p.tpts, p.d_nearest, rp};
-  ransac_detail::launch_score(score, table, b, 1);
+  ransac_detail::launch_score(p, prm.inlier_voxel_resolution, table, b, 1);
   GA_HIP(hipGetLastError());
   clock->mark(5, st);
   SolveOut h{};
@@ -451,41 +416,28 @@ int run(const Problem& p, glim_amd_registration_result* result, glim_amd_gnc_inf
   return GLIM_AMD_OK;
 }
 
-// the entries that take `nearest` from the host
+// the entries that take `nearest` from the host; us5: the five stage times of glim_amd_gnc_profile, over `iters` timed calls
 int run_with_host_nearest(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_gnc_params* params,
                           glim_amd_registration_result* result, glim_amd_gnc_info* info, const Trace* trace, int iters, float* us5) {
   if (!result) return GLIM_AMD_ERR_INVALID;
-  GA_TRY(ransac_detail::check_clouds(target, source));
+  GA_TRY(reg_detail::check_pair(target, source));
   GA_TRY(check_params(params));
-  GA_TRY(ransac_detail::check_nearest(nearest, source->n, target->n));
+  GA_TRY(reg_detail::check_nearest(nearest, source->n, target->n));
   glim_amd_gnc_info local;
   if (!info) info = &local;
-  glim_amd_ctx* ctx = source->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  DeviceTemp d_nearest;
-  if (source->n > 0) {
-    GA_HIP(pool_malloc(&d_nearest.p, (size_t)source->n * sizeof(int)));
-    GA_HIP(hipMemcpyAsync(d_nearest.p, nearest, (size_t)source->n * sizeof(int), hipMemcpyHostToDevice, st));
-    GA_HIP(hipStreamSynchronize(st));
-  }
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, d_nearest.as<int>(), *params};
-  if (!us5) return run(p, result, info, trace, nullptr);
-  StageClock clock;
-  GA_TRY(clock.start());
-  double sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = -1; i < iters; i++) {  // one warm-up call
-    GA_TRY(run(p, result, info, nullptr, &clock));
-    GA_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < 5 && i >= 0; k++) {
-      float ms = 0.0f;
-      GA_HIP(hipEventElapsedTime(&ms, clock.ev[k], clock.ev[k + 1]));
-      sum[k] += (double)ms * 1e3;
+  return reg_detail::with_host_nearest(target, source, nearest, [&](const Pair& p) -> int {
+    if (!us5) return run(p, *params, result, info, trace, nullptr);
+    StageClock clock;
+    GA_TRY(clock.start());
+    double sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = -1; i < iters; i++) {  // one warm-up call
+      GA_TRY(run(p, *params, result, info, nullptr, &clock));
+      GA_HIP(hipStreamSynchronize(p.st));
+      for (int k = 0; k < 5 && i >= 0; k++) GA_HIP(clock.add_us(k, &sum[k]));
     }
-  }
-  for (int k = 0; k < 5; k++) us5[k] = (float)(sum[k] / iters);
-  return GLIM_AMD_OK;
+    for (int k = 0; k < 5; k++) us5[k] = (float)(sum[k] / iters);
+    return GLIM_AMD_OK;
+  });
 }
 
 }  // namespace gnc_detail
@@ -518,32 +470,18 @@ int glim_amd_gnc_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* 
                             glim_amd_registration_result* result, glim_amd_gnc_info* info) {
   using namespace glim_amd;
   using namespace glim_amd::gnc_detail;
-  if (!result || !target_fpfh || !source_fpfh) return GLIM_AMD_ERR_INVALID;
-  GA_TRY(ransac_detail::check_clouds(target, source));
-  glim_amd_ctx* ctx = source->ctx;
-  if ((glim_amd_ctx*)target_fpfh->ctx != ctx || (glim_amd_ctx*)source_fpfh->ctx != ctx) return GLIM_AMD_ERR_INVALID;
-  if (match_flags & ~(uint32_t)GLIM_AMD_FPFH_RECIPROCAL) return GLIM_AMD_ERR_INVALID;
+  if (!result) return GLIM_AMD_ERR_INVALID;
+  GA_TRY(reg_detail::check_fpfh_pair(target, source, target_fpfh, source_fpfh, match_flags));
   GA_TRY(check_params(params));
-  if (target_fpfh->n != target->n || source_fpfh->n != source->n) return GLIM_AMD_ERR_INVALID;
   glim_amd_gnc_info local;
   if (!info) info = &local;
   if (source->n == 0 || target->n == 0) {
     *info = glim_amd_gnc_info{};
-    no_estimate(result);
+    reg_detail::identity_result(result, 0);
     return GLIM_AMD_OK;
   }
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  fpfh_detail::MatchBuffers m;  // (outlives the run: `nearest` is read by the selection kernels)
-  {
-    SyncOnExit in_flight(st);
-    GA_TRY(fpfh_detail::enqueue_match_both(ctx, st, target_fpfh, source_fpfh, match_flags, &m));
-    GA_HIP(hipStreamSynchronize(st));
-    in_flight.dismiss();
-  }
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, m.fwd_i.as<int>(), *params};
-  return run(p, result, info, nullptr, nullptr);
+  return reg_detail::with_matched_nearest(target, source, target_fpfh, source_fpfh, match_flags,
+                                          [&](const Pair& p) { return run(p, *params, result, info, nullptr, nullptr); });
 }
 
 int glim_amd_gnc_debug_trace(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_gnc_params* params,

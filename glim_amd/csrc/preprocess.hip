@@ -24,6 +24,7 @@
 #include "scope_sync.hpp"
 #include "device_math.hpp"
 #include "scan.hpp"
+#include "sample_hash.hpp"  // == orc_sample_hash
 
 using namespace glim_amd;
 
@@ -33,14 +34,6 @@ using u64 = unsigned long long;
 using u32 = unsigned int;
 
 constexpr u64 INVALID_VKEY = ~0ull;
-
-// == orc_sample_hash (splitmix64 of seed + (index + 1) * golden)
-__host__ __device__ inline u64 sample_hash(u64 seed, u64 index) {
-  u64 z = seed + (index + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // ---- K9a: voxel key (x lowest, 21 bits per axis, offset 2^20) + bounding box of the valid coordinates ----
 __global__ __launch_bounds__(256) void pp_key_kernel(int n, const double4* __restrict__ p4, double inv_res, u64* __restrict__ vkey,

@@ -1,8 +1,10 @@
 // ransac.hip -- RANSAC global registration on gfx950: gtsam_points::estimate_pose_ransac as viewer/interactive/manual_loop_close_modal.cpp:431-443
 // calls it, the consumer of fpfh.hip's descriptors and correspondences.  Semantics in include/glim_amd.h ("RANSAC"), layout in DESIGN.md 4.7a.
 //
-// Built as part of gicp.hip's translation unit, after fpfh.hip (whose descriptor object and matcher the *_fpfh entry uses), for the reason the
-// head of fpfh.hip gives: the csrc Makefile is part of the identity of the committed traffic evidence.
+// Built as part of gicp.hip's translation unit, after fpfh.hip, for the reason the head of fpfh.hip gives: the csrc Makefile is part of the
+// identity of the committed traffic evidence.  The host scaffold of the entries is registration_host.hpp, shared with gnc.hip (it is that header
+// which uses fpfh.hip's descriptor object and matcher); the generator is sample_hash.hpp, shared with preprocess.hip; gnc.hip uses this file's
+// occupancy table, round buffers and scoring launch.
 //
 // table      occupancy set of the target: 64-bit keys only, open addressing, power-of-two slots, load <= 0.5, insert = one 64-bit integer
 //            compare-and-swap per probe.  Built twice: into a table sized by the POINTS (the number of voxels is not known yet), which also counts
@@ -21,11 +23,15 @@
 #include "device_math.hpp"
 #include "internal.hpp"
 #include "ransac_pose.hpp"
+#include "registration_host.hpp"
+#include "sample_hash.hpp"
 #include "scope_sync.hpp"
 
 namespace glim_amd {
 namespace ransac_detail {
 
+using glim_amd::sample_hash;
+using reg_detail::Pair;
 using u64 = unsigned long long;
 using u32 = unsigned int;
 
@@ -35,18 +41,9 @@ constexpr int SC_PPL = 4;            // source points per lane
 constexpr int SC_TILE = SC_BLOCK * SC_PPL;
 constexpr int LDS_SLOTS_MAX = 8192;  // 64 KiB of keys: two blocks (16 wavefronts) per compute unit of 160 KiB; <= 4 096 slots: four blocks, the wave limit
 constexpr int MIN_SLOTS = 64;
-constexpr int64_t MAX_POINTS = (int64_t)1 << 27;
 
 // the debug cut of the LDS form (glim_amd_debug_ransac_max_lds_slots): per thread, tests and the timing tool only
 thread_local int g_lds_slots_max = LDS_SLOTS_MAX;
-
-// == preprocess.hip sample_hash (splitmix64 of seed + (index + 1) * golden)
-__host__ __device__ inline u64 sample_hash(u64 seed, u64 index) {
-  u64 z = seed + (index + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ u32 slot_of(u64 key, u32 mask) { return (u32)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask; }
 
@@ -290,27 +287,19 @@ struct RoundBuffers {
   }
 };
 
-struct Problem {
-  glim_amd_ctx* ctx;
-  hipStream_t st;
-  int n_src, n_tgt;
-  const float4 *spts, *tpts;
-  const int* d_nearest;
-  glim_amd_ransac_params prm;
-};
-
-inline void launch_hypotheses(const Problem& p, const RoundBuffers& b, int base, int count) {
-  rs_hypothesis_kernel<<<(count + 255) / 256, 256, 0, p.st>>>(count, base, (u64)p.prm.seed, p.n_src, p.spts, p.tpts, p.d_nearest, p.prm.poly_error_thresh,
-                                                               p.prm.dof, b.samples.as<int>(), b.status.as<int>(), b.poses.as<double>(),
+inline void launch_hypotheses(const Pair& p, const glim_amd_ransac_params& prm, const RoundBuffers& b, int base, int count) {
+  rs_hypothesis_kernel<<<(count + 255) / 256, 256, 0, p.st>>>(count, base, (u64)prm.seed, p.n_src, p.spts, p.tpts, p.d_nearest, prm.poly_error_thresh,
+                                                               prm.dof, b.samples.as<int>(), b.status.as<int>(), b.poses.as<double>(),
                                                                b.counts.as<int>());
 }
-// enough blocks for four per compute unit, never fewer than 16 hypotheses per block (the table copy and the point loads are per block)
-inline void launch_score(const Problem& p, const Table& t, const RoundBuffers& b, int count) {
+// the first `count` hypotheses of `b` against the table of voxels of edge `resolution`.  Enough blocks for four per compute unit, never fewer
+// than 16 hypotheses per block (the table copy and the point loads are per block)
+inline void launch_score(const Pair& p, double resolution, const Table& t, const RoundBuffers& b, int count) {
   const int tiles = (p.n_src + SC_TILE - 1) / SC_TILE;
   const int want = 4 * std::max(p.ctx->num_cus, 1);
   const int hpb = std::min(count, std::max(16, (int)(((int64_t)count * tiles + want - 1) / want)));
   const dim3 grid((unsigned)tiles, (unsigned)((count + hpb - 1) / hpb));
-  const double inv_res = 1.0 / p.prm.inlier_voxel_resolution;
+  const double inv_res = 1.0 / resolution;
   if (t.in_lds) {
     static const hipError_t lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&rs_score_kernel<true>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SLOTS_MAX * (int)sizeof(u64));
@@ -322,8 +311,8 @@ inline void launch_score(const Problem& p, const Table& t, const RoundBuffers& b
                                                         b.status.as<int>(), b.counts.as<int>());
   }
 }
-inline void launch_fold(const Problem& p, const RoundBuffers& b, int base, int count) {
-  rs_fold_kernel<<<1, 256, 0, p.st>>>(count, base, p.prm.early_stop_inlier_rate * (double)p.n_src, b.status.as<int>(), b.counts.as<int>(),
+inline void launch_fold(const Pair& p, const glim_amd_ransac_params& prm, const RoundBuffers& b, int base, int count) {
+  rs_fold_kernel<<<1, 256, 0, p.st>>>(count, base, prm.early_stop_inlier_rate * (double)p.n_src, b.status.as<int>(), b.counts.as<int>(),
                                       b.poses.as<double>(), b.state.as<FoldState>());
 }
 
@@ -335,50 +324,29 @@ int check_params(const glim_amd_ransac_params* p) {
   if (std::isnan(p->early_stop_inlier_rate) || std::isnan(p->poly_error_thresh)) return GLIM_AMD_ERR_INVALID;
   return GLIM_AMD_OK;
 }
-int check_clouds(const glim_amd_cloud* target, const glim_amd_cloud* source) {
-  if (!target || !source) return GLIM_AMD_ERR_INVALID;
-  if ((glim_amd_ctx*)target->ctx != (glim_amd_ctx*)source->ctx) return GLIM_AMD_ERR_INVALID;
-  if (target->n > MAX_POINTS || source->n > MAX_POINTS) return GLIM_AMD_ERR_INVALID;
-  return GLIM_AMD_OK;
-}
-int check_nearest(const int32_t* nearest, int64_t n_src, int64_t n_tgt) {
-  if (!nearest && n_src > 0) return GLIM_AMD_ERR_INVALID;
-  for (int64_t i = 0; i < n_src; i++)
-    if (nearest[i] < -1 || (int64_t)nearest[i] >= n_tgt) return GLIM_AMD_ERR_INVALID;
-  return GLIM_AMD_OK;
-}
-
-void no_hypothesis_result(const glim_amd_ransac_params& prm, glim_amd_registration_result* r) {
-  const double I[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
-  std::memcpy(r->T_target_source, I, sizeof(I));
-  r->inlier_rate = 0.0;
-  r->num_inliers = 0;
-  r->best_iteration = -1;
-  r->iterations_run = prm.max_iterations;
-}
 
 // the rounds; caller holds ctx->mu, the device is set, p.d_nearest is on the device, p.n_src >= 3, p.n_tgt >= 1
-int run_rounds(const Problem& p, glim_amd_registration_result* result) {
+int run_rounds(const Pair& p, const glim_amd_ransac_params& prm, glim_amd_registration_result* result) {
   Table table;
-  GA_TRY(build_table(p.ctx, p.st, p.tpts, p.n_tgt, 1.0 / p.prm.inlier_voxel_resolution, &table));
+  GA_TRY(build_table(p.ctx, p.st, p.tpts, p.n_tgt, 1.0 / prm.inlier_voxel_resolution, &table));
   RoundBuffers b;
   SyncOnExit in_flight(p.st);
   GA_TRY(b.alloc());
   rs_init_state_kernel<<<1, 64, 0, p.st>>>(b.state.as<FoldState>());
   FoldState h{};
   h.stop_it = h.best_it = -1;
-  for (int base = 0; base < p.prm.max_iterations; base += ROUND) {
-    const int count = std::min(ROUND, p.prm.max_iterations - base);
-    launch_hypotheses(p, b, base, count);
-    launch_score(p, table, b, count);
-    launch_fold(p, b, base, count);
+  for (int base = 0; base < prm.max_iterations; base += ROUND) {
+    const int count = std::min(ROUND, prm.max_iterations - base);
+    launch_hypotheses(p, prm, b, base, count);
+    launch_score(p, prm.inlier_voxel_resolution, table, b, count);
+    launch_fold(p, prm, b, base, count);
     GA_HIP(hipGetLastError());
     GA_HIP(read_back_sync(p.ctx, p.st, &h, b.state.p, sizeof(FoldState)));
     if (h.stop_it >= 0) break;
   }
   in_flight.dismiss();  // (every round ended with a synchronise)
   if (h.stop_it < 0 && h.best_it < 0) {
-    no_hypothesis_result(p.prm, result);
+    reg_detail::identity_result(result, prm.max_iterations);
     return GLIM_AMD_OK;
   }
   const bool stopped = h.stop_it >= 0;
@@ -386,7 +354,7 @@ int run_rounds(const Problem& p, glim_amd_registration_result* result) {
   result->num_inliers = stopped ? h.stop_count : h.best_count;
   result->inlier_rate = (double)result->num_inliers / (double)p.n_src;
   result->best_iteration = stopped ? h.stop_it : h.best_it;
-  result->iterations_run = stopped ? h.stop_it + 1 : p.prm.max_iterations;
+  result->iterations_run = stopped ? h.stop_it + 1 : prm.max_iterations;
   return GLIM_AMD_OK;
 }
 
@@ -406,60 +374,19 @@ int glim_amd_ransac_default_params(glim_amd_ransac_params* params) {
   return GLIM_AMD_OK;
 }
 
-int glim_amd_fpfh_create(glim_amd_ctx* ctx, int64_t n, const float* descriptors33, glim_amd_fpfh** out) {
-  using namespace glim_amd;
-  using namespace glim_amd::fpfh_detail;
-  if (!ctx || !out) return GLIM_AMD_ERR_INVALID;
-  *out = nullptr;
-  if (n < 0 || n > (int64_t)(1 << 28) || (n > 0 && !descriptors33)) return GLIM_AMD_ERR_INVALID;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<glim_amd_fpfh, int (*)(glim_amd_fpfh*)> f(new glim_amd_fpfh(), glim_amd_fpfh_destroy);
-  f->ctx = ctx;
-  f->n = n;
-  const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  GA_HIP(pool_malloc(&f->desc, nn * FPFH_STRIDE * sizeof(float)));
-  if (n > 0) {
-    // the device row: 33 bins | the matcher's FMA chain of the row with itself, as fpfh_kernel stores it | 0 0
-    std::vector<float> rows((size_t)n * FPFH_STRIDE, 0.0f);
-    for (int64_t i = 0; i < n; i++) {
-      float* row = &rows[(size_t)i * FPFH_STRIDE];
-      float nn2 = 0.0f;
-      for (int b = 0; b < FPFH_DIM; b++) {
-        row[b] = descriptors33[(size_t)i * FPFH_DIM + b];
-        nn2 = fmaf(row[b], row[b], nn2);
-      }
-      row[FPFH_DIM] = nn2;
-    }
-    GA_HIP(hipMemcpyAsync(f->desc, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream()));
-    GA_HIP(hipStreamSynchronize(ctx->stream()));
-  }
-  *out = f.release();
-  return GLIM_AMD_OK;
-}
-
 int glim_amd_ransac_align(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_ransac_params* params,
                           glim_amd_registration_result* result) {
   using namespace glim_amd;
   using namespace glim_amd::ransac_detail;
   if (!result) return GLIM_AMD_ERR_INVALID;
-  GA_TRY(check_clouds(target, source));
+  GA_TRY(reg_detail::check_pair(target, source));
   GA_TRY(check_params(params));
-  GA_TRY(check_nearest(nearest, source->n, target->n));
+  GA_TRY(reg_detail::check_nearest(nearest, source->n, target->n));
   if (source->n < 3 || target->n == 0) {
-    no_hypothesis_result(*params, result);
+    reg_detail::identity_result(result, params->max_iterations);
     return GLIM_AMD_OK;
   }
-  glim_amd_ctx* ctx = source->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  DeviceTemp d_nearest;
-  GA_HIP(pool_malloc(&d_nearest.p, (size_t)source->n * sizeof(int)));
-  GA_HIP(hipMemcpyAsync(d_nearest.p, nearest, (size_t)source->n * sizeof(int), hipMemcpyHostToDevice, st));
-  GA_HIP(hipStreamSynchronize(st));
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, d_nearest.as<int>(), *params};
-  return run_rounds(p, result);
+  return reg_detail::with_host_nearest(target, source, nearest, [&](const Pair& p) { return run_rounds(p, *params, result); });
 }
 
 int glim_amd_ransac_align_fpfh(const glim_amd_cloud* target, const glim_amd_cloud* source, const glim_amd_fpfh* target_fpfh,
@@ -467,29 +394,15 @@ int glim_amd_ransac_align_fpfh(const glim_amd_cloud* target, const glim_amd_clou
                                glim_amd_registration_result* result) {
   using namespace glim_amd;
   using namespace glim_amd::ransac_detail;
-  if (!result || !target_fpfh || !source_fpfh) return GLIM_AMD_ERR_INVALID;
-  GA_TRY(check_clouds(target, source));
-  glim_amd_ctx* ctx = source->ctx;
-  if ((glim_amd_ctx*)target_fpfh->ctx != ctx || (glim_amd_ctx*)source_fpfh->ctx != ctx) return GLIM_AMD_ERR_INVALID;
-  if (match_flags & ~(uint32_t)GLIM_AMD_FPFH_RECIPROCAL) return GLIM_AMD_ERR_INVALID;
+  if (!result) return GLIM_AMD_ERR_INVALID;
+  GA_TRY(reg_detail::check_fpfh_pair(target, source, target_fpfh, source_fpfh, match_flags));
   GA_TRY(check_params(params));
-  if (target_fpfh->n != target->n || source_fpfh->n != source->n) return GLIM_AMD_ERR_INVALID;
   if (source->n < 3 || target->n == 0) {
-    no_hypothesis_result(*params, result);
+    reg_detail::identity_result(result, params->max_iterations);
     return GLIM_AMD_OK;
   }
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  fpfh_detail::MatchBuffers m;  // (outlives the rounds: `nearest` is read by every hypothesis kernel)
-  {
-    SyncOnExit in_flight(st);
-    GA_TRY(fpfh_detail::enqueue_match_both(ctx, st, target_fpfh, source_fpfh, match_flags, &m));
-    GA_HIP(hipStreamSynchronize(st));
-    in_flight.dismiss();
-  }
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, m.fwd_i.as<int>(), *params};
-  return run_rounds(p, result);
+  return reg_detail::with_matched_nearest(target, source, target_fpfh, source_fpfh, match_flags,
+                                          [&](const Pair& p) { return run_rounds(p, *params, result); });
 }
 
 int glim_amd_debug_ransac_max_lds_slots(int32_t slots) {
@@ -504,94 +417,78 @@ int glim_amd_ransac_debug_hypotheses(const glim_amd_cloud* target, const glim_am
                                      double* poses12, int32_t* inliers, int32_t* table_slots, int32_t* table_in_lds) {
   using namespace glim_amd;
   using namespace glim_amd::ransac_detail;
-  GA_TRY(check_clouds(target, source));
+  GA_TRY(reg_detail::check_pair(target, source));
   GA_TRY(check_params(params));
-  GA_TRY(check_nearest(nearest, source->n, target->n));
+  GA_TRY(reg_detail::check_nearest(nearest, source->n, target->n));
   if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)0x7fffffff) return GLIM_AMD_ERR_INVALID;
   if (source->n == 0) return GLIM_AMD_ERR_INVALID;  // there is nothing to draw from
-  glim_amd_ctx* ctx = source->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  DeviceTemp d_nearest;
-  GA_HIP(pool_malloc(&d_nearest.p, (size_t)source->n * sizeof(int)));
-  GA_HIP(hipMemcpyAsync(d_nearest.p, nearest, (size_t)source->n * sizeof(int), hipMemcpyHostToDevice, st));
-  GA_HIP(hipStreamSynchronize(st));
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, d_nearest.as<int>(), *params};
-  Table table;
-  GA_TRY(build_table(ctx, st, p.tpts, p.n_tgt, 1.0 / params->inlier_voxel_resolution, &table));
-  if (table_slots) *table_slots = (int32_t)table.slots;
-  if (table_in_lds) *table_in_lds = table.in_lds;
-  RoundBuffers b;
-  SyncOnExit in_flight(st);
-  GA_TRY(b.alloc());
-  for (int done = 0; done < count; done += ROUND) {
-    const int c = std::min(ROUND, (int)count - done);
-    launch_hypotheses(p, b, first + done, c);
-    launch_score(p, table, b, c);
-    GA_HIP(hipGetLastError());
-    if (samples) GA_HIP(hipMemcpyAsync(samples + 3 * (size_t)done, b.samples.p, (size_t)c * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (status) GA_HIP(hipMemcpyAsync(status + done, b.status.p, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (poses12) GA_HIP(hipMemcpyAsync(poses12 + 12 * (size_t)done, b.poses.p, (size_t)c * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (inliers) GA_HIP(hipMemcpyAsync(inliers + done, b.counts.p, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st));
-    GA_HIP(hipStreamSynchronize(st));
-  }
-  in_flight.dismiss();
-  return GLIM_AMD_OK;
+  return reg_detail::with_host_nearest(target, source, nearest, [&](const Pair& p) -> int {
+    hipStream_t st = p.st;
+    Table table;
+    GA_TRY(build_table(p.ctx, st, p.tpts, p.n_tgt, 1.0 / params->inlier_voxel_resolution, &table));
+    if (table_slots) *table_slots = (int32_t)table.slots;
+    if (table_in_lds) *table_in_lds = table.in_lds;
+    RoundBuffers b;
+    SyncOnExit in_flight(st);
+    GA_TRY(b.alloc());
+    for (int done = 0; done < count; done += ROUND) {
+      const int c = std::min(ROUND, (int)count - done);
+      launch_hypotheses(p, *params, b, first + done, c);
+      launch_score(p, params->inlier_voxel_resolution, table, b, c);
+      GA_HIP(hipGetLastError());
+      if (samples) GA_HIP(hipMemcpyAsync(samples + 3 * (size_t)done, b.samples.p, (size_t)c * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+      if (status) GA_HIP(hipMemcpyAsync(status + done, b.status.p, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st));
+      if (poses12) GA_HIP(hipMemcpyAsync(poses12 + 12 * (size_t)done, b.poses.p, (size_t)c * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (inliers) GA_HIP(hipMemcpyAsync(inliers + done, b.counts.p, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st));
+      GA_HIP(hipStreamSynchronize(st));
+    }
+    in_flight.dismiss();
+    return GLIM_AMD_OK;
+  });
 }
 
 int glim_amd_ransac_profile(const glim_amd_cloud* target, const glim_amd_cloud* source, const int32_t* nearest, const glim_amd_ransac_params* params,
                             int iters, float* us_hypothesis, float* us_score, float* us_fold, int32_t* table_slots, int32_t* table_in_lds) {
   using namespace glim_amd;
   using namespace glim_amd::ransac_detail;
-  GA_TRY(check_clouds(target, source));
+  GA_TRY(reg_detail::check_pair(target, source));
   GA_TRY(check_params(params));
-  GA_TRY(check_nearest(nearest, source->n, target->n));
+  GA_TRY(reg_detail::check_nearest(nearest, source->n, target->n));
   if (iters <= 0 || source->n == 0) return GLIM_AMD_ERR_INVALID;
-  glim_amd_ctx* ctx = source->ctx;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  DeviceTemp d_nearest;
-  GA_HIP(pool_malloc(&d_nearest.p, (size_t)source->n * sizeof(int)));
-  GA_HIP(hipMemcpyAsync(d_nearest.p, nearest, (size_t)source->n * sizeof(int), hipMemcpyHostToDevice, st));
-  GA_HIP(hipStreamSynchronize(st));
-  const Problem p{ctx, st, (int)source->n, (int)target->n, source->pts, target->pts, d_nearest.as<int>(), *params};
-  Table table;
-  GA_TRY(build_table(ctx, st, p.tpts, p.n_tgt, 1.0 / params->inlier_voxel_resolution, &table));
-  if (table_slots) *table_slots = (int32_t)table.slots;
-  if (table_in_lds) *table_in_lds = table.in_lds;
-  RoundBuffers b;
-  SyncOnExit in_flight(st);
-  GA_TRY(b.alloc());
-  const int count = std::min(ROUND, (int)params->max_iterations);
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& e : ev) GA_HIP(hipEventCreate(&e));
-  double sum[3] = {0.0, 0.0, 0.0};
-  int rc = GLIM_AMD_OK;
-  for (int i = -2; i < iters && rc == GLIM_AMD_OK; i++) {  // two warm-up rounds
-    rs_init_state_kernel<<<1, 64, 0, st>>>(b.state.as<FoldState>());
-    (void)hipEventRecord(ev[0], st);
-    launch_hypotheses(p, b, 0, count);
-    (void)hipEventRecord(ev[1], st);
-    launch_score(p, table, b, count);
-    (void)hipEventRecord(ev[2], st);
-    launch_fold(p, b, 0, count);
-    (void)hipEventRecord(ev[3], st);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = GLIM_AMD_ERR_HIP;
-    for (int k = 0; k < 3 && rc == GLIM_AMD_OK && i >= 0; k++) {
-      float ms = 0.0f;
-      if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) rc = GLIM_AMD_ERR_HIP;
-      sum[k] += (double)ms * 1e3;
+  return reg_detail::with_host_nearest(target, source, nearest, [&](const Pair& p) -> int {
+    hipStream_t st = p.st;
+    Table table;
+    GA_TRY(build_table(p.ctx, st, p.tpts, p.n_tgt, 1.0 / params->inlier_voxel_resolution, &table));
+    if (table_slots) *table_slots = (int32_t)table.slots;
+    if (table_in_lds) *table_in_lds = table.in_lds;
+    RoundBuffers b;
+    SyncOnExit in_flight(st);
+    GA_TRY(b.alloc());
+    const int count = std::min(ROUND, (int)params->max_iterations);
+    reg_detail::StageClock<4> clock;  // (its events go on every path, a failing start() included)
+    GA_TRY(clock.start());
+    double sum[3] = {0.0, 0.0, 0.0};
+    int rc = GLIM_AMD_OK;
+    for (int i = -2; i < iters && rc == GLIM_AMD_OK; i++) {  // two warm-up rounds
+      rs_init_state_kernel<<<1, 64, 0, st>>>(b.state.as<FoldState>());
+      clock.mark(0, st);
+      launch_hypotheses(p, *params, b, 0, count);
+      clock.mark(1, st);
+      launch_score(p, params->inlier_voxel_resolution, table, b, count);
+      clock.mark(2, st);
+      launch_fold(p, *params, b, 0, count);
+      clock.mark(3, st);
+      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = GLIM_AMD_ERR_HIP;
+      for (int k = 0; k < 3 && rc == GLIM_AMD_OK && i >= 0; k++)
+        if (clock.add_us(k, &sum[k]) != hipSuccess) rc = GLIM_AMD_ERR_HIP;
     }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  in_flight.dismiss();
-  if (rc != GLIM_AMD_OK) return rc;
-  if (us_hypothesis) *us_hypothesis = (float)(sum[0] / iters);
-  if (us_score) *us_score = (float)(sum[1] / iters);
-  if (us_fold) *us_fold = (float)(sum[2] / iters);
-  return GLIM_AMD_OK;
+    in_flight.dismiss();
+    if (rc != GLIM_AMD_OK) return rc;
+    if (us_hypothesis) *us_hypothesis = (float)(sum[0] / iters);
+    if (us_score) *us_score = (float)(sum[1] / iters);
+    if (us_fold) *us_fold = (float)(sum[2] / iters);
+    return GLIM_AMD_OK;
+  });
 }
 
 }  // extern "C"

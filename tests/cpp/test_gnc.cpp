@@ -1,7 +1,6 @@
 // Stands in for viewer/interactive/manual_loop_close_modal.cpp:445-458 (which needs Iridescence): the drop-in gtsam_points::estimate_pose_gnc with
 // the modal's argument list and the fields it sets, and the mirror glim_amd::estimate_pose_gnc, on a known-answer case the Python test dumped.
-//   test_gnc <case.bin>    int32 n_target, int32 n_source, int32 dof, uint64 seed, n_target x 4 doubles, n_source x 4 doubles (points),
-//                          n_target x 33 doubles, n_source x 33 doubles (descriptors), 12 doubles expected T_target_source, double inlier_rate
+//   test_gnc <case.bin>    the layout of registration_case.hpp
 // Without an argument: the compile-and-link check only (no device is touched).
 #include <cstdint>
 #include <cstdio>
@@ -13,20 +12,9 @@
 #include <gtsam_points/registration/graduated_non_convexity.hpp>
 #include <gtsam_points/registration/ransac.hpp>
 
+#include "registration_case.hpp"
+
 struct NoTree {};
-
-#define REQUIRE(c)                                                \
-  do {                                                            \
-    if (!(c)) {                                                   \
-      std::printf("FAILED %s (%s:%d)\n", #c, __FILE__, __LINE__); \
-      return 1;                                                   \
-    }                                                             \
-  } while (0)
-
-template <class T>
-static bool read_n(std::FILE* f, T* p, std::size_t n) {
-  return std::fread(p, sizeof(T), n, f) == n;
-}
 
 int main(int argc, char** argv) {
   static_assert(sizeof(glim_amd_gnc_params) == 72 && sizeof(glim_amd_gnc_info) == 48, "the layouts glim_amd/_lib.py binds");
@@ -38,19 +26,13 @@ int main(int argc, char** argv) {
     std::printf("test_gnc OK (no case given: nothing run)\n");
     return 0;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  REQUIRE(f != nullptr);
-  std::int32_t nt = 0, ns = 0, dof = 0;
-  std::uint64_t seed_in = 0;
-  REQUIRE(read_n(f, &nt, 1) && read_n(f, &ns, 1) && read_n(f, &dof, 1) && read_n(f, &seed_in, 1) && nt > 0 && ns > 0);
-  std::vector<Eigen::Vector4d> tp((std::size_t)nt), sp((std::size_t)ns);
-  std::vector<gtsam_points::FPFHSignature> tf((std::size_t)nt), sf((std::size_t)ns);
-  REQUIRE(read_n(f, tp[0].data(), (std::size_t)nt * 4) && read_n(f, sp[0].data(), (std::size_t)ns * 4));
-  for (auto& d : tf) REQUIRE(read_n(f, d.data(), 33));
-  for (auto& d : sf) REQUIRE(read_n(f, d.data(), 33));
-  double T[12], rate = 0.0;
-  REQUIRE(read_n(f, T, 12) && read_n(f, &rate, 1));
-  std::fclose(f);
+  Case in;
+  REQUIRE(in.load(argv[1]) == 0);
+  const std::int32_t nt = in.nt, ns = in.ns, dof = in.dof;
+  const std::uint64_t seed_in = in.seed;
+  std::vector<Eigen::Vector4d>&tp = in.tp, &sp = in.sp;
+  std::vector<gtsam_points::FPFHSignature>&tf = in.tf, &sf = in.sf;
+  const double *T = in.T, rate = in.rate;
 
   auto target = std::make_shared<gtsam_points::PointCloud>(), source = std::make_shared<gtsam_points::PointCloud>();
   target->points = tp.data();

@@ -1,7 +1,6 @@
 // Stands in for viewer/interactive/manual_loop_close_modal.cpp:431-443 (which needs Iridescence): the drop-in gtsam_points::estimate_pose_ransac
 // with the modal's argument list, and the mirror glim_amd::estimate_pose_ransac, on a known-answer case the Python test dumped.
-//   test_ransac <case.bin>    int32 n_target, int32 n_source, int32 dof, uint64 seed, n_target x 4 doubles, n_source x 4 doubles (points),
-//                             n_target x 33 doubles, n_source x 33 doubles (descriptors), 12 doubles expected T_target_source, double inlier_rate
+//   test_ransac <case.bin>    the layout of registration_case.hpp
 // Without an argument: the compile-and-link check only (no device is touched).
 #include <cstdint>
 #include <cstdio>
@@ -11,20 +10,9 @@
 #include <gtsam_points/features/fpfh_estimation.hpp>
 #include <gtsam_points/registration/ransac.hpp>
 
+#include "registration_case.hpp"
+
 struct NoTree {};
-
-#define REQUIRE(c)                                                \
-  do {                                                            \
-    if (!(c)) {                                                   \
-      std::printf("FAILED %s (%s:%d)\n", #c, __FILE__, __LINE__); \
-      return 1;                                                   \
-    }                                                             \
-  } while (0)
-
-template <class T>
-static bool read_n(std::FILE* f, T* p, std::size_t n) {
-  return std::fread(p, sizeof(T), n, f) == n;
-}
 
 int main(int argc, char** argv) {
   gtsam_points::RANSACParams params;
@@ -34,19 +22,13 @@ int main(int argc, char** argv) {
     std::printf("test_ransac OK (no case given: nothing run)\n");
     return 0;
   }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  REQUIRE(f != nullptr);
-  std::int32_t nt = 0, ns = 0, dof = 0;
-  std::uint64_t seed = 0;
-  REQUIRE(read_n(f, &nt, 1) && read_n(f, &ns, 1) && read_n(f, &dof, 1) && read_n(f, &seed, 1) && nt > 0 && ns > 0);
-  std::vector<Eigen::Vector4d> tp((std::size_t)nt), sp((std::size_t)ns);
-  std::vector<gtsam_points::FPFHSignature> tf((std::size_t)nt), sf((std::size_t)ns);
-  REQUIRE(read_n(f, tp[0].data(), (std::size_t)nt * 4) && read_n(f, sp[0].data(), (std::size_t)ns * 4));
-  for (auto& d : tf) REQUIRE(read_n(f, d.data(), 33));
-  for (auto& d : sf) REQUIRE(read_n(f, d.data(), 33));
-  double T[12], rate = 0.0;
-  REQUIRE(read_n(f, T, 12) && read_n(f, &rate, 1));
-  std::fclose(f);
+  Case in;
+  REQUIRE(in.load(argv[1]) == 0);
+  const std::int32_t nt = in.nt, ns = in.ns, dof = in.dof;
+  const std::uint64_t seed = in.seed;
+  std::vector<Eigen::Vector4d>&tp = in.tp, &sp = in.sp;
+  std::vector<gtsam_points::FPFHSignature>&tf = in.tf, &sf = in.sf;
+  const double *T = in.T, rate = in.rate;
 
   gtsam_points::PointCloud target, source;
   target.points = tp.data();

@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 
 import fpfh_restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from registration_cases import build_drop_in_cpp
 S = np.sqrt(0.5)
 
 
@@ -103,17 +102,7 @@ def test_new_entry_points_refuse_null_handles():
 
 def build_cpp(tmp_path):
     """tests/cpp/test_fpfh.cpp over the drop-in tree and the stand-in GLIM headers"""
-    from glim_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    exe = str(tmp_path / "test_fpfh")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "adapters", "gtsam_points_hip"), "-I" + os.path.join(ROOT, "adapters", "gtsam"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "cpp", "glim_standin"), os.path.join(ROOT, "tests", "cpp", "test_fpfh.cpp"),
-           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-           "-L/opt/rocm/lib", "-lamdhip64"]
-    subprocess.check_call(cmd)
-    return exe
+    return build_drop_in_cpp(tmp_path, "test_fpfh")
 
 
 def test_drop_in_header_and_mirror_compile_against_the_stand_in_headers(tmp_path):

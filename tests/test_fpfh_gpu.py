@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import fpfh_restatement as R
+from registration_cases import room_scan as _room_scan
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +31,6 @@ def ctx():
     from glim_amd import api
 
     return api.Context(0, 1)
-
-
-def _room_scan(sigma):
-    from glim_amd import synth
-
-    return synth.scan(synth.Scene.small_room(), synth.pose(0.5, -0.3, 1.2, yaw=0.3), synth.lidar_directions(32, 256), 0, sigma=sigma)[:, :3]
 
 
 def _device_cloud(ctx, pts32, normals32=None):

@@ -6,7 +6,6 @@ mu_k, so that rounding does not compound and the gate is a single step's.  Condi
 every step.  The list, c_s / c_t and D2 are compared exactly (the restatement sums the centroids in the documented tree).
 
 Measured on an MI355X, worst error / gate: 3.4e-5 over the 64 iterations of the 2 851-entry lists, 3.6e-3 on the 3-entry list (the largest)."""
-import struct
 import subprocess
 
 import numpy as np
@@ -14,6 +13,9 @@ import pytest
 
 import gnc_restatement as G
 import ransac_restatement as R
+from registration_cases import described_crops, make_case, room_points, write_drop_in_case
+from registration_cases import result_bytes as _result_bytes
+from registration_cases import upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -24,43 +26,6 @@ def ctx():
     from glim_amd import api
 
     return api.Context(0, 1)
-
-
-def _motion(yaw, pitch, t):
-    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
-    M = np.eye(4)
-    M[:3, :3] = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1.0]]) @ np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
-    M[:3, 3] = t
-    return M
-
-
-def room_points(n, seed):
-    from glim_amd import synth
-
-    pts = synth.scan(synth.Scene.small_room(), synth.pose(0.5, -0.3, 1.2, yaw=0.3), synth.lidar_directions(32, 256), 0, sigma=0.01)[:, :3]
-    return pts[np.sort(np.random.default_rng(seed).choice(len(pts), n, replace=False))].astype(np.float32)
-
-
-def make_case(source, seed, clutter, extent, redirected=0.30, unmatched=0.05, noise=0.0, pitch=0.25):
-    """target = rigid copy of the source (+ Gaussian noise) + `clutter` random points; nearest = identity with a share redirected at random and a
-    share set to -1"""
-    rng = np.random.default_rng(seed)
-    M = _motion(0.6, pitch, [1.5, -2.0, 0.4])
-    copy = (source.astype(np.float64) @ M[:3, :3].T + M[:3, 3] + noise * rng.normal(size=(len(source), 3))).astype(np.float32)
-    target = np.concatenate([copy, rng.uniform(-extent, extent, (clutter, 3)).astype(np.float32)])
-    n = len(source)
-    nearest = np.arange(n, dtype=np.int32)
-    pick = rng.permutation(n)
-    k1, k2 = int(redirected * n), int(unmatched * n)
-    nearest[pick[:k1]] = rng.integers(0, len(target), k1)
-    nearest[pick[k1:k1 + k2]] = -1
-    return {"source": source, "target": target, "nearest": nearest, "M": M}
-
-
-def _upload(ctx, case):
-    from glim_amd import api
-
-    return api.PointCloudGPU.clone(case["target"], ctx=ctx), api.PointCloudGPU.clone(case["source"], ctx=ctx)
 
 
 def _params(**kw):
@@ -78,10 +43,6 @@ def cases(ctx):
         c["clouds"] = _upload(ctx, c)
         out[dof] = c
     return out
-
-
-def _result_bytes(r):
-    return r.T_target_source.tobytes() + struct.pack("<dqii", r.inlier_rate, r.num_inliers, r.best_iteration, r.iterations_run)
 
 
 def check_teacher_forced(case, tr, dof, expect_iterations):
@@ -338,6 +299,25 @@ def test_two_calls_and_a_second_context_return_the_same_bytes(cases):
             other.close()
 
 
+def test_profile_reports_the_stages_and_leaves_no_state(cases):
+    """glim_amd_gnc_profile on the dof-6 case, two timed calls, without and with the tuple test: the five stage times are finite and not negative,
+    every stage that always launches something takes time, and gnc_align returns the same bytes and info before and after.  No wall-clock
+    threshold: the times are only looked at."""
+    from glim_amd import api
+
+    case = cases[6]
+    for prm in (_params(seed=11), _params(seed=11, tuple_check=True, max_num_tuples=500, max_iterations=16)):
+        args = (*case["clouds"], case["nearest"], prm)
+        before = api.gnc_align(*args)
+        prof = api.gnc_profile(*args, iters=2)
+        print(prof)
+        assert len(prof) == 5 and all(np.isfinite(v) and v >= 0 for v in prof.values())
+        for k in ("select_us", "gather_and_solve_us", "table_us", "score_us"):
+            assert prof[k] > 0, k
+        after = api.gnc_align(*args)
+        assert before.best_iteration >= 0 and _result_bytes(before) == _result_bytes(after) and before.info == after.info
+
+
 def test_invalid_arguments_with_real_handles(ctx, cases):
     from glim_amd import api
 
@@ -375,18 +355,8 @@ def test_invalid_arguments_with_real_handles(ctx, cases):
 
 @pytest.fixture(scope="module")
 def described(ctx):
-    """two overlapping crops of a room scan with normals and FPFH descriptors, as test_fpfh_gpu builds them"""
-    from glim_amd import api
-
-    pts = room_points(2000, 11)
-    order = np.argsort(pts[:, 0], kind="stable")
-    out = {}
-    for name, idx in (("target", np.sort(order[:1537])), ("source", np.sort(order[-1000:]))):
-        c = api.PointCloudGPU.clone(pts[idx], ctx=ctx)
-        c.find_neighbors(10, download=False)
-        c.estimate_covariances(10)
-        out[name] = (c, c.estimate_fpfh(0.6), pts[idx])
-    return out
+    """two overlapping crops of a room scan with normals and FPFH descriptors"""
+    return described_crops(ctx)
 
 
 @pytest.mark.parametrize("reciprocal", [False, True])
@@ -408,19 +378,10 @@ def test_cpp_drop_in_returns_the_python_result(ctx, described, tmp_path):
     from glim_amd import api
     from test_gnc import build_cpp
 
-    (tc, tf, tp), (sc, sf, sp) = described["target"], described["source"]
+    (tc, tf, _), (sc, sf, _) = described["target"], described["source"]
     prm = _params(seed=77, dof=4, max_init_samples=10000, max_num_tuples=5000)
     r = api.gnc_align_fpfh(tc, sc, tf, sf, prm, reciprocal=True)
     path = tmp_path / "case.bin"
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<iiiQ", len(tp), len(sp), 4, 77))
-        for p in (tp, sp):
-            p4 = np.ones((len(p), 4))
-            p4[:, :3] = p
-            fh.write(p4.tobytes())
-        for f in (tf, sf):
-            fh.write(f.download().astype(np.float64).tobytes())
-        fh.write(np.ascontiguousarray(r.T_target_source[:3]).tobytes())
-        fh.write(struct.pack("<d", r.inlier_rate))
+    write_drop_in_case(path, described, 4, 77, r)
     out = subprocess.run([build_cpp(tmp_path), str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "test_gnc OK (1537 x 1000 points, dof 4)" in out.stdout, out.stdout + out.stderr

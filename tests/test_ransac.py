@@ -14,25 +14,13 @@ import numpy as np
 import pytest
 
 import ransac_restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rot(axis, angle):
-    a = np.asarray(axis, dtype=np.float64)
-    a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+from registration_cases import build_drop_in_cpp, build_pose_program
+from registration_cases import rot as _rot
 
 
 @pytest.fixture(scope="module")
 def pose_programs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ransac_pose")
-    src = os.path.join(ROOT, "tests", "cpp", "test_ransac_pose.cpp")
-    plain, san = str(d / "pose"), str(d / "pose_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", san])
-    return d, (plain, san)
+    return build_pose_program(tmp_path_factory, "ransac_pose")
 
 
 def _run(programs, cases):
@@ -203,17 +191,7 @@ def test_new_entry_points_refuse_null_handles_and_fill_the_defaults():
 
 def build_cpp(tmp_path):
     """tests/cpp/test_ransac.cpp over the drop-in tree and the stand-in GLIM headers"""
-    from glim_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    exe = str(tmp_path / "test_ransac")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "adapters", "gtsam_points_hip"), "-I" + os.path.join(ROOT, "adapters", "gtsam"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "cpp", "glim_standin"), os.path.join(ROOT, "tests", "cpp", "test_ransac.cpp"),
-           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-           "-L/opt/rocm/lib", "-lamdhip64"]
-    subprocess.check_call(cmd)
-    return exe
+    return build_drop_in_cpp(tmp_path, "test_ransac")
 
 
 def test_drop_in_header_and_mirror_compile_against_the_stand_in_headers(tmp_path):

@@ -5,13 +5,15 @@ Per hypothesis: samples equal; status equal wherever the restatement's edge and 
 may fall inside, asserted on the restatement); poses within the gates on cond <= 100; inliers within [count - ambiguous, count + ambiguous], and
 at most 1 % of the hypotheses may have ambiguous > 0 (a condition on the input, asserted on the restatement; the seeds were chosen on the CPU).
 The result rule is checked exactly, on the device's own debug records."""
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 import ransac_restatement as R
+from registration_cases import described_crops, make_case, room_points, write_drop_in_case
+from registration_cases import result_bytes as _result_bytes
+from registration_cases import upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -28,37 +30,6 @@ def ctx():
     return api.Context(0, 1)
 
 
-def _motion(yaw, pitch, t):
-    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
-    M = np.eye(4)
-    M[:3, :3] = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1.0]]) @ np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
-    M[:3, 3] = t
-    return M
-
-
-def room_points(n, seed):
-    from glim_amd import synth
-
-    pts = synth.scan(synth.Scene.small_room(), synth.pose(0.5, -0.3, 1.2, yaw=0.3), synth.lidar_directions(32, 256), 0, sigma=0.01)[:, :3]
-    return pts[np.sort(np.random.default_rng(seed).choice(len(pts), n, replace=False))].astype(np.float32)
-
-
-def make_case(source, seed, clutter, extent, redirected=0.30, unmatched=0.05, noise=0.0):
-    """target = rigid copy of the source (+ Gaussian noise) + `clutter` random points; nearest = identity with a share redirected at random and a
-    share set to -1"""
-    rng = np.random.default_rng(seed)
-    M = _motion(0.6, 0.25, [1.5, -2.0, 0.4])
-    copy = (source.astype(np.float64) @ M[:3, :3].T + M[:3, 3] + noise * rng.normal(size=(len(source), 3))).astype(np.float32)
-    target = np.concatenate([copy, rng.uniform(-extent, extent, (clutter, 3)).astype(np.float32)])
-    n = len(source)
-    nearest = np.arange(n, dtype=np.int32)
-    pick = rng.permutation(n)
-    k1, k2 = int(redirected * n), int(unmatched * n)
-    nearest[pick[:k1]] = rng.integers(0, len(target), k1)
-    nearest[pick[k1:k1 + k2]] = -1
-    return {"source": source, "target": target, "nearest": nearest, "M": M}
-
-
 def parity_case():
     return make_case(room_points(3001, 21), seed=5, clutter=2000, extent=6.0)
 
@@ -72,12 +43,6 @@ def result_rule_case():
     """a noisy copy (sigma 8 cm) and 60 % wrong correspondences: the counts of the good hypotheses differ, so that the running maximum still rises
     in the third round (seed chosen on the CPU; the tests assert it on the device's records)"""
     return make_case(room_points(3001, 21), seed=RULE_SEED, clutter=2000, extent=6.0, redirected=0.6, unmatched=0.0, noise=0.08)
-
-
-def _upload(ctx, case):
-    from glim_amd import api
-
-    return api.PointCloudGPU.clone(case["target"], ctx=ctx), api.PointCloudGPU.clone(case["source"], ctx=ctx)
 
 
 def _params(**kw):
@@ -166,10 +131,6 @@ def test_both_table_forms_count_the_same_on_one_input(parity):
         assert whole[k][3:].tobytes() == a[k].tobytes(), k  # a hypothesis does not depend on where its round starts
 
 
-def _result_bytes(r):
-    return r.T_target_source.tobytes() + struct.pack("<dqii", r.inlier_rate, r.num_inliers, r.best_iteration, r.iterations_run)
-
-
 def _check_result_rule(clouds, nearest, n_source, records, prm):
     from glim_amd import api
 
@@ -246,6 +207,31 @@ def test_two_calls_and_a_second_context_return_the_same_bytes(parity):
         for cl in clouds:
             cl.close()
         other.close()
+
+
+def test_profile_reports_the_round_and_leaves_no_state(parity):
+    """glim_amd_ransac_profile on the parity case (3 001 source points: one scoring tile and a remainder; the table in LDS), two timed rounds: the
+    three kernel times are finite and positive, the table is the one ransac_debug_hypotheses reports on the same arguments, the LDS cut moves it
+    to global memory, and ransac_align returns the same bytes before and after.  No wall-clock threshold: the times are only looked at."""
+    from glim_amd import _lib, api
+
+    prm = _params(seed=11, max_iterations=1500, early_stop_inlier_rate=2.0)
+    args = (*parity["clouds"], parity["nearest"], prm)
+    before = api.ransac_align(*args)
+    rec = api.ransac_debug_hypotheses(*args, 0, 1)
+    prof = api.ransac_profile(*args, iters=2)
+    print(prof)
+    for k in ("hypothesis_us", "score_us", "fold_us"):
+        assert np.isfinite(prof[k]) and prof[k] > 0, k
+    assert (prof["table_slots"], prof["table_in_lds"]) == (rec["table_slots"], rec["table_in_lds"]) and prof["table_in_lds"] == 1
+    assert _lib.lib().glim_amd_debug_ransac_max_lds_slots(0) == 0
+    try:
+        cut = api.ransac_profile(*args, iters=2)
+    finally:
+        _lib.lib().glim_amd_debug_ransac_max_lds_slots(8192)
+    assert cut["table_in_lds"] == 0 and cut["table_slots"] == prof["table_slots"]
+    after = api.ransac_align(*args)
+    assert before.best_iteration >= 0 and _result_bytes(before) == _result_bytes(after)
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, TILE + 1])
@@ -344,18 +330,8 @@ def test_invalid_arguments_with_real_handles(ctx, parity):
 
 @pytest.fixture(scope="module")
 def described(ctx):
-    """two overlapping crops of a room scan with normals and FPFH descriptors, as test_fpfh_gpu builds them"""
-    from glim_amd import api
-
-    pts = room_points(2000, 11)
-    order = np.argsort(pts[:, 0], kind="stable")
-    out = {}
-    for name, idx in (("target", np.sort(order[:1537])), ("source", np.sort(order[-1000:]))):
-        c = api.PointCloudGPU.clone(pts[idx], ctx=ctx)
-        c.find_neighbors(10, download=False)
-        c.estimate_covariances(10)
-        out[name] = (c, c.estimate_fpfh(0.6), pts[idx])
-    return out
+    """two overlapping crops of a room scan with normals and FPFH descriptors"""
+    return described_crops(ctx)
 
 
 @pytest.mark.parametrize("reciprocal", [False, True])
@@ -388,19 +364,10 @@ def test_cpp_drop_in_returns_the_python_result(ctx, described, tmp_path):
     from glim_amd import api
     from test_ransac import build_cpp
 
-    (tc, tf, tp), (sc, sf, sp) = described["target"], described["source"]
+    (tc, tf, _), (sc, sf, _) = described["target"], described["source"]
     prm = _params(seed=77, dof=4)
     r = api.ransac_align_fpfh(tc, sc, tf, sf, prm)
     path = tmp_path / "case.bin"
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<iiiQ", len(tp), len(sp), 4, 77))
-        for p in (tp, sp):
-            p4 = np.ones((len(p), 4))
-            p4[:, :3] = p
-            fh.write(p4.tobytes())
-        for f in (tf, sf):
-            fh.write(f.download().astype(np.float64).tobytes())
-        fh.write(np.ascontiguousarray(r.T_target_source[:3]).tobytes())
-        fh.write(struct.pack("<d", r.inlier_rate))
+    write_drop_in_case(path, described, 4, 77, r)
     out = subprocess.run([build_cpp(tmp_path), str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "test_ransac OK (1537 x 1000 points, dof 4)" in out.stdout, out.stdout + out.stderr
