@@ -56,6 +56,8 @@ using u32 = unsigned int;
 constexpr int BLOCK = 256;
 constexpr int NACC = 28;
 constexpr int GICP_MAX_RING = 64;
+// the walk counts a cell edge as this fraction of h, so that rounding in the cell assignment never makes a distance bound optimistic
+constexpr double GICP_EDGE_SHRINK = 0.999999;
 __constant__ int c_acc_of_upper_g[21] = {0, 1, 2, 6, 7, 8, 3, 4, 9, 10, 11, 5, 12, 13, 14, 15, 16, 17, 18, 19, 20};
 
 // ---- index build ----
@@ -176,12 +178,12 @@ __device__ __forceinline__ int nearest(const GicpArgs& a, double qx, double qy, 
   if (!(tx >= -1048576.0 && tx < 1048576.0 && ty >= -1048576.0 && ty < 1048576.0 && tz >= -1048576.0 && tz < 1048576.0)) return -1;
   const int cx = fast_floor_d(tx), cy = fast_floor_d(ty), cz = fast_floor_d(tz);
   double margin = fmin(fmin(tx - (double)cx, (double)(cx + 1) - tx), fmin(fmin(ty - (double)cy, (double)(cy + 1) - ty), fmin(tz - (double)cz, (double)(cz + 1) - tz)));
-  margin = fmax(0.0, margin * a.h * 0.999999);
+  margin = fmax(0.0, margin * a.h * GICP_EDGE_SHRINK);
   int best = -1, best_idx = 0x7fffffff;
   best_d = __longlong_as_double(0x7ff0000000000000ll);
   for (int ring = 0; ring <= a.max_ring; ring++) {
     if (ring >= 1) {
-      const double reach = (double)(ring - 1) * a.h * 0.999999 + margin;  // every unscanned point is at least this far
+      const double reach = (double)(ring - 1) * a.h * GICP_EDGE_SHRINK + margin;  // every unscanned point is at least this far
       const double r2 = reach * reach;
       if (best_d < r2 || r2 > a.max_sq) break;  // proven nearest (strict: an unscanned tie could carry a smaller index) / beyond the radius
     }
@@ -195,7 +197,7 @@ __device__ __forceinline__ int nearest(const GicpArgs& a, double qx, double qy, 
             const double gx = dx > 0 ? (double)(cx + dx) - tx : (dx < 0 ? tx - (double)(cx + dx + 1) : 0.0);
             const double gy = dy > 0 ? (double)(cy + dy) - ty : (dy < 0 ? ty - (double)(cy + dy + 1) : 0.0);
             const double gz = dz > 0 ? (double)(cz + dz) - tz : (dz < 0 ? tz - (double)(cz + dz + 1) : 0.0);
-            const double gap = a.h * 0.999999;
+            const double gap = a.h * GICP_EDGE_SHRINK;
             const double ex = fmax(0.0, gx) * gap, ey = fmax(0.0, gy) * gap, ez = fmax(0.0, gz) * gap;
             const double g2 = ex * ex + ey * ey + ez * ez;
             if (g2 > best_d || g2 > a.max_sq) continue;
@@ -706,11 +708,13 @@ struct GicpTarget {
   int ring_cap = 0;             // most rings the index's walk may take; 0: no walk (a map searches the cells of its neighbour mode)
   int64_t max_source = INT64_MAX;  // source points beyond which the kind's entry points refuse the call
   uint64_t generation = 0;      // moves when positions in the target change their meaning (never for an index)
-  // rings after which the scanned cube covers the correspondence radius `d`; the walk is bounded, so a radius far beyond what the index was
-  // sized for (cells are hint/3 .. hint wide) is refused rather than searched incompletely: -1
+  // rings after which the scanned cube covers the correspondence radius `d`: the first ring R whose reach R * h * GICP_EDGE_SHRINK, as
+  // nearest() counts it, is no less than d -- by that same count every point beyond ring R is farther than d, so a further ring finds nothing.
+  // The walk is bounded: a radius that needs more than ring_cap rings (d beyond ring_cap * h * GICP_EDGE_SHRINK, with h between hint / 3
+  // and hint; so 21 x hint always fits) is refused rather than searched incompletely: -1
   int rings(double d) const {
     if (ring_cap == 0) return 0;
-    const double r = std::ceil(d / args.h) + 1.0;
+    const double r = std::ceil(d / (args.h * GICP_EDGE_SHRINK));
     return r <= (double)ring_cap ? (int)r : -1;
   }
 };

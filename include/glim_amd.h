@@ -174,8 +174,12 @@ int glim_amd_cloud_deskew(const glim_amd_cloud* pre, const double* T_imu_lidar12
  * src/glim/mapping/global_mapping_pose_graph.cpp:393-394 (loop validation; passes the target's pre-built tree). */
 typedef struct glim_amd_nn_index glim_amd_nn_index; /* the target's search structure (gtsam_points::KdTree at global_mapping_pose_graph.cpp:393) */
 /* Built once per target cloud (which needs covariances for the factor calls and must outlive the index), reused by every
- * linearisation.  max_correspondence_distance_hint sizes the grid cells (hint/3 .. hint wide); the calls below accept any distance up
- * to 21 x hint and return GLIM_AMD_ERR_UNSUPPORTED beyond that (the ring walk is bounded at 64 cells: rebuild with a larger hint). */
+ * linearisation.  max_correspondence_distance_hint sizes the grid cells: their edge h is chosen from the target's density between hint/3
+ * and hint.  The ring walk is bounded at 64 cells: the calls below accept any distance up to 64 x 0.999999 x h -- every distance up to
+ * 21 x hint for any target, up to just under 64 x hint for a sparse one -- and return GLIM_AMD_ERR_UNSUPPORTED beyond that (rebuild with
+ * a larger hint).  The grid spans 2^20 cells either side of the origin on each axis: a target point outside it (a tiny hint, a far
+ * point), like a non-finite one, is kept out of the index and is never a correspondence, and a transformed source point outside it has
+ * none; every other answer is what it would be without those points. */
 int glim_amd_nn_index_create(const glim_amd_cloud* target, double max_correspondence_distance_hint, glim_amd_nn_index** out);
 int glim_amd_nn_index_destroy(glim_amd_nn_index* index);
 /* IntegratedGICPFactor::linearize at T_target_source (flags: GLIM_AMD_FACTOR_BINARY fills the target-side blocks). */
