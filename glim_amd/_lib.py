@@ -226,6 +226,7 @@ SYMBOLS = {
     "glim_amd_shard_layout": (_i, [_lp, _i32, _i32, _lp, _lp, _ip, _lp]),
     "glim_amd_debug_resident_stop": (_i, [_i]),
     "glim_amd_debug_resident_stats": (_i, [_i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _ip]),
+    "glim_amd_debug_resident_post_stats": (_i, [_i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "glim_amd_debug_deskew_table": (_i, [_i64, _dp, _dp, _i32, _dp, _dp, _d, _dp, _dp, _ip, _dp, _i32, _ip]),
     "glim_amd_cloud_deskew": (_i, [_vp, _dp, _i32, _dp, _dp, _d, _dp, _dp, _i32, _pp]),
     "glim_amd_cloud_save_compact": (_i, [_vp, C.c_char_p]),

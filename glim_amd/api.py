@@ -1084,6 +1084,14 @@ def resident_stats(ctx=None):
     return {"launches": a.value, "requests": b.value, "alive": bool(c.value)}
 
 
+def resident_post_stats(ctx=None):
+    """Debug: requests of the device's resident session by the way they were posted (glim_amd_debug_resident_post_stats, switch resident_post)."""
+    ctx = ctx or default_context()
+    a, b = C.c_uint64(), C.c_uint64()
+    check(lib().glim_amd_debug_resident_post_stats(int(getattr(ctx, "device", 0)), C.byref(a), C.byref(b)), "glim_amd_debug_resident_post_stats")
+    return {"direct": a.value, "lines": b.value}
+
+
 def plan_stats(ctx=None):
     """Debug: factor plans built for new lists, how many of them in the buffers of an evicted plan, idle plans cached (glim_amd_debug_plan_stats)."""
     ctx = ctx or default_context()

@@ -41,6 +41,7 @@ struct DiagKey {
 const char* const kPathWords[] = {"auto", "grid", "chunks", "brute", nullptr};
 const char* const kKernelWords[] = {"auto", "wave64", "pair", "qgroup", nullptr};
 const char* const kResidentWords[] = {"0", "1", "auto", nullptr};
+const char* const kResidentPostWords[] = {"lines", "direct", "auto", nullptr};
 const DiagKey kDiagKeys[] = {
   {"knn_path", &Diag::knn_path, kPathWords, 0, 3},
   {"knn_kernel", &Diag::knn_kernel, kKernelWords, 0, 3},
@@ -63,6 +64,7 @@ const DiagKey kDiagKeys[] = {
   {"pp_fast", &Diag::pp_fast, nullptr, 0, 1},
   {"resident", &Diag::resident, kResidentWords, 0, 2},
   {"resident_idle_us", &Diag::resident_idle_us, nullptr, 100, 1000000},
+  {"resident_post", &Diag::resident_post, kResidentPostWords, 0, 2},
   {"cull", &Diag::cull, nullptr, 0, 2},
   {"small_rows", &Diag::small_rows, nullptr, 0, 4096},
   {"pool", &Diag::pool, nullptr, 0, 1},

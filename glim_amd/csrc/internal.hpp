@@ -132,6 +132,10 @@ struct Diag {
   int resident = 2;       // resident=0|1|auto                  repeated synchronous linearisations of a small set go through a resident kernel (no launch per
                           //                                    call); auto (default): only in a context created with priority 1 (the odometry module's)
   int resident_idle_us = 1000;  // resident_idle_us=<n>         the resident kernel leaves after this long without a request
+  int resident_post = 2;  // resident_post=lines|direct|auto    how a session gets its poses: request lines in host memory that its leader fetches and
+                          //                                    re-publishes on the device (lines), or granules the host stores straight into device
+                          //                                    memory through the large BAR (direct); auto (default): direct where the device memory is
+                          //                                    host-visible and the set is small (vgicp.hip RESIDENT_DIRECT_MAX_FACTORS), else lines
   int pp_fast = 1;        // pp_fast=0|1                        random-grid preprocessing: one sort + counting ranks, one synchronise (preprocess.hip)
   int fuse = 1;           // fuse=0|1                           small synchronous sets: ONE dispatch (factors finalised inside the factor kernel)
   int host_rotate = 1;    // host_rotate=0|1                     small synchronous linearisations (one dispatch / resident session): raw sums come back, the host rotates the record
@@ -149,6 +153,7 @@ struct Diag {
   char knn_debug[256] = "";   // knn_debug=<file>                dump per-wavefront work counters of the 64-query chunk kernel
 };
 enum { RESIDENT_OFF = 0, RESIDENT_ON = 1, RESIDENT_AUTO = 2 };
+enum { RESIDENT_POST_LINES = 0, RESIDENT_POST_DIRECT = 1, RESIDENT_POST_AUTO = 2 };
 enum { KNN_PATH_AUTO = 0, KNN_PATH_GRID = 1, KNN_PATH_CHUNKS = 2, KNN_PATH_BRUTE = 3 };
 enum { KNN_KERNEL_AUTO = 0, KNN_KERNEL_WAVE64 = 1, KNN_KERNEL_PAIR = 2 };
 const Diag& process_diag();                        // GLIM_AMD_DIAG, parsed once

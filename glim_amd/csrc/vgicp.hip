@@ -33,6 +33,8 @@
 
 #include "device_math.hpp"
 #include "internal.hpp"
+#include "pose_granule.hpp"
+#include "record_expand.hpp"
 
 using namespace glim_amd;
 
@@ -148,6 +150,9 @@ struct FinalizeArgs {
   const int* finmap;         // factor ids, plane-form segment first (null for a single-factor set: factor 0)
   // pre-cull (vgicp_kernel<..., CULL>): 4 words per row of the general segment, written by cull_kernel on the same stream just before the launch
   const unsigned long long* cull_words;
+  // resident session whose host posts the poses itself (ResidentArgs::direct), else null: a pose granule of this block's factor.  A finaliser
+  // that waits for rows looks at it every 64 spins and gives the rows up when it carries the exit tag (resident_kernel "idle-out race")
+  const char* exit_watch;
 };
 
 // ---- tagged rows: the hand-off of the single-dispatch synchronous call --------------------------------------------------------------
@@ -162,6 +167,8 @@ constexpr int TAG_ROW_BYTES = TAG_PIECES * 16;
 constexpr unsigned int AUX_SYSTEM = 17u;                 // sc0 sc1: system scope (host-mapped memory: through to the host at once)
 constexpr unsigned int AUX_SC1 = 16u;                    // cache policy of the raw buffer intrinsics: agent-coherent (write-through / L2-bypass)
 constexpr unsigned int AUX_SC1_VOLATILE = 16u | (1u << 31);  // ... and not to be hoisted out of / merged across the polling loop
+constexpr unsigned int AUX_SYSTEM_VOLATILE = 17u | (1u << 31);  // sc0 sc1, polled: fine-grained device memory the HOST stores into (large BAR)
+constexpr unsigned int RES_EXIT = 0xffffffffu;               // tag of a resident session's pose granules: the session ends
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 
 // The last step of a linearisation -- rotate_block / rotate_part / rotate_element, the slot mapping compact_from_rot and the host's
@@ -375,6 +382,15 @@ __device__ __forceinline__ void fused_finalize(const FactorDesc& d, int f, const
       if (spins > (1u << 20)) {
         lost = true;
         break;
+      }
+      if (fa.exit_watch && (spins & 63u) == 63u) {
+        // the session is ending under this request (its leader idled out while the host posted): the rows will not come
+        const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(fa.exit_watch), 0, 16, 0x00020000);
+        const v4i_t w = __builtin_amdgcn_raw_buffer_load_b128(wsrc, 0, 0, AUX_SYSTEM_VOLATILE);
+        if ((unsigned int)w.y == RES_EXIT && (unsigned int)w.w == RES_EXIT) {
+          lost = true;
+          break;
+        }
       }
       __builtin_amdgcn_s_sleep(4);
     }
@@ -1035,6 +1051,8 @@ __global__ __launch_bounds__(256) void cull_kernel(const FactorDesc* __restrict_
 //   blocks workers .. workers + nf - 1    finalise one factor each (fused_finalize: same bits as every other form); block `workers` also LEADS:
 //                                         it polls the request word in host memory, reads the poses the host left beside it and re-publishes
 //                                         them in device memory as {double, tag} granules -- which is also the "go" signal for everyone else
+// (switch resident_post=direct, the default where the device memory is host-visible and the set is small: the HOST stores those granules itself,
+//  through the large BAR, and the leader's fetch-and-republish hop -- 1.5 us in which nothing is computed -- is gone: ResidentArgs::direct.)
 // Tags of a resident session have bit 31 set (the launch-per-call forms count from 1), 0xffffffff = exit.  The leader exits on its own after
 // `idle_polls` empty polls (a few milliseconds), so a device-wide synchronise elsewhere in the process can never wait for long, and every
 // other wait is bounded as well: a session that loses its leader dies instead of hanging the device.
@@ -1046,7 +1064,9 @@ struct ResidentArgs {
   char* rows16;                    // tagged partial rows (the plan's)
   char* rec16;                     // host-mapped record granules (the plan's)
   int raw_record;                  // the finalisers store raw records, the host rotates (FinalizeArgs::raw_record): fixed for the session's life
-  char* pose16;                    // device: replicas x num_factors x 12 pose granules {double, tag, 0}
+  char* pose16;                    // device: replicas x num_factors x 12 pose granules {lo32, tag, hi32, tag} of one double each.  A granule
+                                   // is whole only when both tags agree: the host's aligned 8-byte stores through the BAR arrive as units, a
+                                   // 16-byte one is not known to, and PCIe may reorder the halves -- with this form neither matters
   int replicas;                    // copies of the pose granules (block b watches copy b % replicas: 512 blocks polling ONE 192-byte spot is a hot
                                    // spot on one memory channel that slows everything else on the device)
   // host-mapped request lines of 64 bytes each: {7 doubles of the pose array, tag}.  The host writes every line's doubles, then every line's
@@ -1057,8 +1077,15 @@ struct ResidentArgs {
   unsigned int* mail;              // host-mapped: [16] alive (1 while the kernel serves, 0 once it has left)
   unsigned int first_tag;          // the last tag served before this launch
   unsigned int idle_polls;         // leader: empty polls before it leaves
+  // direct != 0 (switch resident_post): the HOST stores the pose granules itself, through the large BAR into fine-grained device memory
+  // (resident_post_direct); no block reads host memory on the request path and everyone loads the granules at system scope.  The leader block
+  // only keeps the lifecycle: it waits like the others, and after idle_ticks (s_memrealtime, 100 MHz) without a request it stores exit
+  // granules into every replica and clears `alive`.
+  int direct;
+  unsigned int idle_ticks;
   // Device timeline of the LAST request served (glim_amd_debug_resident_timeline; null = off): s_memrealtime stamps (100 MHz), device memory.
   //   [0] leader: request seen in host memory        [1] leader: poses re-published on the device
+  //       (direct: both are "the leader block saw the pose in device memory", i.e. [2]: the hop they used to bracket does not exist)
   //   [2] finaliser of factor 0: pose seen           [3] ... every row of its factor summed (all tags arrived)      [4] ... record stored towards the host
   //   [5] ... its 32 group sums added   [6] ... its blocks rotated (finalize_tail)   [7] shader-clock ticks (s_memtime) between [2] and [4]
   //   [8 + 4 b + {0, 1, 2, 3}] worker block b: pose seen, first row computed (block-reduced), row granules published, point loop left (before the reduction)
@@ -1068,38 +1095,49 @@ constexpr int TL_WORKER0 = 8;
 __device__ __forceinline__ void tl_stamp(unsigned long long* tl, int slot) {
   if (tl && threadIdx.x == 0) tl[slot] = __builtin_amdgcn_s_memrealtime();
 }
-constexpr unsigned int RES_EXIT = 0xffffffffu;
 
 // wave 0, lanes 0..11: wait for the 12 pose granules of factor f.  exact != 0: until their tag is `exact`; otherwise until it is a session tag
 // different from `last`.  Returns the tag through s_tag (RES_EXIT when the session ends or the wait gives up) and the pose through s_pose.
 // (Round 6 also had every block read the HOST's request lines of its own factor when a request was due, to save the leader's re-publication hop
 //  -- 1.15 us median, 1.43 us for the last worker: 257 blocks reading host memory turned a 12 us call into a 385 us one and slowed a kernel launched
 //  beside the session 32x; one reader is what the link serves well.  profiles/r06/probe/resident_direct_host_poll_refuted.json)
-__device__ __forceinline__ void wait_pose(const ResidentArgs& ra, int f, unsigned int last, unsigned int exact, double* s_pose, unsigned int* s_tag) {
+// Exit dominates: a whole granule with the exit tag in ANY of the 12 lanes ends the wait at once -- in a direct session the host's granules of a
+// request and the leader's exit granules can interleave (resident_kernel "idle-out race"), and a block must not wait for the rest of a request
+// the session will not serve.
+// idle_ticks != 0 (the leader of a direct session): the wait also ends, with RES_EXIT, after that many 100 MHz ticks.
+__device__ __forceinline__ void wait_pose(const ResidentArgs& ra, int f, unsigned int last, unsigned int exact, double* s_pose, unsigned int* s_tag,
+                                          unsigned int idle_ticks = 0u) {
   if (threadIdx.x < 64) {
     const int lane = (int)threadIdx.x < 12 ? (int)threadIdx.x : 0;
     const int copy = (int)blockIdx.x % ra.replicas;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ra.pose16 + ((size_t)copy * ra.num_factors + f) * 12 * 16, 0, 12 * 16, 0x00020000);
     v4i_t g;
+    uint64_t bits = 0ull;
     unsigned int tag = RES_EXIT;
     const unsigned int limit = ra.idle_polls * 64u + (1u << 16);
+    const unsigned long long t_start = idle_ticks ? __builtin_amdgcn_s_memrealtime() : 0ull;
     for (unsigned int spins = 0; spins < limit; spins++) {
-      g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, 0, AUX_SC1_VOLATILE);
-      const unsigned int t = (unsigned int)g.z;
-      const bool mine = exact ? (t == exact || t == RES_EXIT) : ((t & 0x80000000u) != 0u && t != last);
-      // every lane must see the SAME new tag (the leader writes the 12 granules of a factor with one store instruction, but they travel separately)
+      // (the cache policy is an immediate of the instruction: two loads, one taken)
+      if (ra.direct) g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, 0, AUX_SYSTEM_VOLATILE);
+      else g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, 0, AUX_SC1_VOLATILE);
+      unsigned int t;
+      const bool whole = unpack_pose_granule((uint32_t)g.x, (uint32_t)g.y, (uint32_t)g.z, (uint32_t)g.w, &t, &bits);  // (pose_granule.hpp)
+      if (__any(whole && t == RES_EXIT)) break;
+      const bool mine = whole && (exact ? t == exact : ((t & 0x80000000u) != 0u && t != last));
+      // every lane must see the SAME new tag (the 12 granules of a factor travel separately, whoever writes them)
       const unsigned int t0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
       if (__all(mine && t == t0)) {
         tag = t0;
         break;
       }
+      if (idle_ticks && (spins & 7u) == 7u && __builtin_amdgcn_s_memrealtime() - t_start > (unsigned long long)idle_ticks) break;
       // back off: a request that follows the previous one within microseconds is seen at once; a session that has been quiet for a while
       // polls every few microseconds instead of hammering the fabric beside whatever else runs on the device
       if (spins < 32) __builtin_amdgcn_s_sleep(4);
       else if (spins < 256) __builtin_amdgcn_s_sleep(24);
       else __builtin_amdgcn_s_sleep(100);
     }
-    if (threadIdx.x < 12) s_pose[threadIdx.x] = __longlong_as_double(((long long)(unsigned int)g.y << 32) | (long long)(unsigned int)g.x);
+    if (threadIdx.x < 12) s_pose[threadIdx.x] = __longlong_as_double((long long)bits);
     if (threadIdx.x == 0) *s_tag = tag;
   }
   __syncthreads();
@@ -1128,7 +1166,7 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
     for (int r = b; r < ra.total_rows && first_row < 0; r += ra.workers)
       if (ra.blockmap[r].x >= 0) first_row = r;
   for (;;) {
-    if (leader) {
+    if (leader && !ra.direct) {
       // ---- wait for a request in host memory; re-publish the poses (device granules) or the end of the session.  Word w of the request
       // lines (8 per line: 7 doubles + tag) is polled by thread w -- the first LEAD_WORDS words in one sweep; a longer request is read in
       // further sweeps once its first lines carry the new tag.
@@ -1186,7 +1224,7 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
         const int line = w >> 3, slot = w & 7, i = line * 7 + slot;  // index into the pose array
         if (w < words && slot < 7 && i < nd) {
           const long long bits = req != RES_EXIT ? (long long)v : 0ll;
-          const v4i_t g = {(int)(bits & 0xffffffffll), (int)(bits >> 32), (int)req, 0};
+          const v4i_t g = {(int)(bits & 0xffffffffll), (int)req, (int)(bits >> 32), (int)req};
           for (int c = 0; c < ra.replicas; c++) __builtin_amdgcn_raw_buffer_store_b128(g, rsrc, (c * nd + i) * 16, 0, AUX_SC1);
         }
       }
@@ -1200,10 +1238,31 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
     }
     if (finaliser) {
       const int f = ra.finmap ? ra.finmap[b - ra.workers] : 0;
-      wait_pose(ra, f, last, leader ? s_tag : 0u, s_pose, &s_tag);
+      const bool keeper = leader && ra.direct;  // direct session: the leader block keeps the lifecycle, nothing else
+      wait_pose(ra, f, last, (leader && !ra.direct) ? s_tag : 0u, s_pose, &s_tag, keeper ? ra.idle_ticks : 0u);
       const unsigned int tag = s_tag;
-      if (tag == RES_EXIT) return;
+      if (tag == RES_EXIT) {
+        if (keeper) {
+          // ---- idle-out race.  The host may be storing the granules of a request at this very moment: its halves and these interleave, so
+          // nobody decides atomically between "serve" and "leave".  Three rules make that safe: exit dominates (wait_pose: a block that sees
+          // the exit tag in any of its 12 lanes leaves at once); a finaliser that waits for rows looks at a pose granule of its factor every 64
+          // spins and gives the rows up on exit (fused_finalize, FinalizeArgs::exit_watch); and the host, finding `alive` cleared and no
+          // record of this block's factor -- it has left -- stops what is left of the session, starts a fresh one and posts the request
+          // again under a fresh tag (run_resident).  A record that does arrive under the call's tag is valid: every row in it was computed by a
+          // worker that saw 12 whole granules of that tag.
+          const int ng = ra.replicas * ra.num_factors * 12;
+          const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ra.pose16, 0, ng * 16, 0x00020000);
+          const v4i_t g = {0, (int)RES_EXIT, 0, (int)RES_EXIT};
+          for (int i = (int)threadIdx.x; i < ng; i += BLOCK) __builtin_amdgcn_raw_buffer_store_b128(g, rsrc, i * 16, 0, AUX_SYSTEM);
+          if (threadIdx.x == 0) __hip_atomic_store(ra.mail + 16, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+      }
       unsigned long long* const tlf = (b == ra.workers) ? ra.timeline : nullptr;  // (the finaliser of the plan's first factor keeps the account)
+      if (keeper) {
+        tl_stamp(tlf, 0);
+        tl_stamp(tlf, 1);
+      }
       tl_stamp(tlf, 2);
       const unsigned long long shader_ticks0 = tlf ? __builtin_amdgcn_s_memtime() : 0ull;  // (shader clock counter: with the 100 MHz stamps it gives the clock the session runs at)
       FinalizeArgs fa;
@@ -1220,6 +1279,7 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       fa.raw_record = ra.raw_record;
       fa.finmap = ra.finmap;
       fa.cull_words = nullptr;
+      fa.exit_watch = ra.direct ? ra.pose16 + ((size_t)(b % ra.replicas) * ra.num_factors + f) * 12 * 16 : nullptr;
       const FactorDesc d = ra.descs[f];
       fused_finalize<8>(d, f, fa, MODE_LINEARIZE, reinterpret_cast<double (*)[PARTIAL_STRIDE]>(s_lds), s_lds + FIN_GROUPS * PARTIAL_STRIDE, s_pose, tlf ? tlf + 3 : nullptr);
       tl_stamp(tlf, 4);
@@ -1455,12 +1515,6 @@ __global__ __launch_bounds__(BLOCK) void overlap_kernel(const OverlapInline in, 
   }
 }
 
-void hat3(const double* a, double* H) {
-  H[0] = 0; H[1] = -a[2]; H[2] = a[1];
-  H[3] = a[2]; H[4] = 0; H[5] = -a[0];
-  H[6] = -a[1]; H[7] = a[0]; H[8] = 0;
-}
-
 }  // namespace
 
 
@@ -1483,6 +1537,15 @@ constexpr size_t PLAN_CACHE_MAX = 16;    // idle plans kept per context
 #define GLIM_AMD_HOST_ROTATE_MAX 8
 #endif
 constexpr int HOST_ROTATE_MAX_FACTORS = GLIM_AMD_HOST_ROTATE_MAX;
+// Sets of at most this many factors have their poses posted by the host straight into the session's device granules (resident_post=auto; the
+// switch set to `direct` takes every set a session serves).  Measured like HOST_ROTATE_MAX_FACTORS (profiles/r08/probe/direct_pose_ab.json;
+// resident_post=lines / direct alternating in one process, 16 x 256 frames): the call gains 1.15 us at 1 factor, 2.57 at 2 (the second request
+// line is a second PCIe read of the leader's), 2.09 at 4, 1.09 at 8 (one replica instead of eight from 5 factors on) and 1.55 us at 34, the
+// largest set measured -- 816 eight-byte stores of the host's through the write-combining BAR mapping still cost less than the leader's hop.
+#ifndef GLIM_AMD_RESIDENT_DIRECT_MAX
+#define GLIM_AMD_RESIDENT_DIRECT_MAX 34
+#endif
+constexpr int RESIDENT_DIRECT_MAX_FACTORS = GLIM_AMD_RESIDENT_DIRECT_MAX;
 constexpr int RESIDENT_MAX_FACTORS = 64;  // sets a resident session may serve (vgicp.hip "resident sessions")
 constexpr int FUSED_MAX_FACTORS = 1024, FUSED_MAX_ROWS = 16384;  // sets that may take the single-dispatch form (2.6 MB of tagged rows at most)
 constexpr size_t HOST_POSES_MAX = 256;   // synchronous sets up to this many factors: poses read by the kernels from host-mapped memory (96 B per factor over PCIe)
@@ -1994,6 +2057,7 @@ FinalizeArgs finalize_args(const glim_amd_factor_set* set, double* out, long lon
   fa.out_row_offset = row_offset;
   fa.done_counter = plan->d_done;
   fa.host_flag = poll ? plan->h_flag_dev : nullptr;
+  fa.exit_watch = nullptr;
   fa.seq = plan->poll_seq;
   fa.num_factors = (int)set->entries.size();
   fa.rows16 = plan->d_rows16;
@@ -2210,9 +2274,16 @@ struct ResidentSession {
   unsigned int *h_mail = nullptr, *h_mail_dev = nullptr;  // [16] alive
   unsigned long long *h_lines = nullptr, *h_lines_dev = nullptr;  // request lines {7 doubles, tag} (ResidentArgs::h_lines)
   char* d_pose16 = nullptr;
+  // direct posting (switch resident_post): the pose granules in fine-grained device memory, which the host stores into through the same pointer
+  // where the device's memory is host-visible (large BAR).  fine_state: 0 not tried yet, 1 usable, -1 not available on this device
+  char* d_pose16_fine = nullptr;
+  int fine_state = 0;
   unsigned int counter = 0, last_tag = 0;
   bool launched = false;
   bool raw_record = false;  // what the running kernel was launched with (ResidentArgs::raw_record)
+  bool direct = false;      // ... (ResidentArgs::direct)
+  int replicas = 1, num_factors = 0;  // ... (the layout the host posts into when direct)
+  unsigned long long posted_direct = 0, posted_lines = 0;  // requests by the way they were posted (glim_amd_debug_resident_post_stats)
   std::atomic<bool> busy{false};
   std::chrono::steady_clock::time_point last_use;
   unsigned long long launches = 0, requests = 0;
@@ -2241,10 +2312,57 @@ void resident_post(ResidentSession& S, const double* poses, size_t n, unsigned i
   std::atomic_thread_fence(std::memory_order_release);
 }
 
+// the request of a DIRECT session: every replica's granules of every factor, value halves with the new tag, replica by replica; one sfence
+// behind the last store pushes the write-combining buffers out
+void resident_post_direct(ResidentSession& S, const double* poses, size_t n, unsigned int tag) {
+  volatile unsigned long long* G = reinterpret_cast<volatile unsigned long long*>(S.d_pose16_fine);
+  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(poses);
+  for (int c = 0; c < S.replicas; c++) {
+    volatile unsigned long long* R = G + 2 * (size_t)c * n;
+    for (size_t i = 0; i < n; i++) {
+      uint64_t h0, h1;
+      pack_pose_granule(src[i], tag, &h0, &h1);  // (pose_granule.hpp)
+      R[2 * i] = h0;
+      R[2 * i + 1] = h1;
+    }
+  }
+  __builtin_ia32_sfence();
+}
+
+// every granule of the direct buffer gets `tag` and a zero value (0: a fresh session's "nothing yet"; RES_EXIT: the session ends)
+void resident_fill_direct(ResidentSession& S, unsigned int tag) {
+  volatile unsigned long long* G = reinterpret_cast<volatile unsigned long long*>(S.d_pose16_fine);
+  const unsigned long long half = (unsigned long long)tag << 32;
+  for (size_t i = 0; i < RESIDENT_POSE16_BYTES / 8; i++) G[i] = half;
+  __builtin_ia32_sfence();
+}
+
+// does a session of this context serve a set of nf factors with direct posting?  (S.mu held, device current.)  The device memory has to be
+// host-visible -- asked of the attribute alone, no store is tried to find out -- and the fine-grained allocation has to succeed.
+bool resident_direct_applies(ResidentSession& S, const glim_amd_ctx* ctx, size_t nf) {
+  const int mode = ctx->diag.resident_post;
+  if (mode == RESIDENT_POST_LINES) return false;
+  if (mode == RESIDENT_POST_AUTO && nf > (size_t)RESIDENT_DIRECT_MAX_FACTORS) return false;
+  if (S.fine_state == 0) {
+    S.fine_state = -1;
+    int large_bar = 0;
+    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, ctx->device) == hipSuccess && large_bar) {
+      void* p = nullptr;
+      if (hipExtMallocWithFlags(&p, RESIDENT_POSE16_BYTES, hipDeviceMallocFinegrained) == hipSuccess && p) {
+        S.d_pose16_fine = static_cast<char*>(p);
+        S.fine_state = 1;
+      }
+    }
+    if (S.fine_state < 0) (void)hipGetLastError();
+  }
+  return S.fine_state > 0;
+}
+
 // S.mu held.  Ends the resident kernel (if any) and waits for it.
 void resident_stop(ResidentSession& S) {
   if (!S.launched) return;
-  if (S.h_lines) {
+  if (S.direct) resident_fill_direct(S, RES_EXIT);
+  else if (S.h_lines) {
     const size_t lines = RESIDENT_MAX_LINES;
     for (size_t l = lines; l-- > 0;) reinterpret_cast<volatile unsigned long long*>(S.h_lines)[l * 8 + 7] = RES_EXIT;
     std::atomic_thread_fence(std::memory_order_seq_cst);
@@ -2300,7 +2418,11 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
     if ((unsigned int)*tagw == RES_EXIT) *tagw = S.last_tag;
   }
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  GA_HIP(hipMemsetAsync(S.d_pose16, 0, RESIDENT_POSE16_BYTES, S.stream));  // stale granules (an earlier session's exit tags) must not be read as news
+  // stale granules (an earlier session's exit tags) must not be read as news.  A direct session's are cleared by the HOST, through the BAR and
+  // before the launch -- zeros, not a session tag: a store of the host's can then never race a clear on the device's side.
+  const bool direct = resident_direct_applies(S, ctx, (size_t)nf);
+  if (direct) resident_fill_direct(S, 0u);
+  else GA_HIP(hipMemsetAsync(S.d_pose16, 0, RESIDENT_POSE16_BYTES, S.stream));
   ResidentArgs ra;
   ra.descs = plan->d_descs;
   ra.blockmap = plan->d_blockmap;
@@ -2312,7 +2434,9 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
   ra.rows16 = plan->d_rows16;
   ra.rec16 = plan->h_rec16_dev;
   ra.raw_record = host_rotate_applies(ctx->diag, (size_t)nf) ? 1 : 0;
-  ra.pose16 = S.d_pose16;
+  ra.pose16 = direct ? S.d_pose16_fine : S.d_pose16;
+  ra.direct = direct ? 1 : 0;
+  ra.idle_ticks = (unsigned int)std::min<long long>((long long)ctx->diag.resident_idle_us * 100ll, 0x7fffffffll);
   ra.replicas = nf <= 4 ? 8 : 1;  // (a larger set's blocks watch different factors' granules anyway)
   ra.h_lines = S.h_lines_dev;
   ra.num_lines = (nf * 12 + 6) / 7;
@@ -2337,6 +2461,9 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
   GA_HIP(hipGetLastError());
   S.launched = true;
   S.raw_record = ra.raw_record != 0;
+  S.direct = direct;
+  S.replicas = ra.replicas;
+  S.num_factors = nf;
   S.plan = plan;
   S.ctx = ctx;
   S.launches++;
@@ -2353,6 +2480,8 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
   FactorPlan* plan = nullptr;
   unsigned int tag = 0;
   bool raw = false;  // the session that answers was launched with raw records
+  bool posted_direct = false;
+  bool timed = false;  // the device timeline is on: the host's round trip of this request goes beside it
   std::chrono::steady_clock::time_point t_post;
   {
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -2374,6 +2503,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     }
     // the switch was flipped under a live session: its kernel keeps the form it was launched with, so it is restarted like for any other plan change
     if (S.launched && S.raw_record != host_rotate_applies(diag, nf)) resident_stop(S);
+    if (S.launched && S.direct != resident_direct_applies(S, ctx, nf)) resident_stop(S);  // (resident_post: likewise)
     if (S.launched && reinterpret_cast<volatile unsigned int*>(S.h_mail)[16] == 0u) {
       (void)hipStreamSynchronize(S.stream);  // it has idled out
       S.launched = false;
@@ -2384,14 +2514,23 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     }
     raw = S.raw_record;
     tag = next_session_tag(S);
-    t_post = std::chrono::steady_clock::now();
-    resident_post(S, T_lin, nf * 12, tag);
+    // one clock read per call (`now`, the take-over rule's); the round trip is read only beside a device timeline
+    timed = S.timeline_on;
+    if (timed) t_post = std::chrono::steady_clock::now();
+    if (S.direct) {
+      resident_post_direct(S, T_lin, nf * 12, tag);
+      S.posted_direct++;
+      posted_direct = true;
+    } else {
+      resident_post(S, T_lin, nf * 12, tag);
+      S.posted_lines++;
+    }
     S.busy.store(true);
     S.last_use = now;
     S.requests++;
   }
   bool ok = collect_tagged_records(plan, nf, tag, reinterpret_cast<volatile unsigned int*>(S.h_mail) + 16);
-  S.last_request_host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_post).count();
+  if (timed) S.last_request_host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_post).count();
   if (!ok) {
     // the kernel left (idle time-out racing with this request) or is stuck: make sure it is gone, start a fresh one, which finds the pending
     // request in the mailbox
@@ -2399,11 +2538,22 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     std::lock_guard<std::mutex> slock(S.mu);
     (void)hipSetDevice(ctx->device);
     reinterpret_cast<volatile unsigned int*>(S.h_mail)[16] = 0u;
+    // (a direct session: blocks that took this request's granules for a request -- the leader's exit granules landed first -- are still there)
+    if (S.direct) resident_fill_direct(S, RES_EXIT);
     (void)hipStreamSynchronize(S.stream);
     S.launched = false;
     int rc = resident_launch(S, set, plan);
     raw = S.raw_record;  // (the fresh kernel answers the pending request in ITS form)
-    if (rc == GLIM_AMD_OK) ok = collect_tagged_records(plan, nf, tag, nullptr);  // (the request lines still hold this request)
+    if (rc == GLIM_AMD_OK && S.direct) {
+      // the launch cleared the granules: the request is posted again, under a fresh tag (a record granule of the old one may still arrive)
+      tag = next_session_tag(S);
+      resident_post_direct(S, T_lin, nf * 12, tag);
+      S.posted_direct++;
+    } else if (rc == GLIM_AMD_OK && posted_direct) {
+      resident_post(S, T_lin, nf * 12, tag);  // (the switch was flipped meanwhile: the lines have not seen this request)
+      S.posted_lines++;
+    }
+    if (rc == GLIM_AMD_OK) ok = collect_tagged_records(plan, nf, tag, nullptr);  // (lines: the request lines still hold this request)
     if (!ok) {
       resident_stop(S);
       S.busy.store(false);
@@ -2422,6 +2572,15 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
 }
 
 }  // namespace
+
+extern "C" int glim_amd_debug_resident_post_stats(int device, uint64_t* direct, uint64_t* lines) {
+  if (device < 0 || device >= 16) return GLIM_AMD_ERR_INVALID;
+  ResidentSession& S = g_resident[device];
+  std::lock_guard<std::mutex> slock(S.mu);
+  if (direct) *direct = S.posted_direct;
+  if (lines) *lines = S.posted_lines;
+  return GLIM_AMD_OK;
+}
 
 extern "C" int glim_amd_debug_resident_stats(int device, uint64_t* launches, uint64_t* requests, int32_t* alive) {
   if (device < 0 || device >= 16) return GLIM_AMD_ERR_INVALID;
@@ -2725,58 +2884,10 @@ int glim_amd_factor_set_size(const glim_amd_factor_set* set, int32_t* n) {
 
 int glim_amd_expand_compact(const double* c, const double* T, uint32_t flags, glim_amd_linearized6* out) {
   if (!c || !out) return GLIM_AMD_ERR_INVALID;
-  memset(out, 0, sizeof(*out));
-  out->num_inliers = (int64_t)llround(c[0]);
-  out->error = c[1];
-  int k = 2;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++) {
-      out->H_ss[6 * i + j] = c[k];
-      out->H_ss[6 * j + i] = c[k];
-      k++;
-    }
-  for (int i = 0; i < 6; i++) out->b_s[i] = c[k++];
-  if ((flags & GLIM_AMD_FACTOR_BINARY) && T) {
-    // Ad = Adjoint(delta^-1) = [R^T 0; -R^T hat(t) R^T]   ([omega; v] ordering)
-    double Rt[9], Ht[9], Ad[36];
-    for (int r = 0; r < 3; r++)
-      for (int cc = 0; cc < 3; cc++) Rt[3 * r + cc] = T[4 * cc + r];
-    const double t[3] = {T[3], T[7], T[11]};
-    hat3(t, Ht);
-    memset(Ad, 0, sizeof(Ad));
-    for (int r = 0; r < 3; r++)
-      for (int cc = 0; cc < 3; cc++) {
-        Ad[6 * r + cc] = Rt[3 * r + cc];
-        Ad[6 * (r + 3) + cc + 3] = Rt[3 * r + cc];
-        double s = 0.0;
-        for (int m = 0; m < 3; m++) s += Rt[3 * r + m] * Ht[3 * m + cc];
-        Ad[6 * (r + 3) + cc] = -s;
-      }
-    double AtH[36];  // Ad^T H_ss
-    for (int i = 0; i < 6; i++)
-      for (int j = 0; j < 6; j++) {
-        double s = 0.0;
-        for (int m = 0; m < 6; m++) s += Ad[6 * m + i] * out->H_ss[6 * m + j];
-        AtH[6 * i + j] = s;
-      }
-    for (int i = 0; i < 6; i++) {
-      for (int j = 0; j < 6; j++) {
-        double s = 0.0;
-        for (int m = 0; m < 6; m++) s += AtH[6 * i + m] * Ad[6 * m + j];
-        out->H_tt[6 * i + j] = s;
-        out->H_ts[6 * i + j] = -AtH[6 * i + j];
-      }
-      double s = 0.0;
-      for (int m = 0; m < 6; m++) s += Ad[6 * m + i] * out->b_s[m];
-      out->b_t[i] = -s;
-    }
-    // symmetrise H_tt against rounding
-    for (int i = 0; i < 6; i++)
-      for (int j = i + 1; j < 6; j++) {
-        const double s = 0.5 * (out->H_tt[6 * i + j] + out->H_tt[6 * j + i]);
-        out->H_tt[6 * i + j] = out->H_tt[6 * j + i] = s;
-      }
-  }
+  double adj[ADJOINT_DOUBLES];
+  const bool binary = (flags & GLIM_AMD_FACTOR_BINARY) && T;
+  if (binary) binary_adjoint(T, adj);
+  expand_compact_record(c, binary ? adj : nullptr, out);  // (record_expand.hpp)
   return GLIM_AMD_OK;
 }
 
@@ -2785,9 +2896,23 @@ int glim_amd_factor_set_linearize(glim_amd_factor_set* set, const double* T, gli
   const size_t nf = set->entries.size();
   if (nf == 0) return GLIM_AMD_OK;
   if (!T || !out) return GLIM_AMD_ERR_INVALID;
+  // The adjoint of a binary factor depends on the pose alone.  For a small set it is computed BEFORE the call goes to the device -- the host
+  // would otherwise do it with the record in hand and the caller waiting; the stretch between posting a request and its record is idle time
+  // only once the request is out, so it sits in front of run_sync, where it delays the request by the few nanoseconds of 27 multiplications
+  // a factor and takes ~10x that off the tail.  Larger sets compute it factor by factor behind the call, as before.
+  constexpr size_t ADJ_AHEAD = 4;
+  double adj[ADJ_AHEAD * ADJOINT_DOUBLES];
+  const bool ahead = nf <= ADJ_AHEAD;
+  if (ahead)
+    for (size_t f = 0; f < nf; f++)
+      if (set->entries[f].flags & GLIM_AMD_FACTOR_BINARY) binary_adjoint(T + 12 * f, adj + f * ADJOINT_DOUBLES);
   GA_TRY(run_sync(set, MODE_LINEARIZE, T, nullptr));
   const double* rec = set->plan->h_compact;
-  for (size_t f = 0; f < nf; f++) glim_amd_expand_compact(rec + f * COMPACT, T + 12 * f, set->entries[f].flags, &out[f]);
+  for (size_t f = 0; f < nf; f++) {
+    const bool binary = (set->entries[f].flags & GLIM_AMD_FACTOR_BINARY) != 0;
+    if (ahead) expand_compact_record(rec + f * COMPACT, binary ? adj + f * ADJOINT_DOUBLES : nullptr, &out[f]);
+    else glim_amd_expand_compact(rec + f * COMPACT, T + 12 * f, set->entries[f].flags, &out[f]);
+  }
   return GLIM_AMD_OK;
 }
 

@@ -26,7 +26,10 @@ extern "C" {
  * fuse=0|1 (small synchronous sets in ONE dispatch), host_rotate=0|1 (linearisations of the smallest such sets, and of a resident session's, return
  * raw sums and the host applies the R^T B R rotation of the record; 0: the device's finalisers do; same bits either way), resident=0|1|auto + resident_idle_us=<n> (repeated synchronous linearisations of a small set
  * served by a resident kernel that leaves after <n> us without a request; auto, the default: only in a context created with priority 1 -- the
- * session costs whatever else runs on the device 1.3-1.4x while it is alive, so it is opt-in), pp_fast=0|1 (random-grid preprocessing without sorts),
+ * session costs whatever else runs on the device 1.3-1.4x while it is alive, so it is opt-in),
+ * resident_post=lines|direct|auto (how a session gets its poses: request lines in host memory that its leader fetches and re-publishes on the device,
+ * or granules the host stores straight into device memory through the large BAR; auto, the default: direct where the device's memory is host-visible
+ * and the set is small, lines otherwise; same bits either way, a live session is restarted when the switch flips), pp_fast=0|1 (random-grid preprocessing without sorts),
  * small_rows=<n> (partial rows ONE factor of a small synchronous set is planned into at most; 0, the default: one per compute unit -- round 5: two),
  * cull=0|1|2 (general-form sets of >= 16 384 plan rows -- 2: of any size --: a pre-pass marks the wavefront trips whose chunk box misses the target's occupancy mask and the
  * factor kernel walks the live trips only; same bits either way),
@@ -142,9 +145,14 @@ int glim_amd_gnc_profile(const glim_amd_cloud* target, const glim_amd_cloud* sou
  * on the device and takes its requests through host-mapped memory; it leaves by itself after `resident_idle_us` without a request): kernel
  * launches and requests served so far, whether one is alive right now. */
 int glim_amd_debug_resident_stats(int device, uint64_t* launches, uint64_t* requests, int32_t* alive);
+/* ... and how its requests were posted so far (switch resident_post): granules stored by the host into device memory (direct), or request lines in
+ * host memory (lines).  Either pointer may be NULL. */
+int glim_amd_debug_resident_post_stats(int device, uint64_t* direct, uint64_t* lines);
 /* Device timeline of the resident session's LAST request: ends the session, reports (us / num_fields may be NULL / 0: switch only)
  * and leaves the stamps on (enable != 0) or off for the sessions that start afterwards.  Microseconds, device stamps (s_memrealtime, 10 ns) relative
- * to the moment the session's leader saw the request in host memory:
+ * to the moment the session's leader saw the request in host memory (a session whose host posts the poses itself, resident_post=direct, has no such
+ * moment and no re-publication: [1] is 0 there and everything is relative to the leader block seeing the pose in device memory, i.e. [11] is 0 too,
+ * and the stamps sit earlier by the host -> device transit that [0] - [15] then contains in full):
  *   [0] host clock: posting the request -> last record granule seen      [1] leader: poses re-published on the device
  *   [2..4] worker blocks: pose seen, min / median / max   [5..7] first row computed   [8..10] row granules published
  *   [11] finaliser of factor 0: pose seen   [12] every row of its factor summed   [13] record stored towards the host
