@@ -1,10 +1,7 @@
 // fpfh.hip -- FPFH descriptors of a device cloud and nearest-descriptor matching on gfx950: the two data-parallel stages of global registration
 // (gtsam_points::estimate_fpfh and the KdTreeX<FPFH_DIM> queries of viewer/interactive/manual_loop_close_modal.cpp:376-463).  Semantics in
-// include/glim_amd.h ("FPFH"), layout and measurements in DESIGN.md 4.7.
-//
-// Built as part of gicp.hip's translation unit (included at its end), like ivox.hpp: the csrc Makefile is part of the identity the committed
-// traffic evidence of the factor kernel is stamped with, so it does not change for a file the factor kernel never sees.  The file stands alone
-// otherwise (own includes, own namespace) and compiles on its own with `hipcc -c fpfh.hip`.
+// include/glim_amd.h ("FPFH"), layout and measurements in DESIGN.md 4.7.  fpfh.hpp declares what the global-registration entries use of this
+// file: the descriptor object and the matcher's device side.
 //
 // estimate:  cell grid of edge >= r over the cloud (cells dense inside the bounding box, one border cell all round; stable radix sort of sort.hip
 //            on the cell index, exclusive scan of scan.hpp over the cell counts), so the neighbours of a point lie in the 27 cells around it = 9
@@ -24,15 +21,10 @@
 #include <vector>
 
 #include "device_math.hpp"
+#include "fpfh.hpp"
 #include "internal.hpp"
 #include "scan.hpp"
 #include "scope_sync.hpp"
-
-struct glim_amd_fpfh {
-  CtxRef ctx;
-  int64_t n = 0;
-  float* desc = nullptr;  // n x FPFH_STRIDE: 33 bins | squared norm of the row (the matcher's FMA chain) | 0 0
-};
 
 namespace glim_amd {
 namespace fpfh_detail {
@@ -419,11 +411,7 @@ inline void match_splits(const glim_amd_ctx* ctx, int na, int nb, int* splits, i
   *splits = (b_tiles + *tiles_per_split - 1) / *tiles_per_split;
 }
 
-// the device side of glim_amd_fpfh_match: nearest target row of every source row into b->fwd_i / b->fwd_d, the reciprocal pass when asked for.
-// Both sets are non-empty; the caller holds ctx->mu, synchronises `st` and keeps `b` until then.
-struct MatchBuffers {
-  DeviceTemp part_d, part_i, fwd_d, fwd_i, back_d, back_i;
-};
+// the device side of glim_amd_fpfh_match (fpfh.hpp)
 int enqueue_match_both(glim_amd_ctx* ctx, hipStream_t st, const glim_amd_fpfh* target, const glim_amd_fpfh* source, uint32_t flags, MatchBuffers* b) {
   const int na = (int)source->n, nb = (int)target->n;
   const bool reciprocal = (flags & GLIM_AMD_FPFH_RECIPROCAL) != 0;

@@ -1,6 +1,6 @@
 // gicp_align.hip -- GICP fine registration on gfx950 (include/glim_amd.h "GICP fine registration"): B independent Levenberg-Marquardt loops over
-// the rigid GICP factor, one host synchronisation.  Compiled as part of gicp.hip's translation unit (included at its end): the per-point algebra,
-// the block epilogue, the ordered sum and the target description are that file's, called here, not copied.
+// the rigid GICP factor, one host synchronisation.  The per-point algebra, the block epilogue, the ordered sum and the target description are
+// gicp_factor.hpp's (the map's description ivox_map.hpp's), shared with gicp.hip: called here, not copied.
 //
 //   problem table   per problem: the factor kernel's arguments (target half from gicp_target(), source half from set_source), the map's search
 //                   object when the targets are device iVoxes, and where its partial rows are (first, count)
@@ -12,9 +12,20 @@
 //                   rule of lm_step.hpp, the next candidate pose and the state, one trace entry when a trace was asked for.
 //   the call        1 + max_trials rounds are enqueued up front, then one copy of the states, then ONE hipStreamSynchronize.  No persistent
 //                   kernel, no grid-wide wait, no host decision in between; every loop in both kernels has a bound known at launch.
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <mutex>
 #include <vector>
 
+#include "device_math.hpp"
+#include "gicp_factor.hpp"
+#include "internal.hpp"
+#include "ivox_map.hpp"
 #include "lm_step.hpp"
+#include "scope_sync.hpp"
+
+using namespace glim_amd;
 
 namespace {
 

@@ -1,8 +1,8 @@
 // gnc.hip -- GNC global registration on gfx950: gtsam_points::estimate_pose_gnc as viewer/interactive/manual_loop_close_modal.cpp:445-458 calls it,
 // the second consumer of fpfh.hip's descriptors and correspondences.  Semantics in include/glim_amd.h ("GNC"), layout in DESIGN.md 4.7b.
 //
-// Built as part of gicp.hip's translation unit, after ransac.hip, for the reason the head of fpfh.hip gives.  It uses ransac.hip's occupancy table,
-// round buffers and scoring launch (and, through ransac.hip, the generator of sample_hash.hpp) and registration_host.hpp's host scaffold.
+// It uses ransac.hip's occupancy table, round buffers and scoring launch (ransac_table.hpp), the generator of sample_hash.hpp and
+// registration_host.hpp's host scaffold.
 //
 // select   keep[i] = candidate and matched and both points finite (the candidate marks are plain stores of one value), exclusive scan of scan.hpp,
 //          compaction into (source index, target index) pairs in ascending i.
@@ -20,7 +20,9 @@
 #include "device_math.hpp"
 #include "gnc_pose.hpp"
 #include "internal.hpp"
+#include "ransac_table.hpp"
 #include "registration_host.hpp"
+#include "sample_hash.hpp"
 #include "scan.hpp"
 #include "scope_sync.hpp"
 

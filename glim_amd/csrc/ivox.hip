@@ -1,6 +1,6 @@
-// ivox.hpp -- the device iVox: gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox), the incremental target model of GLIM's
-// LiDAR-only continuous-time odometry (odometry_estimation_ct.cpp:56-63 creates it, :229-235 inserts every finished frame).  Part of gicp.hip's
-// translation unit (included there, after its search helpers and run_gicp): the factors over the map are gicp.hip's, over gicp_target(map) below.
+// ivox.hip -- the device iVox: gtsam_points::IncrementalVoxelMap<FlatContainer> (gtsam_points::iVox), the incremental target model of GLIM's
+// LiDAR-only continuous-time odometry (odometry_estimation_ct.cpp:56-63 creates it, :229-235 inserts every finished frame).  The container and
+// its insert; the map object itself and its description as a target are ivox_map.hpp's, and the factors over the map are gicp.hip's.
 //
 // Semantics (upstream recall; include/glim_amd.h states them in full): a voxel is floor(p / leaf) of the STORED (FP32) point; insert takes the
 // points in input order, a new voxel is appended in first-seen order, a cell drops a point when it is full or when a point already in it is
@@ -18,30 +18,17 @@
 // point is written by the lane that owns the next place, and the wavefront leaves when the cell is full.  No atomics touch point data (the
 // table claim is a compare-and-swap on distinct keys, the point total an integer sum): the map does not depend on scheduling.
 // Eviction compacts the surviving slots in order into fresh arrays and rebuilds the table.  Every call returns with the stream idle.
-#pragma once
+#include <algorithm>
+#include <cmath>
+#include <vector>
 
-struct glim_amd_ivox {
-  CtxRef ctx;
-  double leaf = 1.0, inv_leaf = 1.0;
-  double min_dist = 0.1;                      // FlatContainer::Setting::min_sq_dist_in_cell = min_dist^2
-  int cap = 20;                               // max_num_points_in_cell (1..64: a cell never holds more than one wavefront's lanes)
-  int lru_horizon = 10, lru_clear_cycle = 10, lru_counter = 0;
-  int mode = 7;                               // neighbour voxel mode of the search
-  int num_slots = 0;                          // voxels
-  int64_t num_points = 0;
-  int slot_cap = 0, init_slots = 1024;
-  unsigned int tsize = 0;                     // table entries (power of two), 0 before the first insert
-  unsigned long long* tkeys = nullptr;
-  int* tslots = nullptr;
-  unsigned long long* skey = nullptr;         // per slot
-  int* scount = nullptr;
-  int* slru = nullptr;
-  float4* pts = nullptr;                      // slot_cap * cap
-  float4* covA = nullptr;
-  float2* covB = nullptr;
-  uint64_t generation = 1;                    // moves with every insert: what a factor's kept correspondences are checked against
-  std::atomic<int> live_factors{0};           // continuous-time factors built on the map; destroy is refused while one lives
-};
+#include "device_math.hpp"
+#include "internal.hpp"
+#include "ivox_map.hpp"
+#include "scan.hpp"
+#include "scope_sync.hpp"
+
+using namespace glim_amd;
 
 namespace {
 
@@ -362,34 +349,6 @@ int ivox_sweep(glim_amd_ivox* m, hipStream_t st) {
   return GLIM_AMD_OK;
 }
 
-constexpr int64_t IVOX_MAX_SOURCE = 1 << 28;  // source points of a rigid factor over the map
-
-// the map as a target of the factor kernels (gicp.hip, GicpTarget), as it is now
-GicpTarget gicp_target(const glim_amd_ivox* m, bool lock = true) {
-  GicpTarget t;
-  if (!m) return t;
-  t.ctx = m->ctx;
-  if (lock) t.held = std::unique_lock<std::mutex>(t.ctx->mu);
-  t.args.sorted = m->pts;
-  t.args.tA = m->covA;
-  t.args.tB = m->covB;
-  t.args.nt = (int)m->num_points;
-  t.args.h = m->leaf;
-  t.args.inv_h = m->inv_leaf;
-  t.ivox = true;
-  t.nn.keys = m->tkeys;
-  t.nn.slots = m->tslots;
-  t.nn.counts = m->scount;
-  t.nn.mask = m->tsize - 1;
-  t.nn.cap = m->cap;
-  t.nn.nnb = m->mode;
-  t.nn.inv_leaf = m->inv_leaf;
-  t.empty = m->num_slots == 0;
-  t.max_source = IVOX_MAX_SOURCE;
-  t.generation = m->generation;
-  return t;
-}
-
 }  // namespace
 
 extern "C" {
@@ -584,28 +543,6 @@ int glim_amd_ivox_voxel_points(const glim_amd_ivox* m, double* points4) {
       points4[4 * o + 2] = q.z;
       points4[4 * o + 3] = 1.0;
     }
-  return GLIM_AMD_OK;
-}
-
-// IntegratedGICPFactor_<iVox, PointCloud>: gicp.hip's rigid factor over the map
-int glim_amd_ivox_gicp_linearize(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
-                                 double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out) {
-  return gicp_linearize(gicp_target(target), source, T_target_source12, max_correspondence_distance, flags, out);
-}
-
-int glim_amd_ivox_gicp_error(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
-                             double max_correspondence_distance, double* error, int64_t* num_inliers) {
-  return gicp_error(gicp_target(target), source, T_target_source12, max_correspondence_distance, error, num_inliers);
-}
-
-int glim_amd_ivox_gicp_correspondences(const glim_amd_ivox* target, const glim_amd_cloud* source, const double* T_target_source12,
-                                       double max_correspondence_distance, int64_t* correspondences) {
-  if (!correspondences || !source) return GLIM_AMD_ERR_INVALID;
-  // the kernels write 32-bit positions; this entry point owns the 64-bit buffer and widens (a longer source is refused by run_gicp)
-  std::vector<int32_t> corr32((size_t)std::min<int64_t>(source->n, IVOX_MAX_SOURCE));
-  double compact[COMPACT];
-  GA_TRY(run_gicp(gicp_target(target), source, T_target_source12, max_correspondence_distance, false, compact, corr32.data()));
-  std::copy(corr32.begin(), corr32.end(), correspondences);
   return GLIM_AMD_OK;
 }
 

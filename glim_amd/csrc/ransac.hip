@@ -1,10 +1,9 @@
 // ransac.hip -- RANSAC global registration on gfx950: gtsam_points::estimate_pose_ransac as viewer/interactive/manual_loop_close_modal.cpp:431-443
 // calls it, the consumer of fpfh.hip's descriptors and correspondences.  Semantics in include/glim_amd.h ("RANSAC"), layout in DESIGN.md 4.7a.
 //
-// Built as part of gicp.hip's translation unit, after fpfh.hip, for the reason the head of fpfh.hip gives: the csrc Makefile is part of the
-// identity of the committed traffic evidence.  The host scaffold of the entries is registration_host.hpp, shared with gnc.hip (it is that header
-// which uses fpfh.hip's descriptor object and matcher); the generator is sample_hash.hpp, shared with preprocess.hip; gnc.hip uses this file's
-// occupancy table, round buffers and scoring launch.
+// The host scaffold of the entries is registration_host.hpp, shared with gnc.hip (it is that header which uses fpfh.hip's descriptor object and
+// matcher, through fpfh.hpp); the generator is sample_hash.hpp, shared with preprocess.hip; ransac_table.hpp declares what gnc.hip uses of this
+// file: the occupancy table, the round buffers and the scoring launch.
 //
 // table      occupancy set of the target: 64-bit keys only, open addressing, power-of-two slots, load <= 0.5, insert = one 64-bit integer
 //            compare-and-swap per probe.  Built twice: into a table sized by the POINTS (the number of voxels is not known yet), which also counts
@@ -23,6 +22,7 @@
 #include "device_math.hpp"
 #include "internal.hpp"
 #include "ransac_pose.hpp"
+#include "ransac_table.hpp"
 #include "registration_host.hpp"
 #include "sample_hash.hpp"
 #include "scope_sync.hpp"
@@ -30,10 +30,7 @@
 namespace glim_amd {
 namespace ransac_detail {
 
-using glim_amd::sample_hash;
 using reg_detail::Pair;
-using u64 = unsigned long long;
-using u32 = unsigned int;
 
 constexpr int ROUND = 1024;          // hypotheses per round: the early stop is looked at once per round
 constexpr int SC_BLOCK = 512;        // lanes of a scoring block (8 wavefronts)
@@ -242,12 +239,6 @@ inline u32 pow2_at_least(uint64_t v) {
   return s;
 }
 
-struct Table {
-  DeviceTemp keys;
-  u32 slots = 0;
-  int in_lds = 0;
-};
-
 // occupancy set of `n` target points at 1 / inv_res; synchronises `st` once (the voxel count)
 int build_table(glim_amd_ctx* ctx, hipStream_t st, const float4* pts, int n, double inv_res, Table* out) {
   int voxels = 0;
@@ -275,26 +266,22 @@ int build_table(glim_amd_ctx* ctx, hipStream_t st, const float4* pts, int n, dou
   return GLIM_AMD_OK;
 }
 
-struct RoundBuffers {
-  DeviceTemp samples, status, poses, counts, state;
-  int alloc() {
-    GA_HIP(pool_malloc(&samples.p, (size_t)ROUND * 3 * sizeof(int)));
-    GA_HIP(pool_malloc(&status.p, (size_t)ROUND * sizeof(int)));
-    GA_HIP(pool_malloc(&poses.p, (size_t)ROUND * 12 * sizeof(double)));
-    GA_HIP(pool_malloc(&counts.p, (size_t)ROUND * sizeof(int)));
-    GA_HIP(pool_malloc(&state.p, sizeof(FoldState)));
-    return GLIM_AMD_OK;
-  }
-};
+int RoundBuffers::alloc() {
+  GA_HIP(pool_malloc(&samples.p, (size_t)ROUND * 3 * sizeof(int)));
+  GA_HIP(pool_malloc(&status.p, (size_t)ROUND * sizeof(int)));
+  GA_HIP(pool_malloc(&poses.p, (size_t)ROUND * 12 * sizeof(double)));
+  GA_HIP(pool_malloc(&counts.p, (size_t)ROUND * sizeof(int)));
+  GA_HIP(pool_malloc(&state.p, sizeof(FoldState)));
+  return GLIM_AMD_OK;
+}
 
 inline void launch_hypotheses(const Pair& p, const glim_amd_ransac_params& prm, const RoundBuffers& b, int base, int count) {
   rs_hypothesis_kernel<<<(count + 255) / 256, 256, 0, p.st>>>(count, base, (u64)prm.seed, p.n_src, p.spts, p.tpts, p.d_nearest, prm.poly_error_thresh,
                                                                prm.dof, b.samples.as<int>(), b.status.as<int>(), b.poses.as<double>(),
                                                                b.counts.as<int>());
 }
-// the first `count` hypotheses of `b` against the table of voxels of edge `resolution`.  Enough blocks for four per compute unit, never fewer
-// than 16 hypotheses per block (the table copy and the point loads are per block)
-inline void launch_score(const Pair& p, double resolution, const Table& t, const RoundBuffers& b, int count) {
+// the first `count` hypotheses of `b` against the table of voxels of edge `resolution` (ransac_table.hpp)
+void launch_score(const Pair& p, double resolution, const Table& t, const RoundBuffers& b, int count) {
   const int tiles = (p.n_src + SC_TILE - 1) / SC_TILE;
   const int want = 4 * std::max(p.ctx->num_cus, 1);
   const int hpb = std::min(count, std::max(16, (int)(((int64_t)count * tiles + want - 1) / want)));

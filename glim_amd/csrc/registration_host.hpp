@@ -1,11 +1,11 @@
 // registration_host.hpp -- the host scaffold the global-registration entries share (ransac.hip, gnc.hip): the argument checks, the two ways a
 // correspondence list reaches the device (uploaded from the host, or matched there from two descriptor sets), the "nothing estimated" result and
-// the HIP-event clock of the profile entries.  Host code only, part of gicp.hip's translation unit: it follows fpfh.hip, whose descriptor object
-// and matcher with_matched_nearest uses.
+// the HIP-event clock of the profile entries.  Host code only; with_matched_nearest uses fpfh.hip's descriptor object and matcher (fpfh.hpp).
 #pragma once
 #include <cstring>
 #include <mutex>
 
+#include "fpfh.hpp"
 #include "internal.hpp"
 #include "scope_sync.hpp"
 
