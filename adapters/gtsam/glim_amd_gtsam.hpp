@@ -277,6 +277,12 @@ public:
     return out;
   }
   const std::shared_ptr<IntegratedCT_GICPFactor>& impl() const { return impl_; }
+  // odometry_estimation_ct.cpp:176-183 without the host loop: glim_amd::align_ct of <glim_amd/ct_align.hpp>, which the caller includes --
+  // align(values, CtAlignTerms, LMParams) -> CtAlignResult with the poses of keys()[0], keys()[1]
+  template <class Terms, class Params>
+  auto align(const gtsam::Values& values, const Terms& terms, const Params& params) const {
+    return impl_->align(to_values(values), terms, params);
+  }
 
 private:
   Values to_values(const gtsam::Values& values) const {

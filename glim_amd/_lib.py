@@ -168,6 +168,49 @@ class AlignTraceEntry(C.Structure):
     ]
 
 
+class CtAlignTerms(C.Structure):
+    """glim_amd_ct_align_terms (include/glim_amd.h "CT-GICP frame alignment")"""
+
+    _fields_ = [
+        ("T_location", C.c_double * 12),
+        ("location_precision", C.c_double),
+        ("T_between", C.c_double * 12),
+        ("between_precision", C.c_double),
+    ]
+
+
+class CtAlignResult(C.Structure):
+    """glim_amd_ct_align_result"""
+
+    _fields_ = [
+        ("X", C.c_double * 12),
+        ("Y", C.c_double * 12),
+        ("linearized", CtLinearized),
+        ("cost", C.c_double),
+        ("location_cost", C.c_double),
+        ("between_cost", C.c_double),
+        ("lam", C.c_double),
+        ("iterations", C.c_int32),
+        ("trials", C.c_int32),
+        ("status", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class CtAlignTraceEntry(C.Structure):
+    """glim_amd_ct_align_trace_entry (include/glim_amd_diag.h)"""
+
+    _fields_ = [
+        ("X", C.c_double * 12),
+        ("Y", C.c_double * 12),
+        ("lam", C.c_double),
+        ("record", C.c_double * 92),
+        ("cost", C.c_double),
+        ("accepted", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -282,6 +325,11 @@ SYMBOLS = {
     "glim_amd_gicp_align_batch": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_gicp_align_batch_incremental": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_debug_gicp_align_trace": (_i, [_i32, _pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry)]),
+    "glim_amd_ct_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_ct_align": (_i, [_vp, _dp, _dp, C.POINTER(CtAlignTerms), C.POINTER(LMParams), C.POINTER(CtAlignResult)]),
+    "glim_amd_debug_ct_align_trace": (_i, [_vp, _dp, _dp, C.POINTER(CtAlignTerms), C.POINTER(LMParams), C.POINTER(CtAlignResult),
+                                           C.POINTER(CtAlignTraceEntry)]),
+    "glim_amd_debug_ct_align_poses": (_i, [_vp, _dp, _dp, _ip, _i32, _dp, _dp, _dp]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -1391,6 +1391,79 @@ def gicp_align_debug_trace(targets, sources, T_init, max_correspondence_distance
     return results, traces
 
 
+def ct_align_params(**kw):
+    """LMParams with GLIM's continuous-time odometry values (glim_amd_ct_align_default_params): lambda_initial 1e-10, absolute_error_tol 1e-2,
+    max_iterations 8 (odometry_estimation_ct.cpp:176-183)."""
+    p = dict(lambda_initial=1e-10, absolute_error_tol=1e-2, max_iterations=8)
+    p.update(kw)
+    return LMParams(**p)
+
+
+def _ct_record(c):
+    """a glim_amd_ct_linearized as IntegratedCT_GICPFactor.linearize returns it"""
+    a = np.frombuffer(c, dtype=np.float64, count=122).copy()
+    return {"num_inliers": int(c.num_inliers), "error": float(a[1]), "H_00": a[2:38].reshape(6, 6), "H_01": a[38:74].reshape(6, 6),
+            "H_11": a[74:110].reshape(6, 6), "b_0": a[110:116], "b_1": a[116:122]}
+
+
+class CtAlignResult:
+    """glim_amd_ct_align_result: the last kept pair X, Y (4 x 4), the factor's record at it (`linearized`, as IntegratedCT_GICPFactor.linearize
+    returns it), the total cost and the two terms' costs, the counts, the status (ALIGN_STATUS) and the lambda after the last trial.  `raw` holds
+    the bytes of the C structure."""
+
+    def __init__(self, c):
+        self.raw = bytes(c)
+        self.X, self.Y = np.eye(4), np.eye(4)
+        self.X[:3] = np.array(c.X[:]).reshape(3, 4)
+        self.Y[:3] = np.array(c.Y[:]).reshape(3, 4)
+        self.linearized = _ct_record(c.linearized)
+        self.error = self.linearized["error"]
+        self.num_inliers = self.linearized["num_inliers"]
+        self.cost = c.cost
+        self.location_cost = c.location_cost
+        self.between_cost = c.between_cost
+        self.iterations = c.iterations
+        self.trials = c.trials
+        self.status = c.status
+        self.status_name = ALIGN_STATUS.get(c.status, "?")
+        self.lam = c.lam
+
+
+def _ct_align_args(factor, values, location_prior, between, params):
+    X, Y = factor._xy(values)
+    terms = _lib.CtAlignTerms()
+    none = True
+    for term, pose, prec in ((location_prior, "T_location", "location_precision"), (between, "T_between", "between_precision")):
+        if term is not None:
+            T, k = term
+            getattr(terms, pose)[:] = list(pose12(T))
+            setattr(terms, prec, float(k))
+            none = False
+    prm = (params or ct_align_params())
+    return X, Y, (None if none else C.byref(terms)), prm
+
+
+def ct_align_debug_trace(factor, values, location_prior=None, between=None, params=None):
+    """Test window (glim_amd_debug_ct_align_trace): IntegratedCT_GICPFactor.align's result plus one dict per round run -- round 0 is the initial
+    pair -- with the pair evaluated (`X`, `Y`, 4 x 4), the `lam` its step was solved with, the factor's `record` there (92 doubles), the total
+    `cost`, `accepted` and the `status` after the round (0: still running)."""
+    X, Y, terms, prm = _ct_align_args(factor, values, location_prior, between, params)
+    rounds = 1 + prm.resolved_max_trials()
+    out = _lib.CtAlignResult()
+    trace = (_lib.CtAlignTraceEntry * rounds)()
+    pc = prm._c()
+    check(lib().glim_amd_debug_ct_align_trace(factor._h, _dp(X), _dp(Y), terms, C.byref(pc), C.byref(out), trace), "glim_amd_debug_ct_align_trace")
+    r = CtAlignResult(out)
+    rows = []
+    for k in range(min(rounds, r.trials + 1)):
+        e = trace[k]
+        Xk, Yk = np.eye(4), np.eye(4)
+        Xk[:3] = np.array(e.X[:]).reshape(3, 4)
+        Yk[:3] = np.array(e.Y[:]).reshape(3, 4)
+        rows.append({"X": Xk, "Y": Yk, "lam": e.lam, "record": np.array(e.record[:]), "cost": e.cost, "accepted": bool(e.accepted), "status": e.status})
+    return r, rows
+
+
 class IntegratedCT_GICPFactor:
     """gtsam_points::IntegratedCT_GICPFactor (point-cloud target, KdTree) on the device: GLIM's continuous-time odometry cost
     (odometry_estimation_ct.cpp:158-183).  One scan between key0 (X, the pose at scan begin) and key1 (Y, at scan end); every point moves
@@ -1427,15 +1500,36 @@ class IntegratedCT_GICPFactor:
         X, Y = self._xy(values)
         L = CtLinearized()
         check(lib().glim_amd_ct_gicp_linearize(self._h, _dp(X), _dp(Y), C.byref(L)), "glim_amd_ct_gicp_linearize")
-        a = np.frombuffer(L, dtype=np.float64, count=122).copy()
-        return {"num_inliers": int(L.num_inliers), "error": float(a[1]), "H_00": a[2:38].reshape(6, 6), "H_01": a[38:74].reshape(6, 6),
-                "H_11": a[74:110].reshape(6, 6), "b_0": a[110:116], "b_1": a[116:122]}
+        return _ct_record(L)
 
     def error(self, values, with_inliers=False):
         X, Y = self._xy(values)
         e, n = C.c_double(), C.c_int64()
         check(lib().glim_amd_ct_gicp_error(self._h, _dp(X), _dp(Y), C.byref(e), C.byref(n)), "glim_amd_ct_gicp_error")
         return (e.value, n.value) if with_inliers else e.value
+
+    def align(self, values, location_prior=None, between=None, params=None):
+        """The whole frame optimisation of odometry_estimation_ct.cpp:158-195 on the device, one host synchronisation (glim_amd_ct_align):
+        Levenberg-Marquardt over values[key0], values[key1] on this factor plus the optional terms location_prior = (T, precision) on X and
+        between = (T, precision) on X^-1 Y.  params: LMParams, default ct_align_params().  Returns a CtAlignResult; the state error() reuses
+        is left as it was."""
+        X, Y, terms, prm = _ct_align_args(self, values, location_prior, between, params)
+        out = _lib.CtAlignResult()
+        pc = prm._c()
+        check(lib().glim_amd_ct_align(self._h, _dp(X), _dp(Y), terms, C.byref(pc), C.byref(out)), "glim_amd_ct_align")
+        return CtAlignResult(out)
+
+    def debug_align_poses(self, values):
+        """(T_k n x 4 x 4, D0_k, D1_k n x 6 x 6) as the pose table kernel of align() computes them at `values`."""
+        X, Y = self._xy(values)
+        nb = C.c_int32()
+        check(lib().glim_amd_debug_ct_align_poses(self._h, _dp(X), _dp(Y), C.byref(nb), 0, None, None, None), "glim_amd_debug_ct_align_poses")
+        m = nb.value
+        T, D0, D1 = np.zeros((m, 12)), np.zeros((m, 36)), np.zeros((m, 36))
+        check(lib().glim_amd_debug_ct_align_poses(self._h, _dp(X), _dp(Y), C.byref(nb), m, _dp(T), _dp(D0), _dp(D1)), "glim_amd_debug_ct_align_poses")
+        T44 = np.tile(np.eye(4), (m, 1, 1))
+        T44[:, :3, :] = T.reshape(m, 3, 4)
+        return T44, D0.reshape(m, 6, 6), D1.reshape(m, 6, 6)
 
     def correspondences(self, values):
         X, Y = self._xy(values)

@@ -31,6 +31,7 @@
 #include <memory>
 #include <vector>
 
+#include "ct_factor.hpp"
 #include "device_math.hpp"
 #include "gicp_factor.hpp"
 #include "internal.hpp"
@@ -123,17 +124,6 @@ __global__ __launch_bounds__(256) void gi_gather_kernel(int n, const u64* __rest
   if (tail) runs[s].y = j + 1;
 }
 
-// row-major upper triangle of a symmetric N x N matrix: entry (r, c), r <= c, is at upper_index<N>(r, c); upper_entry<N> is the way back
-template <int N>
-constexpr int upper_index(int r, int c) {
-  return r * N - r * (r - 1) / 2 + (c - r);
-}
-template <int N>
-constexpr void upper_entry(int u, int& r, int& c) {
-  for (r = 0; u >= N - r; r++) u -= N - r;
-  c = r + u;
-}
-
 template <bool LINEARIZE, class NN>
 __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __restrict__ partials, int32_t* __restrict__ corr, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
@@ -172,63 +162,11 @@ __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restr
 }
 
 // ---- the continuous-time factor (IntegratedCT_GICPFactor): the same per-point algebra, one pose per time bucket ----
-// Layout: the points of a bucket are a contiguous index run (the time table never goes back), cut into blocks of at most BLOCK * ppt points, so
-// the pose is uniform per block.  Block b writes its 28 source-frame sums (in T_k's own tangent) to partial row b; ct_bucket_kernel adds the rows
-// of each bucket in block order and maps the bucket's 6 x 6 system through the chain rule [D0_k | D1_k] in FP64; ct_sum_kernel adds the buckets in
-// bucket order.  No atomics: the record is bit-reproducible, for any number of buckets.
-constexpr int CT_POSE_STRIDE = 84;  // doubles per bucket in the pose table: T_k (12, row-major 3x4) | D0_k (36) | D1_k (36), row-major 6x6
-constexpr int CT_ROW = 92;          // doubles per bucket row / in the record: count, error, 78 upper entries of the 12 x 12 H (row-major), 12 of b
-
-struct CtArgs {
-  const int4* blocks;    // (bucket, begin, end, -) per block
-  const double* poses;   // CT_POSE_STRIDE per bucket (the deskewing kernel reads a plain 12-double table instead)
-  int32_t* keep_corr;    // kept correspondences (position in the index's sorted order, or -1), or null
-  float4* keep_m0;       // kept M = (C_B + R_k C_A R_k^T)^-1 (target frame): m00 m01 m02 m11
-  float2* keep_m1;       //                                                      m12 m22
-  int32_t* corr_out;     // original target index or -1 per source point, or null
-};
-
+// The layout, the arguments and the bodies of the three passes are ct_factor.hpp's (gicp_align.hip runs them inside its rounds as well).
 template <bool LINEARIZE, class NN>
 __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];
-  const int4 blk = c.blocks[blockIdx.x];
-  const double* T = c.poses + (size_t)blk.x * CT_POSE_STRIDE;
-  const Rot32 R(T);
-  float acc[NACC];
-#pragma unroll
-  for (int j = 0; j < NACC; j++) acc[j] = 0.f;
-  int inliers = 0;
-  for (int i = blk.y + (int)threadIdx.x; i < blk.z; i += BLOCK) {
-    const float4 p = a.pts[i];
-    double qx, qy, qz;
-    transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
-    double best_d;
-    const int j = nn.find(a, qx, qy, qz, best_d);
-    if (c.corr_out) c.corr_out[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
-    if (c.keep_corr) c.keep_corr[i] = j;
-    if (j < 0) continue;
-    inliers++;
-    float A[6];
-    gicp_point<LINEARIZE>(acc, R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz,
-                          A);
-    if (c.keep_m0) {
-      // M = R A R^T: the source-frame inverse taken back to the target frame
-      const float Rm[9] = {R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22};
-      const float As[9] = {A[0], A[1], A[2], A[1], A[3], A[4], A[2], A[4], A[5]};
-      float W[9];
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) W[3 * r + k] = Rm[3 * r] * As[k] + Rm[3 * r + 1] * As[3 + k] + Rm[3 * r + 2] * As[6 + k];
-      float M[6];
-      const int mr[6] = {0, 0, 0, 1, 1, 2}, mc[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-      for (int u = 0; u < 6; u++) M[u] = W[3 * mr[u]] * Rm[3 * mc[u]] + W[3 * mr[u] + 1] * Rm[3 * mc[u] + 1] + W[3 * mr[u] + 2] * Rm[3 * mc[u] + 2];
-      c.keep_m0[i] = make_float4(M[0], M[1], M[2], M[3]);
-      c.keep_m1[i] = make_float2(M[4], M[5]);
-    }
-  }
-  store_partial_row(acc, inliers, s_red, partials);
+  ct_gicp_block<LINEARIZE, NN>(a, c, partials, nn, s_red);
 }
 
 // error(): the kept correspondences and M at new poses -- e = sum r^T M r, r = b_j - T_k p_i (FP64, then FP32).  Partial rows hold e (27) and the
@@ -272,78 +210,17 @@ __global__ __launch_bounds__(BLOCK) void ct_error_kernel(const GicpArgs a, const
   }
 }
 
-// one block of 64 threads per bucket: its partial rows summed in FP64 in block order -> H_k, b_k (T_k's tangent, the compact record's convention)
-// -> [D0 | D1]^T H_k [D0 | D1] and [D0 | D1]^T b_k
+// one block of 64 threads per bucket (ct_factor.hpp)
 __global__ __launch_bounds__(64) void ct_bucket_kernel(const float* __restrict__ partials, const int* __restrict__ bucket_first, const double* __restrict__ poses,
                                                        double* __restrict__ rows) {
-  __shared__ double s_sum[PARTIAL_STRIDE];
-  __shared__ double s_J[6 * 12];
-  __shared__ double s_H[36];
-  __shared__ double s_b[6];
-  __shared__ double s_W[6 * 12];
-  const int k = blockIdx.x, t = threadIdx.x;
-  const int first = bucket_first[k], last = bucket_first[k + 1];
-  if (t <= 28) {
-    double s = 0.0;
-    for (int r = first; r < last; r++) s += (double)partials[(size_t)r * PARTIAL_STRIDE + t];
-    s_sum[t] = s;
-  }
-  const double* D = poses + (size_t)k * CT_POSE_STRIDE + 12;
-  for (int u = t; u < 72; u += 64) {
-    const int m = u / 12, col = u % 12;
-    s_J[u] = col < 6 ? D[6 * m + col] : D[36 + 6 * m + col - 6];
-  }
-  __syncthreads();
-  if (t < 36) {
-    const int r = t / 6, cc = t % 6;
-    s_H[t] = s_sum[c_acc_of_upper_g[upper_index<6>(min(r, cc), max(r, cc))]];
-  } else if (t < 42) {
-    const int m = t - 36;
-    s_b[m] = m < 3 ? s_sum[21 + m] : -s_sum[21 + m];
-  }
-  __syncthreads();
-  for (int u = t; u < 72; u += 64) {
-    const int m = u / 12, col = u % 12;
-    double s = 0.0;
-    for (int q = 0; q < 6; q++) s += s_H[6 * m + q] * s_J[12 * q + col];
-    s_W[u] = s;
-  }
-  __syncthreads();
-  double* row = rows + (size_t)k * CT_ROW;
-  for (int u = t; u < CT_ROW; u += 64) {
-    double v;
-    if (u == 0) {
-      v = s_sum[28];
-    } else if (u == 1) {
-      v = s_sum[27];
-    } else if (u < 80) {
-      int r, cc;
-      upper_entry<12>(u - 2, r, cc);
-      v = 0.0;
-      for (int m = 0; m < 6; m++) v += s_J[12 * m + r] * s_W[12 * m + cc];
-    } else {
-      const int r = u - 80;
-      v = 0.0;
-      for (int m = 0; m < 6; m++) v += s_J[12 * m + r] * s_b[m];
-    }
-    row[u] = v;
-  }
+  __shared__ CtBucketShared s;
+  ct_bucket_block(partials, bucket_first, poses, rows, s);
 }
 
-// one block: the bucket rows summed in a fixed order (8 groups of ordered_column_sum, then the groups in order) -> the record
-__global__ __launch_bounds__(768) void ct_sum_kernel(const double* __restrict__ rows, int nbk, double* __restrict__ out) {
+// one block: the bucket rows summed in a fixed order -> the record
+__global__ __launch_bounds__(CT_SUM_THREADS) void ct_sum_kernel(const double* __restrict__ rows, int nbk, double* __restrict__ out) {
   __shared__ double s_part[8][96];
-  const int j = threadIdx.x % 96, g = threadIdx.x / 96;
-  double s = 0.0;
-  if (j < CT_ROW) s = ordered_column_sum<double, CT_ROW, 8>(rows, nbk, j, g);
-  s_part[g][j] = s;
-  __syncthreads();
-  if (threadIdx.x < CT_ROW) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) t += s_part[q][threadIdx.x];
-    out[threadIdx.x] = t;
-  }
+  ct_sum_rows<CT_SUM_THREADS>(rows, nbk, s_part, out);
 }
 
 // deskewed_source_points: T[time_index[i]] p_i in FP64 (the source's exact points where it keeps them), table of 12 doubles per bucket
@@ -435,240 +312,11 @@ int gicp_error(const GicpTarget& t, const glim_amd_cloud* source, const double* 
   return GLIM_AMD_OK;
 }
 
-// ---- CT factor, host side: the time table and the bucket poses with their derivatives (FP64, gtsam::Pose3 conventions) ----
-// gtsam's right-perturbation Jacobians: between(X, Y) = X^-1 Y, H_X = -Ad((X^-1 Y)^-1), H_Y = I; compose(A, B): H_A = Ad(B^-1), H_B = I;
-// Expmap(xi): ExpmapDerivative(xi) = J_r(xi); Logmap(T): LogmapDerivative = J_r(Log T)^-1.  Coefficients with a cancelling numerator switch to
-// their Taylor series below 0.02 rad (truncation < 1e-16 there).
-struct Mat6 {
-  double m[36];
-};
-constexpr double CT_SERIES = 0.02;
-
-void ct_hat(const double* w, double* W) {
-  W[0] = 0.0; W[1] = -w[2]; W[2] = w[1];
-  W[3] = w[2]; W[4] = 0.0; W[5] = -w[0];
-  W[6] = -w[1]; W[7] = w[0]; W[8] = 0.0;
-}
-void mm3(const double* A, const double* B, double* C) {
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-// the rotation of a row-major 3 x 4 pose
-void rot_of(const double* T12, double* R) {
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) R[3 * r + k] = T12[4 * r + k];
-}
-// [[A, 0], [B, A]] from row-major 3 x 3 blocks: the shape of the se(3) Jacobians and of the adjoint below
-Mat6 block6(const double* A, const double* B) {
-  Mat6 M{};
-  for (int r = 0; r < 3; r++)
-    for (int k = 0; k < 3; k++) {
-      M.m[6 * r + k] = M.m[6 * (r + 3) + k + 3] = A[3 * r + k];
-      M.m[6 * (r + 3) + k] = B[3 * r + k];
-    }
-  return M;
-}
-void inv3(const double* A, double* B) {
-  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-  const double id = 1.0 / (A[0] * c00 + A[1] * c01 + A[2] * c02);
-  B[0] = c00 * id; B[1] = (A[2] * A[7] - A[1] * A[8]) * id; B[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-  B[3] = c01 * id; B[4] = (A[0] * A[8] - A[2] * A[6]) * id; B[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-  B[6] = c02 * id; B[7] = (A[1] * A[6] - A[0] * A[7]) * id; B[8] = (A[0] * A[4] - A[1] * A[3]) * id;
-}
-// (1 - cos th) / th^2 and (th - sin th) / th^3
-void so3_coeffs(double th, double& b, double& c) {
-  const double t2 = th * th;
-  if (th < CT_SERIES) {
-    b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
-    c = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
-  } else {
-    b = (1.0 - std::cos(th)) / t2;
-    c = (th - std::sin(th)) / (t2 * th);
-  }
-}
-// Pose3::Expmap: T = [Exp(w) | V(w) v], V = I + b W + c W^2.  Not deskew.hip's se3_exp, on purpose: that one repeats the oracle's operation order
-// bit for bit, this one uses series coefficients near zero.
-void se3_exp(const double* xi, double* T12) {
-  double W[9], W2[9];
-  ct_hat(xi, W);
-  mm3(W, W, W2);
-  const double th = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]);
-  const double t2 = th * th;
-  const double a = th < CT_SERIES ? 1.0 - t2 / 6.0 + t2 * t2 / 120.0 : std::sin(th) / th;
-  double b, c;
-  so3_coeffs(th, b, c);
-  for (int r = 0; r < 3; r++) {
-    double tr = 0.0;
-    for (int k = 0; k < 3; k++) {
-      const double I = r == k ? 1.0 : 0.0;
-      T12[4 * r + k] = I + a * W[3 * r + k] + b * W2[3 * r + k];
-      tr += (I + b * W[3 * r + k] + c * W2[3 * r + k]) * xi[3 + k];
-    }
-    T12[4 * r + 3] = tr;
-  }
-}
-// Pose3::Logmap: w = Log(R), v = V(w)^-1 t
-void se3_log(const double* T12, double* xi) {
-  double R[9];
-  rot_of(T12, R);
-  const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
-  const double s = std::sqrt(vx * vx + vy * vy + vz * vz), cth = 0.5 * (R[0] + R[4] + R[8] - 1.0);
-  const double th = std::atan2(s, cth);
-  const double t2 = th * th;
-  const double f = th < CT_SERIES ? 1.0 + t2 / 6.0 + 7.0 * t2 * t2 / 360.0 : th / std::sin(th);
-  xi[0] = f * vx;
-  xi[1] = f * vy;
-  xi[2] = f * vz;
-  double W[9], W2[9], V[9], Vi[9];
-  ct_hat(xi, W);
-  mm3(W, W, W2);
-  double b, c;
-  so3_coeffs(th, b, c);
-  for (int u = 0; u < 9; u++) V[u] = (u % 4 == 0 ? 1.0 : 0.0) + b * W[u] + c * W2[u];
-  inv3(V, Vi);
-  for (int r = 0; r < 3; r++) xi[3 + r] = Vi[3 * r] * T12[3] + Vi[3 * r + 1] * T12[7] + Vi[3 * r + 2] * T12[11];
-}
-// the blocks of Pose3::ExpmapDerivative, [[Jw, 0], [Q, Jw]] (Jw = Rot3::ExpmapDerivative, Q = computeQforExpmapDerivative)
-void se3_jr_blocks(const double* xi, double* Jw, double* Q) {
-  double W[9], V[9], W2[9];
-  ct_hat(xi, W);
-  ct_hat(xi + 3, V);
-  mm3(W, W, W2);
-  const double th = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), t2 = th * th;
-  double b, c;
-  so3_coeffs(th, b, c);
-  for (int u = 0; u < 9; u++) Jw[u] = (u % 4 == 0 ? 1.0 : 0.0) - b * W[u] + c * W2[u];
-  double ca, cb, cc;  // (th - sin) / th^3, (1 - th^2/2 - cos) / th^4, -(cb - 3 (th - sin - th^3/6) / th^5) / 2
-  if (th < CT_SERIES) {
-    ca = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
-    cb = -1.0 / 24.0 + t2 / 720.0 - t2 * t2 / 40320.0;
-    const double cd = -1.0 / 120.0 + t2 / 5040.0 - t2 * t2 / 362880.0;
-    cc = -0.5 * (cb - 3.0 * cd);
-  } else {
-    const double t3 = t2 * th, t4 = t2 * t2, t5 = t4 * th, sn = std::sin(th), cs = std::cos(th);
-    ca = (th - sn) / t3;
-    cb = (1.0 - t2 / 2.0 - cs) / t4;
-    cc = -0.5 * (cb - 3.0 * (th - sn - t3 / 6.0) / t5);
-  }
-  double WV[9], VW[9], WVW[9], WWV[9], VWW[9], WVWW[9], WWVW[9];
-  mm3(W, V, WV);
-  mm3(V, W, VW);
-  mm3(WV, W, WVW);
-  mm3(W2, V, WWV);
-  mm3(V, W2, VWW);
-  mm3(WVW, W, WVWW);
-  mm3(W, WVW, WWVW);
-  for (int u = 0; u < 9; u++)
-    Q[u] = -0.5 * V[u] + ca * (WV[u] + VW[u] - WVW[u]) + cb * (WWV[u] + VWW[u] - 3.0 * WVW[u]) + cc * (WVWW[u] + WWVW[u]);
-}
-// Pose3::ExpmapDerivative
-Mat6 se3_jr(const double* xi) {
-  double Jw[9], Q[9];
-  se3_jr_blocks(xi, Jw, Q);
-  return block6(Jw, Q);
-}
-// Pose3::LogmapDerivative at Log = xi: the block inverse of se3_jr(xi), [[Jw^-1, 0], [-Jw^-1 Q Jw^-1, Jw^-1]]
-Mat6 se3_jr_inv(const double* xi) {
-  double Jw[9], Q[9], Ji[9], T[9], QJ[9];
-  se3_jr_blocks(xi, Jw, Q);
-  inv3(Jw, Ji);
-  mm3(Q, Ji, T);
-  mm3(Ji, T, QJ);
-  for (double& v : QJ) v = -v;
-  return block6(Ji, QJ);
-}
-// Pose3::AdjointMap: [[R, 0], [hat(t) R, R]]
-Mat6 se3_ad(const double* T12) {
-  const double t[3] = {T12[3], T12[7], T12[11]};
-  double R[9], H[9], HR[9];
-  rot_of(T12, R);
-  ct_hat(t, H);
-  mm3(H, R, HR);
-  return block6(R, HR);
-}
-Mat6 mm6(const Mat6& A, const Mat6& B) {
-  Mat6 C{};
-  for (int r = 0; r < 6; r++)
-    for (int c = 0; c < 6; c++) {
-      double s = 0.0;
-      for (int k = 0; k < 6; k++) s += A.m[6 * r + k] * B.m[6 * k + c];
-      C.m[6 * r + c] = s;
-    }
-  return C;
-}
-void se3_compose(const double* A, const double* B, double* C) {
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 4; c++) C[4 * r + c] = A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c] + A[4 * r + 2] * B[8 + c];
-    C[4 * r + 3] += A[4 * r + 3];
-  }
-}
-void se3_inverse(const double* A, double* B) {
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) B[4 * r + c] = A[4 * c + r];
-    B[4 * r + 3] = -(A[r] * A[3] + A[4 + r] * A[7] + A[8 + r] * A[11]);
-  }
-}
-
-}  // namespace
-
-struct glim_amd_ct_gicp_factor {
-  CtxRef ctx;
-  const glim_amd_nn_index* ix = nullptr;  // not owned; null when the target is a device iVox
-  glim_amd_ivox* iv = nullptr;            // not owned (counted in its live_factors: the map cannot be destroyed under the factor)
-  uint64_t kept_gen = 0;                  // the map's generation the kept correspondences were found in
-  const glim_amd_cloud* src = nullptr;    // not owned
-  int n = 0;
-  double max_dist = 1.0;
-  std::vector<double> table;              // normalised bucket times
-  std::vector<int> time_index;            // bucket of every point
-  int nbk = 0, nb = 0;                    // buckets, blocks
-  int4* d_blocks = nullptr;               // (bucket, begin, end, -) per block
-  int* d_bucket_first = nullptr;          // first block of every bucket, nbk + 1 entries
-  int* d_time_index = nullptr;
-  double* d_poses = nullptr;              // CT_POSE_STRIDE per bucket
-  double* h_poses = nullptr;              // pinned staging of the same
-  float* d_partials = nullptr;            // nb partial rows
-  double* d_rows = nullptr;               // nbk bucket rows
-  double* d_out = nullptr;                // CT_ROW doubles
-  int32_t* keep_corr = nullptr;           // the state linearize keeps for error
-  float4* keep_m0 = nullptr;
-  float2* keep_m1 = nullptr;
-  bool kept = false;
-};
-
-namespace {
-
-// the factor's target as it is now (the lock of the call comes with it)
-GicpTarget ct_target(const glim_amd_ct_gicp_factor* f) { return f->ix ? gicp_target(f->ix) : gicp_target(f->iv); }
+// ---- CT factor, host side: the time table and the bucket poses with their derivatives (FP64, gtsam::Pose3 conventions: ct_se3.hpp) ----
+using namespace glim_amd::ct_se3;
 
 // T_k, D0_k, D1_k of every bucket at (X, Y): CT_POSE_STRIDE doubles per bucket
-void ct_poses(const std::vector<double>& table, const double* X, const double* Y, double* out) {
-  double Xi[12], delta[12], vel[6], Dinv[12];
-  se3_inverse(X, Xi);
-  se3_compose(Xi, Y, delta);
-  se3_log(delta, vel);
-  se3_inverse(delta, Dinv);
-  const Mat6 Jlog = se3_jr_inv(vel);
-  Mat6 Hb1 = se3_ad(Dinv);
-  for (double& v : Hb1.m) v = -v;
-  for (size_t k = 0; k < table.size(); k++) {
-    const double tk = table[k];
-    double xi[6], E[12], Ei[12];
-    for (int u = 0; u < 6; u++) xi[u] = tk * vel[u];
-    se3_exp(xi, E);
-    se3_inverse(E, Ei);
-    double* o = out + k * CT_POSE_STRIDE;
-    se3_compose(X, E, o);
-    Mat6 G = mm6(se3_jr(xi), Jlog);  // H_compose_2 H_exp t_k H_log
-    for (double& v : G.m) v *= tk;
-    const Mat6 G0 = mm6(G, Hb1);
-    const Mat6 Ad = se3_ad(Ei);
-    for (int u = 0; u < 36; u++) {
-      o[12 + u] = Ad.m[u] + G0.m[u];
-      o[48 + u] = G.m[u];
-    }
-  }
-}
+void ct_poses(const std::vector<double>& table, const double* X, const double* Y, double* out) { ct_pose_table(table.data(), table.size(), X, Y, out); }
 
 enum { CT_LINEARIZE = 0, CT_ERROR = 1, CT_CORR = 2 };
 
@@ -903,7 +551,7 @@ extern "C" {
 int glim_amd_ct_gicp_destroy(glim_amd_ct_gicp_factor* f) {
   if (!f) return GLIM_AMD_OK;
   if (f->ctx) (void)hipSetDevice(f->ctx->device);
-  void* dev[] = {f->d_blocks, f->d_bucket_first, f->d_time_index, f->d_poses, f->d_partials, f->d_rows, f->d_out, f->keep_corr, f->keep_m0, f->keep_m1};
+  void* dev[] = {f->d_blocks, f->d_bucket_first, f->d_time_index, f->d_table, f->d_poses, f->d_partials, f->d_rows, f->d_out, f->keep_corr, f->keep_m0, f->keep_m1};
   for (void* p : dev)
     if (p) (void)pool_free(p);
   if (f->h_poses) (void)pinned_free(f->h_poses);
@@ -967,6 +615,7 @@ int ct_factor_create(glim_amd_ctx* ctx, const glim_amd_nn_index* target, glim_am
   GA_HIP(pool_malloc(&f->d_blocks, nbb * sizeof(int4)));
   GA_HIP(pool_malloc(&f->d_bucket_first, (nk + 1) * sizeof(int)));
   GA_HIP(pool_malloc(&f->d_time_index, nn * sizeof(int)));
+  GA_HIP(pool_malloc(&f->d_table, nk * sizeof(double)));
   GA_HIP(pool_malloc(&f->d_poses, nk * CT_POSE_STRIDE * sizeof(double)));
   GA_HIP(pinned_malloc(&f->h_poses, nk * CT_POSE_STRIDE * sizeof(double)));
   GA_HIP(pool_malloc(&f->d_partials, nbb * PARTIAL_STRIDE * sizeof(float)));
@@ -980,6 +629,7 @@ int ct_factor_create(glim_amd_ctx* ctx, const glim_amd_nn_index* target, glim_am
     GA_HIP(hipMemcpyAsync(f->d_blocks, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, st));
     GA_HIP(hipMemcpyAsync(f->d_bucket_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
     GA_HIP(hipMemcpyAsync(f->d_time_index, f->time_index.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    GA_HIP(hipMemcpyAsync(f->d_table, f->table.data(), (size_t)f->nbk * sizeof(double), hipMemcpyHostToDevice, st));
     GA_HIP(hipStreamSynchronize(st));
     in_flight.dismiss();
   }
@@ -1013,23 +663,7 @@ int glim_amd_ct_gicp_linearize(glim_amd_ct_gicp_factor* f, const double* X12, co
   if (!f || !X12 || !Y12 || !out) return GLIM_AMD_ERR_INVALID;
   double rec[CT_ROW] = {};
   GA_TRY(run_ct(f, X12, Y12, CT_LINEARIZE, rec, nullptr));
-  memset(out, 0, sizeof(*out));
-  out->num_inliers = (int64_t)llround(rec[0]);
-  out->error = rec[1];
-  double H[144];
-  int u = 2;
-  for (int r = 0; r < 12; r++)
-    for (int c = r; c < 12; c++, u++) H[12 * r + c] = H[12 * c + r] = rec[u];
-  for (int r = 0; r < 6; r++)
-    for (int c = 0; c < 6; c++) {
-      out->H_00[6 * r + c] = H[12 * r + c];
-      out->H_01[6 * r + c] = H[12 * r + c + 6];
-      out->H_11[6 * r + c] = H[12 * (r + 6) + c + 6];
-    }
-  for (int r = 0; r < 6; r++) {
-    out->b_0[r] = rec[80 + r];
-    out->b_1[r] = rec[86 + r];
-  }
+  ct_expand_record(rec, out);
   return GLIM_AMD_OK;
 }
 

@@ -679,6 +679,51 @@ int glim_amd_gicp_align_batch_incremental(const glim_amd_ivox* const* targets, c
                                    const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                    glim_amd_align_result* out);
 
+/* ---- CT-GICP frame alignment: the whole per-frame optimisation of GLIM's LiDAR-only continuous-time odometry
+ *      (src/glim/odometry/odometry_estimation_ct.cpp:158-195) in one call with ONE host synchronisation: Levenberg-Marquardt over the two poses
+ *      of the sweep, X (begin) and Y (end), on the graph { IntegratedCT_GICPFactor, PriorFactor<Pose3>(X) "location consistency",
+ *      BetweenFactor<Pose3>(X, Y) "constant velocity" }.  12 DoF, tangent order [X: omega v | Y: omega v], right perturbation; FP64,
+ *      contraction off; one function for host and device: glim_amd/csrc/ct_lm_step.hpp.
+ *   record     the factor's 12 x 12 record (H_f, b_f, e_f, inliers) at a pair is what glim_amd_ct_gicp_linearize computes there, with the bucket
+ *              pose table computed on the device (it agrees with the host's table to 1e-12).  The state the factor keeps for
+ *              glim_amd_ct_gicp_error is not touched.
+ *   location   r_p = Log(P^-1 X), J_p = J_r(r_p)^-1: adds k_p J_p^T J_p to H[X,X], k_p J_p^T r_p to b[X], k_p r_p^T r_p to the cost.
+ *   between    r_b = Log(D^-1 X^-1 Y), J = [-J_r(r_b)^-1 Ad((X^-1 Y)^-1) | J_r(r_b)^-1]: adds k_b J^T J to H, k_b J^T r_b to b, k_b r_b^T r_b to
+ *              the cost.  GLIM passes the identity for D.  A precision of 0 switches a term off.
+ *   cost       "the error at a pair" is (e_f + location cost) + between cost from the LINEARISING evaluation at that pair: a trial is one search.
+ *   solve      (H + lambda I) delta = -b by 12 x 12 Cholesky; a pivot that is not > 0 is a failed solve (the trial is rejected).
+ *   retract    X' = X Exp(delta[0:6]), Y' = Y Exp(delta[6:12]) as in the GICP fine registration; never re-orthonormalised.
+ *   the rest   round 0, accept / reject, the lambda updates, the statuses (GLIM_AMD_ALIGN_*), the budgets and max_trials = 0 are those of the
+ *              GICP fine registration above; glim_amd_lm_params is reused unchanged.
+ * Deterministic: the same inputs return the same bits, in any context of the same device model. */
+typedef struct {
+  double T_location[12];     /* P: the prior on X (row-major 3 x 4); read only when location_precision > 0 */
+  double location_precision; /* k_p >= 0 (GLIM: 1e-3 "location consistency") */
+  double T_between[12];      /* D: the measurement of X^-1 Y; read only when between_precision > 0 */
+  double between_precision;  /* k_b >= 0 (GLIM: 1e3 "constant velocity", D = identity) */
+} glim_amd_ct_align_terms;
+typedef struct {
+  double X[12];                      /* the last kept pair */
+  double Y[12];
+  glim_amd_ct_linearized linearized; /* the factor's record at it: bit for bit the record (X, Y) was evaluated with */
+  double cost;                       /* (linearized.error + location_cost) + between_cost */
+  double location_cost;
+  double between_cost;
+  double lambda;                     /* after the last trial */
+  int32_t iterations;                /* accepted trials */
+  int32_t trials;
+  int32_t status;                    /* GLIM_AMD_ALIGN_* */
+  int32_t reserved;
+} glim_amd_ct_align_result;
+/* the GICP defaults with GLIM's three CT values: lambda_initial 1e-10, absolute_error_tol 1e-2, max_iterations 8 (:176-183) */
+int glim_amd_ct_align_default_params(glim_amd_lm_params* params);
+/* `factor`: a continuous-time factor over either kind of target.  terms NULL = no terms; params NULL = the defaults above.  Nothing is launched
+ * when an argument is refused: GLIM_AMD_ERR_INVALID: a NULL factor, pose or result, a precision that is NaN or < 0, a term that is on with a
+ * pose that is not finite, an empty source or target, the parameter errors of glim_amd_gicp_align_batch; GLIM_AMD_ERR_STATE: a source or target
+ * without covariances; GLIM_AMD_ERR_UNSUPPORTED: the factor's distance beyond the index's ring walk. */
+int glim_amd_ct_align(glim_amd_ct_gicp_factor* factor, const double* X_init12, const double* Y_init12, const glim_amd_ct_align_terms* terms,
+                      const glim_amd_lm_params* params, glim_amd_ct_align_result* out);
+
 #ifdef __cplusplus
 }
 #endif

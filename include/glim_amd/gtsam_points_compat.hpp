@@ -574,6 +574,13 @@ public:
     return PointCloudGPU::adopt(h, ctx);
   }
   const glim_amd_ct_linearized& linearized() const { return linearized_; }
+  glim_amd_ct_gicp_factor* handle() const { return h_; }
+  // the whole frame optimisation on the device (odometry_estimation_ct.cpp:158-195): glim_amd::align_ct of <glim_amd/ct_align.hpp>, which the
+  // caller includes -- align(values, CtAlignTerms, LMParams) -> CtAlignResult
+  template <class Terms, class Params>
+  auto align(const Values& values, const Terms& terms, const Params& params) const {
+    return align_ct(*this, values, terms, params);
+  }
 
 private:
   // where both constructors end: exactly one of `tree` / `ivox` is set (the library's ct_factor_create, mirrored)

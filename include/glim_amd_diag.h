@@ -246,6 +246,23 @@ typedef struct {
 int glim_amd_debug_gicp_align_trace(int32_t ivox, const void* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
                                     const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                     glim_amd_align_result* out, glim_amd_align_trace_entry* trace);
+/* test window of the CT-GICP frame alignment (glim_amd.h): the same call plus one entry per round, trace[r] for r < 1 + max_trials (max_trials
+ * as resolved).  Round 0 is the initial pair; entries are valid for r <= out->trials, the rest are zero. */
+typedef struct {
+  double X[12];       /* the pair the round evaluated */
+  double Y[12];
+  double lambda;      /* the lambda its step was solved with (lambda_initial in round 0) */
+  double record[92];  /* the factor's record there: num_inliers, error, 78 upper entries of the 12 x 12 H (row-major), 12 of b */
+  double cost;        /* the total cost there */
+  int32_t accepted;
+  int32_t status;     /* after the round; 0 = still running */
+} glim_amd_ct_align_trace_entry;
+int glim_amd_debug_ct_align_trace(glim_amd_ct_gicp_factor* factor, const double* X_init12, const double* Y_init12, const glim_amd_ct_align_terms* terms,
+                                  const glim_amd_lm_params* params, glim_amd_ct_align_result* out, glim_amd_ct_align_trace_entry* trace);
+/* the pose table kernel of the CT-GICP frame alignment alone at (X, Y): T_k | D0_k | D1_k as the device computes them, `table_cap` buckets at
+ * most (12 / 36 / 36 doubles each; any output may be NULL).  The host's table is glim_amd_debug_ct_gicp_poses. */
+int glim_amd_debug_ct_align_poses(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t* num_buckets, int32_t table_cap,
+                                  double* T12_out, double* D0_out, double* D1_out);
 
 #ifdef __cplusplus
 }

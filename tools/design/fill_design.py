@@ -123,6 +123,13 @@ vals.update({'IVX_MAP_POINTS':sp(iv['map']['num_points']), 'IVX_MAP_VOXELS':sp(i
              'IVX_LIN27':f(ivf['ivox_mode27']['linearize']['p50_us'],0), 'IVX_LIN_IDX':f(ivf['index']['linearize']['p50_us'],0),
              'IVX_LIN_RATIO':f(iv['mode1_linearize_over_index_linearize'],2), 'IVX_ERR1':f(ivf['ivox_mode1']['error']['p50_us'],0),
              'IVX_FRAME':f(iv['frame_8_iterations_deskew_covariances_insert']['p50_us']/1e3,2)})
+# ---- the CT-GICP frame alignment (tools/ct_align_time.py) ----
+cta=json.load(open('profiles/ct_align/ct_align_time.json'))
+vals.update({'CTA_SRC':sp(cta['source_points']), 'CTA_TGT':sp(cta['target_points'])})
+for tag,key in (('CTA_IX','index'),('CTA_IV','ivox_mode1')):
+    c=cta['targets'][key]
+    vals.update({tag+'_DEV':f(c['device']['p50_us']/1e3,2), tag+'_HOST':f(c['host_loop']['p50_us']/1e3,2), tag+'_ROUNDS':str(c['rounds']),
+                 tag+'_ROUND':f(c['device_per_round_us'],0), tag+'_RATIO':f(c['host_over_device'],2)})
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
