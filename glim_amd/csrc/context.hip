@@ -61,6 +61,7 @@ const DiagKey kDiagKeys[] = {
   {"view_fused", &Diag::view_fused, nullptr, 0, 1},
   {"fuse", &Diag::fuse, nullptr, 0, 1},
   {"host_rotate", &Diag::host_rotate, nullptr, 0, 1},
+  {"fin_pieces", &Diag::fin_pieces, nullptr, 0, 1},
   {"pp_fast", &Diag::pp_fast, nullptr, 0, 1},
   {"resident", &Diag::resident, kResidentWords, 0, 2},
   {"resident_idle_us", &Diag::resident_idle_us, nullptr, 100, 1000000},

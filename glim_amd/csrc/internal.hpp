@@ -139,6 +139,7 @@ struct Diag {
   int pp_fast = 1;        // pp_fast=0|1                        random-grid preprocessing: one sort + counting ranks, one synchronise (preprocess.hip)
   int fuse = 1;           // fuse=0|1                           small synchronous sets: ONE dispatch (factors finalised inside the factor kernel)
   int host_rotate = 1;    // host_rotate=0|1                     small synchronous linearisations (one dispatch / resident session): raw sums come back, the host rotates the record
+  int fin_pieces = 1;     // fin_pieces=0|1                      resident sessions with raw records: ten finalising blocks per factor, one per record piece (0: one block per factor)
   int view_fused = 1;     // view_fused=0|1                      a map built from a plane-form cloud gets its plane view (A_B records) from the finalise kernel; 0: on first use
   int host_pack = 1;      // host_pack=0|1                       small clouds (<= 32 768 pts) are converted to the device layout on the host, one kernel pulls them over
   int frame_fused = 1;    // frame_fused=0|1                     glim_amd_frame_create: one launch pulls the cloud and builds every level, one writes every level's records

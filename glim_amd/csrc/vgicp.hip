@@ -428,6 +428,99 @@ __device__ __forceinline__ void fused_finalize(const FactorDesc& d, int f, const
   finalize_tail(f, fa, mode, s_part, s_sum, s_T, rows_seen_stamp ? rows_seen_stamp + 2 : nullptr);  // (its first barrier orders the s_T stores before the rotation reads them)
 }
 
+// One finalising block PER RECORD PIECE (resident sessions with raw records, switch fin_pieces): block p of a factor's ten owns granule p of every
+// row -- values 3p .. 3p + 2, i.e. raw slots 3p .. 3p + 2 of the record -- and no block talks to another; the host validates the record granule by
+// granule anyway.  Thread r < nb polls ONE granule, one load outstanding at a time: a block that owns all 2 560 granules of a 256-row factor
+// issues 40 wavefront loads of 64 scattered 16-byte lanes per sweep and accepts a batch of 8 only whole, so the record waits for the first full
+// sweep that STARTS after the last row has landed; here a sweep is one load per wavefront (tools/ubench/row_handoff.hip, 256 rows: every granule
+// held 1.14 us after the last publication instead of 1.72; the forms with several staggered loads of a granule in flight were no faster than
+// today's, they have to drain the younger loads).
+// The sum is fused_finalize's + finalize_tail's, addition by addition: thread (g, v), g < 32, v < 3, adds value 3p + v of rows g, g + 32, ...
+// < nb in that order, in FP64 from 0.0; thread v < 3 then adds the 32 group sums in group order from 0.0 and stores raw slot 3p + v.
+// A block that gives up on a row (bounded spin, or the session's end: exit_watch) stores NaN into ITS granules (records_lost).
+// nb <= BLOCK (the launch keeps one finaliser per factor otherwise).  tl (device timeline, piece 0 of the plan's first factor, else null):
+// [0] all rows held (behind the first barrier), [2] = [3] the group sums are added -- fused_finalize's rows_seen_stamp layout.
+__device__ __forceinline__ void piece_finalize(const FactorDesc& d, int f, int p, const FinalizeArgs& fa, double* s_lds, unsigned long long* tl) {
+  const int first = d.first_block, nb = d.num_blocks;
+  float* s_rows = reinterpret_cast<float*>(s_lds);     // [BLOCK][3]: this piece of every row
+  double* s_group = s_lds + (3 * BLOCK * sizeof(float)) / sizeof(double);  // [FIN_GROUPS][3]
+  static_assert((3 * BLOCK * sizeof(float)) / sizeof(double) + 3 * FIN_GROUPS <= (FIN_GROUPS + 1) * PARTIAL_STRIDE, "the piece sums fit the finalisers' LDS object");
+  // (opaque to the optimiser, as in finalize_tail: nothing derived from the thread index is to be held over the session's life)
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(fa.rows16 + (size_t)first * TAG_ROW_BYTES, 0, nb * TAG_ROW_BYTES, 0x00020000);
+  const int seq = (int)fa.seq;
+  const bool mine = t < nb;
+  const int offset = (mine ? t : 0) * TAG_ROW_BYTES + p * 16;
+  bool have = !mine, lost = false;  // (threads past the last row have nothing to wait for)
+  v4i_t val = {0, 0, 0, 0};
+  for (unsigned int spins = 0;; spins++) {
+    if (!have) {
+      const v4i_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, offset, 0, AUX_SC1_VOLATILE);
+      if (v.w == seq) {
+        have = true;
+        val = v;
+      }
+    }
+    if (__all(have)) break;  // (a lane that holds its granule stops loading; its wavefront goes on until every lane does)
+    if (spins > (1u << 20)) {
+      lost = true;
+      break;
+    }
+    if (fa.exit_watch && (spins & 63u) == 63u) {
+      // the session is ending under this request (its leader idled out while the host posted): the rows will not come
+      const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(fa.exit_watch), 0, 16, 0x00020000);
+      const v4i_t w = __builtin_amdgcn_raw_buffer_load_b128(wsrc, 0, 0, AUX_SYSTEM_VOLATILE);
+      if ((unsigned int)w.y == RES_EXIT && (unsigned int)w.w == RES_EXIT) {
+        lost = true;
+        break;
+      }
+    }
+    __builtin_amdgcn_s_sleep(4);
+  }
+  if (mine) {
+    s_rows[3 * t + 0] = __int_as_float(val.x);
+    s_rows[3 * t + 1] = __int_as_float(val.y);
+    s_rows[3 * t + 2] = __int_as_float(val.z);
+  }
+  const bool any_lost = __syncthreads_or(lost ? 1 : 0) != 0;
+  if (tl && t == 0) tl[0] = __builtin_amdgcn_s_memrealtime();
+  if (t < 3 * FIN_GROUPS) {
+    const int g = t / 3, v = t - 3 * g;
+    constexpr int CHAIN = BLOCK / FIN_GROUPS;  // rows of a group
+    float r[CHAIN];
+#pragma unroll
+    for (int u = 0; u < CHAIN; u++) r[u] = s_rows[3 * max(min(g + FIN_GROUPS * u, nb - 1), 0) + v];  // past the end: a valid row, value unused
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < CHAIN; u++)
+      if (g + FIN_GROUPS * u < nb) s += (double)r[u];
+    s_group[t] = s;
+  }
+  __syncthreads();
+  if (t < 3) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < FIN_GROUPS; k++) acc += s_group[3 * k + t];
+    unsigned long long st = 0ull;
+    if (tl) {
+      __builtin_amdgcn_sched_barrier(0);  // (the stamp stays behind the add chain)
+      st = __builtin_amdgcn_s_memrealtime();
+    }
+    const int j = 3 * p + t;  // raw slot j = accumulator j
+    if (j == 29 && fa.trip_stats && acc > 0.0) atomicAdd(&fa.trip_stats[f & 63], (unsigned long long)acc);
+    if (any_lost) acc = __builtin_nan("");
+    if (j < COMPACT) {
+      const long long bits = __double_as_longlong(acc);
+      const v4i_t g = {(int)(bits & 0xffffffffll), (int)(bits >> 32), seq, 0};
+      // system-scope (sc0 sc1) store: written through to host memory now (finalize_tail)
+      const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(fa.rec16 + (size_t)f * COMPACT * 16, 0, COMPACT * 16, 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b128(g, orsrc, j * 16, 0, AUX_SYSTEM);
+    }
+    if (tl && t == 0) tl[2] = tl[3] = st;
+  }
+}
+
 // resident waves per SIMD the register allocation aims for: the plane-form kernel fits 96 VGPRs (5 waves), the general one needs 99 (4 waves)
 #ifndef GLIM_AMD_MINW_PLANE
 #define GLIM_AMD_MINW_PLANE 5
@@ -1048,7 +1141,8 @@ __global__ __launch_bounds__(256) void cull_kernel(const FactorDesc* __restrict_
 // leader -> 512 worker blocks -> 512 granules back -> completion word 3.3 us).  For GLIM's odometry, which linearises the same small factor
 // list again and again (odometry_estimation_gpu.cpp:383-385, once per optimiser iteration).
 //   blocks 0 .. workers-1                 compute plan rows b, b + workers, ... (compute_row) and publish them as tagged granules
-//   blocks workers .. workers + nf - 1    finalise one factor each (fused_finalize: same bits as every other form); block `workers` also LEADS:
+//   blocks workers .. workers + nf - 1    finalise one factor each (fused_finalize: same bits as every other form) -- in a session with raw records
+//                                         ten blocks per factor, one per record piece (piece_finalize, resident_kernel<.., PIECES>); block `workers` also LEADS:
 //                                         it polls the request word in host memory, reads the poses the host left beside it and re-publishes
 //                                         them in device memory as {double, tag} granules -- which is also the "go" signal for everyone else
 // (switch resident_post=direct, the default where the device memory is host-visible and the set is small: the HOST stores those granules itself,
@@ -1150,7 +1244,10 @@ __device__ __forceinline__ void wait_pose(const ResidentArgs& ra, int f, unsigne
 #ifndef GLIM_AMD_RES_MINW
 #define GLIM_AMD_RES_MINW 4
 #endif
-template <bool PLANE_ONLY>
+// PIECES: TAG_PIECES finalising blocks per factor, one per record piece (piece_finalize; switch fin_pieces, sessions with raw records only): block
+// workers + TAG_PIECES f' + p finalises piece p of factor finmap[f'].  A kernel of its own, so that the sessions that keep one finaliser per
+// factor -- the odometry's 34-factor sets -- run the code they ran before, instruction for instruction.
+template <bool PLANE_ONLY, bool PIECES>
 __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void resident_kernel(const ResidentArgs ra) {
   __shared__ double s_lds[(FIN_GROUPS + 1) * PARTIAL_STRIDE];
   __shared__ double s_pose[12];
@@ -1237,7 +1334,9 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       __syncthreads();
     }
     if (finaliser) {
-      const int f = ra.finmap ? ra.finmap[b - ra.workers] : 0;
+      const int fb = b - ra.workers;
+      const int fi = PIECES ? fb / TAG_PIECES : fb, piece = PIECES ? fb - fi * TAG_PIECES : 0;
+      const int f = ra.finmap ? ra.finmap[fi] : 0;
       const bool keeper = leader && ra.direct;  // direct session: the leader block keeps the lifecycle, nothing else
       wait_pose(ra, f, last, (leader && !ra.direct) ? s_tag : 0u, s_pose, &s_tag, keeper ? ra.idle_ticks : 0u);
       const unsigned int tag = s_tag;
@@ -1281,7 +1380,8 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       fa.cull_words = nullptr;
       fa.exit_watch = ra.direct ? ra.pose16 + ((size_t)(b % ra.replicas) * ra.num_factors + f) * 12 * 16 : nullptr;
       const FactorDesc d = ra.descs[f];
-      fused_finalize<8>(d, f, fa, MODE_LINEARIZE, reinterpret_cast<double (*)[PARTIAL_STRIDE]>(s_lds), s_lds + FIN_GROUPS * PARTIAL_STRIDE, s_pose, tlf ? tlf + 3 : nullptr);
+      if (PIECES) piece_finalize(d, f, piece, fa, s_lds, tlf ? tlf + 3 : nullptr);
+      else fused_finalize<8>(d, f, fa, MODE_LINEARIZE, reinterpret_cast<double (*)[PARTIAL_STRIDE]>(s_lds), s_lds + FIN_GROUPS * PARTIAL_STRIDE, s_pose, tlf ? tlf + 3 : nullptr);
       tl_stamp(tlf, 4);
       if (tlf && threadIdx.x == 0) tlf[7] = __builtin_amdgcn_s_memtime() - shader_ticks0;
       __syncthreads();
@@ -2155,15 +2255,23 @@ bool collect_tagged_records(FactorPlan* plan, size_t nf, unsigned int seq, const
   return true;
 }
 
-// the record of a factor whose finalising block gave up on a row (fused_finalize: NaN sums): its count slot is NaN, which no real result is
-bool records_lost(const FactorPlan* plan, size_t nf) {
+// the record of a factor whose finalising block gave up on a row (fused_finalize: NaN sums): its count slot is NaN, which no real result is.
+// every_slot: records that arrived raw -- their pieces may come from ten independent blocks (piece_finalize), each of which gives up on its own
+// and stores NaN into its own slots; a NaN in any raw slot is a NaN in some slot of the rotated record
+bool records_lost(const FactorPlan* plan, size_t nf, bool every_slot = false) {
   for (size_t f = 0; f < nf; f++)
-    if (std::isnan(plan->h_compact[f * COMPACT])) return true;
+    for (int j = 0; j < (every_slot ? COMPACT : 1); j++)
+      if (std::isnan(plan->h_compact[f * COMPACT + j])) return true;
   return false;
 }
 
 // does a synchronous linearisation of nf factors through the single-dispatch / resident form ship raw records?
 bool host_rotate_applies(const Diag& diag, size_t nf) { return diag.host_rotate && nf >= 1 && nf <= (size_t)HOST_ROTATE_MAX_FACTORS; }
+// does a resident session of this plan finalise every factor in TAG_PIECES blocks, one per record piece (piece_finalize)?  Raw records only, and
+// a thread per row: a factor of more than BLOCK rows (there is none in a session: at most one row per compute unit and factor) keeps the one block
+bool fin_pieces_apply(const Diag& diag, const FactorPlan* plan, size_t nf) {
+  return diag.fin_pieces && host_rotate_applies(diag, nf) && plan->max_rows_per_factor <= BLOCK;
+}
 
 // host side of raw records (a producer launched with raw_record): plan->h_compact holds nf raw records after collect_tagged_records; each
 // becomes the compact record the device finalisers would have stored (same bits: device_math.hpp "record math").  T_lin: the call's poses.
@@ -2281,6 +2389,7 @@ struct ResidentSession {
   unsigned int counter = 0, last_tag = 0;
   bool launched = false;
   bool raw_record = false;  // what the running kernel was launched with (ResidentArgs::raw_record)
+  bool fin_pieces = false;  // ... (resident_kernel<.., PIECES>)
   bool direct = false;      // ... (ResidentArgs::direct)
   int replicas = 1, num_factors = 0;  // ... (the layout the host posts into when direct)
   unsigned long long posted_direct = 0, posted_lines = 0;  // requests by the way they were posted (glim_amd_debug_resident_post_stats)
@@ -2434,6 +2543,7 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
   ra.rows16 = plan->d_rows16;
   ra.rec16 = plan->h_rec16_dev;
   ra.raw_record = host_rotate_applies(ctx->diag, (size_t)nf) ? 1 : 0;
+  const bool pieces = fin_pieces_apply(ctx->diag, plan, (size_t)nf);
   ra.pose16 = direct ? S.d_pose16_fine : S.d_pose16;
   ra.direct = direct ? 1 : 0;
   ra.idle_ticks = (unsigned int)std::min<long long>((long long)ctx->diag.resident_idle_us * 100ll, 0x7fffffffll);
@@ -2456,11 +2566,15 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
       S.timeline_workers = ra.workers;
     }
   }
-  if (plan->plane_rows == plan->total_rows) resident_kernel<true><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
-  else resident_kernel<false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
+  const bool plane_only = plan->plane_rows == plan->total_rows;
+  if (pieces && plane_only) resident_kernel<true, true><<<ra.workers + TAG_PIECES * nf, BLOCK, 0, S.stream>>>(ra);
+  else if (pieces) resident_kernel<false, true><<<ra.workers + TAG_PIECES * nf, BLOCK, 0, S.stream>>>(ra);
+  else if (plane_only) resident_kernel<true, false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
+  else resident_kernel<false, false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
   GA_HIP(hipGetLastError());
   S.launched = true;
   S.raw_record = ra.raw_record != 0;
+  S.fin_pieces = pieces;
   S.direct = direct;
   S.replicas = ra.replicas;
   S.num_factors = nf;
@@ -2503,6 +2617,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     }
     // the switch was flipped under a live session: its kernel keeps the form it was launched with, so it is restarted like for any other plan change
     if (S.launched && S.raw_record != host_rotate_applies(diag, nf)) resident_stop(S);
+    if (S.launched && S.fin_pieces != fin_pieces_apply(diag, plan, nf)) resident_stop(S);  // (fin_pieces: likewise)
     if (S.launched && S.direct != resident_direct_applies(S, ctx, nf)) resident_stop(S);  // (resident_post: likewise)
     if (S.launched && reinterpret_cast<volatile unsigned int*>(S.h_mail)[16] == 0u) {
       (void)hipStreamSynchronize(S.stream);  // it has idled out
@@ -2567,7 +2682,7 @@ int run_resident(glim_amd_factor_set* set, const double* T_lin) {
     S.busy.store(false);
   }
   // a finalising block that gave up on a row (bounded spin) publishes NaN under this call's tag: not a result -- the launch-per-call path answers
-  if (records_lost(plan, nf)) return GLIM_AMD_ERR_UNSUPPORTED;
+  if (records_lost(plan, nf, raw)) return GLIM_AMD_ERR_UNSUPPORTED;
   return GLIM_AMD_OK;
 }
 

@@ -24,7 +24,9 @@ extern "C" {
  * view_fused=0|1 (a voxel map built from a plane-form cloud gets its plane view -- the (C_B + I)^-1 records the plane-form factor kernel reads --
  * from the map's own finalise kernel; 0: on the first factor that needs it),
  * fuse=0|1 (small synchronous sets in ONE dispatch), host_rotate=0|1 (linearisations of the smallest such sets, and of a resident session's, return
- * raw sums and the host applies the R^T B R rotation of the record; 0: the device's finalisers do; same bits either way), resident=0|1|auto + resident_idle_us=<n> (repeated synchronous linearisations of a small set
+ * raw sums and the host applies the R^T B R rotation of the record; 0: the device's finalisers do; same bits either way),
+ * fin_pieces=0|1 (a resident session that returns raw sums finalises every factor in ten blocks, one per piece of the record, each thread waiting for
+ * one granule of one row; 0: one block per factor; same bits either way, a live session is restarted when the switch flips), resident=0|1|auto + resident_idle_us=<n> (repeated synchronous linearisations of a small set
  * served by a resident kernel that leaves after <n> us without a request; auto, the default: only in a context created with priority 1 -- the
  * session costs whatever else runs on the device 1.3-1.4x while it is alive, so it is opt-in),
  * resident_post=lines|direct|auto (how a session gets its poses: request lines in host memory that its leader fetches and re-publishes on the device,
