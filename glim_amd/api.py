@@ -786,6 +786,12 @@ class IntegratedVGICPFactorGPU:
             return 0.0
         return self._linearized[1]["num_inliers"] / max(1, self.source.size())
 
+    def align(self, T_init, params=None):
+        """The fine registration of this (unary) factor's pair from T_init (4 x 4 T_target_source): vgicp_align_batch with one problem."""
+        if self.is_binary:
+            raise GlimAmdError(-1, "IntegratedVGICPFactorGPU.align", "a binary factor: the fine registration keeps the target fixed")
+        return vgicp_align_batch([self.target_voxelmap], [self.source], [T_init], self.flags(), params)[0]
+
 
 class NonlinearFactorSetGPU:
     """gtsam_points::NonlinearFactorSetGPU: linearises every added GPU factor in one fused launch."""
@@ -1389,6 +1395,55 @@ def gicp_align_debug_trace(targets, sources, T_init, max_correspondence_distance
             rows.append({"T": Tk, "lam": e.lam, "compact": np.array(e.compact[:]), "accepted": bool(e.accepted), "status": e.status})
         traces.append(rows)
     return results, traces
+
+
+def _vgicp_align_args(targets, sources, T_init):
+    n = len(sources)
+    if len(targets) != n:
+        raise ValueError("one target per source")
+    if len(T_init) != n:
+        raise ValueError("one initial pose per source")
+    T = np.zeros((n, 12))
+    for i, Ti in enumerate(T_init):
+        T[i] = pose12(Ti)
+    th = (C.c_void_p * max(n, 1))(*[t._h for t in targets])
+    sh = (C.c_void_p * max(n, 1))(*[s._h for s in sources])
+    return n, th, sh, T
+
+
+def vgicp_align_batch(targets, sources, T_init, flags=0, params=None):
+    """VGICP fine registration of len(sources) independent problems in one call and one host synchronisation: Levenberg-Marquardt over one unary
+    IntegratedVGICPFactor each (global_mapping_pose_graph.cpp:405-417 with registration_type "VGICP").  targets[i]: GaussianVoxelMapGPU;
+    sources[i]: PointCloudGPU with covariances; T_init[i]: 4 x 4 T_target_source; flags: 0 or FACTOR_SURFACE_VALIDATION, for every problem.
+    Every trial record is what a NonlinearFactorSetGPU of the same pairs returns at the trial's poses.  Returns one AlignResult per problem."""
+    n, th, sh, T = _vgicp_align_args(targets, sources, T_init)
+    prm = (params or LMParams())._c()
+    out = (_lib.AlignResult * max(n, 1))()
+    check(lib().glim_amd_vgicp_align_batch(th, sh, _dp(T), int(flags), n, C.byref(prm), out), "glim_amd_vgicp_align_batch")
+    return [AlignResult(out[i], sources[i].size()) for i in range(n)]
+
+
+def vgicp_align_debug_trace(targets, sources, T_init, flags=0, params=None):
+    """Test window (glim_amd_debug_vgicp_align_trace): vgicp_align_batch's results plus, per problem, the rounds run, as gicp_align_debug_trace."""
+    params = params or LMParams()
+    n, th, sh, T = _vgicp_align_args(targets, sources, T_init)
+    rounds = 1 + params.resolved_max_trials()
+    prm = params._c()
+    out = (_lib.AlignResult * max(n, 1))()
+    trace = (_lib.AlignTraceEntry * max(n * rounds, 1))()
+    check(lib().glim_amd_debug_vgicp_align_trace(th, sh, _dp(T), int(flags), n, C.byref(prm), out, trace), "glim_amd_debug_vgicp_align_trace")
+    results = [AlignResult(out[i], sources[i].size()) for i in range(n)]
+    return results, [_trace_rows(trace, i, rounds, r.trials) for i, r in enumerate(results)]
+
+
+def _trace_rows(trace, i, rounds, trials):
+    rows = []
+    for k in range(min(rounds, trials + 1)):
+        e = trace[i * rounds + k]
+        Tk = np.eye(4)
+        Tk[:3] = np.array(e.T_candidate[:]).reshape(3, 4)
+        rows.append({"T": Tk, "lam": e.lam, "compact": np.array(e.compact[:]), "accepted": bool(e.accepted), "status": e.status})
+    return rows
 
 
 def ct_align_params(**kw):

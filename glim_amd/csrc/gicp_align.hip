@@ -13,6 +13,12 @@
 //   the call        1 + max_trials rounds are enqueued up front, then one copy of the states, then ONE hipStreamSynchronize.  No persistent
 //                   kernel, no grid-wide wait, no host decision in between; every loop in both kernels has a bound known at launch.
 //
+// The VGICP fine registration (include/glim_amd.h "VGICP fine registration") is the same scheme over voxel-map targets.  The factor's hot loop,
+// its plan and its ordered sum live in vgicp.hip and stay there: a round is vgicp_batch_round (vgicp_batch.hpp: vgicp.hip's row kernels and
+// finalising blocks behind the status check, over a transient plan of the batch's pairs, leaving finished compact records on the device) and
+// vgicp_align_decide_kernel here, which runs the step rule on those records and writes each problem's next candidate into the plan's pose
+// buffer.  The step rule is included by this file alone.
+//
 // The CT frame alignment (include/glim_amd.h "CT-GICP frame alignment") is the same scheme over ONE continuous-time factor and two poses: a round
 // is the pose table kernel (T_k | D0_k | D1_k of every bucket from the candidate pair, ct_se3.hpp), the factor's search pass and bucket pass over
 // the blocks and buffers the factor already has (ct_factor.hpp: the bodies glim_amd_ct_gicp_linearize runs), and the CT decide kernel: the
@@ -31,6 +37,7 @@
 #include "ivox_map.hpp"
 #include "lm_step.hpp"
 #include "scope_sync.hpp"
+#include "vgicp_batch.hpp"
 
 using namespace glim_amd;
 
@@ -119,6 +126,32 @@ __global__ __launch_bounds__(256) void align_decide_kernel(const AlignProblem* _
   }
 }
 
+// ---- the VGICP fine registration: the decide step over records vgicp.hip's round left on the device (vgicp_batch.hpp) ----
+// one thread per problem: the step rule on the finished compact record, the state, and the next candidate into the pose buffer the row kernels
+// of the next round read
+constexpr int VGICP_DECIDE_THREADS = 64;
+__global__ __launch_bounds__(VGICP_DECIDE_THREADS) void vgicp_align_decide_kernel(const double* __restrict__ records, double* __restrict__ poses, lm::State* __restrict__ states,
+                                                                                  int count, const lm::Params prm, glim_amd_align_trace_entry* __restrict__ trace, int round,
+                                                                                  int rounds) {
+  const int p = (int)(blockIdx.x * VGICP_DECIDE_THREADS + threadIdx.x);
+  if (p >= count) return;
+  if (states[p].status != lm::RUNNING) return;
+  double rec[COMPACT];
+  for (int t = 0; t < COMPACT; t++) rec[t] = records[(size_t)p * COMPACT + t];
+  lm::State s = states[p];
+  glim_amd_align_trace_entry e;
+  for (int k = 0; k < 12; k++) e.T_candidate[k] = s.cand[k];
+  e.lambda = s.lambda;
+  lm::step(prm, s, rec);
+  states[p] = s;
+  for (int k = 0; k < 12; k++) poses[12 * (size_t)p + k] = s.cand[k];
+  if (trace) {
+    for (int t = 0; t < COMPACT; t++) e.compact[t] = rec[t];
+    e.accepted = s.accepted;
+    e.status = s.status;
+    trace[(size_t)p * rounds + round] = e;
+  }
+}
 
 // ---- the CT frame alignment ----
 static_assert(sizeof(ct_lm::Terms) == sizeof(glim_amd_ct_align_terms), "ct_lm::Terms is the layout of glim_amd_ct_align_terms");
@@ -412,9 +445,101 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
   return GLIM_AMD_OK;
 }
 
+// the batch over voxel-map targets: a round is vgicp.hip's evaluation of the batch's transient plan (vgicp_batch.hpp: the row kernels of both
+// plan segments, one finalising block per problem) and the decide kernel above.  trace: count * (1 + max_trials) entries, or null
+int run_vgicp_align(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12, uint32_t flags, int32_t count,
+                    const glim_amd_lm_params* params, glim_amd_align_result* out, glim_amd_align_trace_entry* trace_host) {
+  if (count < 0) return GLIM_AMD_ERR_INVALID;
+  if (count == 0) return GLIM_AMD_OK;
+  if (!targets || !sources || !T_init12 || !out) return GLIM_AMD_ERR_INVALID;
+  if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: the target is fixed
+  glim_amd_lm_params prm_c;
+  if (params) prm_c = *params;
+  else lm_default_params(&prm_c);
+  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
+  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
+  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
+  for (int i = 0; i < count; i++)
+    if (!targets[i] || !sources[i]) return GLIM_AMD_ERR_INVALID;
+  glim_amd_ctx* ctx = targets[0]->ctx;
+  for (int i = 0; i < count; i++)
+    if ((glim_amd_ctx*)targets[i]->ctx != ctx || (glim_amd_ctx*)sources[i]->ctx != ctx) return GLIM_AMD_ERR_INVALID;
+  for (int i = 0; i < count; i++) {  // what glim_amd_factor_set_add answers for the pair, then the empty source
+    if (!targets[i]->buckets || !sources[i]->has_covs) return GLIM_AMD_ERR_STATE;
+    if (sources[i]->n == 0 || sources[i]->n > (int64_t)(1u << 28)) return GLIM_AMD_ERR_INVALID;
+  }
+  lm::Params prm;
+  memcpy(&prm, &prm_c, sizeof(prm));
+  const int rounds = 1 + prm.max_trials;
+  std::vector<lm::State> states((size_t)count);
+  for (int i = 0; i < count; i++) lm::init(prm, T_init12 + 12 * (size_t)i, states[(size_t)i]);
+
+  std::unique_lock<std::mutex> held(ctx->mu);  // once for the batch
+  GA_HIP(hipSetDevice(ctx->device));
+  VgicpBatch batch;  // (destroyed last: its plan goes back after the stream has been waited for)
+  DeviceTemp d_states, d_trace;
+  GA_TRY(vgicp_batch_open(ctx, targets, sources, flags, count, &batch));
+  hipStream_t st = batch.stream();
+  SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
+  GA_HIP(pool_malloc(&d_states.p, states.size() * sizeof(lm::State)));
+  const size_t trace_bytes = (size_t)count * rounds * sizeof(glim_amd_align_trace_entry);
+  if (trace_host) {
+    GA_HIP(pool_malloc(&d_trace.p, trace_bytes));
+    GA_HIP(hipMemsetAsync(d_trace.p, 0, trace_bytes, st));
+  }
+  GA_HIP(hipMemcpyAsync(d_states.p, states.data(), states.size() * sizeof(lm::State), hipMemcpyHostToDevice, st));
+  GA_HIP(hipMemcpyAsync(batch.poses(), T_init12, (size_t)count * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+  static_assert(sizeof(lm::State) % sizeof(int) == 0 && offsetof(lm::State, status) % sizeof(int) == 0, "the status word of a state, in ints");
+  const int* d_status = reinterpret_cast<const int*>(d_states.as<char>() + offsetof(lm::State, status));
+  const int stride = (int)(sizeof(lm::State) / sizeof(int));
+  const int decide_blocks = (count + VGICP_DECIDE_THREADS - 1) / VGICP_DECIDE_THREADS;
+  for (int r = 0; r < rounds; r++) {
+    GA_TRY(vgicp_batch_round(&batch, d_status, stride));
+    vgicp_align_decide_kernel<<<decide_blocks, VGICP_DECIDE_THREADS, 0, st>>>(batch.records(), batch.poses(), d_states.as<lm::State>(), count, prm,
+                                                                             d_trace.as<glim_amd_align_trace_entry>(), r, rounds);
+  }
+  GA_HIP(hipGetLastError());
+  GA_HIP(hipMemcpyAsync(states.data(), d_states.p, states.size() * sizeof(lm::State), hipMemcpyDeviceToHost, st));
+  if (trace_host) GA_HIP(hipMemcpyAsync(trace_host, d_trace.p, trace_bytes, hipMemcpyDeviceToHost, st));
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  batch.seen_complete();
+  for (int i = 0; i < count; i++) {
+    const lm::State& s = states[(size_t)i];
+    glim_amd_align_result& o = out[i];
+    memset(&o, 0, sizeof(o));
+    memcpy(o.T_target_source, s.T, sizeof(o.T_target_source));
+    memcpy(o.compact, s.rec, sizeof(o.compact));
+    o.error = s.rec[1];
+    o.num_inliers = (int64_t)llround(s.rec[0]);
+    o.iterations = s.iterations;
+    o.trials = s.trials;
+    o.status = s.status;
+    o.lambda = s.lambda;
+  }
+  return GLIM_AMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int glim_amd_vgicp_align_default_params(glim_amd_lm_params* params) {
+  if (!params) return GLIM_AMD_ERR_INVALID;
+  lm_default_params(params);
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_vgicp_align_batch(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12, uint32_t flags,
+                               int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out) {
+  return run_vgicp_align(targets, sources, T_init12, flags, count, params, out, nullptr);
+}
+
+int glim_amd_debug_vgicp_align_trace(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12, uint32_t flags,
+                                     int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out, glim_amd_align_trace_entry* trace) {
+  if (!trace && count > 0) return GLIM_AMD_ERR_INVALID;
+  return run_vgicp_align(targets, sources, T_init12, flags, count, params, out, trace);
+}
 
 int glim_amd_gicp_align_default_params(glim_amd_lm_params* params) {
   if (!params) return GLIM_AMD_ERR_INVALID;

@@ -35,6 +35,7 @@
 #include "internal.hpp"
 #include "pose_granule.hpp"
 #include "record_expand.hpp"
+#include "vgicp_batch.hpp"
 
 using namespace glim_amd;
 
@@ -1445,6 +1446,38 @@ __global__ __launch_bounds__(BLOCK) void finalize_kernel(const FactorDesc* __res
   const int f = blockIdx.x;
   const FactorDesc d = ip.valid ? ip.d : descs[f];
   finalize_factor(d, f, partials, fa, mode, s_part, s_sum, ip.valid ? ip.m : poses_lin + 12 * (size_t)f);
+}
+
+// ---- the rounds of the VGICP fine registration (vgicp_batch.hpp) ----------------------------------------------------------------------
+// vgicp_kernel<MODE_LINEARIZE, false, PLANE, false, false> and finalize_kernel behind a status check: a block of a factor whose status word is
+// not 0 reads the word and returns (the same for every thread of the block); its row and its record are never read.  The bodies are called,
+// not copied: compute_row with the arguments vgicp_kernel gives it, the row stored as there, finalize_factor as finalize_kernel calls it.
+template <bool PLANE>
+__global__ __launch_bounds__(BLOCK, PLANE ? GLIM_AMD_MINW_PLANE : GLIM_AMD_MINW_GENERAL) void vgicp_align_row_kernel(const FactorDesc* __restrict__ descs, const double* __restrict__ poses_lin,
+                                                                                                                      const int2* __restrict__ blockmap, const int* __restrict__ status,
+                                                                                                                      int status_stride, float* __restrict__ partials, int block_offset,
+                                                                                                                      int blocks_per_round) {
+  __shared__ RedRow s_red[4];
+  const int gblock = block_offset + (int)blockIdx.x;
+  const int2 bm = blockmap[gblock];
+  const int f = bm.x;
+  if (f < 0) return;  // padding block of the XCD-aware map
+  if (status[(size_t)f * status_stride] != 0) return;
+  const FactorDesc d = descs[f];
+  const double* Tl = poses_lin + 12 * (size_t)f;
+  compute_row<MODE_LINEARIZE, false, PLANE>(d, Tl, Tl, bm.y, gblock / blocks_per_round, s_red);
+  const size_t row = (size_t)(d.first_block + bm.y);
+  if (threadIdx.x < PARTIAL_STRIDE) partials[row * PARTIAL_STRIDE + threadIdx.x] = row_value<MODE_LINEARIZE>(s_red, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(BLOCK) void vgicp_align_finalize_kernel(const FactorDesc* __restrict__ descs, const float* __restrict__ partials, const FinalizeArgs fa,
+                                                                     const double* __restrict__ poses_lin, const int* __restrict__ status, int status_stride) {
+  __shared__ double s_part[FIN_GROUPS][PARTIAL_STRIDE];
+  __shared__ double s_sum[PARTIAL_STRIDE];
+  const int f = blockIdx.x;
+  if (status[(size_t)f * status_stride] != 0) return;
+  const FactorDesc d = descs[f];
+  finalize_factor(d, f, partials, fa, MODE_LINEARIZE, s_part, s_sum, poses_lin + 12 * (size_t)f);
 }
 
 // Finalisation of a large set of short factors (configs[3]: 32 640 factors of ~8 rows): one WAVEFRONT per factor, four per block, no block
@@ -2945,6 +2978,55 @@ int overlap_blocks(const glim_amd_ctx* ctx, int64_t n, int lanes_shift) {
 }
 
 }  // namespace
+
+// ---- the batch of the VGICP fine registration (vgicp_batch.hpp) ------------------------------------------------------------------------
+namespace glim_amd {
+
+VgicpBatch::~VgicpBatch() {
+  plan_free(plan);  // (waits for the plan's upload when nobody has seen the stream complete; no session ever served this plan)
+  plan = nullptr;
+}
+
+int vgicp_batch_open(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, uint32_t flags, int count, VgicpBatch* b) {
+  b->set.ctx = ctx;
+  b->set.stream = ctx->stream();
+  for (int i = 0; i < count; i++) b->set.entries.push_back({targets[i], sources[i], flags});
+  // the plan of a caller's set of these pairs (plan_build: the same points per thread, the same block map), but nobody's: not looked up in the
+  // context's cache, not counted, not parked -- the caller's own sets and plans and a live resident session never see it
+  FactorPlan* p = new FactorPlan();
+  make_key(&b->set, p->key);
+  const int rc = plan_build(&b->set, p);
+  if (rc != GLIM_AMD_OK) {
+    (void)hipStreamSynchronize(b->set.stream);  // what plan_build enqueued before it failed (memsets, stream copies) still uses the plan's blocks
+    (void)hipGetLastError();
+    plan_free(p);
+    return rc;
+  }
+  b->plan = p;
+  for (const auto& e : b->set.entries) GA_TRY(voxelmap_wait_ready(e.target, b->set.stream));
+  return plan_upload(&b->set, p);  // (a single-factor plan is not uploaded by plan_build: these kernels take no inline arguments)
+}
+
+int vgicp_batch_round(VgicpBatch* b, const int* status, int stride) {
+  const FactorPlan* plan = b->plan;
+  hipStream_t st = b->set.stream;
+  const int nf = (int)b->set.entries.size();
+  const int per_round = std::max(1, b->set.ctx->num_cus);
+  const int rows0 = plan->plane_rows, rows1 = plan->total_rows - plan->plane_rows;
+  if (rows0 > 0)
+    vgicp_align_row_kernel<true><<<rows0, BLOCK, 0, st>>>(plan->d_descs, plan->d_poses, plan->d_blockmap, status, stride, plan->d_partials, 0, per_round);
+  if (rows1 > 0)  // (no pre-cull: a culled trip adds exact zeros, the rows are the same bits)
+    vgicp_align_row_kernel<false><<<rows1, BLOCK, 0, st>>>(plan->d_descs, plan->d_poses, plan->d_blockmap, status, stride, plan->d_partials, rows0, per_round);
+  FinalizeArgs fa;
+  memset(&fa, 0, sizeof(fa));  // device records only: no mirror, no completion word, no granules, no counters
+  fa.out = plan->d_compact;
+  fa.num_factors = nf;
+  vgicp_align_finalize_kernel<<<nf, BLOCK, 0, st>>>(plan->d_descs, plan->d_partials, fa, plan->d_poses, status, stride);
+  GA_HIP(hipGetLastError());
+  return GLIM_AMD_OK;
+}
+
+}  // namespace glim_amd
 
 extern "C" {
 

@@ -679,6 +679,30 @@ int glim_amd_gicp_align_batch_incremental(const glim_amd_ivox* const* targets, c
                                    const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                    glim_amd_align_result* out);
 
+/* ---- VGICP fine registration: the same loop over one unary IntegratedVGICPFactor(Pose3(), 0, target->voxels, source), the loop GLIM runs at
+ *      src/glim/mapping/global_mapping_pose_graph.cpp:405-417 (loop-candidate validation with registration_type "VGICP", LM <= 10, then `error`
+ *      and `inlier_fraction`, many candidates in parallel :429-450) -- as a batch of B independent problems (voxel map, source, initial
+ *      T_target_source) in one call with ONE host synchronisation.  The target is fixed; one voxel map per problem.
+ * The rule is the one written above the glim_amd_lm_params structure (glim_amd/csrc/lm_step.hpp), with "the record at a pose" read as follows:
+ *   record     the compact record of the VGICP factor.  Every trial record is bit for bit what glim_amd_factor_set_linearize returns for a factor
+ *              set that holds the same `count` pairs in the same order with the same flags, evaluated at the trial's poses.  How a factor's points
+ *              are cut into partial rows depends on the whole set, so the promise is "the same set", not "the factor alone": the bits of a
+ *              problem may differ between batches of different composition (by the rounding of an FP32 sum taken in another order).
+ *   flags      0 or GLIM_AMD_FACTOR_SURFACE_VALIDATION, applied to every problem.  GLIM_AMD_FACTOR_BINARY is refused: the target is fixed.
+ *   result     glim_amd_align_result as above: `error` and `num_inliers` are those of the record at the returned pose (inlier_fraction =
+ *              num_inliers / source size), `compact` goes through glim_amd_expand_compact.
+ * Deterministic: the same batch returns the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
+ * resident session of the context are not touched. */
+/* the values of glim_amd_gicp_align_default_params, unchanged */
+int glim_amd_vgicp_align_default_params(glim_amd_lm_params* params);
+/* `count` problems: targets[i], sources[i], T_init12 + 12 i -> out[i].  params NULL = the defaults.  All handles belong to ONE context (a map
+ * may appear in several problems).  count = 0 is OK.  Nothing is launched when an argument is refused:
+ * GLIM_AMD_ERR_INVALID: a NULL argument or handle, count < 0, a flag other than GLIM_AMD_FACTOR_SURFACE_VALIDATION, handles of two contexts,
+ * an empty source, the parameter errors of glim_amd_gicp_align_batch; GLIM_AMD_ERR_STATE: a map nothing was inserted into or a source without
+ * covariances (as glim_amd_factor_set_add). */
+int glim_amd_vgicp_align_batch(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                               uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out);
+
 /* ---- CT-GICP frame alignment: the whole per-frame optimisation of GLIM's LiDAR-only continuous-time odometry
  *      (src/glim/odometry/odometry_estimation_ct.cpp:158-195) in one call with ONE host synchronisation: Levenberg-Marquardt over the two poses
  *      of the sweep, X (begin) and Y (end), on the graph { IntegratedCT_GICPFactor, PriorFactor<Pose3>(X) "location consistency",

@@ -248,6 +248,11 @@ typedef struct {
 int glim_amd_debug_gicp_align_trace(int32_t ivox, const void* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
                                     const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                     glim_amd_align_result* out, glim_amd_align_trace_entry* trace);
+/* test window of the VGICP fine registration (glim_amd.h "VGICP fine registration"): glim_amd_vgicp_align_batch with the same arguments and
+ * results, plus trace[i * (1 + max_trials) + r] as above */
+int glim_amd_debug_vgicp_align_trace(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                                     uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out,
+                                     glim_amd_align_trace_entry* trace);
 /* test window of the CT-GICP frame alignment (glim_amd.h): the same call plus one entry per round, trace[r] for r < 1 + max_trials (max_trials
  * as resolved).  Round 0 is the initial pair; entries are valid for r <= out->trials, the rest are zero. */
 typedef struct {

@@ -130,6 +130,17 @@ for tag,key in (('CTA_IX','index'),('CTA_IV','ivox_mode1')):
     c=cta['targets'][key]
     vals.update({tag+'_DEV':f(c['device']['p50_us']/1e3,2), tag+'_HOST':f(c['host_loop']['p50_us']/1e3,2), tag+'_ROUNDS':str(c['rounds']),
                  tag+'_ROUND':f(c['device_per_round_us'],0), tag+'_RATIO':f(c['host_over_device'],2)})
+# ---- the VGICP fine registration (tools/vgicp_align_time.py) ----
+import os
+vga_path='profiles/vgicp_align/vgicp_align_time.json'
+if os.path.exists(vga_path):
+    vga=json.load(open(vga_path))['shapes']
+    cell=lambda r,k: f"{r[k]['wall_ms_p50']:.2f} ms for {r[k]['rounds']} rounds, {r[k]['factor_evaluations_used']} evaluations used ({r[k]['wall_us_per_round']:.0f} µs per round, {r[k]['wall_us_per_evaluation_used']:.0f} µs per evaluation used)"
+    vals['VGA_MEASURED']=(f"one box, not repeated, the variants alternating in one process (`tools/vgicp_align_time.py`, `profiles/vgicp_align/vgicp_align_time.json`; a {sp(vga[0]['source_points'])}-point source against the map of a {sp(vga[0]['target_points'])}-point scan, the default parameters).  "
+        +'  '.join(f"B = {r['B']}: device batch {cell(r,'device_batch')}; host-driven loop over `linearize_poses` {cell(r,'host_loop')}." for r in vga)
+        +"  The two loops do not run the same number of evaluations (the device enqueues every round up front, the host loop stops with the last problem): the per-round figures are the comparable ones.  No speedup is claimed.")
+else:
+    vals['VGA_MEASURED']="nothing yet.  `tools/vgicp_align_time.py` writes `profiles/vgicp_align/vgicp_align_time.json` (the device batch against the host-driven loop over `NonlinearFactorSetGPU.linearize_poses`, B = 1 / 16, a 12 000-point source against a 131 072-point map, totals and per-evaluation figures, the variants alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
