@@ -211,6 +211,44 @@ class CtAlignTraceEntry(C.Structure):
     ]
 
 
+BUNDLE_MAX_POSES, BUNDLE_MAX_FACTORS, BUNDLE_MAX_TERMS = 32, 1024, 1024  # GLIM_AMD_BUNDLE_MAX_* (include/glim_amd.h)
+
+
+class BundlePrior(C.Structure):
+    """glim_amd_bundle_prior (include/glim_amd.h "Sub-map bundle optimisation")"""
+
+    _fields_ = [("pose", C.c_int32), ("reserved", C.c_int32), ("T", C.c_double * 12), ("information", C.c_double * 36)]
+
+
+class BundleBetween(C.Structure):
+    """glim_amd_bundle_between"""
+
+    _fields_ = [("pose_i", C.c_int32), ("pose_j", C.c_int32), ("T", C.c_double * 12), ("information", C.c_double * 36)]
+
+
+class BundleResult(C.Structure):
+    """glim_amd_bundle_result"""
+
+    _fields_ = [
+        ("cost", C.c_double),
+        ("factor_cost", C.c_double),
+        ("prior_cost", C.c_double),
+        ("between_cost", C.c_double),
+        ("num_inliers", C.c_int64),
+        ("iterations", C.c_int32),
+        ("trials", C.c_int32),
+        ("status", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lam", C.c_double),
+    ]
+
+
+class BundleTraceRound(C.Structure):
+    """glim_amd_bundle_trace_round (include/glim_amd_diag.h)"""
+
+    _fields_ = [("lam", C.c_double), ("cost", C.c_double), ("accepted", C.c_int32), ("status", C.c_int32)]
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -333,6 +371,12 @@ SYMBOLS = {
     "glim_amd_debug_ct_align_trace": (_i, [_vp, _dp, _dp, C.POINTER(CtAlignTerms), C.POINTER(LMParams), C.POINTER(CtAlignResult),
                                            C.POINTER(CtAlignTraceEntry)]),
     "glim_amd_debug_ct_align_poses": (_i, [_vp, _dp, _dp, _ip, _i32, _dp, _dp, _dp]),
+    "glim_amd_bundle_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_bundle_align": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                   C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult)]),
+    "glim_amd_debug_bundle_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                               C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
+                                               C.POINTER(BundleTraceRound)]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -861,6 +861,22 @@ class NonlinearFactorSetGPU:
         self.last_error_inliers = inl
         return list(err)
 
+    def optimize(self, values, priors=(), betweens=(), params=None):
+        """The sub-map bundle optimisation over this set's factors, which must all be binary (bundle_align; the loop of sub_mapping.cpp:430-452
+        with its PriorFactor and BetweenFactor terms).  values: {key: 4 x 4}; priors: (key, P 4 x 4, information 6 x 6); betweens: (key_i, key_j,
+        D 4 x 4, information 6 x 6).  The poses are ordered by sorted key.  Returns ({key: 4 x 4}, BundleResult).  The set itself is untouched."""
+        if any(not f.is_binary for f in self.factors):
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize", "a unary factor: the bundle is over binary factors")
+        validation = {f.enable_surface_validation for f in self.factors}
+        if len(validation) > 1:
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize", "surface validation on some factors only")
+        keys = sorted(values)
+        at = {k: i for i, k in enumerate(keys)}
+        res = bundle_align([(f.target_voxelmap, f.source, at[f.target_key], at[f.source_key]) for f in self.factors],
+                           [(at[k], P, info) for k, P, info in priors], [(at[i], at[j], D, info) for i, j, D, info in betweens],
+                           [values[k] for k in keys], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx)
+        return {k: res.poses[i] for i, k in enumerate(keys)}, res
+
     def correspondences(self, index, delta):
         n = self.factors[index].source.size()
         corr = np.zeros((n, 4), dtype=np.int32)
@@ -1444,6 +1460,99 @@ def _trace_rows(trace, i, rounds, trials):
         Tk[:3] = np.array(e.T_candidate[:]).reshape(3, 4)
         rows.append({"T": Tk, "lam": e.lam, "compact": np.array(e.compact[:]), "accepted": bool(e.accepted), "status": e.status})
     return rows
+
+
+def bundle_align_params(**kw):
+    """LMParams with the sub-mapping bundle's value (glim_amd_bundle_align_default_params): max_iterations 20 (sub_mapping.cpp:431)."""
+    p = dict(max_iterations=20)
+    p.update(kw)
+    return LMParams(**p)
+
+
+class BundleResult:
+    """glim_amd_bundle_align's answer: the last kept poses (N x 4 x 4), the cost there and its three parts, the factors' inliers, the counts,
+    the status (ALIGN_STATUS), the lambda after the last trial and the F compact records at the poses."""
+
+    def __init__(self, c, X, compact):
+        self.poses = X
+        self.cost, self.factor_cost, self.prior_cost, self.between_cost = c.cost, c.factor_cost, c.prior_cost, c.between_cost
+        self.num_inliers = c.num_inliers
+        self.iterations, self.trials, self.status = c.iterations, c.trials, c.status
+        self.status_name = ALIGN_STATUS.get(c.status, "?")
+        self.lam = c.lam
+        self.compact = compact
+
+
+def _poses44(X12):
+    X = np.tile(np.eye(4), (len(X12), 1, 1))
+    X[:, :3, :] = np.asarray(X12).reshape(-1, 3, 4)
+    return X
+
+
+def _bundle_args(factors, priors, betweens, X_init, ctx):
+    """factors: (voxel map, cloud, target pose index, source pose index); priors: (pose index, P 4 x 4, information 6 x 6); betweens: (i, j,
+    D 4 x 4, information 6 x 6) -> the C arrays"""
+    F, P, Q, N = len(factors), len(priors), len(betweens), len(X_init)
+    if ctx is None:
+        ctx = factors[0][0].ctx if F else default_context()
+    th = (C.c_void_p * max(F, 1))(*[f[0]._h for f in factors])
+    sh = (C.c_void_p * max(F, 1))(*[f[1]._h for f in factors])
+    ti = np.ascontiguousarray([f[2] for f in factors], dtype=np.int32).reshape(F)
+    si = np.ascontiguousarray([f[3] for f in factors], dtype=np.int32).reshape(F)
+    cp = (_lib.BundlePrior * max(P, 1))()
+    for c, (k, T, info) in zip(cp, priors):
+        c.pose = int(k)
+        c.T[:] = list(pose12(T))
+        c.information[:] = list(np.asarray(info, dtype=np.float64).reshape(36))
+    cb = (_lib.BundleBetween * max(Q, 1))()
+    for c, (i, j, T, info) in zip(cb, betweens):
+        c.pose_i, c.pose_j = int(i), int(j)
+        c.T[:] = list(pose12(T))
+        c.information[:] = list(np.asarray(info, dtype=np.float64).reshape(36))
+    X = np.zeros((N, 12))
+    for k, Xk in enumerate(X_init):
+        X[k] = pose12(Xk)
+    return ctx, (ctx._h, th, sh, _ip(ti), _ip(si), F), (cp, P, cb, Q, _dp(X), N), (ti, si, X)
+
+
+def bundle_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
+    """The sub-map bundle optimisation in one call and one host synchronisation: Levenberg-Marquardt over len(X_init) poses on binary VGICP
+    factors, prior and between terms (sub_mapping.cpp:183-216, 430-452).  factors: (GaussianVoxelMapGPU, PointCloudGPU, target pose index,
+    source pose index), evaluated at X_t^-1 X_s; priors: (pose index, P 4 x 4, information 6 x 6); betweens: (i, j, D 4 x 4, information 6 x 6);
+    flags: 0 or FACTOR_SURFACE_VALIDATION.  Every trial record is what a NonlinearFactorSetGPU of the same pairs returns at the trial's relative
+    poses.  Returns a BundleResult."""
+    ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
+    F, N = fa[-1], ta[-1]
+    prm = (params or bundle_align_params())._c()
+    X_out, compact, out = np.zeros((N, 12)), np.zeros((F, _lib.COMPACT_DOUBLES)), _lib.BundleResult()
+    check(lib().glim_amd_bundle_align(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out)), "glim_amd_bundle_align")
+    return BundleResult(out, _poses44(X_out), compact)
+
+
+def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True):
+    """Test window (glim_amd_debug_bundle_align_trace): bundle_align's result plus one dict per round run -- round 0 is the initial poses -- with
+    the candidate poses (`X`, N x 4 x 4), the relative poses as the device computed them (`Tf`, F x 12), the `compact` records there (F x 29), the
+    `lam` the step was solved with, the `cost` the evaluation gave, `accepted` and the `status` after the round.  one_thread: the decide step is
+    bundle_lm_step.hpp's step() in one device thread (the cross-check form).  trace=False: the result alone.  Returns (result, rows, the raw
+    trace arrays of all 1 + max_trials rounds: X, Tf, compact, rounds)."""
+    params = params or bundle_align_params()
+    ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
+    F, N = fa[-1], ta[-1]
+    rounds = 1 + params.resolved_max_trials()
+    prm = params._c()
+    X_out, compact, out = np.zeros((N, 12)), np.zeros((F, _lib.COMPACT_DOUBLES)), _lib.BundleResult()
+    tX, tTf, trec = np.zeros((rounds, N, 12)), np.zeros((rounds, F, 12)), np.zeros((rounds, F, _lib.COMPACT_DOUBLES))
+    tr = (_lib.BundleTraceRound * rounds)()
+    targs = (_dp(tX), _dp(tTf), _dp(trec), tr) if trace else (None, None, None, None)
+    check(lib().glim_amd_debug_bundle_align_trace(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), 1 if one_thread else 0, *targs),
+          "glim_amd_debug_bundle_align_trace")
+    res = BundleResult(out, _poses44(X_out), compact)
+    rows = []
+    if trace and N:
+        for k in range(min(rounds, res.trials + 1)):
+            rows.append({"X": _poses44(tX[k]), "Tf": tTf[k].copy(), "compact": trec[k].copy(), "lam": tr[k].lam, "cost": tr[k].cost,
+                         "accepted": bool(tr[k].accepted), "status": tr[k].status})
+    return res, rows, (tX, tTf, trec, tr)
 
 
 def ct_align_params(**kw):

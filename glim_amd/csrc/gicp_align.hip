@@ -23,12 +23,19 @@
 // is the pose table kernel (T_k | D0_k | D1_k of every bucket from the candidate pair, ct_se3.hpp), the factor's search pass and bucket pass over
 // the blocks and buffers the factor already has (ct_factor.hpp: the bodies glim_amd_ct_gicp_linearize runs), and the CT decide kernel: the
 // ordered sum of the bucket rows, the two terms and the step rule of ct_lm_step.hpp.
+//
+// The sub-map bundle optimisation (include/glim_amd.h "Sub-map bundle optimisation") is the same scheme over N poses and F binary VGICP factors:
+// a round is vgicp_batch_round over the F factors at the candidate's relative poses, all behind the problem's one status word, and the bundle
+// decide kernel: one workgroup that expands the records, assembles the dense 6N x 6N system, factorises it in LDS, retracts the poses and
+// writes the next round's relative poses, every value by the item functions of bundle_lm_step.hpp.
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
+#include "bundle_lm_step.hpp"
 #include "ct_factor.hpp"
 #include "ct_lm_step.hpp"
 #include "device_math.hpp"
@@ -237,6 +244,196 @@ __global__ __launch_bounds__(CT_DECIDE_THREADS) void ct_align_decide_kernel(cons
     else if (t == 26) e.accepted = s_state.accepted;
     else if (t == 27) e.status = s_state.status;
     if (t >= 32 && t < 32 + CT_ROW) e.record[t - 32] = s_rec[t - 32];
+  }
+}
+
+// ---- the sub-map bundle optimisation ----
+static_assert(sizeof(glim_amd_linearized6) == 122 * sizeof(double), "a factor's blocks, in doubles");
+static_assert(sizeof(bundle_lm::Scalars) % sizeof(double) == 0 && offsetof(bundle_lm::Scalars, status) % sizeof(int) == 0, "the scalars of a state");
+static_assert(bundle_lm::MAX_POSES == GLIM_AMD_BUNDLE_MAX_POSES && bundle_lm::MAX_FACTORS == GLIM_AMD_BUNDLE_MAX_FACTORS &&
+                  bundle_lm::MAX_TERMS == GLIM_AMD_BUNDLE_MAX_TERMS,
+              "the caps");
+constexpr int BUNDLE_THREADS = 512;
+static_assert(BUNDLE_THREADS > bundle_lm::MAX_DIM, "a thread per row of the solve, the right-hand side included");
+static_assert(2 * bundle_lm::MAX_FACTORS + 2 * bundle_lm::MAX_TERMS <= bundle_lm::MAX_SYSTEM, "the cost sums are staged where the system is assembled afterwards");
+
+struct BundleTrace {  // device arrays of the diag entry, or all null
+  double *X, *Tf, *rec;
+  glim_amd_bundle_trace_round* rounds;
+};
+
+// T_f of the initial poses, where round 0 evaluates the factors
+__global__ __launch_bounds__(256) void bundle_pose_kernel(const bundle_lm::Problem pr) {
+  for (int f = threadIdx.x; f < pr.g.F; f += 256) bundle_lm::relative_pose(pr.cand, pr.g.ft, pr.g.fs, f, pr.Tf);
+}
+
+// One workgroup: bundle_lm::step across the threads.  Every value is produced by the header's item function, one owner per item: a factor's
+// blocks and a term's contribution (a thread each), an entry of the system (a thread each, its sum in the list's order), column j of the
+// Cholesky factor (thread i takes L[i][j]; the thread of row j + 1 goes on to the pivot of column j + 1, so a column costs ONE barrier), the
+// back substitution by columns (thread i keeps s[i] in a register), a pose's retraction, a factor's relative pose.  The system is packed rows in
+// LDS: the rows of a column step start at different offsets mod 64, row j is a broadcast.  one_thread: thread 0 runs step() as it stands.
+__global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(const bundle_lm::Problem pr, const lm::Params prm, const double* __restrict__ recs,
+                                                                       const BundleTrace tr, int round, int one_thread) {
+#pragma clang fp contract(off)
+  using namespace bundle_lm;
+  __shared__ double s_W[MAX_SYSTEM];
+  __shared__ double s_delta[MAX_DIM];
+  __shared__ double s_sums[4];
+  __shared__ Scalars s_sc;
+  __shared__ int s_bad, s_keep, s_fail;
+  if (pr.s->status != lm::RUNNING) return;  // the same for every thread of the block
+  const int t = threadIdx.x;
+  const Graph& g = pr.g;
+  const int N = g.N, F = g.F, n = 6 * N, nsys = system_doubles(n);
+  const double lambda_before = pr.s->lambda;
+  if (tr.rounds) {
+    for (int u = t; u < 12 * N; u += BUNDLE_THREADS) tr.X[(size_t)round * 12 * N + u] = pr.cand[u];
+    for (int u = t; u < 12 * F; u += BUNDLE_THREADS) tr.Tf[(size_t)round * 12 * F + u] = pr.Tf[u];
+    for (int u = t; u < lm::RECORD * F; u += BUNDLE_THREADS) tr.rec[(size_t)round * lm::RECORD * F + u] = recs[u];
+  }
+  auto finish = [&](const Scalars& s) {  // thread 0
+    *pr.s = s;
+    if (tr.rounds) {
+      glim_amd_bundle_trace_round e;
+      e.lambda = lambda_before;
+      e.cost = s.trial_cost;
+      e.accepted = s.accepted;
+      e.status = s.status;
+      tr.rounds[round] = e;
+    }
+  };
+  if (t == 0) {
+    s_sc = *pr.s;
+    s_sc.accepted = 0;
+    s_bad = s_fail = s_keep = 0;
+  }
+  __syncthreads();
+  if (one_thread) {
+    if (t == 0) {
+      Problem q = pr;
+      q.W = s_W;
+      step(prm, q, recs);
+      finish(*pr.s);
+    }
+    return;
+  }
+  bool bad = false;
+  for (int u = t; u < lm::RECORD * F; u += BUNDLE_THREADS) bad = bad || !lm::finite(recs[u]);
+  for (int u = t; u < 12 * N; u += BUNDLE_THREADS) bad = bad || !lm::finite(pr.cand[u]);
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (s_bad) {
+    if (t == 0) {
+      s_sc.status = lm::NUMERIC;
+      finish(s_sc);
+    }
+    return;
+  }
+  for (int w = t; w < F + g.P + g.Q; w += BUNDLE_THREADS) {
+    if (w < F) expand_factor(recs, pr.Tf, w, pr.lin);
+    else if (w < F + g.P) prior_term(g, pr.cand, w - F, pr.pc);
+    else between_term(g, pr.cand, w - F - g.P, pr.bc);
+  }
+  for (int f = t; f < F; f += BUNDLE_THREADS) {
+    s_W[f] = recs[lm::RECORD * f + 1];
+    s_W[F + f] = recs[lm::RECORD * f];
+  }
+  __syncthreads();
+  for (int q = t; q < g.P; q += BUNDLE_THREADS) s_W[2 * F + q] = pr.pc[PRIOR_STRIDE * q + 42];
+  for (int q = t; q < g.Q; q += BUNDLE_THREADS) s_W[2 * F + g.P + q] = pr.bc[BETWEEN_STRIDE * q + 156];
+  __syncthreads();
+  if (t == 0) s_sums[0] = sum_ascending(s_W, F, 1);
+  if (t == 64) s_sums[1] = sum_ascending(s_W + F, F, 1);
+  if (t == 128) s_sums[2] = sum_ascending(s_W + 2 * F, g.P, 1);
+  if (t == 192) s_sums[3] = sum_ascending(s_W + 2 * F + g.P, g.Q, 1);
+  __syncthreads();
+  for (int u = t, r = 0; u < tri(n); u += BUNDLE_THREADS) {
+    while (tri(r + 1) <= u) r++;
+    s_W[u] = assemble_entry(g, pr.lin, pr.pc, pr.bc, r, u - tri(r));
+  }
+  for (int r = t; r < n; r += BUNDLE_THREADS) s_W[tri(n) + r] = assemble_rhs(g, pr.lin, pr.pc, pr.bc, r);
+  __syncthreads();
+  for (int u = t; u < nsys; u += BUNDLE_THREADS) bad = bad || !lm::finite(s_W[u]);
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (t == 0) {
+    const double cost = (s_sums[0] + s_sums[2]) + s_sums[3];
+    if (s_bad || !lm::finite(cost)) {
+      s_sc.status = lm::NUMERIC;
+      s_keep = -1;
+    } else {
+      s_keep = decide(prm, F, s_sc, cost, s_sums[0], s_sums[2], s_sums[3], s_sums[1]) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  const int keep = s_keep;
+  const bool running = s_sc.status == lm::RUNNING;
+  if (keep > 0) {
+    for (int u = t; u < 12 * N; u += BUNDLE_THREADS) pr.X[u] = pr.cand[u];
+    for (int u = t; u < lm::RECORD * F; u += BUNDLE_THREADS) pr.rec[u] = recs[u];
+  }
+  if (keep > 0 || running) {  // the kept system goes out, the solve's matrix comes in; a thread owns the same entries in both
+    const double lambda = s_sc.lambda;
+    for (int u = t, i = 0; u < nsys; u += BUNDLE_THREADS) {
+      while (i < n && tri(i + 1) <= u) i++;
+      if (keep > 0) pr.S[u] = s_W[u];
+      if (running) s_W[u] = solve_load(keep > 0 ? s_W : pr.S, n, lambda, u, i, u - tri(i));
+    }
+  }
+  if (!running) {
+    if (t == 0) finish(s_sc);
+    return;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const double d = chol_pivot(s_W, 0);
+    if (d > 0.0) s_W[0] = d;
+    else s_fail = 1;
+  }
+  __syncthreads();
+  for (int j = 0; j < n; j++) {  // (a failed pivot is left in place: the columns after it are computed and never used)
+    const int i = j + 1 + t;
+    if (i <= n) {
+      s_W[tri(i) + j] = chol_entry(s_W, i, j);
+      if (t == 0 && i < n) {
+        const double d = chol_pivot(s_W, i);
+        if (d > 0.0) s_W[tri(i) + i] = d;
+        else s_fail = 1;
+      }
+    }
+    __syncthreads();
+  }
+  const bool solved = s_fail == 0;
+  if (solved) {
+    double s = t < n ? s_W[tri(n) + t] : 0.0;
+    for (int k = n - 1; k >= 0; k--) {
+      if (t == k) s_delta[k] = s / s_W[tri(k) + k];
+      __syncthreads();
+      if (t < k) s -= s_W[tri(k) + t] * s_delta[k];
+    }
+  } else if (t < n) {
+    s_delta[t] = 0.0;
+  }
+  __syncthreads();
+  if (t < n) pr.delta[t] = s_delta[t];
+  if (t < N) {
+    if (solved) {
+      lm::retract(pr.X + 12 * t, s_delta + 6 * t, pr.cand + 12 * t);
+    } else {
+      for (int i = 0; i < 12; i++) pr.cand[12 * t + i] = pr.X[12 * t + i];
+    }
+  }
+  __syncthreads();
+  bad = false;
+  for (int u = t; u < 12 * N; u += BUNDLE_THREADS) bad = bad || !lm::finite(pr.cand[u]);
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (!s_bad)
+    for (int f = t; f < F; f += BUNDLE_THREADS) relative_pose(pr.cand, g.ft, g.fs, f, pr.Tf);
+  if (t == 0) {
+    s_sc.solve_ok = solved ? 1 : 0;
+    if (s_bad) s_sc.status = lm::NUMERIC;
+    finish(s_sc);
   }
 }
 
@@ -520,9 +717,213 @@ int run_vgicp_align(const glim_amd_voxelmap* const* targets, const glim_amd_clou
   return GLIM_AMD_OK;
 }
 
+void bundle_default_params(glim_amd_lm_params* p) {
+  lm_default_params(p);
+  p->max_iterations = 20;
+}
+
+bool all_finite_host(const double* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+// The sub-map bundle optimisation.  One block of doubles and one of ints hold the graph, the state and the scratch of the problem, laid out
+// the same on host and device; a round is vgicp_batch_round over the F factors, all behind the problem's ONE status word (stride 0), and the
+// bundle decide kernel, which leaves the next round's T_f in the batch's pose buffer.  trace: the four arrays of the diag entry, or all null.
+int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                     const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
+                     int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
+                     glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host) {
+  using namespace bundle_lm;
+  if (N < 0 || F < 0 || P < 0 || Q < 0) return GLIM_AMD_ERR_INVALID;
+  if (N == 0) return GLIM_AMD_OK;
+  if (!ctx || !X_init12 || !X_out12 || !result) return GLIM_AMD_ERR_INVALID;
+  if (F > 0 && (!targets || !sources || !target_pose || !source_pose)) return GLIM_AMD_ERR_INVALID;
+  if ((P > 0 && !priors) || (Q > 0 && !betweens)) return GLIM_AMD_ERR_INVALID;
+  if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;
+  if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: every factor here is binary
+  glim_amd_lm_params prm_c;
+  if (params) prm_c = *params;
+  else bundle_default_params(&prm_c);
+  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
+  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
+  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
+  if (N > MAX_POSES || F > MAX_FACTORS || P > MAX_TERMS || Q > MAX_TERMS) return GLIM_AMD_ERR_UNSUPPORTED;
+  for (int f = 0; f < F; f++) {
+    if (!targets[f] || !sources[f]) return GLIM_AMD_ERR_INVALID;
+    if (target_pose[f] < 0 || target_pose[f] >= N || source_pose[f] < 0 || source_pose[f] >= N || target_pose[f] == source_pose[f]) return GLIM_AMD_ERR_INVALID;
+    if ((glim_amd_ctx*)targets[f]->ctx != ctx || (glim_amd_ctx*)sources[f]->ctx != ctx) return GLIM_AMD_ERR_INVALID;
+  }
+  for (int p = 0; p < P; p++) {
+    if (priors[p].pose < 0 || priors[p].pose >= N) return GLIM_AMD_ERR_INVALID;
+    if (!all_finite_host(priors[p].T, 12) || !all_finite_host(priors[p].information, 36)) return GLIM_AMD_ERR_INVALID;
+  }
+  for (int q = 0; q < Q; q++) {
+    const glim_amd_bundle_between& b = betweens[q];
+    if (b.pose_i < 0 || b.pose_i >= N || b.pose_j < 0 || b.pose_j >= N || b.pose_i == b.pose_j) return GLIM_AMD_ERR_INVALID;
+    if (!all_finite_host(b.T, 12) || !all_finite_host(b.information, 36)) return GLIM_AMD_ERR_INVALID;
+  }
+  if (!all_finite_host(X_init12, 12 * N)) return GLIM_AMD_ERR_INVALID;
+  for (int f = 0; f < F; f++) {  // what glim_amd_factor_set_add answers for the pair, then the empty source
+    if (!targets[f]->buckets || !sources[f]->has_covs) return GLIM_AMD_ERR_STATE;
+    if (sources[f]->n == 0 || sources[f]->n > (int64_t)(1u << 28)) return GLIM_AMD_ERR_INVALID;
+  }
+  lm::Params prm;
+  memcpy(&prm, &prm_c, sizeof(prm));
+  const int rounds = 1 + prm.max_trials;
+
+  // the two blocks: offsets in doubles / ints
+  const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q);
+  size_t at = 0;
+  auto take = [&](size_t count) {
+    const size_t o = at;
+    at += count;
+    return o;
+  };
+  const size_t o_X = take(12 * (size_t)N), o_cand = take(12 * (size_t)N), o_delta = take(n), o_rec = take((size_t)lm::RECORD * F), o_S = take(nsys),
+               o_pT = take(12 * (size_t)P), o_pL = take(36 * (size_t)P), o_bT = take(12 * (size_t)Q), o_bL = take(36 * (size_t)Q),
+               o_scal = take(sizeof(Scalars) / sizeof(double));
+  const size_t upload_doubles = at;  // what the host fills; the scratch below is written before it is read
+  const size_t o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
+  const size_t total_doubles = at;
+  at = 0;
+  const size_t i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_first = take(tri(N) + 1), i_items = take(nlist);
+  const size_t total_ints = at;
+  std::vector<double> hd(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q, 0.0);
+  std::vector<int> hi(total_ints + (size_t)tri(N), 0);  // (the tail: build_lists' cursors)
+  for (int f = 0; f < F; f++) {
+    hi[i_ft + f] = target_pose[f];
+    hi[i_fs + f] = source_pose[f];
+  }
+  for (int p = 0; p < P; p++) {
+    hi[i_pk + p] = priors[p].pose;
+    memcpy(&hd[o_pT + 12 * (size_t)p], priors[p].T, 12 * sizeof(double));
+    memcpy(&hd[o_pL + 36 * (size_t)p], priors[p].information, 36 * sizeof(double));
+  }
+  for (int q = 0; q < Q; q++) {
+    hi[i_bi + q] = betweens[q].pose_i;
+    hi[i_bj + q] = betweens[q].pose_j;
+    memcpy(&hd[o_bT + 12 * (size_t)q], betweens[q].T, 12 * sizeof(double));
+    memcpy(&hd[o_bL + 36 * (size_t)q], betweens[q].information, 36 * sizeof(double));
+  }
+  auto problem_at = [&](double* d, int* i, double* Tf) {
+    Problem pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.g = Graph{N, F, P, Q, i + i_ft, i + i_fs, i + i_pk, d + o_pT, d + o_pL, i + i_bi, i + i_bj, d + o_bT, d + o_bL, i + i_first, i + i_items};
+    pr.X = d + o_X;
+    pr.cand = d + o_cand;
+    pr.delta = d + o_delta;
+    pr.rec = d + o_rec;
+    pr.S = d + o_S;
+    pr.Tf = Tf;
+    pr.lin = reinterpret_cast<glim_amd_linearized6*>(d + o_lin);
+    pr.pc = d + o_pc;
+    pr.bc = d + o_bc;
+    pr.W = nullptr;  // the kernel's LDS
+    pr.s = reinterpret_cast<Scalars*>(d + o_scal);
+    return pr;
+  };
+  {
+    Problem host = problem_at(hd.data(), hi.data(), nullptr);
+    build_lists(host.g, hi.data() + i_first, hi.data() + i_items, hi.data() + total_ints);
+    init(prm, X_init12, host);
+  }
+
+  std::unique_lock<std::mutex> held(ctx->mu);  // once for the call
+  GA_HIP(hipSetDevice(ctx->device));
+  VgicpBatch batch;  // (destroyed last: its plan goes back after the stream has been waited for)
+  DeviceTemp d_d, d_i, d_tX, d_tTf, d_trec, d_trounds;
+  hipStream_t st = ctx->stream();
+  if (F > 0) {
+    GA_TRY(vgicp_batch_open(ctx, targets, sources, flags, F, &batch));
+    st = batch.stream();
+  }
+  SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
+  GA_HIP(pool_malloc(&d_d.p, std::max<size_t>(1, total_doubles) * sizeof(double)));
+  GA_HIP(pool_malloc(&d_i.p, std::max<size_t>(1, total_ints) * sizeof(int)));
+  BundleTrace tr{nullptr, nullptr, nullptr, nullptr};
+  const size_t tX_bytes = (size_t)rounds * 12 * N * sizeof(double), tTf_bytes = (size_t)rounds * 12 * F * sizeof(double),
+               trec_bytes = (size_t)rounds * lm::RECORD * F * sizeof(double), trounds_bytes = (size_t)rounds * sizeof(glim_amd_bundle_trace_round);
+  if (trace_host.rounds) {
+    GA_HIP(pool_malloc(&d_tX.p, tX_bytes));
+    GA_HIP(pool_malloc(&d_tTf.p, std::max<size_t>(8, tTf_bytes)));
+    GA_HIP(pool_malloc(&d_trec.p, std::max<size_t>(8, trec_bytes)));
+    GA_HIP(pool_malloc(&d_trounds.p, trounds_bytes));
+    GA_HIP(hipMemsetAsync(d_tX.p, 0, tX_bytes, st));
+    GA_HIP(hipMemsetAsync(d_tTf.p, 0, std::max<size_t>(8, tTf_bytes), st));
+    GA_HIP(hipMemsetAsync(d_trec.p, 0, std::max<size_t>(8, trec_bytes), st));
+    GA_HIP(hipMemsetAsync(d_trounds.p, 0, trounds_bytes, st));
+    tr = BundleTrace{d_tX.as<double>(), d_tTf.as<double>(), d_trec.as<double>(), d_trounds.as<glim_amd_bundle_trace_round>()};
+  }
+  GA_HIP(hipMemcpyAsync(d_d.p, hd.data(), upload_doubles * sizeof(double), hipMemcpyHostToDevice, st));
+  if (total_ints) GA_HIP(hipMemcpyAsync(d_i.p, hi.data(), total_ints * sizeof(int), hipMemcpyHostToDevice, st));
+  const Problem pr = problem_at(d_d.as<double>(), d_i.as<int>(), F > 0 ? batch.poses() : d_d.as<double>() + o_Tf0);
+  const int* d_status = reinterpret_cast<const int*>(reinterpret_cast<const char*>(pr.s) + offsetof(Scalars, status));
+  const double* d_recs = F > 0 ? batch.records() : pr.rec;
+  if (F > 0) bundle_pose_kernel<<<1, 256, 0, st>>>(pr);
+  for (int r = 0; r < rounds; r++) {
+    if (F > 0) GA_TRY(vgicp_batch_round(&batch, d_status, 0));
+    bundle_decide_kernel<<<1, BUNDLE_THREADS, 0, st>>>(pr, prm, d_recs, tr, r, one_thread);
+  }
+  GA_HIP(hipGetLastError());
+  Scalars sc;
+  std::vector<double> rec_host((size_t)lm::RECORD * F);
+  GA_HIP(hipMemcpyAsync(X_out12, pr.X, 12 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (F > 0) GA_HIP(hipMemcpyAsync(rec_host.data(), pr.rec, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipMemcpyAsync(&sc, pr.s, sizeof(sc), hipMemcpyDeviceToHost, st));
+  if (trace_host.rounds) {
+    GA_HIP(hipMemcpyAsync(trace_host.X, d_tX.p, tX_bytes, hipMemcpyDeviceToHost, st));
+    if (F > 0 && trace_host.Tf) GA_HIP(hipMemcpyAsync(trace_host.Tf, d_tTf.p, tTf_bytes, hipMemcpyDeviceToHost, st));
+    if (F > 0 && trace_host.rec) GA_HIP(hipMemcpyAsync(trace_host.rec, d_trec.p, trec_bytes, hipMemcpyDeviceToHost, st));
+    GA_HIP(hipMemcpyAsync(trace_host.rounds, d_trounds.p, trounds_bytes, hipMemcpyDeviceToHost, st));
+  }
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  if (F > 0) batch.seen_complete();
+  if (compact_out && F > 0) memcpy(compact_out, rec_host.data(), rec_host.size() * sizeof(double));
+  memset(result, 0, sizeof(*result));
+  result->cost = sc.cost;
+  result->factor_cost = sc.fcost;
+  result->prior_cost = sc.pcost;
+  result->between_cost = sc.bcost;
+  result->num_inliers = (int64_t)llround(sc.inliers);
+  result->iterations = sc.iterations;
+  result->trials = sc.trials;
+  result->status = sc.status;
+  result->lambda = sc.lambda;
+  return GLIM_AMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int glim_amd_bundle_align_default_params(glim_amd_lm_params* params) {
+  if (!params) return GLIM_AMD_ERR_INVALID;
+  bundle_default_params(params);
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                          const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                          const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                          const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result) {
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, 0, BundleTrace{nullptr, nullptr, nullptr, nullptr});
+}
+
+int glim_amd_debug_bundle_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                      const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                      const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                      int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                      double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
+                                      double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds) {
+  const bool any = X_trace || Tf_trace || compact_trace || rounds;
+  if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds});
+}
 
 int glim_amd_vgicp_align_default_params(glim_amd_lm_params* params) {
   if (!params) return GLIM_AMD_ERR_INVALID;

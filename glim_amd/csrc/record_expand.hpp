@@ -9,6 +9,13 @@
 
 #include "../../include/glim_amd.h"
 
+// the bundle optimisation's decide kernel (bundle_lm_step.hpp) runs the same statements on the device; on the host nothing changes
+#if defined(__HIPCC__)
+#define GLIM_AMD_EXPAND_HD __host__ __device__
+#else
+#define GLIM_AMD_EXPAND_HD
+#endif
+
 namespace glim_amd {
 
 // The adjoint a binary factor's target blocks go through depends on the pose alone:
@@ -16,7 +23,7 @@ namespace glim_amd {
 // Only its two distinct non-zero blocks are kept: adj[0..8] = R^T, adj[9..17] = -R^T hat(t) (row-major 3x3 each).  The synchronous call
 // computes them while the device works on the request (vgicp.hip glim_amd_factor_set_linearize).
 constexpr int ADJOINT_DOUBLES = 18;
-inline void binary_adjoint(const double* T, double* adj) {
+GLIM_AMD_EXPAND_HD inline void binary_adjoint(const double* T, double* adj) {
 #pragma clang fp contract(off)
   double* Rt = adj;
   for (int r = 0; r < 3; r++)
@@ -35,9 +42,9 @@ inline void binary_adjoint(const double* T, double* adj) {
 // The products H_tt = Ad^T H_ss Ad, H_ts = -Ad^T H_ss, b_t = -Ad^T b_s leave out the terms that multiply the zero block of Ad; the terms that
 // remain are added in the order of the full six-term sums, starting from +0.0 as those do.  A left-out term is +-0 for every finite record, and
 // adding it changes no partial sum (a sum that starts at +0.0 is never -0.0), so the result has the bits of the full products.
-inline void expand_compact_record(const double* c, const double* adj, glim_amd_linearized6* out) {
+GLIM_AMD_EXPAND_HD inline void expand_compact_record(const double* c, const double* adj, glim_amd_linearized6* out) {
 #pragma clang fp contract(off)
-  memset(out, 0, sizeof(*out));
+  __builtin_memset(out, 0, sizeof(*out));  // (the builtin: memset itself is a host function to a device compiler)
   out->num_inliers = (int64_t)llround(c[0]);
   out->error = c[1];
   int k = 2;

@@ -748,6 +748,74 @@ int glim_amd_ct_align_default_params(glim_amd_lm_params* params);
 int glim_amd_ct_align(glim_amd_ct_gicp_factor* factor, const double* X_init12, const double* Y_init12, const glim_amd_ct_align_terms* terms,
                       const glim_amd_lm_params* params, glim_amd_ct_align_result* out);
 
+/* ---- Sub-map bundle optimisation: the Levenberg-Marquardt optimisation of GLIM's sub-mapping bundle (src/glim/mapping/sub_mapping.cpp:183-216,
+ *      276-315, 430-452; the pose-only parts of global_mapping.cpp have the same shape) in one call with ONE host synchronisation: N poses X_k
+ *      over F binary IntegratedVGICPFactorGPU (voxel map, cloud, target pose t, source pose s; evaluated at T_f = X_t^-1 X_s), P
+ *      PriorFactor<Pose3> (:186) and Q BetweenFactor<Pose3> (:210/:212).  6N DoF, tangent order [X_0: omega v | X_1: omega v | ...], right
+ *      perturbation; FP64, contraction off; one definition for host and device: glim_amd/csrc/bundle_lm_step.hpp.
+ *   record     round r evaluates all F factors at the candidate's T_f, which the device computes (inverse and compose of
+ *              glim_amd/csrc/ct_se3.hpp).  Every trial record of factor f is bit for bit what glim_amd_factor_set_linearize returns for a set
+ *              of the same F pairs in the same order with the same flags at those T_f.  flags: 0 or GLIM_AMD_FACTOR_SURFACE_VALIDATION.
+ *   blocks     those of glim_amd_expand_compact with GLIM_AMD_FACTOR_BINARY at T_f, bit for bit: H_ss, b_s go to pose s; H_tt = Ad^T H_ss Ad,
+ *              b_t = -Ad^T b_s to pose t; H_ts (rows of t, columns of s) and its transpose are the off-diagonal blocks.
+ *   terms      prior: r = Log(P^-1 X), J = J_r(r)^-1.  between: r = Log(D^-1 X_i^-1 X_j), J = [-J_r(r)^-1 Ad((X_i^-1 X_j)^-1) | J_r(r)^-1].
+ *              Each adds J^T L J to H, J^T L r to b and r^T L r to the cost; L is the 6 x 6 information, of which only the upper triangle is
+ *              read.
+ *   system     H dense symmetric 6N x 6N.  Every entry of H and b is a sum that starts at +0.0, over the factors by ascending index, then the
+ *              priors, then the betweens.  cost = ((sum_f e_f) + sum priors) + sum betweens, each by ascending index.  "The cost at a
+ *              candidate" comes from the LINEARISING evaluation: a trial is one evaluation.
+ *   solve      (H + lambda I) delta = -b by Cholesky, L[i][j] = (A[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j] with the subtractions one at a
+ *              time in ascending k.  A pivot that is not > 0 or not finite is a failed solve (the trial is rejected).  A pose that no factor
+ *              or term touches is allowed: its block is lambda I and its step is zero.
+ *   retract    X_k' = X_k Exp(delta_k) as in the GICP fine registration; never re-orthonormalised.
+ *   the rest   round 0, accept / reject, the lambda updates, the statuses (GLIM_AMD_ALIGN_*), the budgets and max_trials = 0 are those of the
+ *              GICP fine registration, with "the error" read as the cost and "inliers" as the sum of the factors' inlier counts (with F = 0
+ *              there are none to ask for).  glim_amd_lm_params is reused unchanged.
+ * The system lives in one workgroup's LDS (160 KiB on gfx950), which sets GLIM_AMD_BUNDLE_MAX_POSES; the factors' blocks live in device memory.
+ * Out of scope: IMU graphs (V, B variables, ImuFactor), ISAM2, translating a gtsam::NonlinearFactorGraph, several devices.
+ * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
+ * resident session of the context are not touched. */
+#define GLIM_AMD_BUNDLE_MAX_POSES 32     /* 192 x 192: 149 760 B of packed triangle and right-hand side in LDS */
+#define GLIM_AMD_BUNDLE_MAX_FACTORS 1024 /* every ordered pair of 32 poses is 992 */
+#define GLIM_AMD_BUNDLE_MAX_TERMS 1024   /* priors; and betweens */
+typedef struct {
+  int32_t pose;
+  int32_t reserved;
+  double T[12];            /* P (row-major 3 x 4) */
+  double information[36];  /* row-major 6 x 6, (omega, v) order; the upper triangle is read */
+} glim_amd_bundle_prior;
+typedef struct {
+  int32_t pose_i, pose_j;  /* different */
+  double T[12];            /* D: the measurement of X_i^-1 X_j */
+  double information[36];
+} glim_amd_bundle_between;
+typedef struct {
+  double cost;             /* (factor_cost + prior_cost) + between_cost at the returned poses */
+  double factor_cost;
+  double prior_cost;
+  double between_cost;
+  int64_t num_inliers;     /* the sum over the factors */
+  int32_t iterations;      /* accepted trials */
+  int32_t trials;
+  int32_t status;          /* GLIM_AMD_ALIGN_* */
+  int32_t reserved;
+  double lambda;           /* after the last trial */
+} glim_amd_bundle_result;
+/* the GICP defaults with max_iterations = 20 (sub_mapping.cpp:431) */
+int glim_amd_bundle_align_default_params(glim_amd_lm_params* params);
+/* Factor f: targets[f], sources[f], target_pose[f], source_pose[f].  X_init12: num_poses x 12.  params NULL = the defaults.  X_out12: num_poses x
+ * 12, the last kept poses; compact_out: NULL or num_factors x 29, the records at them (glim_amd_expand_compact gives the blocks).
+ * num_poses = 0 is OK.  num_factors = 0 with at least one term is valid.  Nothing is launched when an argument is refused:
+ * GLIM_AMD_ERR_INVALID: a NULL argument or handle (an array may be NULL when its count is 0), a negative count, nothing to optimise over
+ * (no factor and no term), a pose index out of range, target_pose[f] == source_pose[f], pose_i == pose_j, a handle of another context than
+ * `ctx`, an empty source, GLIM_AMD_FACTOR_BINARY or an unknown bit in `flags`, a pose or an information that is not finite, the parameter errors
+ * of glim_amd_gicp_align_batch; GLIM_AMD_ERR_STATE: a map nothing was inserted into or a source without covariances (as
+ * glim_amd_factor_set_add); GLIM_AMD_ERR_UNSUPPORTED: more poses, factors or terms than the caps above. */
+int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                          const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                          const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                          const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,23 @@ int glim_amd_debug_ct_align_trace(glim_amd_ct_gicp_factor* factor, const double*
  * most (12 / 36 / 36 doubles each; any output may be NULL).  The host's table is glim_amd_debug_ct_gicp_poses. */
 int glim_amd_debug_ct_align_poses(glim_amd_ct_gicp_factor* factor, const double* X12, const double* Y12, int32_t* num_buckets, int32_t table_cap,
                                   double* T12_out, double* D0_out, double* D1_out);
+/* test window of the sub-map bundle optimisation (glim_amd.h): glim_amd_bundle_align with the same arguments and results, plus, per round
+ * r < 1 + max_trials (max_trials as resolved; round 0 is the initial poses; valid for r <= result->trials, the rest are zero):
+ * X_trace[r] (num_poses x 12, the candidate poses the round evaluated), Tf_trace[r] (num_factors x 12, the relative poses as the device computed
+ * them), compact_trace[r] (num_factors x 29, the records there) and rounds[r].  one_thread != 0: the decide step is bundle_lm_step.hpp's step()
+ * run by ONE device thread, the cross-check of the workgroup form (same bits); it is no production path. */
+typedef struct {
+  double lambda;      /* the lambda the round's step was solved with (lambda_initial in round 0) */
+  double cost;        /* the total cost the round's evaluation gave */
+  int32_t accepted;
+  int32_t status;     /* after the round; 0 = still running */
+} glim_amd_bundle_trace_round;
+int glim_amd_debug_bundle_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                      const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                      const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                      int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                      double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
+                                      double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds);
 
 #ifdef __cplusplus
 }

@@ -141,6 +141,19 @@ if os.path.exists(vga_path):
         +"  The two loops do not run the same number of evaluations (the device enqueues every round up front, the host loop stops with the last problem): the per-round figures are the comparable ones.  No speedup is claimed.")
 else:
     vals['VGA_MEASURED']="nothing yet.  `tools/vgicp_align_time.py` writes `profiles/vgicp_align/vgicp_align_time.json` (the device batch against the host-driven loop over `NonlinearFactorSetGPU.linearize_poses`, B = 1 / 16, a 12 000-point source against a 131 072-point map, totals and per-evaluation figures, the variants alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
+# ---- the sub-map bundle optimisation (tools/bundle_align_time.py) ----
+bun_path='profiles/bundle_align/bundle_align_time.json'
+if os.path.exists(bun_path):
+    bun=json.load(open(bun_path))
+    d,h,r=bun['device_loop'],bun['host_iteration'],bun['round_split']
+    vals['BUNDLE_MEASURED']=(f"one box, not repeated, the variants alternating in one process (`tools/bundle_align_time.py`, `{bun_path}`; the configs[2] bundle: {bun['keyframes']} keyframes of {sp(bun['points_per_cloud'])} points, {bun['factors']} factors, a prior on keyframe 0, the default parameters).  "
+        f"Device loop {d['wall_ms_p50']:.2f} ms for {bun['rounds_enqueued']} enqueued rounds of which {d['rounds_that_ran']} ran ({d['status']}, {d['iterations']} iterations): {d['wall_us_per_round_that_ran']:.0f} µs per round that ran.  "
+        f"The host-driven iteration over the same set (synchronous `linearize` + `error`, bench.py's `lm_iteration_ms`) {h['lm_iteration_ms_p50']:.2f} ms, {h['for_the_same_rounds_ms']:.2f} ms for as many rounds, the host's assembly and solve not counted.  "
+        f"With exactly the rounds it needs enqueued the call takes {bun['device_loop_exact_budget']['wall_ms_p50']:.2f} ms, with round 0 alone {bun['device_loop_round_0_only']['wall_ms_p50']:.2f} ms (the fixed part: arguments, the transient plan, uploads), so a trial round costs {r['trial_round_us']:.0f} µs: "
+        f"the 380 factors' evaluation alone {r['factor_round_us_p50']:.0f} µs; the rest (the decide kernel and the launch gaps), by difference, {r['rest_of_a_round_us_by_difference']:.0f} µs.  "
+        "As measured the device round is SLOWER than the host-driven iteration: the one-workgroup decide kernel is about three quarters of a round.  Where its time goes (the serial item lists of the assembly read from device memory, the 120 barriers of the factorisation, the `noinline` SE(3) items) has not been profiled; unrolling the factorisation's dot loops by eight changed nothing measurable.  What the call saves today is the host's assembly and solve and the per-trial round trips, not time on this bundle; no speedup is claimed.")
+else:
+    vals['BUNDLE_MEASURED']="nothing yet.  `tools/bundle_align_time.py` writes `profiles/bundle_align/bundle_align_time.json` (the device loop on the configs[2] bundle against the host-driven iteration over `linearize` and `error` of the same set, and the split of a round between the factor kernels and the decide kernel, the variants alternating in one process); until that file exists every statement about the speed of this path, the one-workgroup FP64 Cholesky included, is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
