@@ -1401,16 +1401,7 @@ def gicp_align_debug_trace(targets, sources, T_init, max_correspondence_distance
         for r in owned:
             r.close()
     results = [AlignResult(out[i], sources[i].size()) for i in range(n)]
-    traces = []
-    for i, r in enumerate(results):
-        rows = []
-        for k in range(min(rounds, r.trials + 1)):
-            e = trace[i * rounds + k]
-            Tk = np.eye(4)
-            Tk[:3] = np.array(e.T_candidate[:]).reshape(3, 4)
-            rows.append({"T": Tk, "lam": e.lam, "compact": np.array(e.compact[:]), "accepted": bool(e.accepted), "status": e.status})
-        traces.append(rows)
-    return results, traces
+    return results, [_trace_rows(trace, i, rounds, r.trials) for i, r in enumerate(results)]
 
 
 def _vgicp_align_args(targets, sources, T_init):

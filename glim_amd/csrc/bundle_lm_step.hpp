@@ -24,9 +24,9 @@
 //              delta[k] = s[k] / L[k][k], then s[i] -= L[k][i] delta[k] for i < k, k descending from 6N - 1.  A pose no factor or term
 //              touches has the block lambda I and a zero step.
 //   retract    X_k' = X_k Exp(delta_k) with lm::retract.  The rotations are re-orthonormalised NEVER.
-//   the rest   round 0, accept / reject, the lambda updates, the statuses and the budgets are lm_step.hpp's, word for word, with "the error" read
-//              as the cost above and "inliers" as the sum of the factors' inlier counts.  A graph WITHOUT factors (F = 0) has no inliers to
-//              ask for: the two inlier conditions hold there.
+//   the rest   round 0, accept / reject, the lambda updates, the statuses and the budgets are lm::decide of lm_step.hpp, CALLED with "the error"
+//              read as the cost above and "inliers" as the sum of the factors' inlier counts.  A graph WITHOUT factors (F = 0) has no inliers
+//              to ask for: the two inlier conditions hold there.  The terms' residuals and Jacobians are ct_se3.hpp's, called too.
 //
 // The caps: the packed system of MAX_POSES poses, SYSTEM(6 MAX_POSES) = 18 720 doubles = 149 760 B, lives in the 160 KiB of LDS one workgroup of
 // a gfx950 CU may declare, beside 14 KiB for the step and the kernel's words.  MAX_FACTORS covers every ordered pair of MAX_POSES poses (992);
@@ -181,31 +181,14 @@ GLIM_AMD_LM_HD inline void term_products(const double* J, int w, const double* L
 }
 
 GLIM_AMD_BUNDLE_ITEM void prior_term(const Graph& g, const double* X, int p, double* pc) {
-  using namespace ct_se3;
-  double Pi[12], E[12], r[6];
-  se3_inverse(g.pT + 12 * p, Pi);
-  se3_compose(Pi, X + 12 * g.pk[p], E);
-  se3_log(E, r);
-  const Mat6 Ji = se3_jr_inv(r);
+  double r[6];
+  const ct_se3::Mat6 Ji = ct_se3::prior_residual(g.pT + 12 * p, X + 12 * g.pk[p], r);
   term_products(Ji.m, 6, g.pL + 36 * p, r, pc + PRIOR_STRIDE * p);
 }
 
 GLIM_AMD_BUNDLE_ITEM void between_term(const Graph& g, const double* X, int q, double* bc) {
-  using namespace ct_se3;
-  double Xi[12], XY[12], Di[12], E[12], YX[12], r[6], J[72];
-  se3_inverse(X + 12 * g.bi[q], Xi);
-  se3_compose(Xi, X + 12 * g.bj[q], XY);
-  se3_inverse(g.bT + 12 * q, Di);
-  se3_compose(Di, XY, E);
-  se3_log(E, r);
-  se3_inverse(XY, YX);
-  const Mat6 Ji = se3_jr_inv(r);
-  const Mat6 JA = mm6(Ji, se3_ad(YX));
-  for (int m = 0; m < 6; m++)
-    for (int c = 0; c < 6; c++) {
-      J[12 * m + c] = -JA.m[6 * m + c];
-      J[12 * m + 6 + c] = Ji.m[6 * m + c];
-    }
+  double r[6], J[72];
+  ct_se3::between_residual(g.bT + 12 * q, X + 12 * g.bi[q], X + 12 * g.bj[q], r, J);
   term_products(J, 12, g.bL + 36 * q, r, bc + BETWEEN_STRIDE * q);
 }
 
@@ -311,46 +294,22 @@ GLIM_AMD_LM_HD inline bool solve(double* W, int n, double* delta) {
   return true;
 }
 
-// the rule's scalar part: the evaluation at the candidate gave (cost, fcost, pcost, bcost, inliers).  true: the candidate is kept
+// the rule's scalar part: lm::decide on the cost, and the bundle's own bookkeeping.  The evaluation at the candidate gave (cost, fcost, pcost,
+// bcost, inliers).  true: the candidate is kept
 GLIM_AMD_LM_HD inline bool decide(const lm::Params& p, int F, Scalars& s, double cost, double fcost, double pcost, double bcost, double inliers) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
   const bool seen = F == 0 || inliers >= 1.0;
-  bool keep = false;
   s.trial_cost = cost;
-  if (!s.started) {
-    s.started = 1;
-    keep = true;
-  } else {
-    s.trials += 1;
-    const double e_cur = s.cost, e_new = cost;
-    if (s.solve_ok && seen && e_new < e_cur) {
-      keep = true;
-      const double l = s.lambda / p.lambda_factor;
-      s.lambda = l > p.lambda_lower_bound ? l : p.lambda_lower_bound;
-      s.iterations += 1;
-      const double d = e_cur - e_new;
-      if (d <= p.absolute_error_tol / p.error_scale || d / e_cur <= p.relative_error_tol) s.status = lm::CONVERGED;
-    } else {
-      s.lambda = s.lambda * p.lambda_factor;
-      if (!(s.lambda <= p.lambda_upper_bound)) s.status = lm::LAMBDA_BOUND;
-    }
-  }
+  const bool keep = lm::decide(p, s.lambda, s.solve_ok, s.started, s.iterations, s.trials, s.status, s.accepted, s.cost, cost, seen);
   if (keep) {
-    s.accepted = 1;
     s.cost = cost;
     s.fcost = fcost;
     s.pcost = pcost;
     s.bcost = bcost;
     s.inliers = inliers;
-    if (!seen) {  // round 0 only: a trial without inliers is never kept
-      s.status = lm::NO_CORRESPONDENCES;
-      return keep;
-    }
   }
-  if (s.status == lm::RUNNING && s.iterations >= p.max_iterations) s.status = lm::MAX_ITERATIONS;
-  if (s.status == lm::RUNNING && s.trials >= p.max_trials) s.status = lm::MAX_TRIALS;
   return keep;
 }
 

@@ -14,7 +14,8 @@
 //   solve        (H + lambda I) delta = -b by 12 x 12 Cholesky.  A pivot that is not > 0 is a FAILED solve; the candidate is then the kept pair
 //                and the trial is rejected.
 //   retract      X' = X Exp(delta[0:6]), Y' = Y Exp(delta[6:12]) with lm::retract.  The rotations are re-orthonormalised NEVER.
-//   the rest     round 0, accept / reject, the lambda updates, the statuses and the budgets are lm_step.hpp's, word for word: see its head.
+//   the rest     round 0, accept / reject, the lambda updates, the statuses and the budgets are lm::decide of lm_step.hpp, CALLED with "the error"
+//                read as that total cost; the solve is lm::solve_dense<12>, the terms' residuals and Jacobians ct_se3.hpp's.  See lm_step.hpp's head.
 #pragma once
 #include "ct_se3.hpp"
 #include "lm_step.hpp"
@@ -56,11 +57,8 @@ GLIM_AMD_LM_HD inline void assemble(const Terms& t, const double* X, const doubl
   cost_p = 0.0;
   cost_b = 0.0;
   if (t.kp > 0.0) {
-    double Pi[12], E[12], r[6];
-    se3_inverse(t.P, Pi);
-    se3_compose(Pi, X, E);
-    se3_log(E, r);
-    const Mat6 Ji = se3_jr_inv(r);
+    double r[6];
+    const Mat6 Ji = prior_residual(t.P, X, r);
     GLIM_AMD_SE3_UNROLL
     for (int i = 0; i < 36; i++) J[i] = Ji.m[i];
     for (int a = 0; a < 6; a++) {
@@ -80,22 +78,8 @@ GLIM_AMD_LM_HD inline void assemble(const Terms& t, const double* X, const doubl
     cost_p = t.kp * rr;
   }
   if (t.kb > 0.0) {
-    double Xi[12], XY[12], Di[12], E[12], YX[12], r[6];
-    se3_inverse(X, Xi);
-    se3_compose(Xi, Y, XY);
-    se3_inverse(t.D, Di);
-    se3_compose(Di, XY, E);
-    se3_log(E, r);
-    se3_inverse(XY, YX);
-    const Mat6 Ji = se3_jr_inv(r);
-    const Mat6 JA = mm6(Ji, se3_ad(YX));
-    GLIM_AMD_SE3_UNROLL
-    for (int m = 0; m < 6; m++)
-      GLIM_AMD_SE3_UNROLL
-      for (int c = 0; c < 6; c++) {
-        J[12 * m + c] = -JA.m[6 * m + c];
-        J[12 * m + 6 + c] = Ji.m[6 * m + c];
-      }
+    double r[6];
+    between_residual(t.D, X, Y, r, J);
     for (int a = 0; a < 12; a++) {
       for (int b = a; b < 12; b++) {
         double s = 0.0;
@@ -117,37 +101,7 @@ GLIM_AMD_LM_HD inline void assemble(const Terms& t, const double* X, const doubl
 
 // (H + lambda I) delta = -b from a system.  L: SOLVE_WORK doubles of workspace.  false: a pivot of the Cholesky factor is not > 0 (delta is then zero)
 GLIM_AMD_LM_HD inline bool solve(const double* sys, double lambda, double* delta, double* L) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  int u = 2;
-  for (int r = 0; r < 12; r++)
-    for (int c = r; c < 12; c++, u++) L[12 * c + r] = sys[u] + (r == c ? lambda : 0.0);  // lower triangle
-  for (int i = 0; i < 12; i++) delta[i] = 0.0;
-  for (int j = 0; j < 12; j++) {
-    double d = L[12 * j + j];
-    for (int k = 0; k < j; k++) d -= L[12 * j + k] * L[12 * j + k];
-    if (!(d > 0.0) || !lm::finite(d)) return false;
-    d = sqrt(d);
-    L[12 * j + j] = d;
-    for (int i = j + 1; i < 12; i++) {
-      double s = L[12 * i + j];
-      for (int k = 0; k < j; k++) s -= L[12 * i + k] * L[12 * j + k];
-      L[12 * i + j] = s / d;
-    }
-  }
-  double* y = L + 144;
-  for (int i = 0; i < 12; i++) {
-    double s = -sys[80 + i];
-    for (int k = 0; k < i; k++) s -= L[12 * i + k] * y[k];
-    y[i] = s / L[12 * i + i];
-  }
-  for (int i = 11; i >= 0; i--) {
-    double s = y[i];
-    for (int k = i + 1; k < 12; k++) s -= L[12 * k + i] * delta[k];
-    delta[i] = s / L[12 * i + i];
-  }
-  return true;
+  return lm::solve_dense<12>(sys + 2, sys + 80, lambda, delta, L);
 }
 
 // the state before round 0: the next evaluation is at the initial pair
@@ -184,44 +138,18 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, const Terms& t, State& s, c
     s.status = lm::NUMERIC;
     return;
   }
-  bool keep = false;
-  if (!s.started) {
-    s.started = 1;
-    keep = true;
-  } else {
-    s.trials += 1;
-    const double e_cur = s.sys[1], e_new = sys[1];
-    if (s.solve_ok && rec[0] >= 1.0 && e_new < e_cur) {
-      keep = true;
-      for (int i = 0; i < 12; i++) {
-        s.X[i] = s.candX[i];
-        s.Y[i] = s.candY[i];
-      }
-      const double l = s.lambda / p.lambda_factor;
-      s.lambda = l > p.lambda_lower_bound ? l : p.lambda_lower_bound;
-      s.iterations += 1;
-      const double d = e_cur - e_new;
-      if (d <= p.absolute_error_tol / p.error_scale || d / e_cur <= p.relative_error_tol) s.status = lm::CONVERGED;
-    } else {
-      s.lambda = s.lambda * p.lambda_factor;
-      if (!(s.lambda <= p.lambda_upper_bound)) s.status = lm::LAMBDA_BOUND;
+  if (lm::decide(p, s.lambda, s.solve_ok, s.started, s.iterations, s.trials, s.status, s.accepted, s.sys[1], sys[1], rec[0] >= 1.0)) {
+    for (int i = 0; i < 12; i++) {  // (round 0: the initial pair onto itself)
+      s.X[i] = s.candX[i];
+      s.Y[i] = s.candY[i];
     }
-  }
-  if (keep) {
-    s.accepted = 1;
     for (int i = 0; i < RECORD; i++) {
       s.rec[i] = rec[i];
       s.sys[i] = sys[i];
     }
     s.cost_p = cp;
     s.cost_b = cb;
-    if (!(rec[0] >= 1.0)) {  // round 0 only: a trial without inliers is never kept
-      s.status = lm::NO_CORRESPONDENCES;
-      return;
-    }
   }
-  if (s.status == lm::RUNNING && s.iterations >= p.max_iterations) s.status = lm::MAX_ITERATIONS;
-  if (s.status == lm::RUNNING && s.trials >= p.max_trials) s.status = lm::MAX_TRIALS;
   if (s.status != lm::RUNNING) return;
   s.solve_ok = solve(s.sys, s.lambda, s.delta, work + RECORD) ? 1 : 0;
   if (s.solve_ok) {

@@ -257,5 +257,34 @@ GLIM_AMD_SE3_HD inline void ct_pose_table(const double* table, size_t n, const d
   for (size_t k = 0; k < n; k++) ct_pose_bucket(X, s, table[k], out + k * CT_POSE_STRIDE);
 }
 
+// ---- the terms of a pose graph (ct_lm_step.hpp, bundle_lm_step.hpp): residual and Jacobian; what is done with them is the caller's ----
+// a prior P on X: r = Log(P^-1 X); returns d r / d X = J_r(r)^-1
+GLIM_AMD_SE3_HD inline Mat6 prior_residual(const double* P, const double* X, double* r) {
+  double Pi[12], E[12];
+  se3_inverse(P, Pi);
+  se3_compose(Pi, X, E);
+  se3_log(E, r);
+  return se3_jr_inv(r);
+}
+// a measurement D of X^-1 Y: r = Log(D^-1 X^-1 Y); J (6 x 12, row-major) = [d r / d X | d r / d Y] = [-J_r(r)^-1 Ad((X^-1 Y)^-1) | J_r(r)^-1]
+GLIM_AMD_SE3_HD inline void between_residual(const double* D, const double* X, const double* Y, double* r, double* J) {
+  double Xi[12], XY[12], Di[12], E[12], YX[12];
+  se3_inverse(X, Xi);
+  se3_compose(Xi, Y, XY);
+  se3_inverse(D, Di);
+  se3_compose(Di, XY, E);
+  se3_log(E, r);
+  se3_inverse(XY, YX);
+  const Mat6 Ji = se3_jr_inv(r);
+  const Mat6 JA = mm6(Ji, se3_ad(YX));
+  GLIM_AMD_SE3_UNROLL
+  for (int m = 0; m < 6; m++)
+    GLIM_AMD_SE3_UNROLL
+    for (int c = 0; c < 6; c++) {
+      J[12 * m + c] = -JA.m[6 * m + c];
+      J[12 * m + 6 + c] = Ji.m[6 * m + c];
+    }
+}
+
 }  // namespace ct_se3
 }  // namespace glim_amd

@@ -108,6 +108,24 @@ __global__ __launch_bounds__(BLOCK) void align_linearize_kernel(const AlignProbl
   store_partial_row(acc, inliers, s_red, partials);
 }
 
+// what the decide kernels of both batches do with a problem's record, in one thread: the step rule on the state, and the round's trace entry
+// when a trace was asked for (`entry`: the problem's entry of this round, or null).  s: the state after the round
+__device__ __forceinline__ void decide_problem(const lm::Params& prm, lm::State* __restrict__ state, lm::State& s, const double* rec,
+                                               glim_amd_align_trace_entry* __restrict__ entry) {
+  s = *state;
+  glim_amd_align_trace_entry e;
+  for (int k = 0; k < 12; k++) e.T_candidate[k] = s.cand[k];
+  e.lambda = s.lambda;
+  lm::step(prm, s, rec);
+  *state = s;
+  if (entry) {
+    for (int t = 0; t < COMPACT; t++) e.compact[t] = rec[t];
+    e.accepted = s.accepted;
+    e.status = s.status;
+    *entry = e;
+  }
+}
+
 // one block of 256 threads per problem: gicp_finalize_kernel's sum of the problem's rows, then the step rule in thread 0
 __global__ __launch_bounds__(256) void align_decide_kernel(const AlignProblem* __restrict__ table, const float* __restrict__ partials, lm::State* __restrict__ states,
                                                            const lm::Params prm, glim_amd_align_trace_entry* __restrict__ trace, int round, int rounds) {
@@ -119,18 +137,8 @@ __global__ __launch_bounds__(256) void align_decide_kernel(const AlignProblem* _
   if (threadIdx.x != 0) return;
   double rec[COMPACT];
   for (int t = 0; t < COMPACT; t++) rec[t] = compact_entry(s_sum, t);
-  lm::State s = states[p];
-  glim_amd_align_trace_entry e;
-  for (int k = 0; k < 12; k++) e.T_candidate[k] = s.cand[k];
-  e.lambda = s.lambda;
-  lm::step(prm, s, rec);
-  states[p] = s;
-  if (trace) {
-    for (int t = 0; t < COMPACT; t++) e.compact[t] = rec[t];
-    e.accepted = s.accepted;
-    e.status = s.status;
-    trace[(size_t)p * rounds + round] = e;
-  }
+  lm::State s;
+  decide_problem(prm, states + p, s, rec, trace ? trace + ((size_t)p * rounds + round) : nullptr);
 }
 
 // ---- the VGICP fine registration: the decide step over records vgicp.hip's round left on the device (vgicp_batch.hpp) ----
@@ -145,19 +153,9 @@ __global__ __launch_bounds__(VGICP_DECIDE_THREADS) void vgicp_align_decide_kerne
   if (states[p].status != lm::RUNNING) return;
   double rec[COMPACT];
   for (int t = 0; t < COMPACT; t++) rec[t] = records[(size_t)p * COMPACT + t];
-  lm::State s = states[p];
-  glim_amd_align_trace_entry e;
-  for (int k = 0; k < 12; k++) e.T_candidate[k] = s.cand[k];
-  e.lambda = s.lambda;
-  lm::step(prm, s, rec);
-  states[p] = s;
+  lm::State s;
+  decide_problem(prm, states + p, s, rec, trace ? trace + ((size_t)p * rounds + round) : nullptr);
   for (int k = 0; k < 12; k++) poses[12 * (size_t)p + k] = s.cand[k];
-  if (trace) {
-    for (int t = 0; t < COMPACT; t++) e.compact[t] = rec[t];
-    e.accepted = s.accepted;
-    e.status = s.status;
-    trace[(size_t)p * rounds + round] = e;
-  }
 }
 
 // ---- the CT frame alignment ----
@@ -465,10 +463,80 @@ void ct_default_params(glim_amd_lm_params* p) {
   p->max_iterations = 8;
 }
 
-bool pose_finite(const double* T) {
-  for (int k = 0; k < 12; k++)
-    if (!std::isfinite(T[k])) return false;
+void bundle_default_params(glim_amd_lm_params* p) {
+  lm_default_params(p);
+  p->max_iterations = 20;
+}
+
+bool all_finite_host(const double* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!std::isfinite(v[k])) return false;
   return true;
+}
+
+// ---- the host scaffold the four run_* functions share ----
+// the caller's parameters, or the loop's defaults, checked and resolved (max_trials 0 = twice max_iterations); rounds = 1 + max_trials
+int resolve_params(const glim_amd_lm_params* params, void (*defaults)(glim_amd_lm_params*), lm::Params* prm, int* rounds) {
+  glim_amd_lm_params c;
+  if (params) c = *params;
+  else defaults(&c);
+  if (!lm_params_ok(c)) return GLIM_AMD_ERR_INVALID;
+  if (c.max_trials == 0) c.max_trials = 2 * c.max_iterations;
+  if (c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
+  memcpy(prm, &c, sizeof(*prm));
+  *rounds = 1 + prm->max_trials;
+  return GLIM_AMD_OK;
+}
+
+// every handle is non-null and of one context: `ctx`, or the first target's when `ctx` is null.  Returns that context, or null
+template <class Handle>
+glim_amd_ctx* one_context(const Handle* const* targets, const glim_amd_cloud* const* sources, int count, glim_amd_ctx* ctx) {
+  for (int i = 0; i < count; i++) {
+    if (!targets[i] || !sources[i]) return nullptr;
+    if (!ctx) ctx = (glim_amd_ctx*)targets[i]->ctx;
+    if ((glim_amd_ctx*)targets[i]->ctx != ctx || (glim_amd_ctx*)sources[i]->ctx != ctx) return nullptr;
+  }
+  return ctx;
+}
+
+// what glim_amd_factor_set_add answers for each (voxel map, source) pair, then the empty source
+int vgicp_pairs_ok(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, int count) {
+  for (int i = 0; i < count; i++) {
+    if (!targets[i]->buckets || !sources[i]->has_covs) return GLIM_AMD_ERR_STATE;
+    if (sources[i]->n == 0 || sources[i]->n > (int64_t)(1u << 28)) return GLIM_AMD_ERR_INVALID;
+  }
+  return GLIM_AMD_OK;
+}
+
+// a trace array: a cleared device buffer while the call runs and the copy back to the caller's, or nothing at all when the caller gave none
+struct TraceBuffer {
+  DeviceTemp d;
+  void* host = nullptr;
+  size_t bytes = 0;
+  int open(void* host_array, size_t nbytes, hipStream_t st) {
+    if (!host_array) return GLIM_AMD_OK;
+    host = host_array;
+    bytes = nbytes;
+    GA_HIP(pool_malloc(&d.p, std::max<size_t>(8, bytes)));
+    GA_HIP(hipMemsetAsync(d.p, 0, std::max<size_t>(8, bytes), st));
+    return GLIM_AMD_OK;
+  }
+  int fetch(hipStream_t st) {
+    if (host && bytes) GA_HIP(hipMemcpyAsync(host, d.p, bytes, hipMemcpyDeviceToHost, st));
+    return GLIM_AMD_OK;
+  }
+};
+
+void align_result(const lm::State& s, glim_amd_align_result* o) {
+  memset(o, 0, sizeof(*o));
+  memcpy(o->T_target_source, s.T, sizeof(o->T_target_source));
+  memcpy(o->compact, s.rec, sizeof(o->compact));
+  o->error = s.rec[1];
+  o->num_inliers = (int64_t)llround(s.rec[0]);
+  o->iterations = s.iterations;
+  o->trials = s.trials;
+  o->status = s.status;
+  o->lambda = s.lambda;
 }
 
 // the launches of one evaluation of the factor at the state's candidate pair
@@ -486,16 +554,10 @@ int run_ct_align(glim_amd_ct_gicp_factor* f, const double* X_init, const double*
   memset(&tm, 0, sizeof(tm));
   if (terms) memcpy(&tm, terms, sizeof(tm));
   if (!(tm.kp >= 0.0) || !(tm.kb >= 0.0) || !std::isfinite(tm.kp) || !std::isfinite(tm.kb)) return GLIM_AMD_ERR_INVALID;
-  if ((tm.kp > 0.0 && !pose_finite(tm.P)) || (tm.kb > 0.0 && !pose_finite(tm.D))) return GLIM_AMD_ERR_INVALID;
-  glim_amd_lm_params prm_c;
-  if (params) prm_c = *params;
-  else ct_default_params(&prm_c);
-  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
-  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
-  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
+  if ((tm.kp > 0.0 && !all_finite_host(tm.P, 12)) || (tm.kb > 0.0 && !all_finite_host(tm.D, 12))) return GLIM_AMD_ERR_INVALID;
   lm::Params prm;
-  memcpy(&prm, &prm_c, sizeof(prm));
-  const int rounds = 1 + prm.max_trials;
+  int rounds;
+  GA_TRY(resolve_params(params, ct_default_params, &prm, &rounds));
 
   const GicpTarget t = ct_target(f);  // holds the context's lock for the whole call
   if (!f->src->has_covs || !t.usable) return GLIM_AMD_ERR_STATE;
@@ -514,22 +576,19 @@ int run_ct_align(glim_amd_ct_gicp_factor* f, const double* X_init, const double*
   glim_amd_ctx* ctx = f->ctx;
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
-  DeviceTemp d_state, d_trace;
+  DeviceTemp d_state;
+  TraceBuffer trace;
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
   GA_HIP(pool_malloc(&d_state.p, sizeof(ct_lm::State)));
-  const size_t trace_bytes = (size_t)rounds * sizeof(glim_amd_ct_align_trace_entry);
-  if (trace_host) {
-    GA_HIP(pool_malloc(&d_trace.p, trace_bytes));
-    GA_HIP(hipMemsetAsync(d_trace.p, 0, trace_bytes, st));
-  }
+  GA_TRY(trace.open(trace_host, (size_t)rounds * sizeof(glim_amd_ct_align_trace_entry), st));
   GA_HIP(hipMemcpyAsync(d_state.p, &state, sizeof(state), hipMemcpyHostToDevice, st));
   for (int r = 0; r < rounds; r++) {
     launch_ct_round(t, f, a, c, d_state.as<ct_lm::State>(), st);
-    ct_align_decide_kernel<<<1, CT_DECIDE_THREADS, 0, st>>>(f->d_rows, f->nbk, d_state.as<ct_lm::State>(), tm, prm, d_trace.as<glim_amd_ct_align_trace_entry>(), r);
+    ct_align_decide_kernel<<<1, CT_DECIDE_THREADS, 0, st>>>(f->d_rows, f->nbk, d_state.as<ct_lm::State>(), tm, prm, trace.d.as<glim_amd_ct_align_trace_entry>(), r);
   }
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(&state, d_state.p, sizeof(state), hipMemcpyDeviceToHost, st));
-  if (trace_host) GA_HIP(hipMemcpyAsync(trace_host, d_trace.p, trace_bytes, hipMemcpyDeviceToHost, st));
+  GA_TRY(trace.fetch(st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
   memset(out, 0, sizeof(*out));
@@ -553,22 +612,13 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
   if (count < 0) return GLIM_AMD_ERR_INVALID;
   if (count == 0) return GLIM_AMD_OK;
   if (!targets || !sources || !T_init12 || !max_dists || !out) return GLIM_AMD_ERR_INVALID;
-  glim_amd_lm_params prm_c;
-  if (params) prm_c = *params;
-  else lm_default_params(&prm_c);
-  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
-  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
-  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
-  for (int i = 0; i < count; i++) {
-    if (!(max_dists[i] >= 0.0) || !targets[i] || !sources[i]) return GLIM_AMD_ERR_INVALID;
-  }
-  glim_amd_ctx* ctx = targets[0]->ctx;
-  for (int i = 0; i < count; i++) {
-    if ((glim_amd_ctx*)targets[i]->ctx != ctx || (glim_amd_ctx*)sources[i]->ctx != ctx) return GLIM_AMD_ERR_INVALID;
-  }
   lm::Params prm;
-  memcpy(&prm, &prm_c, sizeof(prm));
-  const int rounds = 1 + prm.max_trials;
+  int rounds;
+  GA_TRY(resolve_params(params, lm_default_params, &prm, &rounds));
+  for (int i = 0; i < count; i++)
+    if (!(max_dists[i] >= 0.0)) return GLIM_AMD_ERR_INVALID;
+  glim_amd_ctx* ctx = one_context(targets, sources, count, nullptr);
+  if (!ctx) return GLIM_AMD_ERR_INVALID;
 
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the batch: the descriptions below are taken without the lock
   std::vector<AlignProblem> table((size_t)count);
@@ -601,17 +651,14 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
 
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
-  DeviceTemp d_table, d_blocks, d_states, d_partials, d_trace;
+  DeviceTemp d_table, d_blocks, d_states, d_partials;
+  TraceBuffer trace;
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
   GA_HIP(pool_malloc(&d_table.p, table.size() * sizeof(AlignProblem)));
   GA_HIP(pool_malloc(&d_blocks.p, blocks.size() * sizeof(int4)));
   GA_HIP(pool_malloc(&d_states.p, states.size() * sizeof(lm::State)));
   GA_HIP(pool_malloc(&d_partials.p, (size_t)nb * PARTIAL_STRIDE * sizeof(float)));
-  const size_t trace_bytes = (size_t)count * rounds * sizeof(glim_amd_align_trace_entry);
-  if (trace_host) {
-    GA_HIP(pool_malloc(&d_trace.p, trace_bytes));
-    GA_HIP(hipMemsetAsync(d_trace.p, 0, trace_bytes, st));
-  }
+  GA_TRY(trace.open(trace_host, (size_t)count * rounds * sizeof(glim_amd_align_trace_entry), st));
   GA_HIP(hipMemcpyAsync(d_table.p, table.data(), table.size() * sizeof(AlignProblem), hipMemcpyHostToDevice, st));
   GA_HIP(hipMemcpyAsync(d_blocks.p, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, st));
   GA_HIP(hipMemcpyAsync(d_states.p, states.data(), states.size() * sizeof(lm::State), hipMemcpyHostToDevice, st));
@@ -619,26 +666,14 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
     if (ivox) align_linearize_kernel<IvoxSearch><<<nb, BLOCK, 0, st>>>(d_table.as<AlignProblem>(), d_blocks.as<int4>(), d_states.as<lm::State>(), d_partials.as<float>());
     else align_linearize_kernel<IndexSearch><<<nb, BLOCK, 0, st>>>(d_table.as<AlignProblem>(), d_blocks.as<int4>(), d_states.as<lm::State>(), d_partials.as<float>());
     align_decide_kernel<<<count, 256, 0, st>>>(d_table.as<AlignProblem>(), d_partials.as<float>(), d_states.as<lm::State>(), prm,
-                                               d_trace.as<glim_amd_align_trace_entry>(), r, rounds);
+                                               trace.d.as<glim_amd_align_trace_entry>(), r, rounds);
   }
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(states.data(), d_states.p, states.size() * sizeof(lm::State), hipMemcpyDeviceToHost, st));
-  if (trace_host) GA_HIP(hipMemcpyAsync(trace_host, d_trace.p, trace_bytes, hipMemcpyDeviceToHost, st));
+  GA_TRY(trace.fetch(st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
-  for (int i = 0; i < count; i++) {
-    const lm::State& s = states[(size_t)i];
-    glim_amd_align_result& o = out[i];
-    memset(&o, 0, sizeof(o));
-    memcpy(o.T_target_source, s.T, sizeof(o.T_target_source));
-    memcpy(o.compact, s.rec, sizeof(o.compact));
-    o.error = s.rec[1];
-    o.num_inliers = (int64_t)llround(s.rec[0]);
-    o.iterations = s.iterations;
-    o.trials = s.trials;
-    o.status = s.status;
-    o.lambda = s.lambda;
-  }
+  for (int i = 0; i < count; i++) align_result(states[(size_t)i], out + i);
   return GLIM_AMD_OK;
 }
 
@@ -650,40 +685,25 @@ int run_vgicp_align(const glim_amd_voxelmap* const* targets, const glim_amd_clou
   if (count == 0) return GLIM_AMD_OK;
   if (!targets || !sources || !T_init12 || !out) return GLIM_AMD_ERR_INVALID;
   if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: the target is fixed
-  glim_amd_lm_params prm_c;
-  if (params) prm_c = *params;
-  else lm_default_params(&prm_c);
-  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
-  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
-  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
-  for (int i = 0; i < count; i++)
-    if (!targets[i] || !sources[i]) return GLIM_AMD_ERR_INVALID;
-  glim_amd_ctx* ctx = targets[0]->ctx;
-  for (int i = 0; i < count; i++)
-    if ((glim_amd_ctx*)targets[i]->ctx != ctx || (glim_amd_ctx*)sources[i]->ctx != ctx) return GLIM_AMD_ERR_INVALID;
-  for (int i = 0; i < count; i++) {  // what glim_amd_factor_set_add answers for the pair, then the empty source
-    if (!targets[i]->buckets || !sources[i]->has_covs) return GLIM_AMD_ERR_STATE;
-    if (sources[i]->n == 0 || sources[i]->n > (int64_t)(1u << 28)) return GLIM_AMD_ERR_INVALID;
-  }
   lm::Params prm;
-  memcpy(&prm, &prm_c, sizeof(prm));
-  const int rounds = 1 + prm.max_trials;
+  int rounds;
+  GA_TRY(resolve_params(params, lm_default_params, &prm, &rounds));
+  glim_amd_ctx* ctx = one_context(targets, sources, count, nullptr);
+  if (!ctx) return GLIM_AMD_ERR_INVALID;
+  GA_TRY(vgicp_pairs_ok(targets, sources, count));
   std::vector<lm::State> states((size_t)count);
   for (int i = 0; i < count; i++) lm::init(prm, T_init12 + 12 * (size_t)i, states[(size_t)i]);
 
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the batch
   GA_HIP(hipSetDevice(ctx->device));
   VgicpBatch batch;  // (destroyed last: its plan goes back after the stream has been waited for)
-  DeviceTemp d_states, d_trace;
+  DeviceTemp d_states;
+  TraceBuffer trace;
   GA_TRY(vgicp_batch_open(ctx, targets, sources, flags, count, &batch));
   hipStream_t st = batch.stream();
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
   GA_HIP(pool_malloc(&d_states.p, states.size() * sizeof(lm::State)));
-  const size_t trace_bytes = (size_t)count * rounds * sizeof(glim_amd_align_trace_entry);
-  if (trace_host) {
-    GA_HIP(pool_malloc(&d_trace.p, trace_bytes));
-    GA_HIP(hipMemsetAsync(d_trace.p, 0, trace_bytes, st));
-  }
+  GA_TRY(trace.open(trace_host, (size_t)count * rounds * sizeof(glim_amd_align_trace_entry), st));
   GA_HIP(hipMemcpyAsync(d_states.p, states.data(), states.size() * sizeof(lm::State), hipMemcpyHostToDevice, st));
   GA_HIP(hipMemcpyAsync(batch.poses(), T_init12, (size_t)count * 12 * sizeof(double), hipMemcpyHostToDevice, st));
   static_assert(sizeof(lm::State) % sizeof(int) == 0 && offsetof(lm::State, status) % sizeof(int) == 0, "the status word of a state, in ints");
@@ -693,39 +713,16 @@ int run_vgicp_align(const glim_amd_voxelmap* const* targets, const glim_amd_clou
   for (int r = 0; r < rounds; r++) {
     GA_TRY(vgicp_batch_round(&batch, d_status, stride));
     vgicp_align_decide_kernel<<<decide_blocks, VGICP_DECIDE_THREADS, 0, st>>>(batch.records(), batch.poses(), d_states.as<lm::State>(), count, prm,
-                                                                             d_trace.as<glim_amd_align_trace_entry>(), r, rounds);
+                                                                             trace.d.as<glim_amd_align_trace_entry>(), r, rounds);
   }
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(states.data(), d_states.p, states.size() * sizeof(lm::State), hipMemcpyDeviceToHost, st));
-  if (trace_host) GA_HIP(hipMemcpyAsync(trace_host, d_trace.p, trace_bytes, hipMemcpyDeviceToHost, st));
+  GA_TRY(trace.fetch(st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
   batch.seen_complete();
-  for (int i = 0; i < count; i++) {
-    const lm::State& s = states[(size_t)i];
-    glim_amd_align_result& o = out[i];
-    memset(&o, 0, sizeof(o));
-    memcpy(o.T_target_source, s.T, sizeof(o.T_target_source));
-    memcpy(o.compact, s.rec, sizeof(o.compact));
-    o.error = s.rec[1];
-    o.num_inliers = (int64_t)llround(s.rec[0]);
-    o.iterations = s.iterations;
-    o.trials = s.trials;
-    o.status = s.status;
-    o.lambda = s.lambda;
-  }
+  for (int i = 0; i < count; i++) align_result(states[(size_t)i], out + i);
   return GLIM_AMD_OK;
-}
-
-void bundle_default_params(glim_amd_lm_params* p) {
-  lm_default_params(p);
-  p->max_iterations = 20;
-}
-
-bool all_finite_host(const double* v, int n) {
-  for (int k = 0; k < n; k++)
-    if (!std::isfinite(v[k])) return false;
-  return true;
 }
 
 // The sub-map bundle optimisation.  One block of doubles and one of ints hold the graph, the state and the scratch of the problem, laid out
@@ -743,18 +740,13 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   if ((P > 0 && !priors) || (Q > 0 && !betweens)) return GLIM_AMD_ERR_INVALID;
   if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;
   if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: every factor here is binary
-  glim_amd_lm_params prm_c;
-  if (params) prm_c = *params;
-  else bundle_default_params(&prm_c);
-  if (!lm_params_ok(prm_c)) return GLIM_AMD_ERR_INVALID;
-  if (prm_c.max_trials == 0) prm_c.max_trials = 2 * prm_c.max_iterations;
-  if (prm_c.max_trials > ALIGN_MAX_TRIALS) return GLIM_AMD_ERR_INVALID;
+  lm::Params prm;
+  int rounds;
+  GA_TRY(resolve_params(params, bundle_default_params, &prm, &rounds));
   if (N > MAX_POSES || F > MAX_FACTORS || P > MAX_TERMS || Q > MAX_TERMS) return GLIM_AMD_ERR_UNSUPPORTED;
-  for (int f = 0; f < F; f++) {
-    if (!targets[f] || !sources[f]) return GLIM_AMD_ERR_INVALID;
+  if (!one_context(targets, sources, F, ctx)) return GLIM_AMD_ERR_INVALID;
+  for (int f = 0; f < F; f++)
     if (target_pose[f] < 0 || target_pose[f] >= N || source_pose[f] < 0 || source_pose[f] >= N || target_pose[f] == source_pose[f]) return GLIM_AMD_ERR_INVALID;
-    if ((glim_amd_ctx*)targets[f]->ctx != ctx || (glim_amd_ctx*)sources[f]->ctx != ctx) return GLIM_AMD_ERR_INVALID;
-  }
   for (int p = 0; p < P; p++) {
     if (priors[p].pose < 0 || priors[p].pose >= N) return GLIM_AMD_ERR_INVALID;
     if (!all_finite_host(priors[p].T, 12) || !all_finite_host(priors[p].information, 36)) return GLIM_AMD_ERR_INVALID;
@@ -765,13 +757,7 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     if (!all_finite_host(b.T, 12) || !all_finite_host(b.information, 36)) return GLIM_AMD_ERR_INVALID;
   }
   if (!all_finite_host(X_init12, 12 * N)) return GLIM_AMD_ERR_INVALID;
-  for (int f = 0; f < F; f++) {  // what glim_amd_factor_set_add answers for the pair, then the empty source
-    if (!targets[f]->buckets || !sources[f]->has_covs) return GLIM_AMD_ERR_STATE;
-    if (sources[f]->n == 0 || sources[f]->n > (int64_t)(1u << 28)) return GLIM_AMD_ERR_INVALID;
-  }
-  lm::Params prm;
-  memcpy(&prm, &prm_c, sizeof(prm));
-  const int rounds = 1 + prm.max_trials;
+  GA_TRY(vgicp_pairs_ok(targets, sources, F));
 
   // the two blocks: offsets in doubles / ints
   const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q);
@@ -833,7 +819,8 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the call
   GA_HIP(hipSetDevice(ctx->device));
   VgicpBatch batch;  // (destroyed last: its plan goes back after the stream has been waited for)
-  DeviceTemp d_d, d_i, d_tX, d_tTf, d_trec, d_trounds;
+  DeviceTemp d_d, d_i;
+  TraceBuffer tX, tTf, trec, trounds;
   hipStream_t st = ctx->stream();
   if (F > 0) {
     GA_TRY(vgicp_batch_open(ctx, targets, sources, flags, F, &batch));
@@ -842,20 +829,13 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
   GA_HIP(pool_malloc(&d_d.p, std::max<size_t>(1, total_doubles) * sizeof(double)));
   GA_HIP(pool_malloc(&d_i.p, std::max<size_t>(1, total_ints) * sizeof(int)));
-  BundleTrace tr{nullptr, nullptr, nullptr, nullptr};
-  const size_t tX_bytes = (size_t)rounds * 12 * N * sizeof(double), tTf_bytes = (size_t)rounds * 12 * F * sizeof(double),
-               trec_bytes = (size_t)rounds * lm::RECORD * F * sizeof(double), trounds_bytes = (size_t)rounds * sizeof(glim_amd_bundle_trace_round);
-  if (trace_host.rounds) {
-    GA_HIP(pool_malloc(&d_tX.p, tX_bytes));
-    GA_HIP(pool_malloc(&d_tTf.p, std::max<size_t>(8, tTf_bytes)));
-    GA_HIP(pool_malloc(&d_trec.p, std::max<size_t>(8, trec_bytes)));
-    GA_HIP(pool_malloc(&d_trounds.p, trounds_bytes));
-    GA_HIP(hipMemsetAsync(d_tX.p, 0, tX_bytes, st));
-    GA_HIP(hipMemsetAsync(d_tTf.p, 0, std::max<size_t>(8, tTf_bytes), st));
-    GA_HIP(hipMemsetAsync(d_trec.p, 0, std::max<size_t>(8, trec_bytes), st));
-    GA_HIP(hipMemsetAsync(d_trounds.p, 0, trounds_bytes, st));
-    tr = BundleTrace{d_tX.as<double>(), d_tTf.as<double>(), d_trec.as<double>(), d_trounds.as<glim_amd_bundle_trace_round>()};
+  if (trace_host.rounds) {  // (the entry point has seen to it that the arrays the graph needs come together)
+    GA_TRY(tX.open(trace_host.X, (size_t)rounds * 12 * N * sizeof(double), st));
+    GA_TRY(tTf.open(trace_host.Tf, (size_t)rounds * 12 * F * sizeof(double), st));
+    GA_TRY(trec.open(trace_host.rec, (size_t)rounds * lm::RECORD * F * sizeof(double), st));
+    GA_TRY(trounds.open(trace_host.rounds, (size_t)rounds * sizeof(glim_amd_bundle_trace_round), st));
   }
+  const BundleTrace tr{tX.d.as<double>(), tTf.d.as<double>(), trec.d.as<double>(), trounds.d.as<glim_amd_bundle_trace_round>()};
   GA_HIP(hipMemcpyAsync(d_d.p, hd.data(), upload_doubles * sizeof(double), hipMemcpyHostToDevice, st));
   if (total_ints) GA_HIP(hipMemcpyAsync(d_i.p, hi.data(), total_ints * sizeof(int), hipMemcpyHostToDevice, st));
   const Problem pr = problem_at(d_d.as<double>(), d_i.as<int>(), F > 0 ? batch.poses() : d_d.as<double>() + o_Tf0);
@@ -872,12 +852,10 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   GA_HIP(hipMemcpyAsync(X_out12, pr.X, 12 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
   if (F > 0) GA_HIP(hipMemcpyAsync(rec_host.data(), pr.rec, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   GA_HIP(hipMemcpyAsync(&sc, pr.s, sizeof(sc), hipMemcpyDeviceToHost, st));
-  if (trace_host.rounds) {
-    GA_HIP(hipMemcpyAsync(trace_host.X, d_tX.p, tX_bytes, hipMemcpyDeviceToHost, st));
-    if (F > 0 && trace_host.Tf) GA_HIP(hipMemcpyAsync(trace_host.Tf, d_tTf.p, tTf_bytes, hipMemcpyDeviceToHost, st));
-    if (F > 0 && trace_host.rec) GA_HIP(hipMemcpyAsync(trace_host.rec, d_trec.p, trec_bytes, hipMemcpyDeviceToHost, st));
-    GA_HIP(hipMemcpyAsync(trace_host.rounds, d_trounds.p, trounds_bytes, hipMemcpyDeviceToHost, st));
-  }
+  GA_TRY(tX.fetch(st));
+  GA_TRY(tTf.fetch(st));  // (nothing without factors: no bytes)
+  GA_TRY(trec.fetch(st));
+  GA_TRY(trounds.fetch(st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
   if (F > 0) batch.seen_complete();

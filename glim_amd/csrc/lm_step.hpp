@@ -1,6 +1,7 @@
 // lm_step.hpp -- the step rule of the on-device GICP fine registration (include/glim_amd.h "GICP fine registration"): ONE function, host and
 // device.  gicp_align.hip's decide kernel calls it once per round and problem; tests/cpp/test_lm_step.cpp compiles it with a plain C++ compiler
-// and runs the same statements on the CPU.  The header includes nothing of the project.
+// and runs the same statements on the CPU.  The header includes nothing of the project.  The rule's scalar part (decide) and the dense solve
+// (solve_dense<N>) are also what the CT loop (ct_lm_step.hpp) and the sub-map bundle (bundle_lm_step.hpp) call: they exist here, once.
 //
 // Everything is FP64 with contraction off.  The rule is upstream RECALL of GTSAM's LevenbergMarquardtOptimizer in fixed-lambda-factor mode
 // (diagonalDamping off), which gtsam_points' LevenbergMarquardtOptimizerExt follows; GTSAM is not in the reference tree.
@@ -61,40 +62,47 @@ GLIM_AMD_LM_HD inline bool all_finite(const double* v, int n) {
   return ok;
 }
 
-// (H + lambda I) delta = -b from a record.  false: a pivot of the Cholesky factor is not > 0 (delta is then zero)
-GLIM_AMD_LM_HD inline bool solve(const double* rec, double lambda, double* delta) {
+// (H + lambda I) delta = -b, H symmetric N x N given as its upper triangle in row-major order.  L: N * N + N doubles of workspace (the Cholesky
+// factor, then the forward substitution).  false: a pivot of the factor is not > 0 (delta is then zero)
+template <int N>
+GLIM_AMD_LM_HD inline bool solve_dense(const double* upper, const double* b, double lambda, double* delta, double* L) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  double L[36];
-  int u = 2;
-  for (int r = 0; r < 6; r++)
-    for (int c = r; c < 6; c++, u++) L[6 * c + r] = rec[u] + (r == c ? lambda : 0.0);  // lower triangle
-  for (int i = 0; i < 6; i++) delta[i] = 0.0;
-  for (int j = 0; j < 6; j++) {
-    double d = L[6 * j + j];
-    for (int k = 0; k < j; k++) d -= L[6 * j + k] * L[6 * j + k];
+  int u = 0;
+  for (int r = 0; r < N; r++)
+    for (int c = r; c < N; c++, u++) L[N * c + r] = upper[u] + (r == c ? lambda : 0.0);  // lower triangle
+  for (int i = 0; i < N; i++) delta[i] = 0.0;
+  for (int j = 0; j < N; j++) {
+    double d = L[N * j + j];
+    for (int k = 0; k < j; k++) d -= L[N * j + k] * L[N * j + k];
     if (!(d > 0.0) || !finite(d)) return false;
     d = sqrt(d);
-    L[6 * j + j] = d;
-    for (int i = j + 1; i < 6; i++) {
-      double s = L[6 * i + j];
-      for (int k = 0; k < j; k++) s -= L[6 * i + k] * L[6 * j + k];
-      L[6 * i + j] = s / d;
+    L[N * j + j] = d;
+    for (int i = j + 1; i < N; i++) {
+      double s = L[N * i + j];
+      for (int k = 0; k < j; k++) s -= L[N * i + k] * L[N * j + k];
+      L[N * i + j] = s / d;
     }
   }
-  double y[6];
-  for (int i = 0; i < 6; i++) {
-    double s = -rec[23 + i];
-    for (int k = 0; k < i; k++) s -= L[6 * i + k] * y[k];
-    y[i] = s / L[6 * i + i];
+  double* y = L + N * N;
+  for (int i = 0; i < N; i++) {
+    double s = -b[i];
+    for (int k = 0; k < i; k++) s -= L[N * i + k] * y[k];
+    y[i] = s / L[N * i + i];
   }
-  for (int i = 5; i >= 0; i--) {
+  for (int i = N - 1; i >= 0; i--) {
     double s = y[i];
-    for (int k = i + 1; k < 6; k++) s -= L[6 * k + i] * delta[k];
-    delta[i] = s / L[6 * i + i];
+    for (int k = i + 1; k < N; k++) s -= L[N * k + i] * delta[k];
+    delta[i] = s / L[N * i + i];
   }
   return true;
+}
+
+// the solve from a compact record
+GLIM_AMD_LM_HD inline bool solve(const double* rec, double lambda, double* delta) {
+  double L[36 + 6];
+  return solve_dense<6>(rec + 2, rec + 23, lambda, delta, L);
 }
 
 // out = T Exp(xi), xi = (omega, v)
@@ -145,6 +153,44 @@ GLIM_AMD_LM_HD inline void init(const Params& p, const double* T_init, State& s)
   s.status = RUNNING;
 }
 
+// The scalar part of the rule, for every loop of the family (step below, ct_lm::step, bundle_lm::decide): round 0 and the trial counting, the
+// accept condition and both lambda updates, the statuses and the budgets, on the progress words of a state.  e_cur: the error at what is kept,
+// e_new and has_inliers: of the evaluation at the candidate.  true: the candidate is kept (the caller then copies what it keeps).
+GLIM_AMD_LM_HD inline bool decide(const Params& p, double& lambda, int solve_ok, int& started, int& iterations, int& trials, int& status, int& accepted, double e_cur,
+                                  double e_new, bool has_inliers) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  bool keep = false;
+  if (!started) {
+    started = 1;
+    keep = true;
+  } else {
+    trials += 1;
+    if (solve_ok && has_inliers && e_new < e_cur) {
+      keep = true;
+      const double l = lambda / p.lambda_factor;
+      lambda = l > p.lambda_lower_bound ? l : p.lambda_lower_bound;
+      iterations += 1;
+      const double d = e_cur - e_new;
+      if (d <= p.absolute_error_tol / p.error_scale || d / e_cur <= p.relative_error_tol) status = CONVERGED;
+    } else {
+      lambda = lambda * p.lambda_factor;
+      if (!(lambda <= p.lambda_upper_bound)) status = LAMBDA_BOUND;
+    }
+  }
+  if (keep) {
+    accepted = 1;
+    if (!has_inliers) {  // round 0 only: a trial without inliers is never kept
+      status = NO_CORRESPONDENCES;
+      return keep;
+    }
+  }
+  if (status == RUNNING && iterations >= p.max_iterations) status = MAX_ITERATIONS;
+  if (status == RUNNING && trials >= p.max_trials) status = MAX_TRIALS;
+  return keep;
+}
+
 // One round: `rec` is the record evaluated at s.cand.  Updates what is kept, the status, and the candidate of the next round.
 GLIM_AMD_LM_HD inline void step(const Params& p, State& s, const double* rec) {
 #if defined(__clang__)
@@ -156,33 +202,10 @@ GLIM_AMD_LM_HD inline void step(const Params& p, State& s, const double* rec) {
     s.status = NUMERIC;
     return;
   }
-  if (!s.started) {
-    s.started = 1;
-    s.accepted = 1;
+  if (decide(p, s.lambda, s.solve_ok, s.started, s.iterations, s.trials, s.status, s.accepted, s.rec[1], rec[1], rec[0] >= 1.0)) {
+    for (int i = 0; i < 12; i++) s.T[i] = s.cand[i];  // (round 0: the initial pose onto itself)
     for (int i = 0; i < RECORD; i++) s.rec[i] = rec[i];
-    if (!(rec[0] >= 1.0)) {
-      s.status = NO_CORRESPONDENCES;
-      return;
-    }
-  } else {
-    s.trials += 1;
-    const double e_cur = s.rec[1], e_new = rec[1];
-    if (s.solve_ok && rec[0] >= 1.0 && e_new < e_cur) {
-      s.accepted = 1;
-      for (int i = 0; i < 12; i++) s.T[i] = s.cand[i];
-      for (int i = 0; i < RECORD; i++) s.rec[i] = rec[i];
-      const double l = s.lambda / p.lambda_factor;
-      s.lambda = l > p.lambda_lower_bound ? l : p.lambda_lower_bound;
-      s.iterations += 1;
-      const double d = e_cur - e_new;
-      if (d <= p.absolute_error_tol / p.error_scale || d / e_cur <= p.relative_error_tol) s.status = CONVERGED;
-    } else {
-      s.lambda = s.lambda * p.lambda_factor;
-      if (!(s.lambda <= p.lambda_upper_bound)) s.status = LAMBDA_BOUND;
-    }
   }
-  if (s.status == RUNNING && s.iterations >= p.max_iterations) s.status = MAX_ITERATIONS;
-  if (s.status == RUNNING && s.trials >= p.max_trials) s.status = MAX_TRIALS;
   if (s.status != RUNNING) return;
   s.solve_ok = solve(s.rec, s.lambda, s.delta) ? 1 : 0;
   if (s.solve_ok) {

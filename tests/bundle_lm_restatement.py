@@ -2,8 +2,8 @@
 optimisation"): Levenberg-Marquardt in fixed-lambda-factor mode over N poses on F binary VGICP factors (evaluated at T_f = X_t^-1 X_s), prior
 and between terms.  6N DoF, tangent order [X_0: omega v | X_1: omega v | ...], right perturbation; the conventions of tests/ct_restatement.py.
 Driven by a `linearize(Tf) -> records` callable: F relative poses (4 x 4) in, F records out (the dicts of tests/lm_restatement.py: num_inliers,
-error, H_ss, b_s).  The rule itself -- round 0, accept / reject, the lambda updates, the statuses, the budgets -- is tests/lm_restatement.py's,
-with the error read as the total cost and the inliers as the factors' sum.  A plain module: it holds no tests."""
+error, H_ss, b_s).  The rule itself -- round 0, accept / reject, the lambda updates, the statuses, the budgets -- is lm_restatement.decide, called
+with the error read as the total cost and the inliers as the factors' sum; so are the solve and the pose gate.  A plain module: it holds no tests."""
 import numpy as np
 
 from ct_restatement import adjoint, expmap_derivative, logmap
@@ -14,11 +14,7 @@ DEFAULTS = dict(lmr.DEFAULTS, max_iterations=20)  # the GICP defaults with sub_m
 
 
 def params(**kw):
-    p = dict(DEFAULTS)
-    p.update(kw)
-    if not p["max_trials"]:
-        p["max_trials"] = 2 * p["max_iterations"]
-    return p
+    return lmr.params(DEFAULTS, **kw)
 
 
 def graph(N, factors=(), priors=(), betweens=()):
@@ -111,21 +107,6 @@ def packed(S):
     return np.concatenate([S["H"][np.tril_indices(len(S["b"]))], S["b"]])
 
 
-def solve(S, lam):
-    """(H + lam I) delta = -b by Cholesky -> (ok, delta, gate): lm_restatement.solve over 6N dimensions -- ok False when a pivot is not > 0;
-    gate = 100 cond(H + lam I) eps max(|delta|, 1e-12)"""
-    n = len(S["b"])
-    A = S["H"] + lam * np.eye(n)
-    try:
-        C = np.linalg.cholesky(A)
-    except np.linalg.LinAlgError:
-        return False, np.zeros(n), 0.0
-    if not np.all(np.isfinite(C)) or not np.all(np.diag(C) > 0):
-        return False, np.zeros(n), 0.0
-    d = np.linalg.solve(C.T, np.linalg.solve(C, -S["b"]))
-    return True, d, 100.0 * np.linalg.cond(A) * EPS * max(np.abs(d).max(), 1e-12)
-
-
 def _finite(recs, X):
     return all(np.all(np.isfinite(np.asarray(x, dtype=np.float64)))
                for x in [X] + [v for L in recs for v in (L["error"], L["H_ss"], L["b_s"], float(L["num_inliers"]))])
@@ -151,32 +132,11 @@ def step(p, g, s, recs):
         s["status"] = NUMERIC
         return s
     seen = not g["factors"] or S["inliers"] >= 1
-    if not s["started"]:
-        s["started"], s["accepted"], s["X"], s["recs"], s["sys"] = True, True, s["cand"], recs, S
-        if not seen:
-            s["status"] = NO_CORRESPONDENCES
-            return s
-    else:
-        s["trials"] += 1
-        e_cur, e_new = s["sys"]["cost"], S["cost"]
-        if s["solve_ok"] and seen and e_new < e_cur:
-            s["accepted"], s["X"], s["recs"], s["sys"] = True, s["cand"], recs, S
-            s["lam"] = max(s["lam"] / p["lambda_factor"], p["lambda_lower_bound"])
-            s["iterations"] += 1
-            d = e_cur - e_new
-            if d <= p["absolute_error_tol"] / p["error_scale"] or d / e_cur <= p["relative_error_tol"]:
-                s["status"] = CONVERGED
-        else:
-            s["lam"] = s["lam"] * p["lambda_factor"]
-            if not s["lam"] <= p["lambda_upper_bound"]:
-                s["status"] = LAMBDA_BOUND
-    if s["status"] == RUNNING and s["iterations"] >= p["max_iterations"]:
-        s["status"] = MAX_ITERATIONS
-    if s["status"] == RUNNING and s["trials"] >= p["max_trials"]:
-        s["status"] = MAX_TRIALS
+    if lmr.decide(p, s, s["sys"]["cost"] if s["started"] else None, S["cost"], seen):
+        s["X"], s["recs"], s["sys"] = s["cand"], recs, S
     if s["status"] != RUNNING:
         return s
-    s["solve_ok"], s["delta"], s["gate"] = solve(s["sys"], s["lam"])
+    s["solve_ok"], s["delta"], s["gate"] = lmr.solve(s["sys"]["H"], s["sys"]["b"], s["lam"])
     if s["solve_ok"]:
         s["cand"] = np.stack([Xk @ expmap(s["delta"][6 * k:6 * k + 6]) for k, Xk in enumerate(s["X"])])
     else:
@@ -184,11 +144,6 @@ def step(p, g, s, recs):
     if not np.all(np.isfinite(s["cand"])):
         s["status"] = NUMERIC
     return s
-
-
-def pose_gate(s):
-    """what the step error `gate` does to X_k Exp(delta_k) (tests/test_vgicp_align_gpu.py::pose_gate, with cond taken of the 6N system)"""
-    return 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * EPS * max(1.0, np.abs(s["cand"]).max())
 
 
 def run(linearize, g, X_init, p=None):

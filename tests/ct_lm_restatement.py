@@ -3,7 +3,8 @@ alignment"): Levenberg-Marquardt in fixed-lambda-factor mode over the two poses 
 factor plus a location prior on X and a between term on X^-1 Y.  12 DoF, tangent order [X: omega v | Y: omega v], right perturbation; the
 conventions of tests/ct_restatement.py.  Driven by a `linearize(X, Y) -> record` callable; a record is the dict np_ct_linearize and
 IntegratedCT_GICPFactor.linearize return (num_inliers, error, H_00, H_01, H_11, b_0, b_1).  The rule itself -- round 0, accept / reject, the
-lambda updates, the statuses, the budgets -- is tests/lm_restatement.py's.  A plain module: it holds no tests."""
+lambda updates, the statuses, the budgets -- is lm_restatement.decide, called; so are the solve and the pose gate.  A plain module: it holds no
+tests."""
 import numpy as np
 
 from ct_restatement import _prior, adjoint, expmap_derivative, full_system, logmap
@@ -16,11 +17,7 @@ ROW = 92
 
 
 def params(**kw):
-    p = dict(DEFAULTS)
-    p.update(kw)
-    if not p["max_trials"]:
-        p["max_trials"] = 2 * p["max_iterations"]
-    return p
+    return lmr.params(DEFAULTS, **kw)
 
 
 def terms(location=None, between=None):
@@ -74,20 +71,6 @@ def assemble(tm, X, Y, L):
     return {"H": H, "b": b, "cost": (L["error"] + cp) + cb, "cost_p": cp, "cost_b": cb}
 
 
-def solve(S, lam):
-    """(H + lam I) delta = -b by Cholesky -> (ok, delta, gate): lm_restatement.solve in its 12-DoF form -- ok False when a pivot is not > 0;
-    gate = 100 cond(H + lam I) eps max(|delta|, 1e-12)"""
-    A = S["H"] + lam * np.eye(12)
-    try:
-        C = np.linalg.cholesky(A)
-    except np.linalg.LinAlgError:
-        return False, np.zeros(12), 0.0
-    if not np.all(np.isfinite(C)) or not np.all(np.diag(C) > 0):
-        return False, np.zeros(12), 0.0
-    d = np.linalg.solve(C.T, np.linalg.solve(C, -S["b"]))
-    return True, d, 100.0 * np.linalg.cond(A) * EPS * max(np.abs(d).max(), 1e-12)
-
-
 def _finite(L, X, Y):
     return all(np.all(np.isfinite(np.asarray(x, dtype=np.float64))) for x in (L["error"], full_system(L)[0], full_system(L)[1], X, Y, float(L["num_inliers"])))
 
@@ -111,32 +94,11 @@ def step(p, tm, s, L):
     if not (np.all(np.isfinite(S["H"])) and np.all(np.isfinite(S["b"])) and np.isfinite(S["cost"])):
         s["status"] = NUMERIC
         return s
-    if not s["started"]:
-        s["started"], s["accepted"], s["rec"], s["sys"] = True, True, L, S
-        if not L["num_inliers"] >= 1:
-            s["status"] = NO_CORRESPONDENCES
-            return s
-    else:
-        s["trials"] += 1
-        e_cur, e_new = s["sys"]["cost"], S["cost"]
-        if s["solve_ok"] and L["num_inliers"] >= 1 and e_new < e_cur:
-            s["accepted"], s["X"], s["Y"], s["rec"], s["sys"] = True, s["candX"], s["candY"], L, S
-            s["lam"] = max(s["lam"] / p["lambda_factor"], p["lambda_lower_bound"])
-            s["iterations"] += 1
-            d = e_cur - e_new
-            if d <= p["absolute_error_tol"] / p["error_scale"] or d / e_cur <= p["relative_error_tol"]:
-                s["status"] = CONVERGED
-        else:
-            s["lam"] = s["lam"] * p["lambda_factor"]
-            if not s["lam"] <= p["lambda_upper_bound"]:
-                s["status"] = LAMBDA_BOUND
-    if s["status"] == RUNNING and s["iterations"] >= p["max_iterations"]:
-        s["status"] = MAX_ITERATIONS
-    if s["status"] == RUNNING and s["trials"] >= p["max_trials"]:
-        s["status"] = MAX_TRIALS
+    if lmr.decide(p, s, s["sys"]["cost"] if s["started"] else None, S["cost"], L["num_inliers"] >= 1):
+        s["X"], s["Y"], s["rec"], s["sys"] = s["candX"], s["candY"], L, S
     if s["status"] != RUNNING:
         return s
-    s["solve_ok"], s["delta"], s["gate"] = solve(s["sys"], s["lam"])
+    s["solve_ok"], s["delta"], s["gate"] = lmr.solve(s["sys"]["H"], s["sys"]["b"], s["lam"])
     if s["solve_ok"]:
         s["candX"], s["candY"] = s["X"] @ expmap(s["delta"][:6]), s["Y"] @ expmap(s["delta"][6:])
     else:
@@ -147,9 +109,8 @@ def step(p, tm, s, L):
 
 
 def pose_gate(s):
-    """what the step error `gate` does to X Exp(delta[:6]) and Y Exp(delta[6:]) (tests/test_gicp_align.py::check_against_restatement): rotation
-    entries and V v move by at most (1 + |delta|) times the step error per entry summed over 3 products, plus the rounding of the 3 x 4 product"""
-    return 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * EPS * max(1.0, np.abs(s["candX"]).max(), np.abs(s["candY"]).max())
+    """lm_restatement.pose_gate over the two retractions X Exp(delta[:6]) and Y Exp(delta[6:])"""
+    return lmr.pose_gate(s, ("candX", "candY"))
 
 
 def run(linearize, X_init, Y_init, tm, p=None):

@@ -11,8 +11,9 @@ DEFAULTS = dict(lambda_initial=1e-5, lambda_factor=10.0, lambda_upper_bound=1e5,
                 absolute_error_tol=1e-5, max_iterations=10, max_trials=0, error_scale=1.0)
 
 
-def params(**kw):
-    p = dict(DEFAULTS)
+def params(_defaults=None, **kw):
+    """the defaults (of this loop, or `_defaults`: another loop's) with `kw`, max_trials resolved"""
+    p = dict(DEFAULTS if _defaults is None else _defaults)
     p.update(kw)
     if not p["max_trials"]:
         p["max_trials"] = 2 * p["max_iterations"]
@@ -47,19 +48,26 @@ def expmap(xi):
     return T
 
 
-def solve(L, lam):
-    """(H + lam I) delta = -b by Cholesky -> (ok, delta, gate): ok False when a pivot is not > 0; gate = the bound on |delta - other's delta|
-    that scales itself with the case, 100 cond(H + lam I) eps max(|delta|, 1e-12)"""
-    A = np.asarray(L["H_ss"], dtype=np.float64) + lam * np.eye(6)
+def solve(H, b, lam):
+    """(H + lam I) delta = -b by Cholesky, in any dimension -> (ok, delta, gate): ok False when a pivot is not > 0; gate = the bound on
+    |delta - other's delta| that scales itself with the case, 100 cond(H + lam I) eps max(|delta|, 1e-12)"""
+    n = len(b)
+    A = np.asarray(H, dtype=np.float64) + lam * np.eye(n)
     try:
         C = np.linalg.cholesky(A)
     except np.linalg.LinAlgError:
-        return False, np.zeros(6), 0.0
+        return False, np.zeros(n), 0.0
     if not np.all(np.isfinite(C)) or not np.all(np.diag(C) > 0):
-        return False, np.zeros(6), 0.0
-    y = np.linalg.solve(C, -np.asarray(L["b_s"], dtype=np.float64))
+        return False, np.zeros(n), 0.0
+    y = np.linalg.solve(C, -np.asarray(b, dtype=np.float64))
     d = np.linalg.solve(C.T, y)
     return True, d, 100.0 * np.linalg.cond(A) * EPS * max(np.abs(d).max(), 1e-12)
+
+
+def pose_gate(s, names=("cand",)):
+    """what the step error s['gate'] does to the retractions T Exp(delta) that gave the candidate poses s[name]: rotation entries and V v move
+    by at most (1 + |delta|) times the step error per entry summed over 3 products, plus the rounding of the 3 x 4 product itself"""
+    return 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * EPS * max(1.0, *(np.abs(s[n]).max() for n in names))
 
 
 def _finite(L, T):
@@ -72,25 +80,17 @@ def new_state(T_init, p):
             "iterations": 0, "trials": 0, "status": RUNNING, "accepted": False}
 
 
-def step(p, s, L):
-    """One round: L is the record evaluated at s['cand'].  Returns the new state (the argument is left alone)."""
-    s = dict(s)
-    if s["status"] != RUNNING:
-        return s
-    s["accepted"] = False
-    if not _finite(L, s["cand"]):
-        s["status"] = NUMERIC
-        return s
+def decide(p, s, e_cur, e_new, has_inliers):
+    """The scalar part of the rule, for every loop of the family (lm::decide of lm_step.hpp): round 0 and the trial counting, the accept
+    condition and both lambda updates, the statuses and the budgets, on the progress words of the state `s`, in place.  e_cur: the error at what
+    is kept (not read in round 0), e_new and has_inliers: of the evaluation at the candidate.  True: the candidate is kept."""
+    keep = False
     if not s["started"]:
-        s["started"], s["accepted"], s["rec"] = True, True, L
-        if not L["num_inliers"] >= 1:
-            s["status"] = NO_CORRESPONDENCES
-            return s
+        s["started"] = keep = True
     else:
         s["trials"] += 1
-        e_cur, e_new = s["rec"]["error"], L["error"]
-        if s["solve_ok"] and L["num_inliers"] >= 1 and e_new < e_cur:
-            s["accepted"], s["T"], s["rec"] = True, s["cand"], L
+        if s["solve_ok"] and has_inliers and e_new < e_cur:
+            keep = True
             s["lam"] = max(s["lam"] / p["lambda_factor"], p["lambda_lower_bound"])
             s["iterations"] += 1
             d = e_cur - e_new
@@ -100,13 +100,32 @@ def step(p, s, L):
             s["lam"] = s["lam"] * p["lambda_factor"]
             if not s["lam"] <= p["lambda_upper_bound"]:
                 s["status"] = LAMBDA_BOUND
+    if keep:
+        s["accepted"] = True
+        if not has_inliers:  # round 0 only: a trial without inliers is never kept
+            s["status"] = NO_CORRESPONDENCES
+            return keep
     if s["status"] == RUNNING and s["iterations"] >= p["max_iterations"]:
         s["status"] = MAX_ITERATIONS
     if s["status"] == RUNNING and s["trials"] >= p["max_trials"]:
         s["status"] = MAX_TRIALS
+    return keep
+
+
+def step(p, s, L):
+    """One round: L is the record evaluated at s['cand'].  Returns the new state (the argument is left alone)."""
+    s = dict(s)
     if s["status"] != RUNNING:
         return s
-    s["solve_ok"], s["delta"], s["gate"] = solve(s["rec"], s["lam"])
+    s["accepted"] = False
+    if not _finite(L, s["cand"]):
+        s["status"] = NUMERIC
+        return s
+    if decide(p, s, s["rec"]["error"] if s["started"] else None, L["error"], L["num_inliers"] >= 1):
+        s["T"], s["rec"] = s["cand"], L
+    if s["status"] != RUNNING:
+        return s
+    s["solve_ok"], s["delta"], s["gate"] = solve(s["rec"]["H_ss"], s["rec"]["b_s"], s["lam"])
     s["cand"] = s["T"] @ expmap(s["delta"]) if s["solve_ok"] else s["T"]
     if not np.all(np.isfinite(s["cand"])):
         s["status"] = NUMERIC

@@ -5,15 +5,17 @@ import ctypes as C
 import os
 import re
 import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
 
 import bundle_lm_restatement as blr
 import lm_restatement as lmr
+from align_cases import ROOT, build_cpp, build_driver, check_symbols, params_head
+from align_cases import check_against_restatement as check_rounds
 from glim_amd import se3
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_STABLE = ["glim_amd_bundle_align_default_params", "glim_amd_bundle_align"]
 NEW_DIAG = ["glim_amd_debug_bundle_align_trace"]
 INVALID, STATE, UNSUPPORTED = -1, -3, -6
@@ -24,21 +26,13 @@ EPS = lmr.EPS
 def test_new_symbols_are_declared_once_and_listed():
     from glim_amd import _lib, api
 
-    decl = {h: set(re.findall(r"\b(glim_amd_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", h)).read())) for h in ("glim_amd.h", "glim_amd_diag.h")}
-    for n in NEW_STABLE:
-        assert n in decl["glim_amd.h"] and n not in decl["glim_amd_diag.h"] and n in _lib.SYMBOLS, n
-    for n in NEW_DIAG:
-        assert n in decl["glim_amd_diag.h"] and n not in decl["glim_amd.h"] and n in _lib.SYMBOLS, n
-    mirror = open(os.path.join(ROOT, "include", "glim_amd", "bundle_align.hpp")).read()
-    assert "glim_amd_diag.h" not in mirror and "glim_amd_debug_" not in mirror and "glim_amd_bundle_align(" in mirror
+    mirror = check_symbols(NEW_STABLE, NEW_DIAG, "bundle_align.hpp")
+    assert "glim_amd_bundle_align(" in mirror
     assert '#include "gicp_align.hpp"' in mirror  # LMParams is reused
     head = open(os.path.join(ROOT, "include", "glim_amd.h")).read()
     caps = {k: int(v) for k, v in re.findall(r"#define GLIM_AMD_BUNDLE_(MAX_[A-Z]+) (\d+)", head)}
     assert caps == {"MAX_POSES": _lib.BUNDLE_MAX_POSES, "MAX_FACTORS": _lib.BUNDLE_MAX_FACTORS, "MAX_TERMS": _lib.BUNDLE_MAX_TERMS}
     assert caps["MAX_POSES"] == MAX_POSES >= 20 and caps["MAX_FACTORS"] >= 380
-    L = _lib.lib()
-    for n in NEW_STABLE + NEW_DIAG:
-        assert hasattr(L, n)
     for n in ("bundle_align", "bundle_align_debug_trace", "bundle_align_params"):
         assert callable(getattr(api, n))
     assert callable(api.NonlinearFactorSetGPU.optimize)
@@ -137,9 +131,7 @@ CPP = os.path.join(ROOT, "tests", "cpp", "test_bundle_lm_step.cpp")
 
 @pytest.fixture(scope="module")
 def step_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("bundle_lm_step") / "test_bundle_lm_step")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", CPP, "-o", exe])
-    return exe
+    return build_driver(tmp_path_factory, "bundle_lm_step", "-Wno-unknown-pragmas")
 
 
 def run_cpp(exe, tmp_path, mode, data):
@@ -251,7 +243,7 @@ def test_cholesky_solve_against_numpy(step_exe, tmp_path, n):
     for cond_exp, lam in ((2, 0.0), (6, 1e-5), (9, 1e-3)):
         S = spd_system(rng, n, cond_exp)
         out = run_cpp(step_exe, tmp_path, "solve", np.concatenate([[float(n), lam], blr.packed(S)]))
-        ok, d, gate = blr.solve(S, lam)
+        ok, d, gate = lmr.solve(S["H"], S["b"], lam)
         assert ok and out[0] == 1.0
         assert np.abs(out[1:] - d).max() <= gate, (n, cond_exp, np.abs(out[1:] - d).max(), gate)
 
@@ -282,9 +274,7 @@ def test_a_pivot_that_is_not_positive_is_a_failed_solve(step_exe, tmp_path):
 
 
 def run_cpp_step(exe, tmp_path, p, g, X_init, rounds):
-    head = [p[k] for k in ("lambda_initial", "lambda_factor", "lambda_upper_bound", "lambda_lower_bound", "relative_error_tol", "absolute_error_tol")]
-    head += [float(p["max_iterations"]), float(p["max_trials"]), p["error_scale"]]
-    data = np.concatenate([head, blr.graph_doubles(g), np.concatenate([pose12(x) for x in X_init]), [float(len(rounds))]] +
+    data = np.concatenate([params_head(p), blr.graph_doubles(g), np.concatenate([pose12(x) for x in X_init]), [float(len(rounds))]] +
                           [lmr.compact_of_record(r) for recs in rounds for r in recs])
     N = g["N"]
     rows = run_cpp(exe, tmp_path, "step", data).reshape(len(rounds), 30 * N + 7)
@@ -294,26 +284,10 @@ def run_cpp_step(exe, tmp_path, p, g, X_init, rounds):
             for r in rows]
 
 
-def check_against_restatement(rows, states, cost_floor=0.0):
-    """tests/test_ct_align.py::check_against_restatement over N poses: decisions, counts, statuses and lambda are equal; the step is within the
-    self-scaled gate of the restatement's solve, the poses within what that does to the retractions (bundle_lm_restatement.pose_gate).
-    cost_floor: what a cost that goes to zero is known to, absolutely"""
-    assert len(rows) == len(states)
-    for k, (got, s) in enumerate(zip(rows, states)):
-        assert (got["accepted"], got["status"], got["iterations"], got["trials"]) == (s["accepted"], s["status"], s["iterations"], s["trials"]), k
-        assert got["lam"] == s["lam"], k
-        if s["sys"] is not None:
-            assert abs(got["cost"] - s["sys"]["cost"]) <= 1e-12 * abs(s["sys"]["cost"]) + cost_floor, k
-        if s["status"] != blr.RUNNING:
-            continue
-        assert got["solve_ok"] == s["solve_ok"], k
-        # unlike the single-factor loops the two sides ASSEMBLE their systems themselves, and these agree to 1e-12 of their scale (the assembly
-        # test above), which a solve carries into the step times cond: 1e-12 cond max|delta| = gate / (100 EPS) * 1e-12 on top of the gate
-        s = dict(s, gate=s["gate"] * (1.0 + 1e-12 / (100.0 * EPS)))
-        assert np.abs(got["delta"] - s["delta"]).max() <= s["gate"], (k, np.abs(got["delta"] - s["delta"]).max(), s["gate"])
-        gate = blr.pose_gate(s)
-        for name in ("cand", "X"):
-            assert np.abs(got[name] - s[name]).max() <= gate, (k, name, np.abs(got[name] - s[name]).max(), gate)
+# align_cases.check_against_restatement over N poses.  Unlike the single-factor loops the two sides ASSEMBLE their systems themselves, and these
+# agree to 1e-12 of their scale (the assembly test above), which a solve carries into the step times cond: 1e-12 cond max|delta| =
+# gate / (100 EPS) * 1e-12 on top of the gate
+check_against_restatement = partial(check_rounds, kept=("X",), gate_scale=1.0 + 1e-12 / (100.0 * EPS))
 
 
 # scripted sequences: the factors' errors per round (the same for every factor), the parameters, and how the loop must end
@@ -394,13 +368,7 @@ def test_the_header_is_clean_under_the_sanitizers(tmp_path):
 # ---- the C++ mirror ------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror_compiles_links_and_answers_an_empty_problem(tmp_path):
     """include/glim_amd/bundle_align.hpp: compiled, linked, and run on an empty problem (no device call)"""
-    from glim_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH)
-    exe = str(tmp_path / "test_bundle_align")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_bundle_align.cpp"),
-                           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64"])
+    exe = build_cpp(tmp_path, "bundle_align")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "test_bundle_align OK" in out.stdout, out.stdout + out.stderr
 

@@ -13,16 +13,20 @@ tests/test_vgicp_align_gpu.py).  So the first and fourth case run with relative_
 and third with max_iterations = 2 (MAX_ITERATIONS).  The reject case is the first with max_iterations = 3: AArrrr, MAX_TRIALS, 2 iterations,
 6 trials; its margin 4.0e-3 is 20 x the record tolerance, the one case under 5e-3.  The device's clouds carry the device's own FP32
 covariances, so each test that rests on such a margin asserts it again on the oracle run it makes."""
+from functools import partial
+
 import numpy as np
 import pytest
 
+import align_cases
 import bundle_lm_restatement as blr
 import lm_restatement as lmr
+from align_cases import MOVES, PERT_A, PERT_B, RECORD_TOL, ctx, same_result  # noqa: F401 (ctx: a fixture)
 from test_gicp import POSE_TOL
-from test_vgicp_align_gpu import MOVES, PERT_A, PERT_B
 
 pytestmark = pytest.mark.gpu
-RECORD_TOL = 2e-4
+api_params = partial(align_cases.api_params, factory="bundle_align_params")
+moves = partial(align_cases.moves, cost=True)
 SIZE = (16, 128)
 MAX_POSES = 32
 CONV, TWO, THREE = dict(relative_error_tol=5e-2), dict(max_iterations=2), dict(max_iterations=3)
@@ -35,13 +39,6 @@ CASES = [
 ]
 REJECT_CASE = (3, 0.5, PERT_A, THREE)
 REJECT_MARGIN = 20 * RECORD_TOL  # 4.0e-3
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from glim_amd import api
-
-    return api.Context(0, 1)
 
 
 _SCENES, _MAPS, _ORACLE_MAPS = {}, {}, {}
@@ -109,12 +106,6 @@ def caller_set(ctx, pr):
     return fset
 
 
-def api_params(kw):
-    from glim_amd import api
-
-    return api.bundle_align_params(**kw)
-
-
 def run(pr, kw, **more):
     from glim_amd import api
 
@@ -126,22 +117,8 @@ def same_lin(a, b):
                                     for x, y in zip(a, b))
 
 
-def same_result(a, b):
-    return (np.array_equal(a.poses, b.poses) and (a.cost, a.factor_cost, a.prior_cost, a.between_cost, a.lam) == (b.cost, b.factor_cost, b.prior_cost, b.between_cost, b.lam) and
-            (a.num_inliers, a.iterations, a.trials, a.status) == (b.num_inliers, b.iterations, b.trials, b.status) and np.array_equal(a.compact, b.compact))
-
-
 def pose44(v):
     return np.vstack([np.asarray(v).reshape(3, 4), [0, 0, 0, 1]])
-
-
-def moves(trace):
-    """|e_new - e_cur| / e_cur of every trial of a restatement trace"""
-    out, e_cur = [], trace[0]["cost"]
-    for e in trace[1:]:
-        out.append(abs(e["cost"] - e_cur) / e_cur)
-        e_cur = e["state"]["sys"]["cost"]
-    return out
 
 
 def teacher_forced(ctx, pr, res, rows, p):
@@ -166,7 +143,7 @@ def teacher_forced(ctx, pr, res, rows, p):
         if k == 0:
             assert np.array_equal(e["X"], pr["X0"])
         else:
-            gate = blr.pose_gate(s)
+            gate = lmr.pose_gate(s)
             assert np.abs(e["X"] - s["cand"]).max() <= gate, (k, np.abs(e["X"] - s["cand"]).max(), gate)
         s["cand"] = e["X"]  # teacher forcing: the device's poses are the ones the records belong to
         s = blr.step(p, g, s, [lmr.record_of_compact(c) for c in e["compact"]])

@@ -5,15 +5,16 @@ import ctypes as C
 import os
 import re
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
 
 import ct_lm_restatement as ctl
+from align_cases import ROOT, build_driver, check_against_restatement, check_symbols, params_head
 from ct_align_cases import CASES, case_inputs, cpu_scene, pose_table_cases
 from ct_restatement import ct_poses, expmap, np_ct_linearize, sweep_poses, time_table
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_STABLE = ["glim_amd_ct_align_default_params", "glim_amd_ct_align"]
 NEW_DIAG = ["glim_amd_debug_ct_align_trace", "glim_amd_debug_ct_align_poses"]
 
@@ -21,20 +22,12 @@ NEW_DIAG = ["glim_amd_debug_ct_align_trace", "glim_amd_debug_ct_align_poses"]
 def test_new_symbols_are_declared_once_and_listed():
     from glim_amd import _lib
 
-    decl = {h: re.findall(r"\b(glim_amd_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", h)).read()) for h in ("glim_amd.h", "glim_amd_diag.h")}
-    for n in NEW_STABLE:
-        assert decl["glim_amd.h"].count(n) == 1 and n not in decl["glim_amd_diag.h"] and n in _lib.SYMBOLS, n
-    for n in NEW_DIAG:
-        assert decl["glim_amd_diag.h"].count(n) == 1 and n not in decl["glim_amd.h"] and n in _lib.SYMBOLS, n
+    mirror = check_symbols(NEW_STABLE, NEW_DIAG, "ct_align.hpp")
     for n in NEW_STABLE + NEW_DIAG:  # the counts tests/test_ct_gicp.py and tests/test_ivox.py pin
         assert "ivox" not in n and "ct_gicp" not in n, n
-    mirror = open(os.path.join(ROOT, "include", "glim_amd", "ct_align.hpp")).read()
-    assert "glim_amd_diag.h" not in mirror and "glim_amd_debug_" not in mirror and re.search(r"glim_amd_ct_align\s*\(", mirror)
+    assert re.search(r"glim_amd_ct_align\s*\(", mirror)
     for f in (os.path.join("adapters", "gtsam", "glim_amd_gtsam.hpp"), os.path.join("include", "glim_amd", "gtsam_points_compat.hpp")):
         assert re.search(r"\balign\s*\(", open(os.path.join(ROOT, f)).read()) and "align_ct" in open(os.path.join(ROOT, f)).read(), f
-    L = _lib.lib()
-    for n in NEW_STABLE + NEW_DIAG:
-        assert hasattr(L, n)
     # the structures as the headers lay them out
     assert C.sizeof(_lib.CtAlignTerms) == 26 * 8
     assert C.sizeof(_lib.CtAlignResult) == 24 * 8 + C.sizeof(_lib.CtLinearized) + 4 * 8 + 4 * 4
@@ -42,8 +35,6 @@ def test_new_symbols_are_declared_once_and_listed():
     # ... and as a C compiler does
     src = '#include <stdio.h>\n#include "glim_amd_diag.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(glim_amd_ct_align_terms), ' \
           "sizeof(glim_amd_ct_align_result), sizeof(glim_amd_ct_align_trace_entry)); return 0; }\n"
-    import tempfile
-
     with tempfile.TemporaryDirectory() as tmp:
         open(os.path.join(tmp, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), os.path.join(tmp, "s.c"), "-o", os.path.join(tmp, "s")])
@@ -92,9 +83,7 @@ def test_default_params_and_argument_errors_without_a_device():
 # ---- ct_lm_step.hpp and ct_se3.hpp on the host ---------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ct_step_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ct_lm_step") / "test_ct_lm_step")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "test_ct_lm_step.cpp"), "-o", exe])
-    return exe
+    return build_driver(tmp_path_factory, "ct_lm_step")
 
 
 def pose12(T):
@@ -103,11 +92,9 @@ def pose12(T):
 
 def run_cpp_step(exe, tmp_path, p, tm, X_init, Y_init, records):
     """the C++ step rule over `records` (teacher-forced: record k is what round k evaluated) -> one dict per round"""
-    head = [p[k] for k in ("lambda_initial", "lambda_factor", "lambda_upper_bound", "lambda_lower_bound", "relative_error_tol", "absolute_error_tol")]
-    head += [float(p["max_iterations"]), float(p["max_trials"]), p["error_scale"]]
     P, kp = tm["location"] if tm["location"] is not None else (np.eye(4), 0.0)
     D, kb = tm["between"] if tm["between"] is not None else (np.eye(4), 0.0)
-    data = np.concatenate([head, pose12(X_init), pose12(Y_init), pose12(P), [kp], pose12(D), [kb], [float(len(records))]] + [ctl.row_of_record(L) for L in records])
+    data = np.concatenate([params_head(p), pose12(X_init), pose12(Y_init), pose12(P), [kp], pose12(D), [kb], [float(len(records))]] + [ctl.row_of_record(L) for L in records])
     fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
     data.astype(np.float64).tofile(fin)
     out = subprocess.run([exe, "step", fin, fout], capture_output=True, text=True, timeout=60)
@@ -118,22 +105,7 @@ def run_cpp_step(exe, tmp_path, p, tm, X_init, Y_init, records):
              "iterations": int(r[62]), "trials": int(r[63]), "status": int(r[64]), "accepted": bool(r[65]), "cost": r[66]} for r in rows]
 
 
-def check_against_restatement(rows, trace):
-    """tests/test_gicp_align.py::check_against_restatement in its 12-DoF form: decisions, counts, statuses and lambda are equal; the step is
-    within the self-scaled gate of the restatement's solve, the pairs within what that does to the two retractions (ct_lm_restatement.pose_gate)."""
-    assert len(rows) == len(trace)
-    for k, (got, ref) in enumerate(zip(rows, trace)):
-        s = ref["state"]
-        assert (got["accepted"], got["status"], got["iterations"], got["trials"]) == (s["accepted"], s["status"], s["iterations"], s["trials"]), k
-        assert got["lam"] == s["lam"], k
-        assert abs(got["cost"] - s["sys"]["cost"]) <= 1e-12 * abs(s["sys"]["cost"]), k
-        if s["status"] != ctl.RUNNING:
-            continue
-        assert got["solve_ok"] == s["solve_ok"], k
-        assert np.abs(got["delta"] - s["delta"]).max() <= s["gate"], (k, np.abs(got["delta"] - s["delta"]).max(), s["gate"])
-        gate = ctl.pose_gate(s)
-        for name in ("candX", "candY", "X", "Y"):
-            assert np.abs(got[name] - s[name]).max() <= gate, (k, name, np.abs(got[name] - s[name]).max(), gate)
+PAIR = dict(cand=("candX", "candY"), kept=("X", "Y"))  # the poses of a state, for check_against_restatement
 
 
 @pytest.fixture(scope="module")
@@ -163,7 +135,7 @@ def cost_changes(trace):
 def test_ct_lm_step_follows_the_restatement_over_an_oracle_driven_run(oracle_runs, ct_step_exe, tmp_path, name):
     tm, X0, Y0, final, trace = oracle_runs[name]
     rows = run_cpp_step(ct_step_exe, tmp_path, ctl.params(), tm, X0, Y0, [e["record"] for e in trace])
-    check_against_restatement(rows, trace)
+    check_against_restatement(rows, [e["state"] for e in trace], **PAIR)
     changes = cost_changes(trace)
     print(name, "status", final["status"], "iterations", final["iterations"], "trials", final["trials"], "cost changes", ["%.3g" % c for c in changes])
     # no trial is decided by the last bits of the cost: the decisions above cannot flip between two correct implementations
@@ -213,7 +185,7 @@ def test_ct_lm_step_special_inputs(ct_step_exe, tmp_path):
         trace.append({"state": s})
     assert [e["state"]["accepted"] for e in trace] == [True, False, False, False, False] and s["status"] == ctl.MAX_TRIALS
     rows = run_cpp_step(ct_step_exe, tmp_path, p0, none, T0, T1, records)
-    check_against_restatement(rows, trace)
+    check_against_restatement(rows, [e["state"] for e in trace], **PAIR)
     assert all(not r["solve_ok"] for r in rows[:-1]) and all(np.array_equal(r["candX"], T0) and np.array_equal(r["candY"], T1) for r in rows)
 
 

@@ -2,7 +2,6 @@
 the host's, every trial record is the factor's at the trial's pair, the decisions are those of tests/ct_lm_restatement.py, and the call leaves
 the factor's kept state alone.  Cases and scenes: tests/ct_align_cases.py."""
 import ctypes as C
-import os
 import struct
 import subprocess
 
@@ -10,19 +9,11 @@ import numpy as np
 import pytest
 
 import ct_lm_restatement as ctl
+from align_cases import build_cpp, ctx, packed  # noqa: F401 (ctx: a fixture)
 from ct_align_cases import CASES, case_inputs, pose_table_cases
 from ct_restatement import POSE_TOL, _check_record, expmap, moving_source, np_ct_linearize, static_map, sweep_poses
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from glim_amd import api
-
-    return api.Context(0, 1)
-
 
 _SCENE = {}
 
@@ -278,13 +269,6 @@ def test_cpp_mirror_returns_the_python_result(ctx, tmp_path):
     (tp, tc, _), (sp, sc, _, times) = scene(ctx, 4001)
     X0, Y0, tm, max_d = case_inputs("A")
 
-    def packed(p, c):
-        p4 = np.ones((len(p), 4))
-        p4[:, :3] = p
-        m = np.zeros((len(p), 4, 4))
-        m[:, :3, :3] = c
-        return p4, np.ascontiguousarray(np.transpose(m, (0, 2, 1))).reshape(len(p), 16)
-
     (tp4, tc16), (sp4, sc16) = packed(tp, tc), packed(sp, sc)
     tg, sg = api.PointCloudGPU.clone_packed(tp4, tc16, ctx=ctx), api.PointCloudGPU.clone_packed(sp4, sc16, ctx=ctx)
     f = api.IntegratedCT_GICPFactor(0, 1, tg, sg, max_correspondence_distance=max_d, times=times)
@@ -298,9 +282,6 @@ def test_cpp_mirror_returns_the_python_result(ctx, tmp_path):
         for a in (tp4, tc16, sp4, sc16, times, [max_d], api.pose12(X0), api.pose12(Y0), api.pose12(P), [kp], api.pose12(D), [kb]):
             fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         fh.write(res.raw)
-    exe = str(tmp_path / "test_ct_align")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_ct_align.cpp"),
-                           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64"])
+    exe = build_cpp(tmp_path, "ct_align")
     out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "test_ct_align OK" in out.stdout, out.stdout + out.stderr

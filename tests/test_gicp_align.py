@@ -2,16 +2,14 @@
 the argument errors, and the step rule of glim_amd/csrc/lm_step.hpp compiled with g++ against the NumPy restatement (tests/lm_restatement.py)
 over oracle-driven runs."""
 import ctypes as C
-import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import lm_restatement as lmr
+from align_cases import build_driver, check_against_restatement, check_symbols, params_head
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_STABLE = ["glim_amd_gicp_align_default_params", "glim_amd_gicp_align_batch", "glim_amd_gicp_align_batch_incremental"]
 NEW_DIAG = ["glim_amd_debug_gicp_align_trace"]
 
@@ -19,16 +17,7 @@ NEW_DIAG = ["glim_amd_debug_gicp_align_trace"]
 def test_new_symbols_are_declared_once_and_listed():
     from glim_amd import _lib
 
-    decl = {h: set(re.findall(r"\b(glim_amd_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", h)).read())) for h in ("glim_amd.h", "glim_amd_diag.h")}
-    for n in NEW_STABLE:
-        assert n in decl["glim_amd.h"] and n not in decl["glim_amd_diag.h"] and n in _lib.SYMBOLS, n
-    for n in NEW_DIAG:
-        assert n in decl["glim_amd_diag.h"] and n not in decl["glim_amd.h"] and n in _lib.SYMBOLS, n
-    mirror = open(os.path.join(ROOT, "include", "glim_amd", "gicp_align.hpp")).read()
-    assert "glim_amd_diag.h" not in mirror and "glim_amd_debug_" not in mirror
-    L = _lib.lib()
-    for n in NEW_STABLE + NEW_DIAG:
-        assert hasattr(L, n)
+    check_symbols(NEW_STABLE, NEW_DIAG, "gicp_align.hpp")
     # the structures as the headers lay them out
     assert C.sizeof(_lib.LMParams) == 6 * 8 + 2 * 4 + 8
     assert C.sizeof(_lib.AlignResult) == 12 * 8 + 8 + 8 + 4 * 4 + 8 + 29 * 8
@@ -83,16 +72,12 @@ def test_argument_errors_without_a_device():
 # ---- lm_step.hpp on the host ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lm_step_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("lm_step") / "test_lm_step")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "test_lm_step.cpp"), "-o", exe])
-    return exe
+    return build_driver(tmp_path_factory, "lm_step")
 
 
 def run_cpp(exe, tmp_path, p, T_init, records):
     """the C++ step rule over `records` (teacher-forced: record k is what round k evaluated) -> one dict per round"""
-    head = [p[k] for k in ("lambda_initial", "lambda_factor", "lambda_upper_bound", "lambda_lower_bound", "relative_error_tol", "absolute_error_tol")]
-    head += [float(p["max_iterations"]), float(p["max_trials"]), p["error_scale"]]
-    data = np.concatenate([head, np.asarray(T_init)[:3].reshape(-1), [float(len(records))]] + [lmr.compact_of_record(L) for L in records])
+    data = np.concatenate([params_head(p), np.asarray(T_init)[:3].reshape(-1), [float(len(records))]] + [lmr.compact_of_record(L) for L in records])
     fin, fout = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
     data.astype(np.float64).tofile(fin)
     out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=60)
@@ -101,25 +86,6 @@ def run_cpp(exe, tmp_path, p, T_init, records):
     pose = lambda v: np.vstack([v.reshape(3, 4), [0, 0, 0, 1]])
     return [{"T": pose(r[0:12]), "cand": pose(r[12:24]), "delta": r[24:30], "lam": r[30], "solve_ok": bool(r[31]), "iterations": int(r[32]),
              "trials": int(r[33]), "status": int(r[34]), "accepted": bool(r[35])} for r in rows]
-
-
-def check_against_restatement(rows, trace):
-    """Decisions, counts, statuses and lambda are equal (lambda moves by one division or multiplication per round: the same double on both sides);
-    the step is within the self-scaled gate of lm_restatement.solve -- 100 cond(H + lambda I) eps max(|delta|, 1e-12), from the reference's own
-    matrix -- and the poses within what that step error does to T Exp(delta): rotation entries and V v move by at most (1 + |delta|) times the
-    step error per entry summed over 3 products, plus the rounding of the 3 x 4 product itself."""
-    assert len(rows) == len(trace)
-    for k, (got, ref) in enumerate(zip(rows, trace)):
-        s = ref["state"]
-        assert (got["accepted"], got["status"], got["iterations"], got["trials"]) == (s["accepted"], s["status"], s["iterations"], s["trials"]), k
-        assert got["lam"] == s["lam"], k
-        if s["status"] != lmr.RUNNING:
-            continue
-        assert got["solve_ok"] == s["solve_ok"], k
-        assert np.abs(got["delta"] - s["delta"]).max() <= s["gate"], (k, np.abs(got["delta"] - s["delta"]).max(), s["gate"])
-        pose_gate = 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * lmr.EPS * max(1.0, np.abs(s["cand"]).max())
-        assert np.abs(got["cand"] - s["cand"]).max() <= pose_gate, (k, np.abs(got["cand"] - s["cand"]).max(), pose_gate)
-        assert np.abs(got["T"] - s["T"]).max() <= pose_gate, k
 
 
 def oracle_linearize(orc, pair, max_d):
@@ -137,7 +103,7 @@ def test_lm_step_follows_the_restatement_over_an_oracle_driven_run(orc, small_pa
         p = lmr.params(**kw)
         final, trace = lmr.run(lin, T0, p)
         rows = run_cpp(lm_step_exe, tmp_path, p, T0, [e["record"] for e in trace])
-        check_against_restatement(rows, trace)
+        check_against_restatement(rows, [e["state"] for e in trace])
         assert final["status"] in (lmr.CONVERGED, lmr.MAX_ITERATIONS, lmr.MAX_TRIALS, lmr.LAMBDA_BOUND) and final["iterations"] >= 1
     # the default run ends near the planted motion (at the lambda bound: once the steps are too small to lower the error, every trial is rejected)
     final, trace = lmr.run(lin, T0)
@@ -168,12 +134,12 @@ def test_lm_step_rejects_and_stops_at_the_lambda_bound(orc, small_pair, lm_step_
     final, trace = lmr.run(rising(lin, {1}), T0, p)
     assert [e["accepted"] for e in trace[:3]] == [True, False, True] and trace[1]["state"]["lam"] == 1e4 and final["iterations"] >= 1
     assert np.array_equal(trace[1]["state"]["T"], T0) and trace[2]["lam"] == 1e4
-    check_against_restatement(run_cpp(lm_step_exe, tmp_path, p, T0, [e["record"] for e in trace]), trace)
+    check_against_restatement(run_cpp(lm_step_exe, tmp_path, p, T0, [e["record"] for e in trace]), [e["state"] for e in trace])
     # every trial rises: 1e3 -> 1e4 -> 1e5 -> 1e6 > the bound
     final, trace = lmr.run(rising(lin, set(range(1, 30))), T0, p)
     assert final["status"] == lmr.LAMBDA_BOUND and final["trials"] == 3 and final["iterations"] == 0 and np.array_equal(final["T"], T0)
     rows = run_cpp(lm_step_exe, tmp_path, p, T0, [e["record"] for e in trace])
-    check_against_restatement(rows, trace)
+    check_against_restatement(rows, [e["state"] for e in trace])
     assert rows[-1]["status"] == lmr.LAMBDA_BOUND and np.array_equal(rows[-1]["T"][:3], T0[:3])
 
 
@@ -196,10 +162,10 @@ def test_lm_step_failed_solve_is_a_rejected_trial(orc, small_pair, lm_step_exe, 
         T, lam = s["cand"], s["lam"]
         s = lmr.step(p, s, L)
         trace.append({"T": T, "lam": lam, "record": L, "accepted": s["accepted"], "status": s["status"], "state": s})
-    assert not lmr.solve(records[0], 0.0)[0]
+    assert not lmr.solve(records[0]["H_ss"], records[0]["b_s"], 0.0)[0]
     assert [e["accepted"] for e in trace] == [True, False, False, False, False] and s["status"] == lmr.MAX_TRIALS and s["iterations"] == 0
     rows = run_cpp(lm_step_exe, tmp_path, p, T0, records)
-    check_against_restatement(rows, trace)
+    check_against_restatement(rows, [e["state"] for e in trace])
     assert all(not r["solve_ok"] for r in rows[:-1]) and all(np.array_equal(r["cand"][:3], T0[:3]) for r in rows)
 
 

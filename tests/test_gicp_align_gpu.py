@@ -1,7 +1,6 @@
 """GICP fine registration on the device (include/glim_amd.h "GICP fine registration", glim_amd/csrc/gicp_align.hip): every trial record is the bits
 of IntegratedGICPFactor.linearize at the trial's pose (the partition invariant), the decisions are those of tests/lm_restatement.py, a problem's
 result does not depend on the batch it runs in."""
-import os
 import struct
 import subprocess
 
@@ -9,14 +8,12 @@ import numpy as np
 import pytest
 
 import lm_restatement as lmr
-from test_gicp import POSE_TOL, clouds, rigid_edge_sizes, rigid_edge_subset
+from align_cases import PERT_A, RECORD_TOL, api_params, build_cpp, ctx, packed, pair, same_record, same_result, teacher_forced  # noqa: F401 (ctx: a fixture)
+from test_gicp import POSE_TOL, rigid_edge_sizes, rigid_edge_subset
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RECORD_TOL = 2e-4  # of a device record against the FP64 oracle (tests/test_gicp.py)
 END_GATE = (0.02, 2e-3)  # test_hip_gicp_alignment_converges_like_the_oracle: metres, rotation entries, against the planted motion
 
-PERT_A = [0.01, -0.01, 0.01, 0.08, -0.05, 0.03]
 # (rings, az, perturbation of the planted motion, max_correspondence_distance, parameters).  Chosen with the oracle on the CPU: in all but the last
 # every trial moves the error by more than 5e-3 of itself, far from the record tolerance; the last runs the defaults to the end, where the steps
 # become smaller than that tolerance by the nature of convergence -- the one case that may use the allowance of test 2.
@@ -35,74 +32,16 @@ REJECT_CASE = (16, 128, [-0.002, -0.019, -0.029, 0.086, -0.219, 0.142], 0.3, dic
 MEASURED_VS_ORACLE = (1.295e-07, 7.286e-08)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from glim_amd import api
-
-    return api.Context(0, 1)
-
-
-_PAIRS = {}
-
-
-def pair(orc, ctx, rings, az):
-    """the two scans of tests/test_gicp.py::clouds at a size, built once per module"""
-    from glim_amd import api
-
-    if (rings, az) not in _PAIRS:
-        _PAIRS[(rings, az)] = clouds(orc, api, ctx, rings=rings, az=az)
-    return _PAIRS[(rings, az)]
-
-
-def api_params(kw):
-    from glim_amd import api
-
-    return api.LMParams(**kw)
-
-
-def same_record(compact, T, L):
-    from glim_amd import api
-
-    ex = api.expand_compact(compact, T, 0)
-    return ex["num_inliers"] == L["num_inliers"] and ex["error"] == L["error"] and np.array_equal(ex["H_ss"], L["H_ss"]) and np.array_equal(ex["b_s"], L["b_s"])
-
-
-def same_result(a, b):
-    return (np.array_equal(a.T_target_source, b.T_target_source) and a.error == b.error and a.num_inliers == b.num_inliers and
-            (a.iterations, a.trials, a.status) == (b.iterations, b.trials, b.status) and a.lam == b.lam and np.array_equal(a.compact, b.compact))
-
-
-def pose_gate(s):
-    """lm_restatement's self-scaled gate on the step, carried to T Exp(delta) (tests/test_gicp_align.py::check_against_restatement)"""
-    return 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * lmr.EPS * max(1.0, np.abs(s["cand"]).max())
-
-
-def teacher_forced(factor, result, trace, T0, p):
-    """test 1 for one problem: every trace record is the factor's record at the trace's pose, bit for bit; the restatement, fed that record from
-    the device's own previous state, takes the same decision and proposes the same next pose"""
-    s = lmr.new_state(T0, p)
-    assert len(trace) == result.trials + 1
-    for k, e in enumerate(trace):
-        L = factor.linearize({1: e["T"]})
-        assert same_record(e["compact"], e["T"], L), k
-        assert e["lam"] == s["lam"], k
-        if k == 0:
-            assert np.array_equal(e["T"], T0)
-        else:
-            assert np.abs(e["T"] - s["cand"]).max() <= pose_gate(s), (k, np.abs(e["T"] - s["cand"]).max(), pose_gate(s))
-        s["cand"] = e["T"]  # teacher forcing: the device's pose is the one the record belongs to
-        s = lmr.step(p, s, L)
-        assert (e["accepted"], e["status"]) == (s["accepted"], s["status"]), k
-    assert s["status"] != lmr.RUNNING and (result.status, result.iterations, result.trials) == (s["status"], s["iterations"], s["trials"])
-    assert np.array_equal(result.T_target_source, s["T"]) and result.lam == s["lam"]
-    return s
+def factor_records(f):
+    """the batch of one of align_cases.teacher_forced: the factor's own record at the round's pose"""
+    return lambda poses: [f.linearize({1: poses[0]})]
 
 
 @pytest.mark.parametrize("kind", ["index", "ivox1", "ivox7"])
 def test_every_trial_is_the_factor_record_and_the_restatement_decision(orc, ctx, kind):
     from glim_amd import api
 
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, 32, 384)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (32, 384))
     T0 = delta @ orc.se3_exp(PERT_A)
     if kind == "index":
         target = tg
@@ -111,7 +50,7 @@ def test_every_trial_is_the_factor_record_and_the_restatement_decision(orc, ctx,
     f = api.IntegratedGICPFactor(np.eye(4), 1, target, sg, max_correspondence_distance=0.5)
     for kw in (dict(), dict(lambda_initial=1e-12, max_iterations=3)):
         results, traces = api.gicp_align_debug_trace([f.target_tree], [sg], [T0], 0.5, api_params(kw))
-        s = teacher_forced(f, results[0], traces[0], T0, lmr.params(**kw))
+        s = teacher_forced(factor_records(f), results, traces, [T0], lmr.params(**kw))[0]
         print(kind, kw, "status", results[0].status_name, "iterations", results[0].iterations, "trials", results[0].trials, "inliers", results[0].num_inliers)
         assert s["iterations"] >= 1 and results[0].num_inliers > 100
         assert same_result(results[0], f.align(T0, api_params(kw)))  # the B = 1 form of the factor, without the trace
@@ -126,7 +65,7 @@ def end_to_end(orc, ctx):
 
     out = []
     for rings, az, pert, max_d, kw in CASES:
-        ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, rings, az)
+        ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (rings, az))
         T0 = delta @ orc.se3_exp(pert)
         f = api.IntegratedGICPFactor(np.eye(4), 1, tg, sg, max_correspondence_distance=max_d)
         p = lmr.params(**kw)
@@ -185,7 +124,7 @@ def test_a_rejected_trial_on_the_device(orc, ctx):
     from glim_amd import api
 
     rings, az, pert, max_d, kw = REJECT_CASE
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, rings, az)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (rings, az))
     T0 = delta @ orc.se3_exp(pert)
     p = lmr.params(**kw)
     _, ref = lmr.run(lambda T: orc.gicp_linearize(tp, tc, sp, sc, T, max_d), T0, p)
@@ -196,7 +135,7 @@ def test_a_rejected_trial_on_the_device(orc, ctx):
     assert [e["accepted"] for e in traces[0]] == accepted
     assert traces[0][4]["lam"] == traces[0][3]["lam"] * 10  # the next candidate is solved from the kept record with the new lambda
     assert results[0].status == ref[-1]["status"] and results[0].iterations == 2
-    teacher_forced(f, results[0], traces[0], T0, p)
+    teacher_forced(factor_records(f), results, traces, [T0], p)
     f.close()
 
 
@@ -210,7 +149,7 @@ def problems(orc, ctx):
     1 km away.  Each with its result when run alone."""
     from glim_amd import api
 
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, 32, 384)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (32, 384))
     owner = api.IntegratedGICPFactor(np.eye(4), 1, tg, sg, max_correspondence_distance=1.0)
     sizes = rigid_edge_sizes(ctx.device_info()["num_cus"])
     assert sizes[:4] == [1, 255, 256, 257]
@@ -280,7 +219,7 @@ def test_two_calls_and_a_second_context_return_the_same_bytes(orc, ctx, problems
     from glim_amd import api
 
     plist, alone, prm = problems
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, 32, 384)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (32, 384))
     idx = [0, 1, 2, 9]
     args = lambda t, s: ([t] * len(idx), [s] * len(idx), [plist[i][2] for i in idx], [plist[i][3] for i in idx], prm)
     a = api.gicp_align_batch(*args(tg, sg))
@@ -298,7 +237,7 @@ def test_two_calls_and_a_second_context_return_the_same_bytes(orc, ctx, problems
 def test_argument_errors_with_real_handles(orc, ctx):
     from glim_amd import api
 
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, 16, 128)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (16, 128))
     owner = api.IntegratedGICPFactor(np.eye(4), 1, tg, sg, max_correspondence_distance=1.0)
     ivox = api.IncrementalVoxelMap(1.0, ctx=ctx).insert(tg)
     valid = lambda: api.gicp_align_batch([owner.target_tree], [sg], [delta], 1.0)[0]
@@ -333,7 +272,7 @@ def test_argument_errors_with_real_handles(orc, ctx):
 def test_the_returned_record_is_the_linearisation_at_the_estimate(orc, ctx):
     from glim_amd import api
 
-    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, 24, 256)
+    ((tp, tc, tg), (sp, sc, sg)), delta = pair(orc, ctx, (24, 256))
     T0 = delta @ orc.se3_exp(PERT_A)
     f = api.IntegratedGICPFactor(np.eye(4), 1, tg, sg, max_correspondence_distance=0.5)
     b = api.IntegratedGICPFactor(0, 1, tg, sg, target_tree=f.target_tree, max_correspondence_distance=0.5)
@@ -348,26 +287,11 @@ def test_the_returned_record_is_the_linearisation_at_the_estimate(orc, ctx):
     f.close()
 
 
-def build_cpp(tmp_path):
-    exe = str(tmp_path / "test_gicp_align")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_gicp_align.cpp"),
-                           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64"])
-    return exe
-
-
 def test_cpp_mirror_returns_the_python_result(orc, ctx, tmp_path):
     """tests/cpp/test_gicp_align.cpp calls glim_amd::align_gicp (batch and single form) on clouds it uploads itself from the dumped arrays"""
     from glim_amd import api
 
-    ((tp, tc, _), (sp, sc, _)), delta = pair(orc, ctx, 16, 128)
-
-    def packed(p, c):
-        p4 = np.ones((len(p), 4))
-        p4[:, :3] = p
-        m = np.zeros((len(p), 4, 4))
-        m[:, :3, :3] = c
-        return p4, np.ascontiguousarray(np.transpose(m, (0, 2, 1))).reshape(len(p), 16)
+    ((tp, tc, _), (sp, sc, _)), delta = pair(orc, ctx, (16, 128))
 
     (tp4, tc16), (sp4, sc16) = packed(tp, tc), packed(sp, sc)
     tg, sg = api.PointCloudGPU.clone_packed(tp4, tc16, ctx=ctx), api.PointCloudGPU.clone_packed(sp4, sc16, ctx=ctx)
@@ -382,5 +306,5 @@ def test_cpp_mirror_returns_the_python_result(orc, ctx, tmp_path):
             row = np.concatenate([api.pose12(r.T_target_source), [r.error, r.inlier_fraction, r.iterations, r.trials, r.status], r.linearized()["H_ss"].reshape(-1)])
             assert row.shape == (53,)
             fh.write(row.astype(np.float64).tobytes())
-    out = subprocess.run([build_cpp(tmp_path), str(path)], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([build_cpp(tmp_path, "gicp_align"), str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and f"test_gicp_align OK ({len(tp)} x {len(sp)} points, 2 problems)" in out.stdout, out.stdout + out.stderr

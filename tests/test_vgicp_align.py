@@ -1,34 +1,22 @@
 """VGICP fine registration (include/glim_amd.h "VGICP fine registration"), the part that needs no device: the ABI surface, the default parameters
 and the argument errors that are answered before any HIP call.  The step rule itself is tests/cpp/test_lm_step.cpp's (tests/test_gicp_align.py)."""
 import ctypes as C
-import os
-import re
 import subprocess
 
 import numpy as np
 
 import lm_restatement as lmr
+from align_cases import build_cpp, check_symbols
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_STABLE = ["glim_amd_vgicp_align_default_params", "glim_amd_vgicp_align_batch"]
 NEW_DIAG = ["glim_amd_debug_vgicp_align_trace"]
 INVALID = -1
 
 
 def test_new_symbols_are_declared_once_and_listed():
-    from glim_amd import _lib
-
-    decl = {h: set(re.findall(r"\b(glim_amd_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", h)).read())) for h in ("glim_amd.h", "glim_amd_diag.h")}
-    for n in NEW_STABLE:
-        assert n in decl["glim_amd.h"] and n not in decl["glim_amd_diag.h"] and n in _lib.SYMBOLS, n
-    for n in NEW_DIAG:
-        assert n in decl["glim_amd_diag.h"] and n not in decl["glim_amd.h"] and n in _lib.SYMBOLS, n
-    mirror = open(os.path.join(ROOT, "include", "glim_amd", "vgicp_align.hpp")).read()
-    assert "glim_amd_diag.h" not in mirror and "glim_amd_debug_" not in mirror and "glim_amd_vgicp_align_batch" in mirror
+    mirror = check_symbols(NEW_STABLE, NEW_DIAG, "vgicp_align.hpp")
+    assert "glim_amd_vgicp_align_batch" in mirror
     assert '#include "gicp_align.hpp"' in mirror  # LMParams, AlignResult and, through it, the wrappers of gtsam_points_compat.hpp
-    L = _lib.lib()
-    for n in NEW_STABLE + NEW_DIAG:
-        assert hasattr(L, n)
     from glim_amd import api
 
     for n in ("vgicp_align_batch", "vgicp_align_debug_trace"):
@@ -82,19 +70,8 @@ def test_argument_errors_without_a_device():
     assert api.vgicp_align_batch([], [], []) == []
 
 
-def build_cpp(tmp_path):
-    from glim_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH)
-    exe = str(tmp_path / "test_vgicp_align")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_vgicp_align.cpp"),
-                           "-o", exe, "-L" + os.path.join(ROOT, "glim_amd"), "-lglim_amd", "-Wl,-rpath," + os.path.join(ROOT, "glim_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-L/opt/rocm/lib", "-lamdhip64"])
-    return exe
-
-
 def test_cpp_mirror_compiles_links_and_answers_without_a_device(tmp_path):
     """include/glim_amd/vgicp_align.hpp over the wrappers of gtsam_points_compat.hpp: compiled, linked, and run without a case (the defaults and
     an empty batch: no device call)"""
-    out = subprocess.run([build_cpp(tmp_path)], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([build_cpp(tmp_path, "vgicp_align")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "test_vgicp_align OK (no case given: nothing run)" in out.stdout, out.stdout + out.stderr

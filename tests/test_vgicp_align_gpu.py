@@ -14,24 +14,19 @@ The cases were chosen on the CPU with lm_restatement.run over orc.vgicp_lineariz
   CASES       every trial of every case moves the error by more than 5e-3 of itself (smallest: 0.0168); see the list
 The device's clouds carry the device's own FP32 covariances, so each test that rests on such a condition asserts it again on the oracle run it
 makes itself."""
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import align_cases
 import lm_restatement as lmr
+from align_cases import (BIG, MOVES, PERT_A, PERT_B, PERT_C, PERT_D, RECORD_TOL, SMALL, api_params, build_cpp, ctx, moves, packed, pair,  # noqa: F401 (ctx: a fixture)
+                         same_record, same_result, vmap)
 from test_gicp import POSE_TOL, clouds
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RECORD_TOL = 2e-4  # of a device record against the FP64 oracle (tests/test_gpu_parity.py)
-SMALL, BIG = (16, 128), (32, 384)
-PERT_A = [0.01, -0.01, 0.01, 0.08, -0.05, 0.03]
-PERT_B = [0.02, 0.01, -0.015, 0.15, -0.1, 0.05]
-PERT_C = [0.03, -0.02, 0.02, 0.2, 0.15, -0.05]
-PERT_D = [0.015, 0.001, 0.026, -0.217, 0.171, -0.217]
 THREE = dict(max_iterations=3)
 REJECT_CASE = (SMALL, 0.5, PERT_B, THREE)
 # test 3: (size, resolution, perturbation, parameters) -- the oracle's trials on the CPU:
@@ -42,59 +37,6 @@ CASES = [
     (BIG, 0.5, PERT_B, dict(relative_error_tol=5e-2)),    # AAA rel -0.969 -0.0312: CONVERGED
     (BIG, 1.0, PERT_D, dict(relative_error_tol=5e-2)),    # AAA rel -0.975 -0.0320: CONVERGED
 ]
-MOVES = 5e-3
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from glim_amd import api
-
-    return api.Context(0, 1)
-
-
-_PAIRS, _MAPS = {}, {}
-
-
-def pair(orc, ctx, size):
-    """the two scans of tests/test_gicp.py::clouds at a size, built once per module"""
-    from glim_amd import api
-
-    if size not in _PAIRS:
-        _PAIRS[size] = clouds(orc, api, ctx, rings=size[0], az=size[1])
-    return _PAIRS[size]
-
-
-def vmap(orc, ctx, size, res):
-    """the device voxel map of the target scan of a size at a resolution, built once per module"""
-    from glim_amd import api
-
-    if (size, res) not in _MAPS:
-        ((tp, tc, tg), _), _ = pair(orc, ctx, size)
-        _MAPS[(size, res)] = api.GaussianVoxelMapGPU(res, ctx=ctx).insert(tg)
-    return _MAPS[(size, res)]
-
-
-def api_params(kw):
-    from glim_amd import api
-
-    return api.LMParams(**kw)
-
-
-def same_record(compact, T, L):
-    from glim_amd import api
-
-    ex = api.expand_compact(compact, T, 0)
-    return ex["num_inliers"] == L["num_inliers"] and ex["error"] == L["error"] and np.array_equal(ex["H_ss"], L["H_ss"]) and np.array_equal(ex["b_s"], L["b_s"])
-
-
-def same_result(a, b):
-    return (np.array_equal(a.T_target_source, b.T_target_source) and a.error == b.error and a.num_inliers == b.num_inliers and
-            (a.iterations, a.trials, a.status) == (b.iterations, b.trials, b.status) and a.lam == b.lam and np.array_equal(a.compact, b.compact))
-
-
-def pose_gate(s):
-    """lm_restatement's self-scaled gate on the step, carried to T Exp(delta) (tests/test_gicp_align.py::check_against_restatement)"""
-    return 3 * (1 + np.abs(s["delta"]).max()) * s["gate"] + 16 * lmr.EPS * max(1.0, np.abs(s["cand"]).max())
 
 
 def factor_set(ctx, targets, sources, flags):
@@ -110,45 +52,10 @@ def factor_set(ctx, targets, sources, flags):
 
 
 def teacher_forced(fset, results, traces, T0s, p):
-    """test 1 for one batch: every trace record is the set's record at the trace's poses, bit for bit; the restatement, fed that record from the
-    device's own previous state, takes the same decision and proposes the same next pose.  Round k of the batch is ONE linearize_poses of the
-    set; a problem that has finished keeps its last pose there (its record is not looked at)."""
+    """align_cases.teacher_forced with round k of the batch as ONE linearize_poses of the caller's set"""
     from glim_amd import api
 
-    B = len(results)
-    states = [lmr.new_state(T0, p) for T0 in T0s]
-    for i in range(B):
-        assert len(traces[i]) == results[i].trials + 1
-    for k in range(max(len(t) for t in traces)):
-        poses = [traces[i][min(k, len(traces[i]) - 1)]["T"] for i in range(B)]
-        records = fset.linearize_poses(np.stack([api.pose12(T) for T in poses]))
-        for i in range(B):
-            if k >= len(traces[i]):
-                continue
-            e, s, L = traces[i][k], states[i], records[i]
-            assert same_record(e["compact"], e["T"], L), (i, k)
-            assert e["lam"] == s["lam"], (i, k)
-            if k == 0:
-                assert np.array_equal(e["T"], T0s[i])
-            else:
-                assert np.abs(e["T"] - s["cand"]).max() <= pose_gate(s), (i, k, np.abs(e["T"] - s["cand"]).max(), pose_gate(s))
-            s["cand"] = e["T"]  # teacher forcing: the device's pose is the one the record belongs to
-            s = states[i] = lmr.step(p, s, L)
-            assert (e["accepted"], e["status"]) == (s["accepted"], s["status"]), (i, k)
-    for i, (s, r) in enumerate(zip(states, results)):
-        assert s["status"] != lmr.RUNNING and (r.status, r.iterations, r.trials) == (s["status"], s["iterations"], s["trials"]), i
-        assert np.array_equal(r.T_target_source, s["T"]) and r.lam == s["lam"], i
-        assert same_record(r.compact, r.T_target_source, s["rec"]) and r.error == s["rec"]["error"] and r.num_inliers == s["rec"]["num_inliers"], i
-    return states
-
-
-def moves(trace):
-    """|e_new - e_cur| / e_cur of every trial of a restatement trace"""
-    out, e_cur = [], trace[0]["record"]["error"]
-    for e in trace[1:]:
-        out.append(abs(e["record"]["error"] - e_cur) / e_cur)
-        e_cur = e["state"]["rec"]["error"]
-    return out
+    return align_cases.teacher_forced(lambda poses: fset.linearize_poses(np.stack([api.pose12(T) for T in poses])), results, traces, T0s, p)
 
 
 # ---- 1. the teacher-forced trace ---------------------------------------------------------------------------------------------------------
@@ -396,16 +303,8 @@ def test_a_resident_session_of_the_context_is_left_alone(orc):
 def test_cpp_mirror_returns_the_python_result(orc, ctx, tmp_path):
     """tests/cpp/test_vgicp_align.cpp calls glim_amd::align_vgicp (batch and single form) on clouds it uploads itself from the dumped arrays"""
     from glim_amd import api
-    from test_vgicp_align import build_cpp
 
     ((tp, tc, _), (sp, sc, _)), delta = pair(orc, ctx, SMALL)
-
-    def packed(p, c):
-        p4 = np.ones((len(p), 4))
-        p4[:, :3] = p
-        m = np.zeros((len(p), 4, 4))
-        m[:, :3, :3] = c
-        return p4, np.ascontiguousarray(np.transpose(m, (0, 2, 1))).reshape(len(p), 16)
 
     (tp4, tc16), (sp4, sc16) = packed(tp, tc), packed(sp, sc)
     tg, sg = api.PointCloudGPU.clone_packed(tp4, tc16, ctx=ctx), api.PointCloudGPU.clone_packed(sp4, sc16, ctx=ctx)
@@ -422,5 +321,5 @@ def test_cpp_mirror_returns_the_python_result(orc, ctx, tmp_path):
             row = np.concatenate([api.pose12(r.T_target_source), [r.error, r.inlier_fraction, r.iterations, r.trials, r.status], r.linearized()["H_ss"].reshape(-1)])
             assert row.shape == (53,)
             fh.write(row.astype(np.float64).tobytes())
-    out = subprocess.run([build_cpp(tmp_path), str(path)], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([build_cpp(tmp_path, "vgicp_align"), str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and f"test_vgicp_align OK ({len(tp)} x {len(sp)} points, 2 problems)" in out.stdout, out.stdout + out.stderr
