@@ -6,6 +6,8 @@
 //       -> glim_amd::IntegratedVGICPFactorHIP            (a gtsam::NonlinearFactor: error / linearize / dim / clone + the extras GLIM calls)
 //   gtsam_points::IntegratedGICPFactor(...)                                                            sub_mapping.cpp:202, global_mapping.cpp:400
 //       -> glim_amd::IntegratedGICPFactorHIP
+//   gtsam_points::IntegratedICPFactor(...), IntegratedPointToPlaneICPFactor(...)                        manual_loop_close_modal.cpp:485-490
+//       -> glim_amd::IntegratedICPFactorHIP, glim_amd::IntegratedPointToPlaneICPFactorHIP
 //   gtsam_points::IntegratedCT_GICPFactor(X, Y, target, source, target_tree)                          odometry_estimation_ct.cpp:158-160
 //       -> glim_amd::IntegratedCT_GICPFactorHIP
 //   gtsam_points::NonlinearFactorSetGPU / create_nonlinear_factor_set_gpu()                            odometry_estimation_gpu.cpp:383-385, offline_viewer.cpp:29
@@ -38,6 +40,7 @@
 #include <gtsam_points/types/point_cloud.hpp>
 
 #include <glim_amd/gtsam_points_compat.hpp>
+#include <glim_amd/icp_align.hpp>
 
 // One of the three semantic choices that could not be checked against gtsam_points in the image this repository is developed in:
 // whether IntegratedVGICPFactor{,GPU}::error() returns E = sum r^T M r or E / 2.  H, b -- and with them every Gauss-Newton / LM step -- do not depend
@@ -226,6 +229,57 @@ private:
     return out;
   }
   std::shared_ptr<IntegratedGICPFactor> impl_;
+};
+
+// ---- gtsam_points::IntegratedICPFactor / IntegratedPointToPlaneICPFactor (manual_loop_close_modal.cpp:485-490) -----------
+// the GICP factor's search index and correspondences with the point-to-point (or point-to-plane) metric: neither cloud needs covariances
+class IntegratedICPFactorHIP : public gtsam::NonlinearFactor {
+public:
+  using shared_ptr = std::shared_ptr<IntegratedICPFactorHIP>;
+  IntegratedICPFactorHIP(gtsam::Key target_key, gtsam::Key source_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
+                         NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, bool use_point_to_plane = false)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{target_key, source_key}),
+    impl_(std::make_shared<IntegratedICPFactor>((Key)target_key, (Key)source_key, std::move(target), std::move(source), std::move(target_tree),
+                                                use_point_to_plane)) {}
+  IntegratedICPFactorHIP(const gtsam::Pose3& fixed_target_pose, gtsam::Key source_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
+                         NearestNeighborSearchGPU::ConstPtr target_tree = nullptr, bool use_point_to_plane = false)
+  : gtsam::NonlinearFactor(gtsam::KeyVector{source_key}),
+    impl_(std::make_shared<IntegratedICPFactor>(to_iso(fixed_target_pose), (Key)source_key, std::move(target), std::move(source), std::move(target_tree),
+                                                use_point_to_plane)) {}
+
+  size_t dim() const override { return 6; }
+  gtsam::NonlinearFactor::shared_ptr clone() const override {
+    auto f = std::make_shared<IntegratedICPFactorHIP>(*this);
+    f->impl_ = std::make_shared<IntegratedICPFactor>(*impl_);
+    return f;
+  }
+  void set_max_correspondence_distance(double d) { impl_->set_max_correspondence_distance(d); }
+  void set_num_threads(int n) { impl_->set_num_threads(n); }  // (no-op)
+  double inlier_fraction() const { return impl_->inlier_fraction(); }
+
+  gtsam::GaussianFactor::shared_ptr linearize(const gtsam::Values& values) const override {
+    return make_hessian_factor(keys(), impl_->is_binary(), impl_->linearize(to_values(values)));
+  }
+  double error(const gtsam::Values& values) const override { return impl_->error(to_values(values)); }
+
+private:
+  Values to_values(const gtsam::Values& values) const {
+    Values out;
+    for (const gtsam::Key k : keys()) out[(Key)k] = to_iso(values.at<gtsam::Pose3>(k));
+    return out;
+  }
+  std::shared_ptr<IntegratedICPFactor> impl_;
+};
+
+class IntegratedPointToPlaneICPFactorHIP : public IntegratedICPFactorHIP {
+public:
+  using shared_ptr = std::shared_ptr<IntegratedPointToPlaneICPFactorHIP>;
+  IntegratedPointToPlaneICPFactorHIP(gtsam::Key target_key, gtsam::Key source_key, PointCloudGPU::ConstPtr target, PointCloudGPU::ConstPtr source,
+                                     NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
+  : IntegratedICPFactorHIP(target_key, source_key, std::move(target), std::move(source), std::move(target_tree), true) {}
+  IntegratedPointToPlaneICPFactorHIP(const gtsam::Pose3& fixed_target_pose, gtsam::Key source_key, PointCloudGPU::ConstPtr target,
+                                     PointCloudGPU::ConstPtr source, NearestNeighborSearchGPU::ConstPtr target_tree = nullptr)
+  : IntegratedICPFactorHIP(fixed_target_pose, source_key, std::move(target), std::move(source), std::move(target_tree), true) {}
 };
 
 // ---- gtsam_points::IntegratedCT_GICPFactor (continuous time, point-cloud target) -------------------------------------------

@@ -363,6 +363,11 @@ SYMBOLS = {
     "glim_amd_gicp_align_batch": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_gicp_align_batch_incremental": (_i, [_pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_debug_gicp_align_trace": (_i, [_i32, _pp, _pp, _dp, _dp, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry)]),
+    "glim_amd_icp_linearize": (_i, [_vp, _vp, _dp, _d, _u32, C.POINTER(Linearized6)]),
+    "glim_amd_icp_error": (_i, [_vp, _vp, _dp, _d, _u32, _dp, _lp]),
+    "glim_amd_icp_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_icp_align_batch": (_i, [_pp, _pp, _dp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
+    "glim_amd_debug_icp_align_trace": (_i, [_pp, _pp, _dp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry), _i32]),
     "glim_amd_vgicp_align_default_params": (_i, [C.POINTER(LMParams)]),
     "glim_amd_vgicp_align_batch": (_i, [_pp, _pp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_debug_vgicp_align_trace": (_i, [_pp, _pp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry)]),

@@ -1283,6 +1283,53 @@ class IntegratedGICPFactor:
             pass
 
 
+ICP_POINT_TO_PLANE = 0x4  # GLIM_AMD_ICP_POINT_TO_PLANE
+
+
+class IntegratedICPFactor(IntegratedGICPFactor):
+    """gtsam_points::IntegratedICPFactor on the device (manual_loop_close_modal.cpp:485-490: the fine registration of clouds without
+    covariances).  The constructor forms, the methods and the correspondences are IntegratedGICPFactor's -- the same search index, so
+    `target_tree` may be shared with GICP factors -- over a PointCloudGPU target; neither cloud needs covariances.  use_point_to_plane:
+    IntegratedPointToPlaneICPFactor, which needs the target's normals."""
+
+    def __init__(self, target, source_key, target_frame, source_frame, max_correspondence_distance=1.0, use_point_to_plane=False, target_tree=None):
+        if any(isinstance(t, IncrementalVoxelMap) for t in (target_frame, target_tree)):
+            raise GlimAmdError(-1, "IntegratedICPFactor", "the ICP factors take a point-cloud target (a search index), not an iVox")
+        super().__init__(target, source_key, target_frame, source_frame, target_tree=target_tree, max_correspondence_distance=max_correspondence_distance)
+        self.use_point_to_plane = bool(use_point_to_plane)
+        self._linearize, self._error = "glim_amd_icp_linearize", "glim_amd_icp_error"
+
+    def flags(self):
+        return (FACTOR_BINARY if self.binary else 0) | (ICP_POINT_TO_PLANE if self.use_point_to_plane else 0)
+
+    def linearize(self, values):
+        L = Linearized6()
+        self._call(self._linearize, pose12(self.calc_delta(values)), self.flags(), C.byref(L))
+        out = _lin_to_dict(L)
+        self._inliers = out["num_inliers"]
+        return out
+
+    def error(self, values):
+        e, n = C.c_double(), C.c_int64()
+        self._call(self._error, pose12(self.calc_delta(values)), self.flags(), C.byref(e), C.byref(n))
+        self._inliers = n.value
+        return e.value
+
+    def align(self, T_init, params=None):
+        """The fine registration of this factor's pair from T_init (4 x 4 T_target_source): icp_align_batch with one problem."""
+        r = icp_align_batch([self._target], [self.source_frame], [T_init], self.max_correspondence_distance,
+                            ICP_POINT_TO_PLANE if self.use_point_to_plane else 0, params)[0]
+        self._inliers = r.num_inliers
+        return r
+
+
+class IntegratedPointToPlaneICPFactor(IntegratedICPFactor):
+    """gtsam_points::IntegratedPointToPlaneICPFactor: IntegratedICPFactor with use_point_to_plane."""
+
+    def __init__(self, target, source_key, target_frame, source_frame, max_correspondence_distance=1.0, target_tree=None):
+        super().__init__(target, source_key, target_frame, source_frame, max_correspondence_distance, True, target_tree)
+
+
 class LMParams:
     """glim_amd_lm_params (include/glim_amd.h "GICP fine registration"): GTSAM's LevenbergMarquardtParams fields the fine registration reads.
     max_trials = 0: twice max_iterations."""
@@ -1397,6 +1444,57 @@ def gicp_align_debug_trace(targets, sources, T_init, max_correspondence_distance
         trace = (_lib.AlignTraceEntry * max(n * rounds, 1))()
         check(lib().glim_amd_debug_gicp_align_trace(1 if ivox else 0, th, sh, _dp(T), _dp(dist), n, C.byref(prm), out, trace),
               "glim_amd_debug_gicp_align_trace")
+    finally:
+        for r in owned:
+            r.close()
+    results = [AlignResult(out[i], sources[i].size()) for i in range(n)]
+    return results, [_trace_rows(trace, i, rounds, r.trials) for i, r in enumerate(results)]
+
+
+def icp_align_params(**kw):
+    """LMParams with the ICP fine registration's value (glim_amd_icp_align_default_params): max_iterations 200 (manual_loop_close_modal.cpp:490)."""
+    p = dict(max_iterations=200)
+    p.update(kw)
+    return LMParams(**p)
+
+
+def _icp_align_args(targets, sources, T_init, max_correspondence_distance):
+    owned, ivox, th, sh, T, dist = _align_args(targets, sources, T_init, max_correspondence_distance)
+    if ivox:
+        raise GlimAmdError(-1, "icp_align_batch", "the ICP factors take point-cloud targets (search indices), not iVoxes")
+    return owned, th, sh, T, dist
+
+
+def icp_align_batch(targets, sources, T_init, max_correspondence_distance, flags=0, params=None):
+    """ICP fine registration of len(sources) independent problems in one call: Levenberg-Marquardt over one unary IntegratedICPFactor each
+    (manual_loop_close_modal.cpp:485-490, LM <= 200; params None: icp_align_params()).  targets[i]: a PointCloudGPU (its index is built here)
+    or a search-index handle; sources[i]: PointCloudGPU; no covariances needed; flags: 0 or ICP_POINT_TO_PLANE, for every problem.  At most
+    41 rounds are enqueued between two looks at the statuses.  Returns one AlignResult per problem."""
+    n = len(sources)
+    owned, th, sh, T, dist = _icp_align_args(targets, sources, T_init, max_correspondence_distance)
+    try:
+        prm = (params or icp_align_params())._c()
+        out = (_lib.AlignResult * max(n, 1))()
+        check(lib().glim_amd_icp_align_batch(th, sh, _dp(T), _dp(dist), int(flags), n, C.byref(prm), out), "glim_amd_icp_align_batch")
+    finally:
+        for r in owned:
+            r.close()
+    return [AlignResult(out[i], sources[i].size()) for i in range(n)]
+
+
+def icp_align_debug_trace(targets, sources, T_init, max_correspondence_distance, flags=0, params=None, rounds_per_chunk=0):
+    """Test window (glim_amd_debug_icp_align_trace): icp_align_batch's results plus, per problem, the rounds run, as gicp_align_debug_trace.
+    rounds_per_chunk: rounds enqueued between two looks at the statuses (0: the call's own 41; "all": every round up front)."""
+    n = len(sources)
+    params = params or icp_align_params()
+    owned, th, sh, T, dist = _icp_align_args(targets, sources, T_init, max_correspondence_distance)
+    rounds = 1 + params.resolved_max_trials()
+    chunk = rounds if rounds_per_chunk == "all" else int(rounds_per_chunk)
+    try:
+        prm = params._c()
+        out = (_lib.AlignResult * max(n, 1))()
+        trace = (_lib.AlignTraceEntry * max(n * rounds, 1))()
+        check(lib().glim_amd_debug_icp_align_trace(th, sh, _dp(T), _dp(dist), int(flags), n, C.byref(prm), out, trace, chunk), "glim_amd_debug_icp_align_trace")
     finally:
         for r in owned:
             r.close()

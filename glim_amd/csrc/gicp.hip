@@ -26,6 +26,10 @@
 // factor kernels take the target kind as a template parameter -- IndexSearch = the exact search above, IvoxSearch = the map's bounded search of
 // the voxels of its neighbour mode -- and share everything behind the correspondence.  What ivox.hip and gicp_align.hip use as well -- the
 // searches, the per-point algebra, the block epilogue, the target description -- is gicp_factor.hpp's; the map object is ivox_map.hpp's.
+//
+// The ICP factors (gtsam_points::IntegratedICPFactor, IntegratedPointToPlaneICPFactor; manual_loop_close_modal.cpp:485-490) are the rigid factor
+// with another metric: icp_kernel below runs the same search and epilogue over icp_factor.hpp's per-point algebra, through run_gicp with a metric
+// argument.  Neither cloud needs covariances; point-to-plane reads the target's normals through the original index of the matched point.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -34,6 +38,7 @@
 #include "ct_factor.hpp"
 #include "device_math.hpp"
 #include "gicp_factor.hpp"
+#include "icp_factor.hpp"
 #include "internal.hpp"
 #include "ivox_map.hpp"
 #include "scan.hpp"
@@ -152,6 +157,37 @@ __global__ __launch_bounds__(BLOCK) void gicp_kernel(const GicpArgs a, float* __
   store_partial_row(acc, inliers, s_red, partials);
 }
 
+// The ICP factors (IntegratedICPFactor, IntegratedPointToPlaneICPFactor; include/glim_amd.h "ICP factors") over a search index: gicp_kernel's
+// cut of the source, its search and its epilogue, with icp_factor.hpp's per-point algebra.  normals: the target cloud's, in its original order
+// (PLANE only)
+template <bool LINEARIZE, bool PLANE>
+__global__ __launch_bounds__(BLOCK) void icp_kernel(const GicpArgs a, const float4* __restrict__ normals, float* __restrict__ partials, int32_t* __restrict__ corr) {
+  __shared__ float s_red[4][PARTIAL_STRIDE];
+  const double* T = a.T;
+  const Rot32 R(T);
+  const IndexSearch nn{};
+  float acc[NACC];
+#pragma unroll
+  for (int j = 0; j < NACC; j++) acc[j] = 0.f;
+  int inliers = 0;
+  const int base = blockIdx.x * (BLOCK * a.ppt) + threadIdx.x;
+  for (int it = 0; it < a.ppt; it++) {
+    const int i = base + it * BLOCK;
+    if (i >= a.n) break;
+    const float4 p = a.pts[i];
+    double qx, qy, qz;
+    transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
+    double best_d;
+    const int j = nn.find(a, qx, qy, qz, best_d);
+    if (corr) corr[i] = j >= 0 ? __float_as_int(a.sorted[j].w) : -1;
+    if (j < 0) continue;
+    inliers++;
+    const float4 b = a.sorted[j];
+    icp_point<LINEARIZE, PLANE>(acc, R, p, b, PLANE ? icp_normal(normals, b) : make_float4(0.f, 0.f, 0.f, 0.f), qx, qy, qz);
+  }
+  store_partial_row(acc, inliers, s_red, partials);
+}
+
 // fixed-order FP64 sum of the block partials -> compact record (one block of 256 threads)
 __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restrict__ partials, int nb, int linearize, double* __restrict__ out) {
   __shared__ double s_part[8][PARTIAL_STRIDE];
@@ -255,13 +291,14 @@ inline int bits_for(int range) {
 }
 
 // one synchronous evaluation of the rigid factor over either kind of target; corr_host: n positions (original target index / the map's
-// slot * cap + place, or -1), or null
+// slot * cap + place, or -1), or null.  metric: the GICP factor (both clouds need covariances), or one of the ICP factors over a search index
+// (no covariances; point-to-plane needs the target's normals)
 int run_gicp(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, bool linearize, double* compact_host,
-             int32_t* corr_host) {
+             int32_t* corr_host, Metric metric = Metric::GICP) {
   if (!t.ctx || !source || !T12 || !(max_dist >= 0.0)) return GLIM_AMD_ERR_INVALID;
   if (source->ctx->device != t.ctx->device) return GLIM_AMD_ERR_INVALID;
   if (source->n > t.max_source) return GLIM_AMD_ERR_INVALID;
-  if (!source->has_covs || !t.usable) return GLIM_AMD_ERR_STATE;
+  GA_TRY(metric_state(metric, t, source));
   glim_amd_ctx* ctx = t.ctx;
   GA_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream();
@@ -283,10 +320,17 @@ int run_gicp(const GicpTarget& t, const glim_amd_cloud* source, const double* T1
   GA_HIP(pool_malloc(&partials.p, (size_t)nb * PARTIAL_STRIDE * sizeof(float)));
   GA_HIP(pool_malloc(&compact.p, COMPACT * sizeof(double)));
   if (corr_host) GA_HIP(pool_malloc(&corr.p, (size_t)n * sizeof(int32_t)));
-  with_search(t, [&](auto nn) {
-    if (linearize) gicp_kernel<true, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
-    else gicp_kernel<false, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
-  });
+  if (metric == Metric::GICP) {
+    with_search(t, [&](auto nn) {
+      if (linearize) gicp_kernel<true, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
+      else gicp_kernel<false, decltype(nn)><<<nb, BLOCK, 0, st>>>(a, partials.as<float>(), corr.as<int32_t>(), nn);
+    });
+  } else {
+    const bool plane = metric == Metric::ICP_PLANE;
+    auto launch = [&](auto kernel) { kernel<<<nb, BLOCK, 0, st>>>(a, t.normals, partials.as<float>(), corr.as<int32_t>()); };
+    if (linearize) plane ? launch(icp_kernel<true, true>) : launch(icp_kernel<true, false>);
+    else plane ? launch(icp_kernel<false, true>) : launch(icp_kernel<false, false>);
+  }
   gicp_finalize_kernel<<<1, 256, 0, st>>>(partials.as<float>(), nb, linearize ? 1 : 0, compact.as<double>());
   GA_HIP(hipGetLastError());
   GA_HIP(hipMemcpyAsync(compact_host, compact.p, COMPACT * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -297,16 +341,18 @@ int run_gicp(const GicpTarget& t, const glim_amd_cloud* source, const double* T1
 }
 
 // the three entry points of the rigid factor, over the description of either kind
-int gicp_linearize(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, uint32_t flags, glim_amd_linearized6* out) {
+int gicp_linearize(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, uint32_t flags, glim_amd_linearized6* out,
+                   Metric metric = Metric::GICP) {
   if (!out) return GLIM_AMD_ERR_INVALID;
   double compact[COMPACT];
-  GA_TRY(run_gicp(t, source, T12, max_dist, true, compact, nullptr));
+  GA_TRY(run_gicp(t, source, T12, max_dist, true, compact, nullptr, metric));
   return glim_amd_expand_compact(compact, T12, flags, out);
 }
 
-int gicp_error(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, double* error, int64_t* num_inliers) {
+int gicp_error(const GicpTarget& t, const glim_amd_cloud* source, const double* T12, double max_dist, double* error, int64_t* num_inliers,
+               Metric metric = Metric::GICP) {
   double compact[COMPACT];
-  GA_TRY(run_gicp(t, source, T12, max_dist, false, compact, nullptr));
+  GA_TRY(run_gicp(t, source, T12, max_dist, false, compact, nullptr, metric));
   if (error) *error = compact[1];
   if (num_inliers) *num_inliers = (int64_t)llround(compact[0]);
   return GLIM_AMD_OK;
@@ -518,7 +564,23 @@ int glim_amd_gicp_correspondences(const glim_amd_nn_index* target, const glim_am
                                   double max_correspondence_distance, int32_t* correspondences) {
   if (!correspondences) return GLIM_AMD_ERR_INVALID;
   double compact[COMPACT];
-  return run_gicp(gicp_target(target), source, T_target_source12, max_correspondence_distance, false, compact, correspondences);
+  // the correspondences are the search's alone: clouds without covariances (the ICP factors' case) get them through the point-to-point kernel
+  const GicpTarget t = gicp_target(target);
+  const bool covs = source && source->has_covs && t.usable;
+  return run_gicp(t, source, T_target_source12, max_correspondence_distance, false, compact, correspondences, covs ? Metric::GICP : Metric::ICP_POINT);
+}
+
+// IntegratedICPFactor / IntegratedPointToPlaneICPFactor over the GICP factor's search index
+int glim_amd_icp_linearize(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
+                           double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out) {
+  if (flags & ~(uint32_t)(GLIM_AMD_FACTOR_BINARY | GLIM_AMD_ICP_POINT_TO_PLANE)) return GLIM_AMD_ERR_INVALID;
+  return gicp_linearize(gicp_target(target), source, T_target_source12, max_correspondence_distance, flags & GLIM_AMD_FACTOR_BINARY, out, icp_metric(flags));
+}
+
+int glim_amd_icp_error(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
+                       double max_correspondence_distance, uint32_t flags, double* error, int64_t* num_inliers) {
+  if (flags & ~(uint32_t)(GLIM_AMD_FACTOR_BINARY | GLIM_AMD_ICP_POINT_TO_PLANE)) return GLIM_AMD_ERR_INVALID;
+  return gicp_error(gicp_target(target), source, T_target_source12, max_correspondence_distance, error, num_inliers, icp_metric(flags));
 }
 
 // IntegratedGICPFactor_<iVox, PointCloud>: the rigid factor over the map

@@ -13,6 +13,12 @@
 //   the call        1 + max_trials rounds are enqueued up front, then one copy of the states, then ONE hipStreamSynchronize.  No persistent
 //                   kernel, no grid-wide wait, no host decision in between; every loop in both kernels has a bound known at launch.
 //
+// The ICP fine registration (include/glim_amd.h "ICP fine registration") is the same scheme with the ICP factors' per-point algebra
+// (icp_factor.hpp) in the linearising kernel: icp_align_linearize_kernel, then the same decide kernel.  Its trial budget is 400, and an ICP loop
+// stops after a dozen or two trials, so its rounds are enqueued in chunks: at most 41 at a time, then the states are copied back and the call
+// stops enqueueing when no status is RUNNING.  The state lives on the device, so the chunk length moves no bit of a result; every other loop
+// of this file passes chunk 0 and keeps its single synchronisation.
+//
 // The VGICP fine registration (include/glim_amd.h "VGICP fine registration") is the same scheme over voxel-map targets.  The factor's hot loop,
 // its plan and its ordered sum live in vgicp.hip and stay there: a round is vgicp_batch_round (vgicp_batch.hpp: vgicp.hip's row kernels and
 // finalising blocks behind the status check, over a transient plan of the batch's pairs, leaving finished compact records on the device) and
@@ -40,6 +46,7 @@
 #include "ct_lm_step.hpp"
 #include "device_math.hpp"
 #include "gicp_factor.hpp"
+#include "icp_factor.hpp"
 #include "internal.hpp"
 #include "ivox_map.hpp"
 #include "lm_step.hpp"
@@ -63,6 +70,7 @@ struct AlignProblem {
   GicpArgs a;      // a.T is not used: the pose of a round is the state's candidate
   IvoxSearch nn;   // iVox targets only
   int first, nb;   // the problem's partial rows
+  const float4* normals;  // the target cloud's normals in its original order (the point-to-plane ICP factor only)
 };
 
 template <class NN>
@@ -104,6 +112,38 @@ __global__ __launch_bounds__(BLOCK) void align_linearize_kernel(const AlignProbl
     inliers++;
     float A[6];
     gicp_point<true>(acc, R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22, p, a.sorted[j], a.tA[j], a.tB[j], a.covA[i], a.covB[i], qx, qy, qz, A);
+  }
+  store_partial_row(acc, inliers, s_red, partials);
+}
+
+// icp_kernel<true, PLANE> (gicp.hip) over the blocks of every running problem, in the same way: the ICP fine registration
+template <bool PLANE>
+__global__ __launch_bounds__(BLOCK) void icp_align_linearize_kernel(const AlignProblem* __restrict__ table, const int4* __restrict__ blocks,
+                                                                    const lm::State* __restrict__ states, float* __restrict__ partials) {
+  __shared__ float s_red[4][PARTIAL_STRIDE];
+  const int4 blk = blocks[blockIdx.x];
+  if (states[blk.x].status != lm::RUNNING) return;  // the same for every thread of the block
+  const GicpArgs a = table[blk.x].a;
+  const float4* __restrict__ normals = table[blk.x].normals;
+  const IndexSearch nn{};
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = states[blk.x].cand[k];
+  const Rot32 R(T);
+  float acc[NACC];
+#pragma unroll
+  for (int j = 0; j < NACC; j++) acc[j] = 0.f;
+  int inliers = 0;
+  for (int i = blk.y + (int)threadIdx.x; i < blk.z; i += BLOCK) {
+    const float4 p = a.pts[i];
+    double qx, qy, qz;
+    transform_point_d(T, (double)p.x, (double)p.y, (double)p.z, qx, qy, qz);
+    double best_d;
+    const int j = nn.find(a, qx, qy, qz, best_d);
+    if (j < 0) continue;
+    inliers++;
+    const float4 b = a.sorted[j];
+    icp_point<true, PLANE>(acc, R, p, b, PLANE ? icp_normal(normals, b) : make_float4(0.f, 0.f, 0.f, 0.f), qx, qy, qz);
   }
   store_partial_row(acc, inliers, s_red, partials);
 }
@@ -463,6 +503,11 @@ void ct_default_params(glim_amd_lm_params* p) {
   p->max_iterations = 8;
 }
 
+void icp_default_params(glim_amd_lm_params* p) {
+  lm_default_params(p);
+  p->max_iterations = 200;  // manual_loop_close_modal.cpp:490
+}
+
 void bundle_default_params(glim_amd_lm_params* p) {
   lm_default_params(p);
   p->max_iterations = 20;
@@ -605,16 +650,22 @@ int run_ct_align(glim_amd_ct_gicp_factor* f, const double* X_init, const double*
   return GLIM_AMD_OK;
 }
 
-// the batch over either kind of target: Handle = glim_amd_nn_index or glim_amd_ivox.  trace: count * (1 + max_trials) entries, or null
+// the most rounds the ICP fine registration enqueues before it looks at the statuses: the most the other loops enqueue by default (1 + 2 x 20)
+constexpr int ICP_ROUNDS_PER_CHUNK = 41;
+
+// the batch over either kind of target: Handle = glim_amd_nn_index or glim_amd_ivox.  trace: count * (1 + max_trials) entries, or null.
+// metric: the factor of the loop (the ICP factors: an index only).  chunk: rounds enqueued between two looks at the statuses; 0: all of them up
+// front and ONE synchronisation.  The state lives on the device: the chunk length moves no bit of a result.
 template <class Handle>
 int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources, const double* T_init12, const double* max_dists, int32_t count,
-              const glim_amd_lm_params* params, glim_amd_align_result* out, glim_amd_align_trace_entry* trace_host) {
+              const glim_amd_lm_params* params, glim_amd_align_result* out, glim_amd_align_trace_entry* trace_host, Metric metric = Metric::GICP,
+              int chunk = 0, void (*defaults)(glim_amd_lm_params*) = lm_default_params) {
   if (count < 0) return GLIM_AMD_ERR_INVALID;
   if (count == 0) return GLIM_AMD_OK;
   if (!targets || !sources || !T_init12 || !max_dists || !out) return GLIM_AMD_ERR_INVALID;
   lm::Params prm;
   int rounds;
-  GA_TRY(resolve_params(params, lm_default_params, &prm, &rounds));
+  GA_TRY(resolve_params(params, defaults, &prm, &rounds));
   for (int i = 0; i < count; i++)
     if (!(max_dists[i] >= 0.0)) return GLIM_AMD_ERR_INVALID;
   glim_amd_ctx* ctx = one_context(targets, sources, count, nullptr);
@@ -629,7 +680,7 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
     const GicpTarget t = gicp_target(targets[i], false);
     const glim_amd_cloud* source = sources[i];
     if (source->n > t.max_source) return GLIM_AMD_ERR_INVALID;
-    if (!source->has_covs || !t.usable) return GLIM_AMD_ERR_STATE;
+    GA_TRY(metric_state(metric, t, source));
     if (source->n == 0 || t.empty) return GLIM_AMD_ERR_INVALID;
     const int max_ring = t.rings(max_dists[i]);
     if (max_ring < 0) return GLIM_AMD_ERR_UNSUPPORTED;
@@ -637,6 +688,7 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
     AlignProblem& pr = table[(size_t)i];
     memset(&pr, 0, sizeof(pr));
     pr.a = t.args;
+    pr.normals = t.normals;
     const int n = (int)source->n;
     set_source(&pr.a, source, points_per_thread(ctx, n), max_dists[i]);
     pr.a.max_ring = max_ring;
@@ -662,14 +714,23 @@ int run_align(const Handle* const* targets, const glim_amd_cloud* const* sources
   GA_HIP(hipMemcpyAsync(d_table.p, table.data(), table.size() * sizeof(AlignProblem), hipMemcpyHostToDevice, st));
   GA_HIP(hipMemcpyAsync(d_blocks.p, blocks.data(), blocks.size() * sizeof(int4), hipMemcpyHostToDevice, st));
   GA_HIP(hipMemcpyAsync(d_states.p, states.data(), states.size() * sizeof(lm::State), hipMemcpyHostToDevice, st));
-  for (int r = 0; r < rounds; r++) {
-    if (ivox) align_linearize_kernel<IvoxSearch><<<nb, BLOCK, 0, st>>>(d_table.as<AlignProblem>(), d_blocks.as<int4>(), d_states.as<lm::State>(), d_partials.as<float>());
-    else align_linearize_kernel<IndexSearch><<<nb, BLOCK, 0, st>>>(d_table.as<AlignProblem>(), d_blocks.as<int4>(), d_states.as<lm::State>(), d_partials.as<float>());
-    align_decide_kernel<<<count, 256, 0, st>>>(d_table.as<AlignProblem>(), d_partials.as<float>(), d_states.as<lm::State>(), prm,
-                                               trace.d.as<glim_amd_align_trace_entry>(), r, rounds);
+  auto linearize = align_linearize_kernel<IndexSearch>;
+  if (ivox) linearize = align_linearize_kernel<IvoxSearch>;
+  else if (metric == Metric::ICP_POINT) linearize = icp_align_linearize_kernel<false>;
+  else if (metric == Metric::ICP_PLANE) linearize = icp_align_linearize_kernel<true>;
+  for (int r = 0;;) {
+    for (const int end = chunk > 0 ? std::min(rounds, r + chunk) : rounds; r < end; r++) {
+      linearize<<<nb, BLOCK, 0, st>>>(d_table.as<AlignProblem>(), d_blocks.as<int4>(), d_states.as<lm::State>(), d_partials.as<float>());
+      align_decide_kernel<<<count, 256, 0, st>>>(d_table.as<AlignProblem>(), d_partials.as<float>(), d_states.as<lm::State>(), prm,
+                                                 trace.d.as<glim_amd_align_trace_entry>(), r, rounds);
+    }
+    GA_HIP(hipGetLastError());
+    GA_HIP(hipMemcpyAsync(states.data(), d_states.p, states.size() * sizeof(lm::State), hipMemcpyDeviceToHost, st));
+    if (r == rounds) break;
+    // a chunk's end: the statuses come back with the states, and the loop stops enqueueing when no problem is running
+    GA_HIP(hipStreamSynchronize(st));
+    if (std::none_of(states.begin(), states.end(), [](const lm::State& s) { return s.status == lm::RUNNING; })) break;
   }
-  GA_HIP(hipGetLastError());
-  GA_HIP(hipMemcpyAsync(states.data(), d_states.p, states.size() * sizeof(lm::State), hipMemcpyDeviceToHost, st));
   GA_TRY(trace.fetch(st));
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
@@ -944,6 +1005,29 @@ int glim_amd_debug_gicp_align_trace(int32_t ivox, const void* const* targets, co
   if (!trace && count > 0) return GLIM_AMD_ERR_INVALID;
   if (ivox) return run_align(reinterpret_cast<const glim_amd_ivox* const*>(targets), sources, T_init12, max_correspondence_distances, count, params, out, trace);
   return run_align(reinterpret_cast<const glim_amd_nn_index* const*>(targets), sources, T_init12, max_correspondence_distances, count, params, out, trace);
+}
+
+int glim_amd_icp_align_default_params(glim_amd_lm_params* params) {
+  if (!params) return GLIM_AMD_ERR_INVALID;
+  icp_default_params(params);
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_icp_align_batch(const glim_amd_nn_index* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                             const double* max_correspondence_distances, uint32_t flags, int32_t count, const glim_amd_lm_params* params,
+                             glim_amd_align_result* out) {
+  if (flags & ~(uint32_t)GLIM_AMD_ICP_POINT_TO_PLANE) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: the target is fixed
+  return run_align(targets, sources, T_init12, max_correspondence_distances, count, params, out, nullptr, icp_metric(flags), ICP_ROUNDS_PER_CHUNK,
+                   icp_default_params);
+}
+
+int glim_amd_debug_icp_align_trace(const glim_amd_nn_index* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                                   const double* max_correspondence_distances, uint32_t flags, int32_t count, const glim_amd_lm_params* params,
+                                   glim_amd_align_result* out, glim_amd_align_trace_entry* trace, int32_t rounds_per_chunk) {
+  if (flags & ~(uint32_t)GLIM_AMD_ICP_POINT_TO_PLANE) return GLIM_AMD_ERR_INVALID;
+  if ((!trace && count > 0) || rounds_per_chunk < 0) return GLIM_AMD_ERR_INVALID;
+  return run_align(targets, sources, T_init12, max_correspondence_distances, count, params, out, trace, icp_metric(flags),
+                   rounds_per_chunk > 0 ? rounds_per_chunk : ICP_ROUNDS_PER_CHUNK, icp_default_params);
 }
 
 int glim_amd_ct_align_default_params(glim_amd_lm_params* params) {

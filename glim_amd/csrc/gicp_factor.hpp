@@ -349,6 +349,7 @@ struct GicpTarget {
   bool ivox = false;            // the search object: `nn` when set, IndexSearch otherwise (with_search)
   IvoxSearch nn{};
   bool usable = true;           // the target has covariances
+  const float4* normals = nullptr;  // the target cloud's normals in its original order, or null (an index only: the ICP factors)
   bool empty = true;            // nothing to find: every point is an outlier
   int ring_cap = 0;             // most rings the index's walk may take; 0: no walk (a map searches the cells of its neighbour mode)
   int64_t max_source = INT64_MAX;  // source points beyond which the kind's entry points refuse the call
@@ -380,9 +381,20 @@ GicpTarget gicp_target(const glim_amd_nn_index* ix, bool lock = true) {
   t.args.h = ix->h;
   t.args.inv_h = 1.0 / ix->h;
   t.usable = ix->covA != nullptr;
+  t.normals = (ix->cloud && ix->cloud->has_normals) ? ix->cloud->normals : nullptr;
   t.empty = ix->n == 0;
   t.ring_cap = GICP_MAX_RING;
   return t;
+}
+
+// which per-point algebra a rigid evaluation runs: the GICP factor's (gicp_point), or one of the ICP factors' (icp_factor.hpp) over a search index
+enum class Metric { GICP, ICP_POINT, ICP_PLANE };
+inline Metric icp_metric(uint32_t flags) { return (flags & GLIM_AMD_ICP_POINT_TO_PLANE) ? Metric::ICP_PLANE : Metric::ICP_POINT; }
+// what a metric needs of its clouds: GLIM_AMD_OK or GLIM_AMD_ERR_STATE
+inline int metric_state(Metric m, const GicpTarget& t, const glim_amd_cloud* source) {
+  if (m == Metric::GICP) return (source->has_covs && t.usable) ? GLIM_AMD_OK : GLIM_AMD_ERR_STATE;
+  if (t.ivox) return GLIM_AMD_ERR_STATE;  // (no entry point reaches this: the ICP factors take a search index)
+  return (m == Metric::ICP_PLANE && !t.normals) ? GLIM_AMD_ERR_STATE : GLIM_AMD_OK;
 }
 
 // the source half of the kernels' arguments

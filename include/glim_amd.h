@@ -1,5 +1,7 @@
 /*
  * glim_amd.h -- C ABI of the MI355X-native (gfx950) VGICP scan-matching hot path for GLIM.
+ * gtsam_points' matching-cost family as the reference calls it is all here: the VGICP, GICP, continuous-time GICP and ICP factors, and the
+ * fine registrations over them (GICP, ICP, VGICP, CT frame alignment, sub-map bundle), each one loop on the device.
  *
  * This is the drop-in boundary: plain pointers and sizes, no C++/torch/Eigen types.  Each entry
  * point names the reference interface it replaces.  The reference (koide3/glim v1.2.2) reaches this path through
@@ -61,6 +63,7 @@ typedef struct {
 /* factor flags */
 #define GLIM_AMD_FACTOR_BINARY 0x1             /* fill H_tt, H_ts, b_t (otherwise they are zero: unary factor) */
 #define GLIM_AMD_FACTOR_SURFACE_VALIDATION 0x2 /* IntegratedVGICPFactorGPU::set_enable_surface_validation(true) */
+#define GLIM_AMD_ICP_POINT_TO_PLANE 0x4        /* the ICP factors ("ICP factors" below): IntegratedPointToPlaneICPFactor; otherwise point-to-point */
 
 /* ---- library / context --------------------------------------------------------------------------------------- */
 int glim_amd_version(void);
@@ -188,9 +191,34 @@ int glim_amd_gicp_linearize(const glim_amd_nn_index* target, const glim_amd_clou
 /* IntegratedGICPFactor::error and ::inlier_fraction (num_inliers / source size) -- global_mapping_pose_graph.cpp:404-405. */
 int glim_amd_gicp_error(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                         double max_correspondence_distance, double* error, int64_t* num_inliers);
-/* parity / debug: matched target index per source point, or -1. */
+/* parity / debug: matched target index per source point, or -1.  The correspondences are the search's alone: clouds without covariances
+ * (the ICP factors' case, below) are answered too. */
 int glim_amd_gicp_correspondences(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
                                   double max_correspondence_distance, int32_t* correspondences);
+
+/* ---- ICP factors on device: gtsam_points::IntegratedICPFactor (point-to-point) and IntegratedPointToPlaneICPFactor, the factor GLIM's manual
+ * loop closing refines with when a cloud carries no covariances (src/glim/viewer/interactive/manual_loop_close_modal.cpp:485-490: LM capped at
+ * 200 iterations; with covariances it takes the GICP factor, :476-483).  gtsam_points is not in the reference tree: the rule is upstream RECALL.
+ *   p_i        the source cloud's FP32 coordinates;  q = T p_i in FP64, the GICP factor's own transform
+ *   j          the exact nearest target point within max_correspondence_distance: the GICP factor's search over glim_amd_nn_index -- the same
+ *              index, tie rule (the smaller index) and ring bound, so glim_amd_gicp_correspondences returns these correspondences
+ *   r          b_j - q
+ *   point-to-point   e = sum r^T r,  J_s = [R hat(p) | -R],  H_ss = sum J_s^T J_s,  b_s = sum J_s^T r
+ *   point-to-plane   (GLIM_AMD_ICP_POINT_TO_PLANE) residual and Jacobian weighted ELEMENTWISE by the target normal n_j: r' = n_j o r,
+ *              J' = diag(n_j) J_s, i.e. the metric diag(n_x^2, n_y^2, n_z^2) in the target frame (not n n^T): e = sum r'^T r',
+ *              H_ss = sum J'^T J', b_s = sum J'^T r'.  GLIM itself calls only point-to-point.
+ *   error      carries no 1/2, as the GICP factor's: with frozen correspondences d e / d xi = 2 b_s
+ *   inliers    the matched points
+ *   record     the 29-double compact record of the VGICP / GICP factors; glim_amd_expand_compact gives the binary blocks from it unchanged
+ *   inputs     neither cloud needs covariances.  Point-to-plane needs the TARGET cloud's normals (read through the index, from the cloud the
+ *              index was built over): GLIM_AMD_ERR_STATE without them.
+ * flags: GLIM_AMD_FACTOR_BINARY and / or GLIM_AMD_ICP_POINT_TO_PLANE; any other bit: GLIM_AMD_ERR_INVALID.  Other errors as glim_amd_gicp_linearize
+ * (GLIM_AMD_ERR_UNSUPPORTED: a distance beyond the index's ring walk).  An empty source or target gives the zero record. */
+int glim_amd_icp_linearize(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
+                           double max_correspondence_distance, uint32_t flags, glim_amd_linearized6* out);
+/* IntegratedICPFactor::error and the inlier count at T_target_source (flags as above; GLIM_AMD_FACTOR_BINARY changes nothing here) */
+int glim_amd_icp_error(const glim_amd_nn_index* target, const glim_amd_cloud* source, const double* T_target_source12,
+                       double max_correspondence_distance, uint32_t flags, double* error, int64_t* num_inliers);
 
 /* ---- continuous-time GICP factor on device: gtsam_points::IntegratedCT_GICPFactor_<PointCloud, PointCloud> (KdTree target), the whole
  * per-frame cost of GLIM's LiDAR-only CT odometry (src/glim/odometry/odometry_estimation_ct.cpp:158-183, config_odometry_ct.json).
@@ -678,6 +706,30 @@ int glim_amd_gicp_align_batch(const glim_amd_nn_index* const* targets, const gli
 int glim_amd_gicp_align_batch_incremental(const glim_amd_ivox* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
                                    const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                    glim_amd_align_result* out);
+
+/* ---- ICP fine registration: the same loop over one unary IntegratedICPFactor, what "run fine registration" of GLIM's manual loop closing does
+ *      for clouds without covariances (src/glim/viewer/interactive/manual_loop_close_modal.cpp:485-490, LM <= 200) -- as a batch of B independent
+ *      problems over glim_amd_nn_index targets.  The rule is the one written above the glim_amd_lm_params structure (glim_amd/csrc/lm_step.hpp),
+ *      unchanged; glim_amd_lm_params and glim_amd_align_result are reused.
+ *   record     every trial record is bit for bit what glim_amd_icp_linearize returns at the trial's pose with the same flags
+ *   flags      0 or GLIM_AMD_ICP_POINT_TO_PLANE, applied to every problem.  GLIM_AMD_FACTOR_BINARY is refused: the target is fixed.
+ *   rounds     ICP takes many small steps, so max_trials defaults to 400 -- and a loop that stops after a dozen trials would leave hundreds of
+ *              enqueued rounds that only read a status word.  This loop therefore enqueues at most 41 rounds at a time (the most the other
+ *              loops enqueue by default), reads the problems' states back and stops enqueueing when no status is still running: one host
+ *              synchronisation per 41 rounds, not one per call.  The state lives on the device between chunks, so the result does not
+ *              depend on the chunk length, bit for bit.
+ * Deterministic: the same inputs return the same bits, in any batch, in any context of the same device model. */
+/* the values of glim_amd_gicp_align_default_params with max_iterations = 200 (manual_loop_close_modal.cpp:490) */
+int glim_amd_icp_align_default_params(glim_amd_lm_params* params);
+/* `count` problems: targets[i], sources[i], T_init12 + 12 i, max_correspondence_distances[i] -> out[i].  params NULL = the defaults above.
+ * Nothing is launched when an argument is refused; the refusals are those of glim_amd_gicp_align_batch with two differences: covariances are
+ * not required of either cloud, and GLIM_AMD_ERR_STATE means point-to-plane over a target cloud without normals.  So:
+ * GLIM_AMD_ERR_INVALID: a NULL argument or handle, count < 0, a flag other than GLIM_AMD_ICP_POINT_TO_PLANE, a distance that is NaN or < 0,
+ * handles of two contexts, an empty source or target, the parameter errors of glim_amd_gicp_align_batch; GLIM_AMD_ERR_UNSUPPORTED: a distance
+ * beyond the index's ring walk. */
+int glim_amd_icp_align_batch(const glim_amd_nn_index* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                             const double* max_correspondence_distances, uint32_t flags, int32_t count, const glim_amd_lm_params* params,
+                             glim_amd_align_result* out);
 
 /* ---- VGICP fine registration: the same loop over one unary IntegratedVGICPFactor(Pose3(), 0, target->voxels, source), the loop GLIM runs at
  *      src/glim/mapping/global_mapping_pose_graph.cpp:405-417 (loop-candidate validation with registration_type "VGICP", LM <= 10, then `error`

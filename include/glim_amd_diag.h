@@ -248,6 +248,12 @@ typedef struct {
 int glim_amd_debug_gicp_align_trace(int32_t ivox, const void* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
                                     const double* max_correspondence_distances, int32_t count, const glim_amd_lm_params* params,
                                     glim_amd_align_result* out, glim_amd_align_trace_entry* trace);
+/* test window of the ICP fine registration (glim_amd.h "ICP fine registration"): glim_amd_icp_align_batch with the same arguments and results,
+ * plus trace[i * (1 + max_trials) + r] as above, and the number of rounds enqueued between two looks at the statuses (0 = the call's own 41;
+ * any value >= 1 + max_trials enqueues every round up front).  The chunk length moves no bit of `out` or `trace`. */
+int glim_amd_debug_icp_align_trace(const glim_amd_nn_index* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
+                                   const double* max_correspondence_distances, uint32_t flags, int32_t count, const glim_amd_lm_params* params,
+                                   glim_amd_align_result* out, glim_amd_align_trace_entry* trace, int32_t rounds_per_chunk);
 /* test window of the VGICP fine registration (glim_amd.h "VGICP fine registration"): glim_amd_vgicp_align_batch with the same arguments and
  * results, plus trace[i * (1 + max_trials) + r] as above */
 int glim_amd_debug_vgicp_align_trace(const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const double* T_init12,
