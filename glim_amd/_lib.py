@@ -371,6 +371,10 @@ SYMBOLS = {
     "glim_amd_vgicp_align_default_params": (_i, [C.POINTER(LMParams)]),
     "glim_amd_vgicp_align_batch": (_i, [_pp, _pp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult)]),
     "glim_amd_debug_vgicp_align_trace": (_i, [_pp, _pp, _dp, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), C.POINTER(AlignTraceEntry)]),
+    "glim_amd_keyframe_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_keyframe_align_batch": (_i, [_pp, _ip, _pp, _dp, _dp, C.POINTER(BundlePrior), _i32, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult), _dp]),
+    "glim_amd_debug_keyframe_align_trace": (_i, [_pp, _ip, _pp, _dp, _dp, C.POINTER(BundlePrior), _i32, _u32, _i32, C.POINTER(LMParams), C.POINTER(AlignResult),
+                                                 _dp, C.POINTER(AlignTraceEntry), _dp, _dp, _dp]),
     "glim_amd_ct_align_default_params": (_i, [C.POINTER(LMParams)]),
     "glim_amd_ct_align": (_i, [_vp, _dp, _dp, C.POINTER(CtAlignTerms), C.POINTER(LMParams), C.POINTER(CtAlignResult)]),
     "glim_amd_debug_ct_align_trace": (_i, [_vp, _dp, _dp, C.POINTER(CtAlignTerms), C.POINTER(LMParams), C.POINTER(CtAlignResult),

@@ -1551,6 +1551,91 @@ def _trace_rows(trace, i, rounds, trials):
     return rows
 
 
+KEYFRAME_ALIGN_MAX_TARGETS = 64  # GLIM_AMD_KEYFRAME_ALIGN_MAX_TARGETS
+KEYFRAME_PRIOR_DOUBLES = 28  # a prior's traced contribution: 21 of J^T L J, 6 of J^T L r, r^T L r
+
+
+def _keyframe_args(problems):
+    """problems: (source, [(voxel map, T_world_target 4 x 4), ...], X_init 4 x 4[, prior]); prior: None or (P 4 x 4, information 6 x 6) -> the C
+    arrays"""
+    n = len(problems)
+    first = np.zeros(n + 1, dtype=np.int32)
+    maps, P, priors = [], [], []
+    X = np.zeros((n, 12))
+    for i, pr in enumerate(problems):
+        source, targets, X_init = pr[0], pr[1], pr[2]
+        for m, T in targets:
+            maps.append(m)
+            P.append(pose12(T))
+        first[i + 1] = len(maps)
+        X[i] = pose12(X_init)
+        if len(pr) > 3 and pr[3] is not None:
+            priors.append((i, pr[3][0], pr[3][1]))
+    F = len(maps)
+    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(F, 12))
+    sh = (C.c_void_p * max(n, 1))(*[pr[0]._h for pr in problems])
+    th = (C.c_void_p * max(F, 1))(*[m._h for m in maps])
+    cp = (_lib.BundlePrior * max(len(priors), 1))()
+    for c, (k, T, info) in zip(cp, priors):
+        c.pose = int(k)
+        c.T[:] = list(pose12(T))
+        c.information[:] = list(np.asarray(info, dtype=np.float64).reshape(36))
+    return n, F, first, (sh, _ip(first), th, _dp(P), _dp(X), cp if priors else None, len(priors)), (P, X)
+
+
+def _keyframe_results(problems, out, first, compact):
+    results = []
+    for i, pr in enumerate(problems):
+        r = AlignResult(out[i], pr[0].size() * len(pr[1]))  # the inliers are summed over the factors: the fraction is of M x size
+        r.factor_compact = compact[first[i]:first[i + 1]].copy()  # every factor's record at the returned pose
+        results.append(r)
+    return results
+
+
+def vgicp_align_keyframes(problems, flags=0, params=None):
+    """Scan-to-keyframes VGICP registration of len(problems) independent problems in one call and one host synchronisation: Levenberg-Marquardt
+    over ONE pose on the sum of one unary IntegratedVGICPFactorGPU per (keyframe, voxel-map level) with fixed target poses
+    (odometry_estimation_gpu.cpp:150-165, 183-203).  A problem is (source, [(GaussianVoxelMapGPU, T_world_target 4 x 4), ...], X_init 4 x 4
+    [, prior]) with at most KEYFRAME_ALIGN_MAX_TARGETS targets; X is T_world_source; prior: None or (P 4 x 4, information 6 x 6).  flags: 0 or
+    FACTOR_SURFACE_VALIDATION.  Factor f is evaluated at P_f^-1 X; every trial record is what a NonlinearFactorSetGPU of all the batch's pairs
+    returns at those poses.  Returns one AlignResult per problem -- T_target_source is X, error / num_inliers / compact are the summed record
+    there -- with `factor_compact` (M x 29) attached."""
+    n, F, first, args, keep = _keyframe_args(problems)
+    prm = (params or LMParams())._c()
+    out = (_lib.AlignResult * max(n, 1))()
+    compact = np.zeros((F, _lib.COMPACT_DOUBLES))
+    check(lib().glim_amd_keyframe_align_batch(*args, int(flags), n, C.byref(prm), out, _dp(compact)), "glim_amd_keyframe_align_batch")
+    return _keyframe_results(problems, out, first, compact)
+
+
+def vgicp_align_keyframes_debug_trace(problems, flags=0, params=None):
+    """Test window (glim_amd_debug_keyframe_align_trace): vgicp_align_keyframes' results plus, per problem, one dict per round run -- round 0 is
+    the initial pose -- as gicp_align_debug_trace gives them (`T`: the X evaluated, `compact`: the SUMMED record) with, in addition, `prior`
+    (the prior's 28-double contribution), `Tf` (M x 12, the factor poses as the device computed them) and `factor_compact` (M x 29, the
+    factors' records there)."""
+    params = params or LMParams()
+    n, F, first, args, keep = _keyframe_args(problems)
+    rounds = 1 + params.resolved_max_trials()
+    prm = params._c()
+    out = (_lib.AlignResult * max(n, 1))()
+    compact = np.zeros((F, _lib.COMPACT_DOUBLES))
+    trace = (_lib.AlignTraceEntry * max(n * rounds, 1))()
+    tprior, tTf = np.zeros((max(n, 1), rounds, KEYFRAME_PRIOR_DOUBLES)), np.zeros((rounds, max(F, 1), 12))
+    trec = np.zeros((rounds, max(F, 1), _lib.COMPACT_DOUBLES))
+    check(lib().glim_amd_debug_keyframe_align_trace(*args, int(flags), n, C.byref(prm), out, _dp(compact), trace, _dp(tprior), _dp(tTf), _dp(trec)),
+          "glim_amd_debug_keyframe_align_trace")
+    results = _keyframe_results(problems, out, first, compact)
+    traces = []
+    for i, r in enumerate(results):
+        rows = _trace_rows(trace, i, rounds, r.trials)
+        for k, row in enumerate(rows):
+            row["prior"] = tprior[i, k].copy()
+            row["Tf"] = tTf[k, first[i]:first[i + 1]].copy()
+            row["factor_compact"] = trec[k, first[i]:first[i + 1]].copy()
+        traces.append(rows)
+    return results, traces
+
+
 def bundle_align_params(**kw):
     """LMParams with the sub-mapping bundle's value (glim_amd_bundle_align_default_params): max_iterations 20 (sub_mapping.cpp:431)."""
     p = dict(max_iterations=20)

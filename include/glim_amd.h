@@ -868,6 +868,50 @@ int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* tar
                           const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
                           const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result);
 
+/* ---- Scan-to-keyframes VGICP registration: the LiDAR part of GLIM's frame-to-keyframes matching cost
+ *      (src/glim/odometry/odometry_estimation_gpu.cpp:150-165, 183-203): one unary IntegratedVGICPFactorGPU(fixed_target_pose, X(current),
+ *      voxelmap, frame) per keyframe and per voxel-map level, ALL on the same pose variable -- as a batch of `count` independent problems, each
+ *      one pose X_i (T_world_source) over M_i targets with fixed poses P_f (T_world_target), in one call with ONE host synchronisation.  Also a
+ *      multi-resolution loop-candidate check.  One definition for host and device: glim_amd/csrc/keyframe_lm_step.hpp.
+ * A sum of compact records is a compact record, so the rule is the one written above the glim_amd_lm_params structure
+ * (glim_amd/csrc/lm_step.hpp), unchanged, applied to the summed record; glim_amd_lm_params and glim_amd_align_result are reused.
+ *   poses      factor f of problem i is evaluated at T_f = P_f^-1 X_i (inverse and compose of glim_amd/csrc/ct_se3.hpp, FP64).  With right
+ *              perturbation X Exp(d) gives T_f Exp(d): the H_ss and b_s of every factor are already expressed in d of X and simply add.
+ *   record     every trial record of factor f is bit for bit what glim_amd_factor_set_linearize returns for a set of the same F (map, source)
+ *              pairs in the same order with the same flags at those T_f.  The promise is tied to "the same set", not to the factor alone (see
+ *              the VGICP fine registration above).
+ *   sum        each of the 29 entries of the problem's record is ((+0.0 + r_first) + ...) + r_last over its factors by ascending index, FP64.
+ *   prior      at most one per problem (.pose = the problem's index): r = Log(P^-1 X), J = J_r(r)^-1, the bundle's definitions; J^T L J is
+ *              added to H, J^T L r to b and r^T L r to the error, LAST, after the factors; only the upper triangle of L is read.  The inlier
+ *              count is the factors' sum only: a prior alone never makes a candidate acceptable.
+ *   result     T_target_source holds the last kept X; `error`, `num_inliers` and `compact` are the summed record there (prior included): its
+ *              H_ss is the information a caller hands to a pose graph.  Statuses, budgets and max_trials = 0 are as in the GICP section.
+ *   non-finite an X_init or a P_f that is not finite ends ITS problem with GLIM_AMD_ALIGN_NUMERIC in round 0 (X_init is returned), as a
+ *              non-finite initial pose does in the GICP section; the other problems of the batch run.  Round 0 still evaluates that problem's
+ *              factors at the non-finite T_f, as the VGICP fine registration does for a non-finite T_init; nothing of it is kept.  A
+ *              non-finite prior is refused.
+ *   flags      0 or GLIM_AMD_FACTOR_SURFACE_VALIDATION (GLIM sets it at :162), for every factor.  GLIM_AMD_FACTOR_BINARY is refused.
+ * Deterministic: the same batch returns the same bits, in any context of the same device model.  The caller's factor sets, the context's plans
+ * and a resident session are not touched. */
+#define GLIM_AMD_KEYFRAME_ALIGN_MAX_TARGETS 64 /* per problem; GLIM: (15 keyframes + 2 window frames) x 2 levels = 34 */
+/* the values of glim_amd_gicp_align_default_params, unchanged */
+int glim_amd_keyframe_align_default_params(glim_amd_lm_params* params);
+/* sources: `count`, one per problem.  first_target: count + 1 offsets into the next two arrays, M_i = first_target[i + 1] - first_target[i].
+ * targets: F = first_target[count] maps (a map may appear several times); T_world_target12: F x 12, P_f; X_init12: count x 12.  priors: NULL
+ * with num_priors = 0, or num_priors entries.  params NULL = the defaults.  out: count.  factor_compact_out: NULL or F x 29, every factor's
+ * record at the returned pose of its problem: the records of the last round that was kept.  A problem that ends in round 0 with
+ * NO_CORRESPONDENCES kept round 0: its records are round 0's, with zero inliers.  A problem that kept nothing (NUMERIC in round 0) has zeros.
+ * count = 0 is OK.  Nothing is launched when an argument is refused:
+ * GLIM_AMD_ERR_INVALID: a NULL argument or handle, count < 0, num_priors < 0, offsets that do not ascend from 0, a problem with no target,
+ * handles of two contexts, an empty source, a prior whose pose or information is not finite, a prior index out of range, a second prior for
+ * one problem, GLIM_AMD_FACTOR_BINARY or an unknown bit in `flags`, the parameter errors of glim_amd_gicp_align_batch; GLIM_AMD_ERR_STATE: a
+ * map nothing was inserted into or a source without covariances (as glim_amd_factor_set_add); GLIM_AMD_ERR_UNSUPPORTED: more than
+ * GLIM_AMD_KEYFRAME_ALIGN_MAX_TARGETS targets in a problem. */
+int glim_amd_keyframe_align_batch(const glim_amd_cloud* const* sources, const int32_t* first_target, const glim_amd_voxelmap* const* targets,
+                                  const double* T_world_target12, const double* X_init12, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                                  uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out,
+                                  double* factor_compact_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,17 @@ int glim_amd_debug_bundle_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap
                                       int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
                                       double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
                                       double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds);
+/* test window of the scan-to-keyframes VGICP registration (glim_amd.h): glim_amd_keyframe_align_batch with the same arguments and results,
+ * plus, with R = 1 + max_trials rounds (max_trials as resolved; round 0 is the initial pose; valid for r <= out[i].trials, the rest are zero):
+ * per problem i and round r, rounds[i * R + r] -- T_candidate: the X the round evaluated, lambda: the one its step was solved with, compact:
+ * the SUMMED record (prior included), accepted, status -- and prior_trace[(i * R + r) * 28 ..]: the prior's contribution, the 21 upper entries
+ * of J^T L J, the 6 of J^T L r, then r^T L r (zero without a prior); per round r and factor f of the batch, Tf_trace[(r * F + f) * 12 ..]: T_f as
+ * the device computed it, and compact_trace[(r * F + f) * 29 ..]: the factor's record there.  All four arrays are required. */
+int glim_amd_debug_keyframe_align_trace(const glim_amd_cloud* const* sources, const int32_t* first_target, const glim_amd_voxelmap* const* targets,
+                                        const double* T_world_target12, const double* X_init12, const glim_amd_bundle_prior* priors,
+                                        int32_t num_priors, uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out,
+                                        double* factor_compact_out, glim_amd_align_trace_entry* rounds, double* prior_trace, double* Tf_trace,
+                                        double* compact_trace);
 
 #ifdef __cplusplus
 }

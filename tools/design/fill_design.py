@@ -154,6 +154,17 @@ if os.path.exists(bun_path):
         "As measured the device round is SLOWER than the host-driven iteration: the one-workgroup decide kernel is about three quarters of a round.  Where its time goes (the serial item lists of the assembly read from device memory, the 120 barriers of the factorisation, the `noinline` SE(3) items) has not been profiled; unrolling the factorisation's dot loops by eight changed nothing measurable.  What the call saves today is the host's assembly and solve and the per-trial round trips, not time on this bundle; no speedup is claimed.")
 else:
     vals['BUNDLE_MEASURED']="nothing yet.  `tools/bundle_align_time.py` writes `profiles/bundle_align/bundle_align_time.json` (the device loop on the configs[2] bundle against the host-driven iteration over `linearize` and `error` of the same set, and the split of a round between the factor kernels and the decide kernel, the variants alternating in one process); until that file exists every statement about the speed of this path, the one-workgroup FP64 Cholesky included, is UNMEASURED."
+# ---- the scan-to-keyframes VGICP registration (tools/keyframe_align_time.py) ----
+kfa_path='profiles/keyframe_align/keyframe_align_time.json'
+if os.path.exists(kfa_path):
+    kfa=json.load(open(kfa_path))['shapes']
+    ran=lambda r,k: r[k].get('rounds_that_ran_a_problem', r[k]['rounds'])
+    cell=lambda r,k: f"{r[k]['wall_ms_p50']:.2f} ms for {r[k]['rounds']} rounds of which {ran(r,k)} ran, {r[k]['factor_evaluations_used']} factor evaluations used ({r[k]['wall_ms_p50']*1e3/ran(r,k):.0f} µs per round that ran)"
+    vals['KEYFRAME_MEASURED']=(f"one box, not repeated, the variants alternating in one process (`tools/keyframe_align_time.py`, `{kfa_path}`; a {sp(kfa[0]['source_points'])}-point source against {kfa[0]['targets_per_problem']} maps of {sp(kfa[0]['target_points'])}-point scans, the default parameters).  "
+        +'  '.join(f"B = {r['B']} ({r['factors']} factors): device batch {cell(r,'device_batch')}; host-driven loop over `linearize_poses` {cell(r,'host_loop')}." for r in kfa)
+        +"  The device enqueues every round up front and the host loop stops with the last problem, so both times are divided by the rounds that ran a problem; the enqueued rounds that found every problem finished are in the device's time.  No speedup is claimed.")
+else:
+    vals['KEYFRAME_MEASURED']="nothing yet.  `tools/keyframe_align_time.py` writes `profiles/keyframe_align/keyframe_align_time.json` (the device batch against the host-driven loop over `NonlinearFactorSetGPU.linearize_poses` of the same 34 B pairs, B = 1 / 8, a 12 000-point source against 17 × 2 maps of 131 072-point scans, totals and per-round figures, the variants alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
