@@ -1135,15 +1135,34 @@ RESIDENT_TIMELINE_FIELDS = ("host_round_trip", "leader_published", "worker_pose_
                             "worker_loop_left_max", "finaliser_group_sums_added", "finaliser_blocks_rotated", "shader_clock_mhz")
 
 
-def resident_timeline(device=0, enable=True, read=True):
+RESIDENT_TIMELINE_MAX_BLOCKS = 2048  # GLIM_AMD_RESIDENT_TIMELINE_MAX_BLOCKS
+RESIDENT_TIMELINE_BLOCK_FIELDS = ("pose_seen", "row_computed", "row_published", "loop_left", "hw")  # GLIM_AMD_RESIDENT_TIMELINE_BLOCK_FIELDS each
+
+
+def resident_timeline(device=0, enable=True, read=True, per_block=False):
     """glim_amd_debug_resident_timeline: ends the device's resident session; read=True returns the last request's timeline (microseconds relative to
-    the leader seeing the request; None when no stamped session has run); the stamps stay on / off for the next sessions per `enable`."""
-    us = np.zeros(len(RESIDENT_TIMELINE_FIELDS), dtype=np.float64)
+    the leader seeing the request; None when no stamped session has run); the stamps stay on / off for the next sessions per `enable`.
+    per_block=True adds the key "blocks": arrays with one entry per block of the launch, the workers first -- the four worker stamps (microseconds, -1
+    where a block has none: a finalising block), `worker` (bool), and where the block runs: `hw_id`, `xcc_id` (the registers as read) and `cu`, one
+    integer per compute unit (XCC_ID and the compute-unit, shader-array and shader-engine bits of HW_ID): equal `cu` = same compute unit."""
+    nsum = len(RESIDENT_TIMELINE_FIELDS)
+    nblk = len(RESIDENT_TIMELINE_BLOCK_FIELDS)
+    us = np.zeros(nsum + (2 + nblk * RESIDENT_TIMELINE_MAX_BLOCKS if per_block else 0), dtype=np.float64)
     rc = lib().glim_amd_debug_resident_timeline(int(device), int(bool(enable)), _dp(us) if read else None, len(us) if read else 0)
     if rc == -5 and read:
         return None
     check(rc, "glim_amd_debug_resident_timeline")
-    return dict(zip(RESIDENT_TIMELINE_FIELDS, us.tolist())) if read else None
+    if not read:
+        return None
+    out = dict(zip(RESIDENT_TIMELINE_FIELDS, us[:nsum].tolist()))
+    if per_block:
+        blocks, workers = int(us[nsum]), int(us[nsum + 1])
+        tab = us[nsum + 2 : nsum + 2 + nblk * blocks].reshape(blocks, nblk)
+        hw = tab[:, 4].astype(np.uint64)
+        hw_id, xcc_id = (hw & np.uint64(0xFFFFFFFF)).astype(np.int64), (hw >> np.uint64(32)).astype(np.int64)
+        out["blocks"] = {name: tab[:, k].copy() for k, name in enumerate(RESIDENT_TIMELINE_BLOCK_FIELDS[:4])}
+        out["blocks"].update(worker=np.arange(blocks) < workers, hw_id=hw_id, xcc_id=xcc_id, cu=((xcc_id & 0xF) << 8) | ((hw_id >> 8) & 0xFF))
+    return out
 
 
 def resident_stop(ctx=None):

@@ -66,6 +66,11 @@ constexpr int NACC = 28;  // FP32 accumulators per thread (see layout below); sl
 #ifndef GLIM_AMD_RES_TAILSKIP
 #define GLIM_AMD_RES_TAILSKIP 1
 #endif
+// resident workers: the stream data of a lane's second point is loaded before the pose arrives, like the first point's, and a row of exactly two
+// points per lane runs a flat schedule (compute_row) / 0: the second point is loaded behind the pose, every row walks the two-trip pipeline
+#ifndef GLIM_AMD_RES_FLAT2
+#define GLIM_AMD_RES_FLAT2 1
+#endif
 // the four 16-lane ROW sums of every wavefront go to LDS and whoever forms the row's values adds them as (r3 + r2) + (r1 + r0), what the two
 // row_bcast steps left in lane 63 (same bits; 4 instead of 10 instructions per value and wavefront) / 0: the wavefront sums as before
 #ifndef GLIM_AMD_ROW_SUMS_LDS
@@ -748,12 +753,14 @@ struct PipeCtx {  // wave-uniform context of the pipelined loop
 // TAILSKIP (the resident kernels: a wavefront there walks one or two trips and the caller waits for it): the probe and the stream loads of a point that
 // no lane has -- the last trip's steps (2) and (3), ~80 instructions in front of the last algebra -- are skipped behind a scalar branch.  Nothing
 // that is added depends on them: same bits.  (The launch-per-call kernels walk 30-60 trips and stay as they are: their loop sits at its register cap.)
-template <int MODE, bool FROZEN, bool PLANE, bool TAILSKIP = false>
-__device__ __forceinline__ void pipe_trip_at(const PipeCtx<PLANE>& pc, Probe<PLANE>& pr, PointIn& nxt, int i1, bool ok1, int i2, float (&acc)[NACC], int& wave_inliers,
-                                             int& wave_skips) {
-  const FactorDesc& d = pc.d;
-  // (1) resolve point `it`
-  const Probe<PLANE> cur = pr;
+struct Resolved {  // a resolved probe: whether this lane / any lane of the wavefront has a correspondence, and the (gathered) record
+  bool hit, any_hit;
+  float4 r0, r1;
+  float r2;
+};
+// step (1) of a trip: resolve the probe `cur` (its key gather has been issued) and issue the dependent record gather
+template <bool PLANE>
+__device__ __forceinline__ Resolved resolve_probe(const FactorDesc& d, const Probe<PLANE>& cur, int& wave_inliers, int& wave_skips) {
   unsigned long long k0 = (unsigned long long)__float_as_uint(cur.head.x) | ((unsigned long long)__float_as_uint(cur.head.y) << 32);
   unsigned long long k1 = (unsigned long long)__float_as_uint(cur.head.z) | ((unsigned long long)__float_as_uint(cur.head.w) << 32);
   unsigned int b = cur.bkt;
@@ -807,6 +814,15 @@ __device__ __forceinline__ void pipe_trip_at(const PipeCtx<PLANE>& pc, Probe<PLA
     r1 = gld4(rp + 16);   // c01 c02 c11 c12
     r2 = gld1(rp + 32);   // c22
   }
+  return {hit, any_hit, r0, r1, r2};
+}
+template <int MODE, bool FROZEN, bool PLANE, bool TAILSKIP = false>
+__device__ __forceinline__ void pipe_trip_at(const PipeCtx<PLANE>& pc, Probe<PLANE>& pr, PointIn& nxt, int i1, bool ok1, int i2, float (&acc)[NACC], int& wave_inliers,
+                                             int& wave_skips) {
+  const FactorDesc& d = pc.d;
+  // (1) resolve point `it`
+  const Probe<PLANE> cur = pr;
+  const Resolved rs = resolve_probe<PLANE>(d, cur, wave_inliers, wave_skips);
   if (!TAILSKIP || ok1) {
     // (2) probe of point it+AHEAD (a lane past its last point probes with EMPTY_KEY at a clamped, valid address)
     pr = probe_point<FROZEN, PLANE>(d, nxt, i1, ok1, pc.Tl, pc.Te, pc.R, pc.validate, pc.last);
@@ -814,7 +830,7 @@ __device__ __forceinline__ void pipe_trip_at(const PipeCtx<PLANE>& pc, Probe<PLA
     nxt = load_point<PLANE>(d, (unsigned int)min(i2, pc.last));
   }
   // (4) algebra of point `it`
-  if (any_hit) accumulate_point<MODE, PLANE>(acc, hit, r0, r1, r2, cur, pc.R);
+  if (rs.any_hit) accumulate_point<MODE, PLANE>(acc, rs.hit, rs.r0, rs.r1, rs.r2, cur, pc.R);
   // The key gather the NEXT trip resolves is consumed HERE, at the very end of this trip, and nowhere earlier: without this pin the
   // register allocator recycles two of its destination registers as algebra temporaries and copies them out mid-trip, which puts the
   // s_waitcnt for the HBM gather 85 instructions after its issue instead of a whole trip.
@@ -850,7 +866,10 @@ __device__ __forceinline__ void rotate_priority(int step) {
 // runs the algebra (a lane without a match contributes exact zeros) and the only branch on the hot path is the rare bucket spill.  On return
 // (after a block barrier) s_red[w] holds wavefront w's sums -- as its four 16-lane row sums (GLIM_AMD_ROW_SUMS_LDS; wave_value adds them) -- of
 // accumulator j, [28] its inlier count.
-// first: the stream data of this lane's first point when the caller has loaded it already (a resident worker does, while it waits for its pose).
+// first, second: the stream data of this lane's first and second point when the caller has loaded them already (a resident worker does, while it
+// waits for its pose: with one wavefront per SIMD nothing else covers a load issued behind the pose).  With both, a row of exactly two points per
+// lane -- the single chip-wide factor -- leaves the pipeline for a flat schedule (GLIM_AMD_RES_FLAT2 below); the launch-per-call kernels pass
+// neither and compile to the loop alone.
 // cull (CULL only): this block's four pre-cull words (cull_kernel), one per wavefront: bit t set = trip t of that wavefront has no point or cannot
 // find a correspondence.  The wavefront then walks its LIVE trips only, through the same two-trip pipeline: a culled trip costs nothing at all --
 // no stream load, no FP64 transform, no hash, no key gather (the in-loop skip of an all-miss trip still pays those: 40 % of a trip) -- and since
@@ -858,7 +877,7 @@ __device__ __forceinline__ void rotate_priority(int step) {
 template <int MODE, bool FROZEN, bool PLANE, bool CULL = false, bool TAILSKIP = false>
 __device__ __forceinline__ void compute_row(const FactorDesc& d, const double* __restrict__ Tl, const double* __restrict__ Te, int chunk, int prio_phase,
                                             RedRow* s_red, const PointIn* first = nullptr, const unsigned long long* cull = nullptr,
-                                            unsigned long long* loop_done_stamp = nullptr) {
+                                            unsigned long long* loop_done_stamp = nullptr, const PointIn* second = nullptr) {
   // rotation of the linearisation pose in FP32 (R[r][c])
   // (wave-uniform: the compiler keeps these in SGPRs; forcing readfirstlane changed nothing -- 93 VGPRs either way)
   const float R00 = (float)Tl[0], R01 = (float)Tl[1], R02 = (float)Tl[2];
@@ -907,12 +926,26 @@ __device__ __forceinline__ void compute_row(const FactorDesc& d, const double* _
         t2 = pop(live);
       }
     } else {
+    if (GLIM_AMD_RES_FLAT2 && first && second && ppt == 2) {
+      // flat schedule of a resident worker's two points (wave-uniform branch): both key gathers in flight before the first is resolved, both
+      // record gathers before the first algebra -- two dependent gathers in front of the sums instead of the pipeline's three (key 0 -> record 0
+      // beside key 1 -> record 1), and the FP64 transform of point 1 between key gather 0 and its wait.  Point 0 is added to every accumulator
+      // before point 1, as in the loop; a lane without a second point probes with EMPTY_KEY at a clamped address, as there.
+      rotate_priority(1 + prio_phase);  // (what the loop's last trip leaves)
+      const Probe<PLANE> pr0 = probe_point<FROZEN, PLANE>(d, *first, base, true, Tl, Te, R, validate, last);
+      const Probe<PLANE> pr1 = probe_point<FROZEN, PLANE>(d, *second, base + stride, true, Tl, Te, R, validate, last);
+      const Resolved rs0 = resolve_probe<PLANE>(d, pr0, wave_inliers, wave_skips);
+      const Resolved rs1 = resolve_probe<PLANE>(d, pr1, wave_inliers, wave_skips);
+      if (rs0.any_hit) accumulate_point<MODE, PLANE>(acc, rs0.hit, rs0.r0, rs0.r1, rs0.r2, pr0, R);
+      if (rs1.any_hit) accumulate_point<MODE, PLANE>(acc, rs1.hit, rs1.r0, rs1.r1, rs1.r2, pr1, R);
+    } else {
     PointIn nxt = first ? *first : load_point<PLANE>(d, (unsigned int)min(base, last));
     Probe<PLANE> pr = probe_point<FROZEN, PLANE>(d, nxt, base, ppt > 0, Tl, Te, R, validate, last);
-    nxt = load_point<PLANE>(d, (unsigned int)min(base + stride, last));
+    nxt = second ? *second : load_point<PLANE>(d, (unsigned int)min(base + stride, last));
     for (int it = 0; it < ppt; it++) {
       rotate_priority(it + prio_phase);
       pipe_trip<MODE, FROZEN, PLANE, TAILSKIP>(pc, pr, nxt, it, acc, wave_inliers, wave_skips);
+    }
     }
     }
   }
@@ -980,9 +1013,59 @@ __device__ __forceinline__ float row_value(const RedRow* s_red, int j) {
   return live ? (wave_value(s_red, 0, j) + wave_value(s_red, 1, j)) + (wave_value(s_red, 2, j) + wave_value(s_red, 3, j)) : 0.f;
 }
 
-// tagged granules (see TAG_PIECES): thread p < 10 publishes values 3p .. 3p + 2 and the call's tag with ONE write-through 16-byte store
+// tagged granules (see TAG_PIECES): granule p = values 3p .. 3p + 2 and the call's tag, ONE write-through 16-byte store each.
+// GLIM_AMD_ROW_LANES (default): lane 4p + v of wavefront 0 forms ONE value, 3p + v -- its 16 LDS reads are independent and go out before the first
+// wait --, two quad_perm moves bring the values of lanes 4p + 1 and 4p + 2 into lane 4p, and lane 4p stores the granule.  The row index is made
+// wave-uniform explicitly, so that the buffer descriptor is scalar and the store needs no loop over distinct descriptors.  Same expression per
+// value (row_value), same granule, same store: same bits.
+// 0: thread p < 10 forms the three values of its granule one after the other (48 LDS reads per lane, the last value's as eight dependent round trips).
+#ifndef GLIM_AMD_ROW_LANES
+#define GLIM_AMD_ROW_LANES 1
+#endif
+// row_value for a lane-dependent j < PARTIAL_STRIDE with every LDS read issued before the first addition: the same expression, the same bits.
+// (Left to itself the compiler reads two sums, waits, adds, reads the next two: eight dependent LDS round trips on a path the caller waits for.)
+template <int MODE>
+__device__ __forceinline__ float row_value_batched(const RedRow* s_red, int j) {
+  float x[4][RED_ROWS];
+#pragma unroll
+  for (int w = 0; w < 4; w++)
+#pragma unroll
+    for (int r = 0; r < RED_ROWS; r++) x[w][r] = s_red[w][r][j];
+#pragma unroll
+  for (int w = 0; w < 4; w++)
+#pragma unroll
+    for (int r = 0; r < RED_ROWS; r++) asm volatile("" : "+v"(x[w][r]));  // all of them exist here: the reads are out, the sums follow
+  float wv[4];
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+#if GLIM_AMD_ROW_SUMS_LDS
+    wv[w] = (x[w][3] + x[w][2]) + (x[w][1] + x[w][0]);  // wave_value
+#else
+    wv[w] = x[w][0];
+#endif
+  }
+  const bool live = (MODE == MODE_LINEARIZE) ? (j <= 29) : (j >= 27 && j <= 29);  // row_value
+  return live ? (wv[0] + wv[1]) + (wv[2] + wv[3]) : 0.f;
+}
 template <int MODE>
 __device__ __forceinline__ void publish_row_tagged(const RedRow* s_red, char* rows16, size_t row, unsigned int tag) {
+#if GLIM_AMD_ROW_LANES
+  int t = (int)threadIdx.x;
+  asm volatile("" : "+v"(t));  // the lane's constants below are formed HERE, three instructions, not kept in registers around a resident session's loop
+  if (t < 4 * TAG_PIECES) {  // (lanes 0..39 of wavefront 0: whole quads, so every quad_perm source lane is active)
+    const int p = t >> 2, v = t & 3;
+    static_assert(3 * (TAG_PIECES - 1) + 3 < PARTIAL_STRIDE, "the idle fourth lane of a quad reads inside the row");
+    const float mine = row_value_batched<MODE>(s_red, 3 * p + v);
+    const float v1 = dpp_f<0x55, 0xF>(mine);  // quad_perm [1,1,1,1]
+    const float v2 = dpp_f<0xAA, 0xF>(mine);  // quad_perm [2,2,2,2]
+    const size_t urow = (size_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)row);  // (a plan has far fewer than 2^31 rows)
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(rows16 + urow * TAG_ROW_BYTES, 0, TAG_ROW_BYTES, 0x00020000);
+    if (v == 0) {
+      const v4i_t piece = {__float_as_int(mine), __float_as_int(v1), __float_as_int(v2), (int)tag};
+      __builtin_amdgcn_raw_buffer_store_b128(piece, rsrc, p * 16, 0, AUX_SC1);
+    }
+  }
+#else
   if (threadIdx.x < TAG_PIECES) {
     const int j = 3 * (int)threadIdx.x;
     const v4i_t piece = {__float_as_int(row_value<MODE>(s_red, j)), __float_as_int(row_value<MODE>(s_red, j + 1)), __float_as_int(row_value<MODE>(s_red, j + 2)),
@@ -990,6 +1073,7 @@ __device__ __forceinline__ void publish_row_tagged(const RedRow* s_red, char* ro
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(rows16 + row * TAG_ROW_BYTES, 0, TAG_ROW_BYTES, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b128(piece, rsrc, (int)threadIdx.x * 16, 0, AUX_SC1);
   }
+#endif
 }
 
 // The fused factor kernel.  MODE: linearise (28 sums) or error only.  FROZEN: residual at a separate evaluation pose with correspondences
@@ -1184,9 +1268,14 @@ struct ResidentArgs {
   //   [2] finaliser of factor 0: pose seen           [3] ... every row of its factor summed (all tags arrived)      [4] ... record stored towards the host
   //   [5] ... its 32 group sums added   [6] ... its blocks rotated (finalize_tail)   [7] shader-clock ticks (s_memtime) between [2] and [4]
   //   [8 + 4 b + {0, 1, 2, 3}] worker block b: pose seen, first row computed (block-reduced), row granules published, point loop left (before the reduction)
+  //   [TL_HWID0 + b] EVERY block b < TL_HWID_BLOCKS, finalisers included, once per launch: where it runs -- HW_ID in the low word (gfx9 layout: CU
+  //       4 bits from bit 8, shader array bit 12, shader engine from bit 13), XCC_ID in the high one.  Blocks with the same (XCC_ID, HW_ID bits
+  //       8..15) share a compute unit.
   unsigned long long* timeline;
 };
 constexpr int TL_WORKER0 = 8;
+constexpr int TL_HWID0 = TL_WORKER0 + 4 * 1024;
+constexpr int TL_HWID_BLOCKS = GLIM_AMD_RESIDENT_TIMELINE_MAX_BLOCKS;
 __device__ __forceinline__ void tl_stamp(unsigned long long* tl, int slot) {
   if (tl && threadIdx.x == 0) tl[slot] = __builtin_amdgcn_s_memrealtime();
 }
@@ -1257,13 +1346,18 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
   const int b = (int)blockIdx.x;
   const bool finaliser = b >= ra.workers, leader = b == ra.workers;
   unsigned int last = ra.first_tag;
+  if (ra.timeline && b < TL_HWID_BLOCKS && threadIdx.x == 0) {  // (device timeline: where this block runs; a block stays on its compute unit)
+    const unsigned int hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_HW_ID, HW_REG_XCC_ID, 32 bits each
+    ra.timeline[TL_HWID0 + b] = ((unsigned long long)xcc << 32) | hw;
+  }
   // the first real row of a worker decides which factor's pose granules it watches between requests (a worker that owns only padding rows of
   // an XCD-aware map watches factor 0: it still has to see the session end)
   int first_row = -1;
   if (!finaliser)
     for (int r = b; r < ra.total_rows && first_row < 0; r += ra.workers)
       if (ra.blockmap[r].x >= 0) first_row = r;
-  for (;;) {
+  // a finalising block and a worker block each run a loop of their own: what one role keeps in registers around its loop the other never holds
+  for (; finaliser;) {
     if (leader && !ra.direct) {
       // ---- wait for a request in host memory; re-publish the poses (device granules) or the end of the session.  Word w of the request
       // lines (8 per line: 7 doubles + tag) is polled by thread w -- the first LEAD_WORDS words in one sweep; a longer request is read in
@@ -1389,6 +1483,8 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       last = tag;
       continue;
     }
+  }
+  for (;;) {
     // ---- worker: its rows of this request
     if (first_row < 0) {
       wait_pose(ra, 0, last, 0u, s_pose, &s_tag);  // nothing to compute: this block only follows the session
@@ -1403,13 +1499,21 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
     for (int r = first_row; r < ra.total_rows; r += ra.workers) {
       const int2 bm = ra.blockmap[r];
       if (bm.x < 0) continue;
-      // everything that does not depend on the pose is fetched BEFORE the wait: the descriptor and this lane's first point
+      // everything that does not depend on the pose is fetched BEFORE the wait: the descriptor and this lane's first two points
       const FactorDesc d = ra.descs[bm.x];
       PointIn p0;
+#if GLIM_AMD_RES_FLAT2
+      PointIn p1;  // ... and its second (compute_row's own clamp: a lane without one loads the factor's last point and does not use it)
+#endif
       {
         const unsigned int i0 = (unsigned int)min(bm.y * BLOCK + (int)threadIdx.x, max(d.n - 1, 0));
         if (PLANE_ONLY || d.plane) p0 = load_point<true>(d, i0);
         else p0 = load_point<false>(d, i0);
+#if GLIM_AMD_RES_FLAT2
+        const unsigned int i1 = (unsigned int)max(min(bm.y * BLOCK + (int)threadIdx.x + d.num_blocks * BLOCK, d.n - 1), 0);
+        if (PLANE_ONLY || d.plane) p1 = load_point<true>(d, i1);
+        else p1 = load_point<false>(d, i1);
+#endif
       }
       if (bm.x != have) {
         wait_pose(ra, bm.x, last, tag, s_pose, &s_tag);
@@ -1427,8 +1531,13 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       }
       unsigned long long* const tlw = (ra.timeline && r == first_row) ? ra.timeline + TL_WORKER0 + 4 * b : nullptr;
       tl_stamp(tlw, 0);
-      if (PLANE_ONLY || d.plane) compute_row<MODE_LINEARIZE, false, true, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr);
-      else compute_row<MODE_LINEARIZE, false, false, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr);
+#if GLIM_AMD_RES_FLAT2
+      const PointIn* const second = &p1;
+#else
+      const PointIn* const second = nullptr;
+#endif
+      if (PLANE_ONLY || d.plane) compute_row<MODE_LINEARIZE, false, true, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, second);
+      else compute_row<MODE_LINEARIZE, false, false, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, second);
       tl_stamp(tlw, 1);
       publish_row_tagged<MODE_LINEARIZE>(s_red, ra.rows16, (size_t)(d.first_block + bm.y), tag);
       tl_stamp(tlw, 2);
@@ -2432,11 +2541,11 @@ struct ResidentSession {
   // device timeline (glim_amd_debug_resident_timeline): on from the next launch when `timeline_on`; the buffer outlives the sessions
   bool timeline_on = false;
   unsigned long long* d_timeline = nullptr;
-  int timeline_workers = 0;
+  int timeline_workers = 0, timeline_blocks = 0;  // of the last stamped launch: worker blocks, all blocks
   double last_request_host_us = 0.0;  // host: from posting the last request to its last record granule
 };
 ResidentSession g_resident[16];
-constexpr size_t TIMELINE_WORDS = TL_WORKER0 + 4 * 1024;
+constexpr size_t TIMELINE_WORDS = TL_HWID0 + TL_HWID_BLOCKS;
 
 unsigned int next_session_tag(ResidentSession& S) {
   S.counter = (S.counter >= 0x7ffffff0u) ? 1u : S.counter + 1u;
@@ -2600,10 +2709,12 @@ int resident_launch(ResidentSession& S, glim_amd_factor_set* set, FactorPlan* pl
     }
   }
   const bool plane_only = plan->plane_rows == plan->total_rows;
-  if (pieces && plane_only) resident_kernel<true, true><<<ra.workers + TAG_PIECES * nf, BLOCK, 0, S.stream>>>(ra);
-  else if (pieces) resident_kernel<false, true><<<ra.workers + TAG_PIECES * nf, BLOCK, 0, S.stream>>>(ra);
-  else if (plane_only) resident_kernel<true, false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
-  else resident_kernel<false, false><<<ra.workers + nf, BLOCK, 0, S.stream>>>(ra);
+  const int blocks = ra.workers + (pieces ? TAG_PIECES : 1) * nf;
+  if (ra.timeline) S.timeline_blocks = blocks;
+  if (pieces && plane_only) resident_kernel<true, true><<<blocks, BLOCK, 0, S.stream>>>(ra);
+  else if (pieces) resident_kernel<false, true><<<blocks, BLOCK, 0, S.stream>>>(ra);
+  else if (plane_only) resident_kernel<true, false><<<blocks, BLOCK, 0, S.stream>>>(ra);
+  else resident_kernel<false, false><<<blocks, BLOCK, 0, S.stream>>>(ra);
   GA_HIP(hipGetLastError());
   S.launched = true;
   S.raw_record = ra.raw_record != 0;
@@ -2802,6 +2913,17 @@ extern "C" int glim_amd_debug_resident_timeline(int device, int enable, double* 
       put(19, rel(h[5]));
       put(20, rel(h[6]));
       put(21, (h[4] > h[2] && h[2]) ? (double)h[7] / ((double)(h[4] - h[2]) * 0.01) : 0.0);  // shader ticks per microsecond = MHz
+      // per block (a caller that asks for more than the summary): [22] blocks of the launch, [23] its worker blocks, then
+      // GLIM_AMD_RESIDENT_TIMELINE_BLOCK_FIELDS values per block: pose seen, first row computed, row granules published, point loop left
+      // (-1: no stamp -- a finaliser, a worker without a row) and where it runs (HW_ID + 2^32 XCC_ID: 36 bits, exact in a double)
+      const int nb = std::min(S.timeline_blocks, TL_HWID_BLOCKS);
+      put(22, (double)nb);
+      put(23, (double)S.timeline_workers);
+      for (int k = 0; k < nb; k++) {
+        const unsigned long long* p = k < S.timeline_workers ? &h[(size_t)TL_WORKER0 + 4 * (size_t)k] : nullptr;
+        for (int s = 0; s < 4; s++) put(24 + 5 * k + s, (p && p[s]) ? rel(p[s]) : -1.0);
+        put(24 + 5 * k + 4, (double)h[(size_t)TL_HWID0 + (size_t)k]);
+      }
     }
   }
   S.timeline_on = enable != 0;

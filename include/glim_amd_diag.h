@@ -162,8 +162,17 @@ int glim_amd_debug_resident_post_stats(int device, uint64_t* direct, uint64_t* l
  *   [16..18] worker blocks: point loop left (before the wave / block reduction), min / median / max
  *   [19] finaliser: its 32 group sums added   [20] its 3x3 blocks rotated (the record store follows; = [19] for a raw record, which the host rotates)
  *   [21] NOT a time: the shader clock the session ran at between [11] and [13], MHz (s_memtime ticks per s_memrealtime microsecond)
+ * A caller that passes more than GLIM_AMD_RESIDENT_TIMELINE_FIELDS fields also gets the account block by block (who is late, and where it runs):
+ *   [22] blocks of the launch (B)   [23] its worker blocks (blocks 0 .. [23] - 1; the others finalise)
+ *   [24 + 5 b + {0, 1, 2, 3}] block b: pose seen, first row computed, row granules published, point loop left; -1 where the block has no such
+ *       stamp (a finalising block, a worker without a row)
+ *   [24 + 5 b + 4] where block b runs: HW_REG_HW_ID + 2^32 * HW_REG_XCC_ID as the block read them (gfx9 HW_ID layout: compute unit in bits 8..11,
+ *       shader array bit 12, shader engine from bit 13).  Two blocks share a compute unit when XCC_ID and bits 8..15 of HW_ID agree.
+ *   GLIM_AMD_RESIDENT_TIMELINE_FIELDS + 2 + 5 * GLIM_AMD_RESIDENT_TIMELINE_MAX_BLOCKS fields hold every launch.
  * GLIM_AMD_ERR_STATE: a request is in flight, or no session has run with the stamps on. */
 #define GLIM_AMD_RESIDENT_TIMELINE_FIELDS 22
+#define GLIM_AMD_RESIDENT_TIMELINE_BLOCK_FIELDS 5
+#define GLIM_AMD_RESIDENT_TIMELINE_MAX_BLOCKS 2048
 int glim_amd_debug_resident_timeline(int device, int enable, double* microseconds, int32_t num_fields);
 /* ends the device's resident session now instead of letting it idle out (GLIM_AMD_ERR_STATE while a request is in flight). */
 int glim_amd_debug_resident_stop(int device);
