@@ -249,6 +249,33 @@ class BundleTraceRound(C.Structure):
     _fields_ = [("lam", C.c_double), ("cost", C.c_double), ("accepted", C.c_int32), ("status", C.c_int32)]
 
 
+class BaParams(C.Structure):
+    """glim_amd_ba_params (include/glim_amd.h "Plane / edge bundle-adjustment factors and ball selection")"""
+
+    _fields_ = [("min_radius", C.c_double), ("max_radius", C.c_double), ("plane_eps", C.c_double)]
+
+
+class BaStats(C.Structure):
+    """glim_amd_ba_stats"""
+
+    _fields_ = [("num_points", C.c_int64), ("sum", C.c_double * 3), ("sum_cross", C.c_double * 6), ("eigenvalues", C.c_double * 3)]
+
+
+class BaRadiusResult(C.Structure):
+    """glim_amd_ba_radius_result"""
+
+    _fields_ = [("radius", C.c_double), ("num_points", C.c_int64), ("eigenvalues", C.c_double * 3), ("trials", C.c_int32), ("stop", C.c_int32)]
+
+
+class BaTraceEntry(C.Structure):
+    """glim_amd_ba_trace_entry (include/glim_amd_diag.h)"""
+
+    _fields_ = [("radius", C.c_double), ("count", C.c_int64), ("eigenvalues", C.c_double * 3), ("decision", C.c_int32), ("reserved", C.c_int32)]
+
+
+BA_MAX_FRAMES, BA_MAX_TRIALS, BA_MOMENT_DOUBLES, BA_DEGENERATE = 128, 10, 13, 0x1  # GLIM_AMD_BA_* (include/glim_amd.h)
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -386,6 +413,18 @@ SYMBOLS = {
     "glim_amd_debug_bundle_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
                                                C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
                                                C.POINTER(BundleTraceRound)]),
+    "glim_amd_ba_default_params": (_i, [C.POINTER(BaParams)]),
+    "glim_amd_ba_ball_select": (_i, [_pp, _i32, _dp, _dp, _d, _i64, _ip, _lp]),
+    "glim_amd_ba_ball_stats": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaStats)]),
+    "glim_amd_ba_auto_radius": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaParams), C.POINTER(BaRadiusResult)]),
+    "glim_amd_debug_ba_auto_radius_trace": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaParams), C.POINTER(BaRadiusResult), C.POINTER(BaTraceEntry), _ip]),
+    "glim_amd_debug_ba_eigen3": (_i, [_vp, _i32, _dp, _dp, _dp]),
+    "glim_amd_ba_factor_create": (_i, [_vp, _i32, _i64, _dp, _ip, _i32, _pp]),
+    "glim_amd_ba_factor_create_from_ball": (_i, [_pp, _i32, _dp, _dp, _d, _i32, _pp]),
+    "glim_amd_ba_factor_info": (_i, [_vp, _ip, _lp, _ip, _ip, _dp]),
+    "glim_amd_ba_factor_error": (_i, [_vp, _dp, _dp, C.POINTER(C.c_uint32)]),
+    "glim_amd_ba_factor_linearize": (_i, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint32)]),
+    "glim_amd_ba_factor_destroy": (_i, [_vp]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

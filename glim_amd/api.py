@@ -2083,3 +2083,188 @@ def overlap_gpu_batch(queries, ctx=None):
     out = np.zeros(len(queries), dtype=np.float64)
     check(lib().glim_amd_overlap_batch(ctx._h, len(queries), _ip(nt), hs, _dp(T), srcs, _dp(out)), "glim_amd_overlap_batch")
     return out.tolist()
+
+
+# ---- plane / edge bundle-adjustment factors and ball selection (include/glim_amd.h) ----
+def clone_exact(points, ctx=None):
+    """A cloud that keeps its points in FP64 (glim_amd_cloud_create_exact): what the ball selection reads without the rounding of clone()."""
+    ctx = ctx or default_context()
+    points = np.asarray(points, dtype=np.float64).reshape(len(points), -1) if len(points) else np.zeros((0, 3))
+    p4 = np.ones((len(points), 4), dtype=np.float64)
+    p4[:, :3] = points[:, :3]
+    h = C.c_void_p()
+    check(lib().glim_amd_cloud_create_exact(ctx._h, len(p4), _dp(p4), C.byref(h)), "glim_amd_cloud_create_exact")
+    return PointCloudGPU(h, ctx)
+
+
+class BundleAdjustmentParams:
+    """The radius search's limits (bundle_adjustment_modal.cpp:21-25)."""
+
+    def __init__(self, min_radius=0.1, max_radius=5.0, plane_eps=0.01):
+        self.min_radius, self.max_radius, self.plane_eps = float(min_radius), float(max_radius), float(plane_eps)
+
+    def _c(self):
+        return _lib.BaParams(self.min_radius, self.max_radius, self.plane_eps)
+
+
+def _ball_args(clouds, poses, center):
+    S = len(clouds)
+    if len(poses) != S:
+        raise ValueError("one pose per cloud")
+    T = np.zeros((max(S, 1), 12))
+    for i, Ti in enumerate(poses):
+        T[i] = pose12(Ti)
+    c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(3))
+    hs = (C.c_void_p * max(S, 1))(*[cl._h for cl in clouds])
+    return hs, S, T, c
+
+
+def ba_ball_select(clouds, poses, center, radius, capacity=None):
+    """extract_points (bundle_adjustment_modal.cpp:143-161) over device clouds: -> (pairs, count).  pairs: min(count, capacity) x 2 int32
+    (sub-map index, point index), ascending; count: how many points the ball holds, whatever the capacity (default: every point)."""
+    hs, S, T, c = _ball_args(clouds, poses, center)
+    if capacity is None:
+        capacity = sum(cl.size() for cl in clouds)
+    pairs = np.zeros((max(int(capacity), 1), 2), dtype=np.int32)
+    n = C.c_int64()
+    check(lib().glim_amd_ba_ball_select(hs, S, _dp(T), _dp(c), float(radius), int(capacity), _ip(pairs), C.byref(n)), "glim_amd_ba_ball_select")
+    return pairs[: min(n.value, int(capacity))].copy(), n.value
+
+
+def ba_ball_stats(clouds, poses, center, radius):
+    """calc_eigenvalues (:163-184) of the ball's points: {num_points, sum (3), sum_cross (3 x 3), eigenvalues (3, ascending)}."""
+    hs, S, T, c = _ball_args(clouds, poses, center)
+    out = _lib.BaStats()
+    check(lib().glim_amd_ba_ball_stats(hs, S, _dp(T), _dp(c), float(radius), C.byref(out)), "glim_amd_ba_ball_stats")
+    s6 = np.array(out.sum_cross[:])
+    return {"num_points": out.num_points, "sum": np.array(out.sum[:]), "eigenvalues": np.array(out.eigenvalues[:]),
+            "sum_cross": np.array([[s6[0], s6[1], s6[2]], [s6[1], s6[3], s6[4]], [s6[2], s6[4], s6[5]]])}
+
+
+BA_STOP = {0: "trials", 1: "range", 2: "few_points", 3: "plane_eps"}
+BA_DECISION = {0: "initial", 1: "taken", 2: "range", 3: "few_points", 4: "plane_eps"}
+
+
+def ba_auto_radius(clouds, poses, center, radius, params=None, trace=False):
+    """auto_radius (:186-227) in one call and one host synchronisation: {radius, num_points, eigenvalues, trials, stop}; with trace=True
+    also "trace": one {radius, count, eigenvalues, decision} per evaluation (the window of include/glim_amd_diag.h)."""
+    hs, S, T, c = _ball_args(clouds, poses, center)
+    prm = (params or BundleAdjustmentParams())._c()
+    out = _lib.BaRadiusResult()
+    if trace:
+        ent = (_lib.BaTraceEntry * (_lib.BA_MAX_TRIALS + 1))()
+        ne = C.c_int32()
+        check(lib().glim_amd_debug_ba_auto_radius_trace(hs, S, _dp(T), _dp(c), float(radius), C.byref(prm), C.byref(out), ent, C.byref(ne)),
+              "glim_amd_debug_ba_auto_radius_trace")
+    else:
+        check(lib().glim_amd_ba_auto_radius(hs, S, _dp(T), _dp(c), float(radius), C.byref(prm), C.byref(out)), "glim_amd_ba_auto_radius")
+    res = {"radius": out.radius, "num_points": out.num_points, "eigenvalues": np.array(out.eigenvalues[:]), "trials": out.trials,
+           "stop": BA_STOP.get(out.stop, out.stop)}
+    if trace:
+        res["trace"] = [{"radius": e.radius, "count": e.count, "eigenvalues": np.array(e.eigenvalues[:]), "decision": BA_DECISION.get(e.decision, e.decision)}
+                        for e in ent[: ne.value]]
+    return res
+
+
+def ba_debug_eigen3(matrices, ctx=None):
+    """csrc/eig3_direct.hpp on the device, one thread per 3 x 3 symmetric matrix: -> (eigenvalues n x 3 ascending, eigenvectors n x 3 x 3 with
+    [i, k] the k-th eigenvector)."""
+    ctx = ctx or default_context()
+    m = np.ascontiguousarray(np.asarray(matrices, dtype=np.float64).reshape(-1, 9))
+    lam, U = np.zeros((len(m), 3)), np.zeros((len(m), 9))
+    check(lib().glim_amd_debug_ba_eigen3(ctx._h, len(m), _dp(m), _dp(lam), _dp(U)), "glim_amd_debug_ba_eigen3")
+    return lam, U.reshape(-1, 3, 3)
+
+
+class PlaneEVMFactor:
+    """gtsam_points::PlaneEVMFactor on the device: the cost is the smallest eigenvalue of the covariance of the points of K frames moved by
+    their poses.  The points are reduced to per-frame moments once, at creation; error() and linearize() read the moments only."""
+
+    KIND = 0
+
+    def __init__(self, handle, ctx):
+        self._h, self.ctx = handle, ctx
+        K, N = C.c_int32(), C.c_int64()
+        check(lib().glim_amd_ba_factor_info(self._h, C.byref(K), C.byref(N), None, None, None), "glim_amd_ba_factor_info")
+        self._K, self._N = K.value, N.value
+
+    @classmethod
+    def from_ball(cls, clouds, poses, center, radius):
+        """The factor create_factor builds (:229-245): the ball's points, frame by frame, without leaving the device.  frames() are the
+        indices of the clouds that had a point in the ball."""
+        hs, S, T, c = _ball_args(clouds, poses, center)
+        h = C.c_void_p()
+        check(lib().glim_amd_ba_factor_create_from_ball(hs, S, _dp(T), _dp(c), float(radius), cls.KIND, C.byref(h)), "glim_amd_ba_factor_create_from_ball")
+        return cls(h, clouds[0].ctx)
+
+    @classmethod
+    def from_points(cls, points, frame_index, num_frames=None, ctx=None):
+        """points: n x 3, frame-local; frame_index: n entries in [0, num_frames).  What add(point, key) collects."""
+        ctx = ctx or default_context()
+        p = np.ascontiguousarray(np.asarray(points, dtype=np.float64)[:, :3])
+        fi = np.ascontiguousarray(np.asarray(frame_index, dtype=np.int32))
+        if len(fi) != len(p):
+            raise ValueError("one frame index per point")
+        if num_frames is None:
+            num_frames = int(fi.max()) + 1 if len(fi) else 0
+        h = C.c_void_p()
+        check(lib().glim_amd_ba_factor_create(ctx._h, cls.KIND, len(p), _dp(p), _ip(fi), int(num_frames), C.byref(h)), "glim_amd_ba_factor_create")
+        return cls(h, ctx)
+
+    def num_points(self):
+        return self._N
+
+    def num_frames(self):
+        return self._K
+
+    def frames(self):
+        kept = np.zeros(self._K, dtype=np.int32)
+        check(lib().glim_amd_ba_factor_info(self._h, None, None, None, _ip(kept), None), "glim_amd_ba_factor_info")
+        return kept
+
+    def moments(self):
+        """K x 13: n | c_f | v_f | P_f (00 01 02 11 12 22)"""
+        m = np.zeros((self._K, _lib.BA_MOMENT_DOUBLES))
+        check(lib().glim_amd_ba_factor_info(self._h, None, None, None, None, _dp(m)), "glim_amd_ba_factor_info")
+        return m
+
+    def _poses(self, poses):
+        if len(poses) != self._K:
+            raise ValueError(f"{self._K} poses expected")
+        T = np.zeros((self._K, 12))
+        for i, Ti in enumerate(poses):
+            T[i] = pose12(Ti)
+        return T
+
+    def error(self, poses, with_status=False):
+        T = self._poses(poses)
+        cost, st = C.c_double(), C.c_uint32()
+        check(lib().glim_amd_ba_factor_error(self._h, _dp(T), C.byref(cost), C.byref(st)), "glim_amd_ba_factor_error")
+        return (cost.value, st.value) if with_status else cost.value
+
+    def linearize(self, poses):
+        """{cost, g (6 K), H (6 K x 6 K), status}; tangent order [rotation, translation] per frame, perturbation T Exp(xi).  The
+        HessianFactor of it is (G = H, g = -g, f = 2 cost)."""
+        T = self._poses(poses)
+        n = 6 * self._K
+        cost, st = C.c_double(), C.c_uint32()
+        g, H = np.zeros(n), np.zeros((n, n))
+        check(lib().glim_amd_ba_factor_linearize(self._h, _dp(T), C.byref(cost), _dp(g), _dp(H), C.byref(st)), "glim_amd_ba_factor_linearize")
+        return {"cost": cost.value, "g": g, "H": H, "status": st.value}
+
+    def close(self):
+        if self._h:
+            check(lib().glim_amd_ba_factor_destroy(self._h), "glim_amd_ba_factor_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EdgeEVMFactor(PlaneEVMFactor):
+    """gtsam_points::EdgeEVMFactor: the cost is the sum of the two smallest eigenvalues."""
+
+    KIND = 1

@@ -912,6 +912,118 @@ int glim_amd_keyframe_align_batch(const glim_amd_cloud* const* sources, const in
                                   uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out,
                                   double* factor_compact_out);
 
+/* ---- Plane / edge bundle-adjustment factors and ball selection ------------------------------------------------------------------------
+ * The device side of the reference's plane bundle-adjustment tool (src/glim/viewer/interactive/bundle_adjustment_modal.cpp): the ball
+ * selection of extract_points (:143-161), the statistics of calc_eigenvalues (:163-184), the radius search of auto_radius (:186-227) and the
+ * factor create_factor builds (:229-245), gtsam_points::PlaneEVMFactor (and its sibling EdgeEVMFactor).
+ *
+ *   inputs     S device clouds, S poses T_s (3x4 row-major FP64, world <- sub-map), a centre c and a radius r.  A point's coordinates are the
+ *              cloud's exact FP64 points where it keeps them (preprocessed, deskewed, merged and glim_amd_cloud_create_exact clouds), otherwise
+ *              its FP32 points widened to double.  Known difference: the reference's points are doubles and glim_amd_cloud_create rounds
+ *              them to float; a caller who needs the reference's booleans at the ball's surface uploads with glim_amd_cloud_create_exact.
+ *   selection  d = t - c is rounded once (three subtractions), then per point
+ *                  q_x = ((R00 p_x + R01 p_y) + R02 p_z) + d_x      (likewise q_y, q_z; every product and sum rounded, no FMA)
+ *                  qq  = (q_x q_x + q_y q_y) + q_z q_z
+ *              and the point is selected iff qq < r r (r r rounded once; strict, as at :154).  Pairs (sub-map index, point index) come out
+ *              ascending in sub-map, then in point -- the reference's loop order -- by a stable compaction over a prefix sum; no atomic
+ *              decides an order.  The call always reports the total count and writes at most `capacity` pairs, the first ones.
+ *   statistics N, s = sum q and S = sum q q^T (00 01 02 11 12 22) over the selection, then mean = s / N, cov = (S - mean s^T) / N (:177-178)
+ *              and the three eigenvalues, ascending, by the closed-form solver the reference calls (computeDirect, :181).  N = 0 gives zero
+ *              sums and NaN eigenvalues.  Every FP64 sum runs in an order that depends on the point order alone: the points are cut into
+ *              blocks of 256 in (sub-map, point) order, a block sums its values by one fixed tree over its lanes, and an ordered pass
+ *              adds the block sums: by ascending block inside 64 runs of consecutive blocks, then the 64 run sums by ascending run.  No
+ *              floating-point atomic.  Two calls give the same bits.
+ *   auto radius the rule of :186-227 with radii as doubles.  r0 is evaluated; then at most GLIM_AMD_BA_MAX_TRIALS trials, each at 0.8 r if
+ *              lambda_0 / lambda_2 > plane_eps at the current radius r, otherwise at 1.1 r.  The search stops without taking the trial when
+ *              the trial leaves [min_radius, max_radius], or selects fewer than 10 points, or is larger than r0 with
+ *              lambda_0 / lambda_2 > plane_eps.  Every trial is enqueued up front, a small device state decides each, later rounds idle
+ *              once the search has stopped, and the host synchronises ONCE.  The transformed points are kept across the rounds (32 B per
+ *              point), so a trial is a filtered reduction.
+ *   factor     K <= GLIM_AMD_BA_MAX_FRAMES frames, each with points in its own local frame.  kind GLIM_AMD_BA_PLANE: cost lambda_0;
+ *              GLIM_AMD_BA_EDGE: cost lambda_0 + lambda_1.  Creation is the only pass over points: per frame f, with c_f the frame's first
+ *              point in factor order, it keeps n_f, v_f = sum (p - c_f) and P_f = sum (p - c_f)(p - c_f)^T (FP64, ordered sums as above,
+ *              per frame).  error() and linearize() take K poses -- any poses -- and read the moments only:
+ *                  tau = R c_f + t,  sum q = sum_f (R v + n tau),  sum q q^T = sum_f (R P R^T + R v tau^T + tau (R v)^T + n tau tau^T),
+ *                  m = sum q / N,  C = sum q q^T / N - m m^T,  eigenpairs (lambda_k, u_k) of C (same solver)
+ *              with tau taken about the tau of frame 0 (C does not depend on the origin; only tau - m is used below).  For the eigenvalue
+ *              index e (0; edge: 0 and 1, the results added) and k != e, per frame: c_k = R^T u_k, alpha_k = u_k . (tau - m),
+ *              A_k = c_k . v + n alpha_k, B_k = P c_k + alpha_k v + A_k c_f, s = v + n c_f, Pt = P + v c_f^T + c_f v^T + n c_f c_f^T.
+ *              Tangent order [rotation, translation], perturbation T Exp(xi) (dq/dxi = [-R hat(p), R]):
+ *                  g_f  = (2 / N) [B_e x c_e ; A_e c_e]
+ *                  H_ff += (2 / N) [[hat(c_e) Pt hat(c_e)^T, (s x c_e) c_e^T], [. ^T, n c_e c_e^T]]
+ *                  H   -= (2 / N^2) S S^T,  S_f = [s x c_e ; n c_e]
+ *                  H   += sum_{k != e} (2 / N^2) / (lambda_e - lambda_k) W_k W_k^T,  W_k,f = [B_e x c_k + B_k x c_e ; A_e c_k + A_k c_e]
+ *              For the edge kind the k = 1 term of e = 0 and the k = 0 term of e = 1 are the same W W^T with opposite coefficients: their
+ *              sum is zero and neither is formed (nor can their gap set the DEGENERATE bit).
+ *              H is symmetric (bit for bit) and in general indefinite -- the last terms are negative for lambda_0 --: callers damp it.
+ *              When |lambda_e - lambda_k| <= 1e-12 max(lambda_2, DBL_MIN) that k term is dropped and GLIM_AMD_BA_DEGENERATE is set in the
+ *              status word.  A factor of fewer than 3 points is refused (GLIM_AMD_ERR_INVALID).  The cost is the eigenvalue sum, unscaled.
+ * Deterministic: the same call returns the same bits. */
+#define GLIM_AMD_BA_MAX_FRAMES 128
+#define GLIM_AMD_BA_MAX_TRIALS 10
+#define GLIM_AMD_BA_PLANE 0
+#define GLIM_AMD_BA_EDGE 1
+#define GLIM_AMD_BA_DEGENERATE 0x1u
+#define GLIM_AMD_BA_MOMENT_DOUBLES 13 /* per frame: n | c_f (3) | v_f (3) | P_f (00 01 02 11 12 22) */
+enum { /* why the radius search ended */
+  GLIM_AMD_BA_STOP_TRIALS = 0,     /* all GLIM_AMD_BA_MAX_TRIALS trials were taken */
+  GLIM_AMD_BA_STOP_RANGE = 1,      /* the next trial left [min_radius, max_radius] */
+  GLIM_AMD_BA_STOP_FEW_POINTS = 2, /* the trial selected fewer than 10 points */
+  GLIM_AMD_BA_STOP_PLANE_EPS = 3   /* a trial larger than r0 had lambda_0 / lambda_2 > plane_eps */
+};
+typedef struct glim_amd_ba_params { /* bundle_adjustment_modal.cpp:21-25 */
+  double min_radius; /* 0.1 */
+  double max_radius; /* 5.0 */
+  double plane_eps;  /* 0.01 */
+} glim_amd_ba_params;
+typedef struct glim_amd_ba_stats {
+  int64_t num_points;
+  double sum[3];
+  double sum_cross[6]; /* 00 01 02 11 12 22 */
+  double eigenvalues[3];
+} glim_amd_ba_stats;
+typedef struct glim_amd_ba_radius_result {
+  double radius;      /* the last radius that was kept */
+  int64_t num_points; /* selected at that radius */
+  double eigenvalues[3];
+  int32_t trials; /* trials that were evaluated (<= GLIM_AMD_BA_MAX_TRIALS; r0 itself is not a trial) */
+  int32_t stop;   /* GLIM_AMD_BA_STOP_* */
+} glim_amd_ba_radius_result;
+typedef struct glim_amd_ba_factor glim_amd_ba_factor; /* a child of its context */
+
+int glim_amd_ba_default_params(glim_amd_ba_params* params);
+/* clouds: num_clouds >= 1 handles of one context (a cloud may be empty); T_world_submap12: num_clouds x 12; pairs: NULL with capacity 0, or
+ * capacity x 2 int32.  GLIM_AMD_ERR_INVALID: a NULL argument or handle, num_clouds < 1, clouds of two contexts, a radius that is NaN,
+ * infinite or <= 0, capacity < 0, a pose or centre that is not finite, more than 2^31 - 257 points in all. */
+int glim_amd_ba_ball_select(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12, const double* center3,
+                            double radius, int64_t capacity, int32_t* pairs, int64_t* count);
+int glim_amd_ba_ball_stats(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12, const double* center3,
+                           double radius, glim_amd_ba_stats* out);
+/* params NULL = the defaults.  Also GLIM_AMD_ERR_INVALID: min_radius > max_radius, or a parameter that is NaN. */
+int glim_amd_ba_auto_radius(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12, const double* center3,
+                            double radius0, const glim_amd_ba_params* params, glim_amd_ba_radius_result* out);
+/* A factor from host arrays: points3 is n x 3 (frame-local), frame_index n entries in [0, num_frames).  Factor order is ascending frame
+ * index, then the order given.  Frames without a point are dropped; glim_amd_ba_factor_info returns the kept indices, ascending.
+ * GLIM_AMD_ERR_INVALID: a NULL argument, a kind other than GLIM_AMD_BA_PLANE / GLIM_AMD_BA_EDGE, n < 3, num_frames < 1 or
+ * > GLIM_AMD_BA_MAX_FRAMES, a frame index out of range, a point that is not finite. */
+int glim_amd_ba_factor_create(glim_amd_ctx* ctx, int32_t kind, int64_t n, const double* points3, const int32_t* frame_index,
+                              int32_t num_frames, glim_amd_ba_factor** out);
+/* A factor from the ball selection, which never leaves the device: frame f holds the selected points of the f-th sub-map that has any,
+ * in point order, in that sub-map's frame.  Arguments as glim_amd_ba_ball_select; also GLIM_AMD_ERR_INVALID: fewer than 3 points selected
+ * or more than GLIM_AMD_BA_MAX_FRAMES sub-maps with a selected point. */
+int glim_amd_ba_factor_create_from_ball(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                                        const double* center3, double radius, int32_t kind, glim_amd_ba_factor** out);
+/* any output may be NULL.  kept_index: K entries; moments: K x GLIM_AMD_BA_MOMENT_DOUBLES */
+int glim_amd_ba_factor_info(const glim_amd_ba_factor* factor, int32_t* num_frames, int64_t* num_points, int32_t* kind, int32_t* kept_index,
+                            double* moments);
+/* poses12: K x 12, the poses of the kept frames in their order.  status: GLIM_AMD_BA_DEGENERATE or 0 (may be NULL).
+ * GLIM_AMD_ERR_INVALID: a NULL factor, pose array or output, a pose that is not finite. */
+int glim_amd_ba_factor_error(const glim_amd_ba_factor* factor, const double* poses12, double* cost, uint32_t* status);
+/* g: 6 K; H: 6 K x 6 K row-major, the whole matrix.  One small kernel over the frames and one fill over the block pairs; no point is read. */
+int glim_amd_ba_factor_linearize(const glim_amd_ba_factor* factor, const double* poses12, double* cost, double* g, double* H,
+                                 uint32_t* status);
+int glim_amd_ba_factor_destroy(glim_amd_ba_factor* factor);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,29 @@ int glim_amd_debug_keyframe_align_trace(const glim_amd_cloud* const* sources, co
                                         int32_t num_priors, uint32_t flags, int32_t count, const glim_amd_lm_params* params, glim_amd_align_result* out,
                                         double* factor_compact_out, glim_amd_align_trace_entry* rounds, double* prior_trace, double* Tf_trace,
                                         double* compact_trace);
+/* test window of the radius search of the plane bundle-adjustment tool (glim_amd.h): glim_amd_ba_auto_radius with the same arguments and
+ * result, plus one entry per evaluation in `entries` (1 + GLIM_AMD_BA_MAX_TRIALS of them; *num_entries are filled): entry 0 is r0, entry i
+ * the i-th trial.  An entry whose decision is GLIM_AMD_BA_TRACE_RANGE was not evaluated: its count is -1 and its eigenvalues are NaN. */
+enum {
+  GLIM_AMD_BA_TRACE_INITIAL = 0,    /* r0: always kept */
+  GLIM_AMD_BA_TRACE_TAKEN = 1,      /* the trial became the current radius */
+  GLIM_AMD_BA_TRACE_RANGE = 2,      /* outside [min_radius, max_radius]: the search stopped */
+  GLIM_AMD_BA_TRACE_FEW_POINTS = 3, /* fewer than 10 points: stopped */
+  GLIM_AMD_BA_TRACE_PLANE_EPS = 4   /* larger than r0 and lambda_0 / lambda_2 > plane_eps: stopped */
+};
+typedef struct {
+  double radius;
+  int64_t count;
+  double eigenvalues[3];
+  int32_t decision;
+  int32_t reserved;
+} glim_amd_ba_trace_entry;
+int glim_amd_debug_ba_auto_radius_trace(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                                        const double* center3, double radius0, const glim_amd_ba_params* params,
+                                        glim_amd_ba_radius_result* out, glim_amd_ba_trace_entry* entries, int32_t* num_entries);
+/* the eigen-solver of the plane bundle-adjustment statistics and factors (csrc/eig3_direct.hpp) run by one device thread per matrix:
+ * m9: count x 9 row-major symmetric; evals: count x 3 ascending; evecs: count x 9, evecs[3 k + r] = component r of eigenvector k */
+int glim_amd_debug_ba_eigen3(glim_amd_ctx* ctx, int32_t count, const double* m9, double* evals, double* evecs);
 
 #ifdef __cplusplus
 }

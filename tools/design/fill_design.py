@@ -165,6 +165,17 @@ if os.path.exists(kfa_path):
         +"  The device enqueues every round up front and the host loop stops with the last problem, so both times are divided by the rounds that ran a problem; the enqueued rounds that found every problem finished are in the device's time.  No speedup is claimed.")
 else:
     vals['KEYFRAME_MEASURED']="nothing yet.  `tools/keyframe_align_time.py` writes `profiles/keyframe_align/keyframe_align_time.json` (the device batch against the host-driven loop over `NonlinearFactorSetGPU.linearize_poses` of the same 34 B pairs, B = 1 / 8, a 12 000-point source against 17 × 2 maps of 131 072-point scans, totals and per-round figures, the variants alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
+# ---- the plane bundle-adjustment tool (tools/plane_ba_time.py) ----
+pba_path='profiles/plane_ba/plane_ba_time.json'
+if os.path.exists(pba_path):
+    pba=json.load(open(pba_path)); pd,ph=pba['device'],pba['numpy_restatement']
+    vals['PLANE_BA_MEASURED']=(f"one box, one run (`tools/plane_ba_time.py`, `{pba_path}`; {pba['submaps']} sub-maps of {sp(pba['points_per_submap'])} points, a wall through the centre, r₀ = {pba['r0']:g} selecting {sp(pba['selected_at_r0'])} points in {pba['frames_in_factor']} frames; "
+        f"synchronous calls timed on the host, median of {pba['repeats']}).  Device: select {pd['select_ms']:.2f} ms, statistics {pd['stats_ms']:.2f} ms, the whole radius search ({pba['auto_radius']['evaluations']} evaluations, one synchronisation) {pd['auto_radius_ms']:.2f} ms, "
+        f"factor creation from the ball {pd['factor_create_from_ball_ms']:.2f} ms, one linearize {pd['linearize_ms']:.3f} ms, one error {pd['error_ms']:.3f} ms.  "
+        f"The NumPy restatement of the same steps: select {ph['select_ms']:.0f} ms, select + statistics {ph['select_and_stats_ms']:.0f} ms, the radius search {ph['auto_radius_ms']:.0f} ms, the factor in point form {ph['factor_linearize_point_form_ms']:.0f} ms.  "
+        "Every device figure includes the upload of the sub-map descriptors and the transform pass over all points; nothing beyond these two programs is compared and no speed-up was promised in advance.")
+else:
+    vals['PLANE_BA_MEASURED']="nothing yet.  `tools/plane_ba_time.py` writes `profiles/plane_ba/plane_ba_time.json` (24 sub-maps of 65 536 points, r₀ = 1: select, statistics, the whole radius search, factor creation and one linearize beside the NumPy restatement of the same steps); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
