@@ -276,6 +276,37 @@ class BaTraceEntry(C.Structure):
 BA_MAX_FRAMES, BA_MAX_TRIALS, BA_MOMENT_DOUBLES, BA_DEGENERATE = 128, 10, 13, 0x1  # GLIM_AMD_BA_* (include/glim_amd.h)
 
 
+class EditWindow(C.Structure):
+    """glim_amd_edit_window (include/glim_amd.h "Map editing")"""
+
+    _fields_ = [("center", C.c_double * 3), ("resolution", C.c_double), ("window", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EditOutlierParams(C.Structure):
+    """glim_amd_edit_outlier_params"""
+
+    _fields_ = [("radius_offset", C.c_double), ("stddev_thresh", C.c_double), ("num_neighbors", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EditRegionGrowingParams(C.Structure):
+    """glim_amd_edit_region_growing_params"""
+
+    _fields_ = [("distance_threshold", C.c_double), ("cos_angle_threshold", C.c_double), ("dilation_radius", C.c_double), ("use_normals", C.c_int32),
+                ("max_hops", C.c_int32)]
+
+
+class EditRegionResult(C.Structure):
+    """glim_amd_edit_region_result"""
+
+    _fields_ = [("count", C.c_int64), ("num_candidates", C.c_int64), ("seed", C.c_int32 * 2), ("rounds", C.c_int32), ("status", C.c_int32),
+                ("seed_qq", C.c_double)]
+
+
+EDIT_BOX, EDIT_SPHERE, EDIT_WINDOW, EDIT_WINDOW_BALL = 0, 1, 2, 3  # GLIM_AMD_EDIT_* (include/glim_amd.h)
+EDIT_ROUNDS_PER_LOOK = 32
+EDIT_OK, EDIT_EMPTY, EDIT_FEW_POINTS = 0, 1, 2
+
+
 class GlimAmdError(RuntimeError):
     def __init__(self, code, where, detail=""):
         self.code = code
@@ -425,6 +456,11 @@ SYMBOLS = {
     "glim_amd_ba_factor_error": (_i, [_vp, _dp, _dp, C.POINTER(C.c_uint32)]),
     "glim_amd_ba_factor_linearize": (_i, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint32)]),
     "glim_amd_ba_factor_destroy": (_i, [_vp]),
+    "glim_amd_edit_select": (_i, [_pp, _i32, _dp, _i32, C.POINTER(EditWindow), _d, _i64, _ip, _lp]),
+    "glim_amd_edit_select_outliers": (_i, [_pp, _i32, _dp, C.POINTER(EditWindow), _d, C.POINTER(EditOutlierParams), _i64, _ip, _lp, _ip]),
+    "glim_amd_edit_region_grow": (_i, [_pp, _i32, _dp, C.POINTER(EditWindow), C.POINTER(EditRegionGrowingParams), _i64, _ip, _ip,
+                                       C.POINTER(EditRegionResult)]),
+    "glim_amd_edit_remove_points": (_i, [_vp, _i64, _ip, _pp]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

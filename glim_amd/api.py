@@ -2268,3 +2268,128 @@ class EdgeEVMFactor(PlaneEVMFactor):
     """gtsam_points::EdgeEVMFactor: the cost is the sum of the two smallest eigenvalues."""
 
     KIND = 1
+
+
+# ---- map editing: point selection, region growing, removal (include/glim_amd.h "Map editing") ----
+EDIT_BOX, EDIT_SPHERE, EDIT_WINDOW, EDIT_WINDOW_BALL = _lib.EDIT_BOX, _lib.EDIT_SPHERE, _lib.EDIT_WINDOW, _lib.EDIT_WINDOW_BALL
+EDIT_ROUNDS_PER_LOOK = _lib.EDIT_ROUNDS_PER_LOOK
+EDIT_STATUS = {_lib.EDIT_OK: "ok", _lib.EDIT_EMPTY: "empty", _lib.EDIT_FEW_POINTS: "few_points"}
+
+
+class RegionGrowingParams:
+    """Region growing over the candidates of the window.  The three thresholds' defaults are a recollection of
+    gtsam_points::RegionGrowingParams, which is not in the reference tree.  angle_threshold is in radians; its cosine is taken once, here."""
+
+    def __init__(self, distance_threshold=0.5, angle_threshold=np.deg2rad(10.0), dilation_radius=0.5, use_normals=False, max_hops=0):
+        self.distance_threshold, self.angle_threshold, self.dilation_radius = float(distance_threshold), float(angle_threshold), float(dilation_radius)
+        self.use_normals, self.max_hops = bool(use_normals), int(max_hops)
+
+    def cos_angle_threshold(self):
+        return float(np.cos(self.angle_threshold))
+
+    def _c(self):
+        return _lib.EditRegionGrowingParams(self.distance_threshold, self.cos_angle_threshold(), self.dilation_radius, int(self.use_normals), self.max_hops)
+
+
+def _edit_matrices(clouds, matrices):
+    S = len(clouds)
+    if len(matrices) != S:
+        raise ValueError("one matrix per cloud")
+    M = np.zeros((max(S, 1), 12))
+    for i, Mi in enumerate(matrices):
+        M[i] = pose12(Mi)
+    hs = (C.c_void_p * max(S, 1))(*[cl._h for cl in clouds])
+    return hs, S, M
+
+
+def _edit_window(center, resolution, window):
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    return _lib.EditWindow((C.c_double * 3)(*c), float(resolution), int(window), 0)
+
+
+def edit_local_matrices(model_matrix, poses):
+    """T_local_submap = inv(model matrix) T_world_submap per sub-map (points_selector.cpp:630, :637), FP64 on the host: S matrices 3 x 4."""
+    inv = np.linalg.inv(np.asarray(model_matrix, dtype=np.float64).reshape(4, 4))
+    out = []
+    for T in poses:
+        T4 = np.eye(4)
+        T4[:3, :4] = np.asarray(T, dtype=np.float64)[:3, :4]
+        out.append((inv @ T4)[:3, :4].copy())
+    return out
+
+
+def edit_select(clouds, poses, mode, model_matrix=None, center=None, radius=0.0, resolution=2.0, window=5, capacity=None):
+    """The editor's selections over device clouds -> (pairs, count).  mode EDIT_BOX / EDIT_SPHERE: the unit box / sphere of the gizmo's
+    model matrix (select_points_tool, :623-674); EDIT_WINDOW: the cells around `center` (collect_neighbor_point_ids, :85-112);
+    EDIT_WINDOW_BALL: those within `radius` of it (select_points_radius, :677-700).  pairs: min(count, capacity) x 2 int32 (sub-map, point),
+    ascending."""
+    if mode in (EDIT_BOX, EDIT_SPHERE):
+        hs, S, M = _edit_matrices(clouds, edit_local_matrices(model_matrix, poses))
+        win = None
+    else:
+        hs, S, M = _edit_matrices(clouds, poses)
+        win = C.byref(_edit_window(center, resolution, window))
+    if capacity is None:
+        capacity = sum(cl.size() for cl in clouds)
+    pairs = np.zeros((max(int(capacity), 1), 2), dtype=np.int32)
+    n = C.c_int64()
+    check(lib().glim_amd_edit_select(hs, S, _dp(M), int(mode), win, float(radius), int(capacity), _ip(pairs), C.byref(n)), "glim_amd_edit_select")
+    return pairs[: min(n.value, int(capacity))].copy(), n.value
+
+
+def edit_select_outliers(clouds, poses, center, radius, radius_offset=1.0, num_neighbors=10, stddev_thresh=2.0, resolution=2.0, window=5, capacity=None):
+    """select_outlier_points_radius (:703-759) -> (pairs, count, status): the points within `radius` of `center` whose mean distance to
+    their k nearest neighbours -- among the points within radius + radius_offset -- is not below mean + stddev_thresh * std.
+    status "few_points": fewer candidates than k, nothing selected."""
+    hs, S, M = _edit_matrices(clouds, poses)
+    win = _edit_window(center, resolution, window)
+    prm = _lib.EditOutlierParams(float(radius_offset), float(stddev_thresh), int(num_neighbors), 0)
+    if capacity is None:
+        capacity = sum(cl.size() for cl in clouds)
+    pairs = np.zeros((max(int(capacity), 1), 2), dtype=np.int32)
+    n, st = C.c_int64(), C.c_int32()
+    check(lib().glim_amd_edit_select_outliers(hs, S, _dp(M), C.byref(win), float(radius), C.byref(prm), int(capacity), _ip(pairs), C.byref(n), C.byref(st)),
+          "glim_amd_edit_select_outliers")
+    return pairs[: min(n.value, int(capacity))].copy(), n.value, EDIT_STATUS.get(st.value, st.value)
+
+
+def edit_region_grow(clouds, poses, center, params=None, resolution=2.0, window=5, capacity=None):
+    """select_points_segmentation, region growing (:798-810) -> {pairs, levels, count, num_candidates, seed, seed_qq, rounds, status}.
+    pairs ascending; levels[i] = hops of pairs[i] from the seed (dilated points: last level + 1)."""
+    hs, S, M = _edit_matrices(clouds, poses)
+    win = _edit_window(center, resolution, window)
+    prm = (params or RegionGrowingParams())._c()
+    if capacity is None:
+        capacity = sum(cl.size() for cl in clouds)
+    pairs = np.zeros((max(int(capacity), 1), 2), dtype=np.int32)
+    levels = np.zeros(max(int(capacity), 1), dtype=np.int32)
+    out = _lib.EditRegionResult()
+    check(lib().glim_amd_edit_region_grow(hs, S, _dp(M), C.byref(win), C.byref(prm), int(capacity), _ip(pairs), _ip(levels), C.byref(out)),
+          "glim_amd_edit_region_grow")
+    wr = min(out.count, int(capacity))
+    return {"pairs": pairs[:wr].copy(), "levels": levels[:wr].copy(), "count": out.count, "num_candidates": out.num_candidates,
+            "seed": (out.seed[0], out.seed[1]), "seed_qq": out.seed_qq, "rounds": out.rounds, "status": EDIT_STATUS.get(out.status, out.status)}
+
+
+def edit_remove_points(cloud, indices):
+    """A NEW cloud without the listed points (any order, duplicates allowed), the others in their original order with every per-point array
+    the cloud holds; the input cloud is untouched (gtsam_points::sample with the surviving indices, :537-562).  Neighbours are dropped."""
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+    h = C.c_void_p()
+    check(lib().glim_amd_edit_remove_points(cloud._h, len(idx), _ip(idx) if len(idx) else None, C.byref(h)), "glim_amd_edit_remove_points")
+    g = PointCloudGPU(h, cloud.ctx)
+    g._k = 0
+    g._has_intensities = getattr(cloud, "_has_intensities", False)
+    return g
+
+
+def edit_remove_selected(clouds, pairs):
+    """remove_selected_points (:513-562): the sorted pairs are partitioned by sub-map, and every sub-map that is touched gets a new cloud.
+    -> a list like `clouds` in which the untouched sub-maps are the very objects passed in."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ids = np.sort((pairs[:, 0].astype(np.uint64) << np.uint64(32)) | pairs[:, 1].astype(np.uint64))
+    sub = (ids >> np.uint64(32)).astype(np.int64)
+    out = list(clouds)
+    for s in np.unique(sub):
+        out[int(s)] = edit_remove_points(clouds[int(s)], (ids[sub == s] & np.uint64(0xFFFFFFFF)).astype(np.int32))
+    return out

@@ -24,6 +24,7 @@
 #include "scope_sync.hpp"
 #include "device_math.hpp"
 #include "scan.hpp"
+#include "outlier_stat.hpp"
 #include "sample_hash.hpp"  // == orc_sample_hash
 
 using namespace glim_amd;
@@ -598,59 +599,7 @@ __global__ __launch_bounds__(256) void pp_gather_out_ranked_kernel(const int* __
   if (inten) inten[o] = I[i];
 }
 
-// ---- statistical outlier removal (gtsam_points::remove_outliers): mean distance to the k nearest neighbours ----
-__global__ __launch_bounds__(256) void pp_mean_dist_kernel(int f, const double4* __restrict__ P, const int* __restrict__ nb, int k,
-                                                           double* __restrict__ d, double* __restrict__ partial) {
-  __shared__ double s_sum[4], s_sq[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double di = 0.0;
-  if (i < f) {
-    const double4 p = P[i];
-    double s = 0.0;
-    for (int j = 0; j < k; j++) {
-      const double4 q = P[nb[(size_t)i * k + j]];
-      const double dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-      s += __dsqrt_rn(dadd(dadd(dmul(dx, dx), dmul(dy, dy)), dmul(dz, dz)));
-    }
-    di = s / (double)k;
-    d[i] = di;
-  }
-  // deterministic block sums of d and d^2 (fixed butterfly order), one partial pair per block
-  double a = di, b = dmul(di, di);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_sum[threadIdx.x >> 6] = a;
-    s_sq[threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-    partial[2 * blockIdx.x + 1] = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
-  }
-}
-
-__global__ void pp_outlier_thresh_kernel(int f, int blocks, const double* __restrict__ partial, double std_mul, double* __restrict__ thresh) {
-  double sum = 0.0, sq = 0.0;
-  for (int b = 0; b < blocks; b++) {  // block order: deterministic
-    sum += partial[2 * b];
-    sq += partial[2 * b + 1];
-  }
-  const double mean = sum / (double)f;
-  const double var = sq / (double)f - dmul(mean, mean);
-  *thresh = dadd(mean, dmul(std_mul, sqrt(var > 0.0 ? var : 0.0)));
-}
-
-__global__ __launch_bounds__(256) void pp_inlier_flag_kernel(int f, const double* __restrict__ d, const double* __restrict__ thresh,
-                                                             int* __restrict__ flags) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i > f) return;
-  flags[i] = (i < f && d[i] < *thresh) ? 1 : 0;
-}
-
+// ---- statistical outlier removal (gtsam_points::remove_outliers): the mean-distance statistic is outlier_stat.hpp ----
 __global__ __launch_bounds__(256) void pp_compact_index_kernel(int m, const int* __restrict__ flags, const int* __restrict__ pos, u32* __restrict__ idx) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < m && flags[i]) idx[pos[i]] = (u32)i;
@@ -1117,18 +1066,13 @@ int glim_amd_preprocess(glim_amd_ctx* ctx, int64_t n64, const double* points4, c
     std::lock_guard<std::mutex> lock(ctx->mu);
     GA_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream();
-    const int blocks = grid_for(f);
-    DeviceTemp d, partial, thresh, flags, pos, tiles, idx;
-    GA_HIP(pool_malloc(&d.p, (size_t)f * sizeof(double)));
-    GA_HIP(pool_malloc(&partial.p, (size_t)blocks * 2 * sizeof(double)));
-    GA_HIP(pool_malloc(&thresh.p, sizeof(double)));
+    OutlierScratch stat;
+    DeviceTemp flags, pos, tiles, idx;
     GA_HIP(pool_malloc(&flags.p, (size_t)(f + 1) * sizeof(int)));
     GA_HIP(pool_malloc(&pos.p, (size_t)(f + 1) * sizeof(int)));
     GA_HIP(pool_malloc(&tiles.p, scan_scratch_ints((unsigned int)f + 1) * sizeof(int)));
     GA_HIP(pool_malloc(&idx.p, (size_t)f * sizeof(u32)));
-    pp_mean_dist_kernel<<<blocks, 256, 0, st>>>(f, c->pts64, c->neighbors, k, d.as<double>(), partial.as<double>());
-    pp_outlier_thresh_kernel<<<1, 1, 0, st>>>(f, blocks, partial.as<double>(), prm->outlier_std_mul_factor, thresh.as<double>());
-    pp_inlier_flag_kernel<<<grid_for(f + 1), 256, 0, st>>>(f, d.as<double>(), thresh.as<double>(), flags.as<int>());
+    GA_HIP(outlier_inlier_flags(st, f, c->pts64, c->neighbors, k, prm->outlier_std_mul_factor, &stat, flags.as<int>()));
     GA_HIP(exclusive_scan_int(st, flags.as<int>(), (unsigned int)f + 1, tiles.as<int>(), pos.as<int>()));
     pp_compact_index_kernel<<<grid_for(f), 256, 0, st>>>(f, flags.as<int>(), pos.as<int>(), idx.as<u32>());
     GA_HIP(hipGetLastError());

@@ -1024,6 +1024,108 @@ int glim_amd_ba_factor_linearize(const glim_amd_ba_factor* factor, const double*
                                  uint32_t* status);
 int glim_amd_ba_factor_destroy(glim_amd_ba_factor* factor);
 
+/* ---- Map editing: point selection, region growing, removal ---------------------------------------------------------------------------
+ * The device side of the reference's map editor (src/glim/viewer/editor/points_selector.cpp): the box / sphere gizmo (:623-674), the
+ * radius selection (:677-700), the statistical outliers in a radius (:703-759), region growing (:798-810) and the removal of the selection
+ * from the sub-map clouds (:513-562).  Min-cut segmentation (:774-797) is not built: a sequential max-flow whose source is not in the
+ * reference tree.
+ *
+ *   inputs     S device clouds and S matrices M_s (3x4 row-major FP64); point coordinates as for the ball selection above (the exact FP64
+ *              points where the cloud keeps them, FP32 widened otherwise).  The transformed point is
+ *                  v_x = ((M00 p_x + M01 p_y) + M02 p_z) + M03      (likewise v_y, v_z; every product and sum rounded, no FMA)
+ *   selection  pairs (sub-map index, point index), int32, ascending in sub-map and then in point, by a stable compaction over a prefix
+ *              sum; no atomic decides an order or a result.  Every call reports the true count and writes at most `capacity` pairs, the
+ *              first ones.  Modes:
+ *                BOX / SPHERE   M_s = T_local_submap = inv(gizmo model matrix) T_world_submap, formed by the caller (:630, :637; the C++
+ *                               and Python mirrors do it).  Box: -0.5 < v_k < 0.5 for all k (:648).  Sphere: (v_x v_x + v_y v_y) + v_z v_z
+ *                               < 1.0 (:654).  Both strict.
+ *                WINDOW         M_s = T_world_submap.  collect_neighbor_point_ids (:85-112) as a set: the point's cell is
+ *                               floor(v_k * (1.0 / resolution)) -- the product of :177 / :593 --, the window's centre cell is
+ *                               floor(c_k / resolution) -- the division of :87 --, and the point is kept iff every cell coordinate lies
+ *                               within `window` cells of the centre's.
+ *                WINDOW_BALL    WINDOW and e = v - c, qq = (e_x e_x + e_y e_y) + e_z e_z, qq < r r (r r rounded once; strict, :690-691).
+ *                               The point is transformed first and the centre subtracted after: not the d = t - c form of
+ *                               glim_amd_ba_ball_select.
+ *   outliers   (:703-759) candidates = WINDOW_BALL with radius r + radius_offset; their world points go into a transient cloud in pair
+ *              order (its FP32 image holds e = v - c, which keeps the neighbour search's rounding to that of a few metres); the exact kNN
+ *              (k = num_neighbors <= 32, query included) and the statistic of glim_amd_preprocess's outlier removal run on it: d_i = mean
+ *              distance to the k neighbours, threshold = mean(d) + stddev_thresh * std(d), inlier iff d_i < threshold.  Returned: the
+ *              candidates with qq < r r that are not inliers.  Candidates between r and r + radius_offset take part in the statistic and
+ *              are never returned.  Fewer candidates than k: count 0 and status GLIM_AMD_EDIT_FEW_POINTS (:730-733).
+ *   region growing  gtsam_points::region_growing_* is not in the reference tree; these semantics are this project's and do not depend on
+ *              a traversal order.  Candidates: the WINDOW selection around the picked point c (:800).  Seed: the candidate with the
+ *              smallest qq to c, ties to the smaller pair.  Edge i-j: dd = (dx dx + dy dy) + dz dz < distance_threshold^2 (rounded once),
+ *              strict; with use_normals additionally |n_i . n_j| >= cos_angle_threshold, n the cloud's FP32 normal widened and rotated
+ *              to world in the order above (every cloud that has points needs normals: GLIM_AMD_ERR_STATE otherwise).  Cluster: the connected component
+ *              of the seed; level = hop count from the seed (seed 0); max_hops > 0 keeps levels <= max_hops.  Dilation: with
+ *              dilation_radius > 0 every other candidate strictly within it of a cluster point joins at level (last level + 1); no normal
+ *              test.  No candidate: count 0 and status GLIM_AMD_EDIT_EMPTY.  The growth is rounds of one kernel in which every
+ *              unassigned candidate looks for a neighbour of a lower level in a uniform grid; the rounds are enqueued
+ *              GLIM_AMD_EDIT_ROUNDS_PER_LOOK at a time and the host reads the rounds' counters between chunks, so a cluster of any
+ *              diameter terminates.  `rounds` is the number of growth rounds that assigned a point (= the last level before dilation).
+ *   removal    a NEW cloud of the points whose index is not listed, in their original order (gtsam_points::sample with the surviving
+ *              indices, :561); the input cloud is untouched.  Every per-point array the cloud holds (FP32 / FP64 points, covariances,
+ *              normals, times, intensities, the host copy of the times) is gathered bit for bit; has-covariances, has-normals and the
+ *              plane form are carried over; neighbour lists are dropped (their indices are stale); factor streams rebuild on first use.
+ *              Indices in any order, duplicates allowed (:554 marks a slot twice without harm); an index outside [0, size) is refused --
+ *              the `>` of :549 is an off-by-one and is not reproduced.
+ * Deterministic: the same call returns the same bits.  Without a device every call returns GLIM_AMD_ERR_NO_DEVICE. */
+#define GLIM_AMD_EDIT_BOX 0
+#define GLIM_AMD_EDIT_SPHERE 1
+#define GLIM_AMD_EDIT_WINDOW 2
+#define GLIM_AMD_EDIT_WINDOW_BALL 3
+#define GLIM_AMD_EDIT_ROUNDS_PER_LOOK 32 /* growth rounds enqueued between two looks of the host */
+enum { GLIM_AMD_EDIT_OK = 0, GLIM_AMD_EDIT_EMPTY = 1 /* no candidate in the window */, GLIM_AMD_EDIT_FEW_POINTS = 2 /* fewer candidates than k */ };
+typedef struct glim_amd_edit_window { /* points_selector.cpp:22-23 */
+  double center[3];  /* the picked point */
+  double resolution; /* map_cell_resolution, 2.0 */
+  int32_t window;    /* cell_selection_window, 5 */
+  int32_t reserved;  /* 0 */
+} glim_amd_edit_window;
+typedef struct glim_amd_edit_outlier_params { /* :35-37 */
+  double radius_offset;  /* 1.0 */
+  double stddev_thresh;  /* 2.0 */
+  int32_t num_neighbors; /* 10 */
+  int32_t reserved;      /* 0 */
+} glim_amd_edit_outlier_params;
+/* The three thresholds' defaults are a recollection of gtsam_points::RegionGrowingParams, which is not in the reference tree. */
+typedef struct glim_amd_edit_region_growing_params {
+  double distance_threshold;  /* 0.5 (recollection) */
+  double cos_angle_threshold; /* cos(10 degrees) = 0.984807753012208 (recollection); the caller takes the cosine, once */
+  double dilation_radius;     /* 0.5 (recollection); 0 = no dilation */
+  int32_t use_normals;        /* 0 */
+  int32_t max_hops;           /* 0 = unlimited */
+} glim_amd_edit_region_growing_params;
+typedef struct glim_amd_edit_region_result {
+  int64_t count;          /* points of the cluster, whatever the capacity */
+  int64_t num_candidates; /* points in the window */
+  int32_t seed[2];        /* (sub-map, point); -1 -1 without a candidate */
+  int32_t rounds;         /* growth rounds that assigned a point */
+  int32_t status;         /* GLIM_AMD_EDIT_OK / GLIM_AMD_EDIT_EMPTY */
+  double seed_qq;         /* squared distance of the seed to the picked point */
+} glim_amd_edit_region_result;
+
+/* matrices12: num_clouds x 12 -- T_local_submap for BOX / SPHERE (window may be NULL, radius is ignored), T_world_submap otherwise.
+ * num_clouds may be 0 (count 0).  pairs: NULL with capacity 0, or capacity x 2 int32.  GLIM_AMD_ERR_INVALID: a NULL argument or handle,
+ * num_clouds < 0, clouds of two contexts, an unknown mode, capacity < 0, a matrix or centre that is not finite, a resolution that is NaN,
+ * infinite or <= 0, window < 0, (WINDOW_BALL) a radius that is NaN, infinite or <= 0, more than 2^31 - 257 points in all. */
+int glim_amd_edit_select(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* matrices12, int32_t mode,
+                         const glim_amd_edit_window* window, double radius, int64_t capacity, int32_t* pairs, int64_t* count);
+/* select_outlier_points_radius (:703-759).  params NULL = the defaults; status may be NULL.  Also GLIM_AMD_ERR_INVALID: num_neighbors < 1, an
+ * offset < 0 or a parameter that is not finite; GLIM_AMD_ERR_UNSUPPORTED: num_neighbors > 32. */
+int glim_amd_edit_select_outliers(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                                  const glim_amd_edit_window* window, double radius, const glim_amd_edit_outlier_params* params, int64_t capacity,
+                                  int32_t* pairs, int64_t* count, int32_t* status);
+/* select_points_segmentation, region growing (:798-810).  params NULL = the defaults; levels: NULL, or capacity int32 (the level of each
+ * returned pair).  Also GLIM_AMD_ERR_INVALID: a distance threshold that is NaN, infinite or <= 0, a dilation radius that is NaN, infinite
+ * or < 0, a cosine that is NaN, max_hops < 0; GLIM_AMD_ERR_STATE: use_normals and a cloud without normals. */
+int glim_amd_edit_region_grow(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                              const glim_amd_edit_window* window, const glim_amd_edit_region_growing_params* params, int64_t capacity,
+                              int32_t* pairs, int32_t* levels, glim_amd_edit_region_result* out);
+/* remove_selected_points (:537-562) for one sub-map.  indices: n entries (NULL with n 0).  *out: a new cloud of the same context, to be
+ * destroyed by the caller.  GLIM_AMD_ERR_INVALID: a NULL cloud or output, n < 0, an index outside [0, size). */
+int glim_amd_edit_remove_points(const glim_amd_cloud* cloud, int64_t n, const int32_t* indices, glim_amd_cloud** out);
+
 #ifdef __cplusplus
 }
 #endif

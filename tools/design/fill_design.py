@@ -176,6 +176,21 @@ if os.path.exists(pba_path):
         "Every device figure includes the upload of the sub-map descriptors and the transform pass over all points; nothing beyond these two programs is compared and no speed-up was promised in advance.")
 else:
     vals['PLANE_BA_MEASURED']="nothing yet.  `tools/plane_ba_time.py` writes `profiles/plane_ba/plane_ba_time.json` (24 sub-maps of 65 536 points, r₀ = 1: select, statistics, the whole radius search, factor creation and one linearize beside the NumPy restatement of the same steps); until that file exists every statement about the speed of this path is UNMEASURED."
+# ---- the map editor (tools/map_edit_time.py) ----
+me_path='profiles/map_edit/map_edit_time.json'
+if os.path.exists(me_path):
+    me=json.load(open(me_path)); st=me['steps']
+    both=lambda k: f"{st[k]['device_ms']:.2f} ms against {st[k]['numpy_restatement_ms']:.0f} ms"
+    rs,rb=me['region_growing_small_window'],me['region_growing_default_window']
+    vals['MAP_EDIT_MEASURED']=(f"one box, one run (`tools/map_edit_time.py`, `{me_path}`; {me['submaps']} sub-maps of {sp(me['points_per_submap'])} points, a wall through the picked point; "
+        f"synchronous calls timed on the host, median of {me['repeats']}, the NumPy restatement of the same step beside each, median of {me['restatement_repeats']}, in one process).  Device against restatement: "
+        f"box ({sp(me['selected']['box'])} points selected) {both('box')}, sphere {both('sphere')}, window ({sp(me['selected']['window'])}) {both('window')}, radius {me['radius']:g} ({sp(me['selected']['radius'])}) {both('radius')}, "
+        f"outliers in that radius ({sp(me['selected']['outliers'])}) {both('outliers')}, region growing in a 1 m window ({sp(rs['num_candidates'])} candidates, cluster {sp(rs['count'])}, {rs['rounds']} rounds) {both('region_growing_small_window')}.  "
+        f"Device only: region growing in the editor's default window ({sp(rb['num_candidates'])} candidates, cluster {sp(rb['count'])}, {rb['rounds']} rounds in chunks of {me['rounds_per_look']}) {st['region_growing_default_window']['device_ms']:.2f} ms "
+        f"({st['region_growing_default_window']['device_ms']*1e3/max(rb['rounds'],1):.0f} µs per round, the selection, sort and read-backs included), removing that cluster from the sub-maps it touches {st['remove_selected']['device_ms']:.2f} ms.  "
+        "Every compared step returned the restatement's pairs.  The restatement is single-threaded NumPy (its region growing a dense distance matrix): the figures describe these two programs, nothing was profiled, and no speed-up is claimed.")
+else:
+    vals['MAP_EDIT_MEASURED']="nothing yet.  `tools/map_edit_time.py` writes `profiles/map_edit/map_edit_time.json` (24 sub-maps of 65 536 points: the four selections, the outliers, region growing and the removal beside the NumPy restatement of the same steps, alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
