@@ -302,9 +302,25 @@ class EditRegionResult(C.Structure):
                 ("seed_qq", C.c_double)]
 
 
+class EditMinCutParams(C.Structure):
+    """glim_amd_edit_min_cut_params"""
+
+    _fields_ = [("distance_sigma", C.c_double), ("angle_sigma", C.c_double), ("foreground_mask_radius", C.c_double), ("background_mask_radius", C.c_double),
+                ("foreground_weight", C.c_double), ("background_weight", C.c_double), ("k_neighbors", C.c_int32), ("use_normals", C.c_int32),
+                ("max_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EditMinCutResult(C.Structure):
+    """glim_amd_edit_min_cut_result"""
+
+    _fields_ = [("count", C.c_int64), ("num_candidates", C.c_int64), ("num_edges", C.c_int64), ("num_foreground", C.c_int64), ("num_background", C.c_int64),
+                ("flow", C.c_int64), ("rounds", C.c_int32), ("looks", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 EDIT_BOX, EDIT_SPHERE, EDIT_WINDOW, EDIT_WINDOW_BALL = 0, 1, 2, 3  # GLIM_AMD_EDIT_* (include/glim_amd.h)
 EDIT_ROUNDS_PER_LOOK = 32
-EDIT_OK, EDIT_EMPTY, EDIT_FEW_POINTS = 0, 1, 2
+EDIT_OK, EDIT_EMPTY, EDIT_FEW_POINTS, EDIT_NO_SEED, EDIT_ROUND_LIMIT = 0, 1, 2, 3, 4
+EDIT_CAP_SCALE, EDIT_MIN_CUT_MAX_ROUNDS = 65536, 65536
 
 
 class GlimAmdError(RuntimeError):
@@ -461,6 +477,10 @@ SYMBOLS = {
     "glim_amd_edit_region_grow": (_i, [_pp, _i32, _dp, C.POINTER(EditWindow), C.POINTER(EditRegionGrowingParams), _i64, _ip, _ip,
                                        C.POINTER(EditRegionResult)]),
     "glim_amd_edit_remove_points": (_i, [_vp, _i64, _ip, _pp]),
+    "glim_amd_edit_min_cut": (_i, [_pp, _i32, _dp, C.POINTER(EditWindow), C.POINTER(EditMinCutParams), _i64, _ip, C.POINTER(EditMinCutResult)]),
+    "glim_amd_diag_edit_min_cut_graph": (_i, [_pp, _i32, _dp, C.POINTER(EditWindow), C.POINTER(EditMinCutParams), _i64, _ip, _ip, _ip, _i64, _ip, _ip,
+                                              C.POINTER(EditMinCutResult)]),
+    "glim_amd_diag_max_flow": (_i, [_vp, _i32, _i64, _ip, _ip, _ip, _ip, _i32, _ip, _lp, _ip, _ip, _ip]),
     "glim_amd_merge_frames":(_i, [_vp, _i32, _dp, C.POINTER(_dp), C.POINTER(_dp), _lp, _d, _i32, _i32, C.c_uint64, _pp]),
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

@@ -2273,7 +2273,10 @@ class EdgeEVMFactor(PlaneEVMFactor):
 # ---- map editing: point selection, region growing, removal (include/glim_amd.h "Map editing") ----
 EDIT_BOX, EDIT_SPHERE, EDIT_WINDOW, EDIT_WINDOW_BALL = _lib.EDIT_BOX, _lib.EDIT_SPHERE, _lib.EDIT_WINDOW, _lib.EDIT_WINDOW_BALL
 EDIT_ROUNDS_PER_LOOK = _lib.EDIT_ROUNDS_PER_LOOK
-EDIT_STATUS = {_lib.EDIT_OK: "ok", _lib.EDIT_EMPTY: "empty", _lib.EDIT_FEW_POINTS: "few_points"}
+EDIT_OK, EDIT_EMPTY, EDIT_FEW_POINTS, EDIT_NO_SEED, EDIT_ROUND_LIMIT = _lib.EDIT_OK, _lib.EDIT_EMPTY, _lib.EDIT_FEW_POINTS, _lib.EDIT_NO_SEED, _lib.EDIT_ROUND_LIMIT
+EDIT_CAP_SCALE, EDIT_MIN_CUT_MAX_ROUNDS = _lib.EDIT_CAP_SCALE, _lib.EDIT_MIN_CUT_MAX_ROUNDS
+EDIT_STATUS = {_lib.EDIT_OK: "ok", _lib.EDIT_EMPTY: "empty", _lib.EDIT_FEW_POINTS: "few_points", _lib.EDIT_NO_SEED: "no_seed",
+               _lib.EDIT_ROUND_LIMIT: "round_limit"}
 
 
 class RegionGrowingParams:
@@ -2369,6 +2372,82 @@ def edit_region_grow(clouds, poses, center, params=None, resolution=2.0, window=
     wr = min(out.count, int(capacity))
     return {"pairs": pairs[:wr].copy(), "levels": levels[:wr].copy(), "count": out.count, "num_candidates": out.num_candidates,
             "seed": (out.seed[0], out.seed[1]), "seed_qq": out.seed_qq, "rounds": out.rounds, "status": EDIT_STATUS.get(out.status, out.status)}
+
+
+class MinCutParams:
+    """Min-cut segmentation around the picked point (include/glim_amd.h "Map editing", min-cut).  The sigmas and k are a recollection of
+    gtsam_points::MinCutParams, which is not in the reference tree; the radii and the weight are the editor's (points_selector.cpp:42-44).
+    angle_sigma is in radians.  background_weight 0: the foreground weight.  max_rounds 0: EDIT_MIN_CUT_MAX_ROUNDS."""
+
+    def __init__(self, distance_sigma=0.25, angle_sigma=np.deg2rad(10.0), foreground_mask_radius=0.5, background_mask_radius=5.0, foreground_weight=10.0,
+                 background_weight=0.0, k_neighbors=20, use_normals=False, max_rounds=0):
+        self.distance_sigma, self.angle_sigma = float(distance_sigma), float(angle_sigma)
+        self.foreground_mask_radius, self.background_mask_radius = float(foreground_mask_radius), float(background_mask_radius)
+        self.foreground_weight, self.background_weight = float(foreground_weight), float(background_weight)
+        self.k_neighbors, self.use_normals, self.max_rounds = int(k_neighbors), bool(use_normals), int(max_rounds)
+
+    def _c(self):
+        return _lib.EditMinCutParams(self.distance_sigma, self.angle_sigma, self.foreground_mask_radius, self.background_mask_radius, self.foreground_weight,
+                                     self.background_weight, self.k_neighbors, int(self.use_normals), self.max_rounds, 0)
+
+
+def _min_cut_counts(out):
+    return {"count": out.count, "num_candidates": out.num_candidates, "num_edges": out.num_edges, "num_foreground": out.num_foreground,
+            "num_background": out.num_background, "flow": out.flow, "rounds": out.rounds, "looks": out.looks, "status": EDIT_STATUS.get(out.status, out.status)}
+
+
+def edit_min_cut(clouds, poses, center, params=None, resolution=2.0, window=5, capacity=None):
+    """select_points_segmentation, min-cut (:774-797) -> {pairs, count, num_candidates, num_edges, num_foreground, num_background, flow,
+    rounds, looks, status}.  pairs ascending: the points on the source side of the minimal minimum cut between the points within the
+    foreground radius of `center` and those beyond the background radius, over the k-nearest-neighbour graph of the candidates."""
+    hs, S, M = _edit_matrices(clouds, poses)
+    win = _edit_window(center, resolution, window)
+    prm = (params or MinCutParams())._c()
+    if capacity is None:
+        capacity = sum(cl.size() for cl in clouds)
+    pairs = np.zeros((max(int(capacity), 1), 2), dtype=np.int32)
+    out = _lib.EditMinCutResult()
+    check(lib().glim_amd_edit_min_cut(hs, S, _dp(M), C.byref(win), C.byref(prm), int(capacity), _ip(pairs), C.byref(out)), "glim_amd_edit_min_cut")
+    res = _min_cut_counts(out)
+    res["pairs"] = pairs[: min(out.count, int(capacity))].copy()
+    return res
+
+
+def diag_edit_min_cut_graph(clouds, poses, center, params=None, resolution=2.0, window=5):
+    """glim_amd_diag_edit_min_cut_graph: the graph edit_min_cut builds -> {candidates, source_cap, sink_cap, edges, edge_cap, + the counts}"""
+    hs, S, M = _edit_matrices(clouds, poses)
+    win = _edit_window(center, resolution, window)
+    prm = (params or MinCutParams())._c()
+    out = _lib.EditMinCutResult()
+    none = None
+    check(lib().glim_amd_diag_edit_min_cut_graph(hs, S, _dp(M), C.byref(win), C.byref(prm), 0, none, none, none, 0, none, none, C.byref(out)),
+          "glim_amd_diag_edit_min_cut_graph")
+    m, E = max(out.num_candidates, 1), max(out.num_edges, 1)
+    pairs, src, snk = np.zeros((m, 2), dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+    edges, cap = np.zeros((E, 2), dtype=np.int32), np.zeros(E, dtype=np.int32)
+    check(lib().glim_amd_diag_edit_min_cut_graph(hs, S, _dp(M), C.byref(win), C.byref(prm), m, _ip(pairs), _ip(src), _ip(snk), E, _ip(edges), _ip(cap),
+                                                 C.byref(out)), "glim_amd_diag_edit_min_cut_graph")
+    res = _min_cut_counts(out)
+    m, E = out.num_candidates, out.num_edges
+    res.update(candidates=pairs[:m].copy(), source_cap=src[:m].copy(), sink_cap=snk[:m].copy(), edges=edges[:E].copy(), edge_cap=cap[:E].copy())
+    return res
+
+
+def diag_max_flow(ctx, n, edges, edge_cap, source_cap, sink_cap, max_rounds=0):
+    """glim_amd_diag_max_flow: the min-cut solver alone on a caller's undirected graph -> {member, flow, rounds, looks, status}"""
+    edges = np.ascontiguousarray(np.asarray(edges, dtype=np.int32).reshape(-1, 2))
+    cap = np.ascontiguousarray(np.asarray(edge_cap, dtype=np.int32).reshape(-1))
+    src = np.ascontiguousarray(np.asarray(source_cap, dtype=np.int32).reshape(-1))
+    snk = np.ascontiguousarray(np.asarray(sink_cap, dtype=np.int32).reshape(-1))
+    if len(cap) != len(edges) or len(src) != n or len(snk) != n:
+        raise ValueError("one capacity per edge, one source and one sink capacity per node")
+    member = np.zeros(max(int(n), 1), dtype=np.int32)
+    flow, rounds, looks, status = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+    ptr = lambda a: _ip(a) if len(a) else None  # noqa: E731
+    check(lib().glim_amd_diag_max_flow(ctx._h, int(n), len(edges), ptr(edges), ptr(cap), ptr(src), ptr(snk), int(max_rounds), _ip(member), C.byref(flow),
+                                       C.byref(rounds), C.byref(looks), C.byref(status)), "glim_amd_diag_max_flow")
+    return {"member": member[: int(n)].copy(), "flow": flow.value, "rounds": rounds.value, "looks": looks.value,
+            "status": EDIT_STATUS.get(status.value, status.value)}
 
 
 def edit_remove_points(cloud, indices):

@@ -1,5 +1,5 @@
 // map_edit.hip -- device side of the reference's map editor (src/glim/viewer/editor/points_selector.cpp): point selection over many sub-maps
-// with the editor's predicates, the statistical outliers in a radius, region growing, and the removal of points from a device cloud.
+// with the editor's predicates, the statistical outliers in a radius, region growing, min-cut segmentation, and the removal of points from a device cloud.
 // Semantics: include/glim_amd.h "Map editing"; the predicates themselves: map_edit.hpp.
 //
 // Passes (one lane per point, 256-thread blocks, FP64):
@@ -9,6 +9,8 @@
 //   edit_seed_*           lexicographic minimum of (qq, candidate) in two stages
 //   edit_cell_key_kernel  cell of a uniform grid per candidate -> sort.hip -> edit_cell_range_kernel (first / last position of every cell)
 //   edit_round_kernel     one growth round: an unassigned candidate takes level rho iff a neighbour in its 27 cells has a level < rho and an edge to it
+//   edit_mc_*             min-cut: the candidates' neighbour graph -- edge keys from the kNN -> sort.hip -> unique -> capacities, terminal
+//                         capacities; the flow itself is min_cut.hip's
 //   edit_keep_* / edit_gather_kernel   removal: keep flags, prefix sum, gather of every per-point array
 #include <algorithm>
 #include <climits>
@@ -17,6 +19,7 @@
 
 #include "internal.hpp"
 #include "map_edit.hpp"
+#include "min_cut.hpp"
 #include "outlier_stat.hpp"
 #include "scan.hpp"
 #include "scope_sync.hpp"
@@ -274,6 +277,60 @@ static __global__ __launch_bounds__(256) void edit_outlier_flag_kernel(const dou
   flags[i] = (i < m && W[i].w < r2 && !inlier[i]) ? 1 : 0;
 }
 
+// ---- min-cut: the candidates' neighbour graph ----
+// keys[i K + t] = (min << 32 | max) of candidate i and its t-th neighbour; an entry equal to i itself gets the key (m << 32), past every edge
+static __global__ __launch_bounds__(256) void edit_mc_key_kernel(const int* __restrict__ nb, int m, int K, u64* __restrict__ keys) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= m * K) return;
+  const int i = p / K, j = nb[p];
+  u64 key = (u64)(u32)m << 32;
+  if (j != i && j >= 0 && j < m) key = ((u64)(u32)min(i, j) << 32) | (u64)(u32)max(i, j);
+  keys[p] = key;
+}
+// keys sorted: flags[p] = the key is an edge and differs from its predecessor; flags[total] = 0
+static __global__ __launch_bounds__(256) void edit_mc_unique_kernel(const u64* __restrict__ keys, int total, int m, int* __restrict__ flags) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p > total) return;
+  flags[p] = (p < total && (keys[p] >> 32) < (u64)m && (p == 0 || keys[p - 1] != keys[p])) ? 1 : 0;
+}
+// the flagged keys in their order (ascending), with their capacities
+static __global__ __launch_bounds__(256) void edit_mc_edge_kernel(const u64* __restrict__ keys, const int* __restrict__ flags, const int* __restrict__ pos,
+                                                                  int total, const double4* __restrict__ P, const double4* __restrict__ Nw, double sigma_d,
+                                                                  double sigma_a, int2* __restrict__ edges, int* __restrict__ cap) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= total || !flags[p]) return;
+  const int i = (int)(keys[p] >> 32), j = (int)(keys[p] & 0xffffffffull);
+  const double4 a4 = P[i], b4 = P[j];
+  const double a[3] = {a4.x, a4.y, a4.z}, b[3] = {b4.x, b4.y, b4.z};
+  int c;
+  if (Nw) {
+    const double4 n4 = Nw[i], o4 = Nw[j];
+    const double na[3] = {n4.x, n4.y, n4.z}, nb[3] = {o4.x, o4.y, o4.z};
+    c = min_cut_edge_capacity(a, b, sigma_d, na, nb, sigma_a);
+  } else {
+    c = min_cut_edge_capacity(a, b, sigma_d, nullptr, nullptr, 0.0);
+  }
+  edges[pos[p]] = make_int2(i, j);
+  cap[pos[p]] = c;
+}
+// terminal capacities from the predicate's qq; counts[0] / counts[1] += foreground / background points (counters of integers: any order)
+static __global__ __launch_bounds__(256) void edit_mc_terminal_kernel(const double4* __restrict__ W, int m, double fg2, double bg2, int fg_cap, int bg_cap,
+                                                                      int* __restrict__ src, int* __restrict__ snk, int* __restrict__ counts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool fg = false, bg = false;
+  if (i < m) {
+    const double qq = W[i].w;
+    fg = qq < fg2, bg = qq >= bg2;
+    src[i] = fg ? fg_cap : 0;
+    snk[i] = bg ? bg_cap : 0;
+  }
+  const u64 mf = __ballot(fg), mb = __ballot(bg);
+  if ((threadIdx.x & 63) == 0) {
+    if (mf) atomicAdd(counts, __popcll(mf));
+    if (mb) atomicAdd(counts + 1, __popcll(mb));
+  }
+}
+
 // ---- removal ----
 static __global__ __launch_bounds__(256) void edit_keep_fill_kernel(int n, int* __restrict__ keep) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -450,6 +507,140 @@ static Grid make_grid(const Predicate& pred, double resolution, double reach, in
   g.inv_h = 1.0 / h;
   g.pad = 0;
   return g;
+}
+
+// ---- min-cut ----
+struct MinCutSetup {
+  glim_amd_edit_min_cut_params prm;
+  Predicate pred;
+  int total = 0;
+  int fg_cap = 0, bg_cap = 0;
+};
+
+// the checks of glim_amd_edit_min_cut, in the order of glim_amd_edit_region_grow
+static int min_cut_setup(const glim_amd_cloud* const* clouds, int32_t S, const double* M12, const glim_amd_edit_window* window,
+                         const glim_amd_edit_min_cut_params* params, MinCutSetup* s) {
+  glim_amd_edit_min_cut_params prm = {0.25, 0.17453292519943295, 0.5, 5.0, 10.0, 0.0, 20, 0, 0, 0};
+  if (params) prm = *params;
+  const double reals[6] = {prm.distance_sigma, prm.angle_sigma, prm.foreground_mask_radius, prm.background_mask_radius, prm.foreground_weight, prm.background_weight};
+  if (!finite_n(reals, 6) || !(prm.distance_sigma > 0.0) || !(prm.angle_sigma > 0.0) || !(prm.foreground_mask_radius > 0.0) ||
+      !(prm.foreground_mask_radius < prm.background_mask_radius) || !(prm.foreground_weight > 0.0) || prm.background_weight < 0.0 || prm.k_neighbors < 1 ||
+      prm.max_rounds < 0)
+    return GLIM_AMD_ERR_INVALID;
+  if (prm.background_weight == 0.0) prm.background_weight = prm.foreground_weight;
+  if (!capacity_fits(prm.foreground_weight) || !capacity_fits(prm.background_weight)) return GLIM_AMD_ERR_INVALID;
+  if (prm.k_neighbors > 31) return GLIM_AMD_ERR_UNSUPPORTED;
+  GA_TRY(make_predicate(MODE_WINDOW_BALL, window, prm.background_mask_radius + 1.0, &s->pred));
+  GA_TRY(check_clouds(clouds, S, M12, &s->total));
+  if (prm.use_normals)
+    for (int c = 0; c < S; c++)
+      if (clouds[c]->n > 0 && (!clouds[c]->has_normals || !clouds[c]->normals)) return GLIM_AMD_ERR_STATE;
+  s->prm = prm;
+  s->fg_cap = quantize_capacity(prm.foreground_weight);
+  s->bg_cap = quantize_capacity(prm.background_weight);
+  return GLIM_AMD_OK;
+}
+
+// the candidates and their graph on the device; the transient cloud is destroyed with the structure, outside every lock scope
+struct MinCutGraph {
+  CloudGuard tc;
+  Selection sel;
+  DeviceTemp W, Nw, edges, cap, src, snk;
+  int m = 0, E = 0, num_fg = 0, num_bg = 0;
+  int status = GLIM_AMD_EDIT_EMPTY;
+};
+
+// Takes the context's mutex itself, twice around the neighbour search (which takes it too).  Leaves status EMPTY / FEW_POINTS / NO_SEED with
+// the counts known so far, or OK with every array built.
+static int min_cut_graph(const glim_amd_cloud* const* clouds, int32_t S, const double* M12, const MinCutSetup& s, MinCutGraph* g) {
+  glim_amd_ctx* ctx = clouds[0]->ctx;
+  const int K = s.prm.k_neighbors + 1;
+  const bool normals = s.prm.use_normals != 0;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    GA_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream();
+    SyncOnExit in_flight(st);
+    GA_TRY(select_enqueue(st, clouds, S, M12, s.total, s.pred, s.total, &g->sel));
+    int m = 0;
+    GA_HIP(read_back_sync(ctx, st, &m, g->sel.pos.as<int>() + s.total, sizeof(int)));
+    if (m < 0 || m > s.total) return GLIM_AMD_ERR_HIP;
+    g->m = m;
+    if (m < K) {
+      in_flight.dismiss();
+      g->status = m == 0 ? GLIM_AMD_EDIT_EMPTY : GLIM_AMD_EDIT_FEW_POINTS;
+      return GLIM_AMD_OK;
+    }
+    if ((int64_t)m * K > (int64_t)0x7fffffff - 257) return GLIM_AMD_ERR_INVALID;
+    g->tc.c = new glim_amd_cloud();
+    g->tc.c->ctx = ctx;
+    g->tc.c->n = m;
+    GA_HIP(pool_malloc(&g->tc.c->pts, (size_t)m * sizeof(float4)));
+    GA_HIP(pool_malloc(&g->tc.c->pts64, (size_t)m * sizeof(double4)));
+    GA_HIP(pool_malloc(&g->W.p, (size_t)m * sizeof(double4)));
+    if (normals) GA_HIP(pool_malloc(&g->Nw.p, (size_t)m * sizeof(double4)));
+    edit_world_kernel<<<grid_for(m), 256, 0, st>>>(g->sel.pairs.as<int>(), m, g->sel.descs.as<SubDesc>(), s.pred, g->W.as<double4>(), g->Nw.as<double4>(),
+                                                   g->tc.c->pts, g->tc.c->pts64);
+    GA_HIP(hipGetLastError());
+    GA_HIP(hipStreamSynchronize(st));
+    in_flight.dismiss();
+  }
+  GA_TRY(glim_amd_cloud_find_neighbors(g->tc.c, K, nullptr));  // takes the context's mutex itself
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  const int m = g->m, total = m * K;
+  // sized by the candidate count: the keys, and the terminal arrays
+  DeviceTemp ka, kb, va, vb, sort_scratch, flags, pos, tiles, counts;
+  GA_HIP(pool_malloc(&ka.p, (size_t)total * sizeof(u64)));
+  GA_HIP(pool_malloc(&kb.p, (size_t)total * sizeof(u64)));
+  GA_HIP(pool_malloc(&va.p, (size_t)total * sizeof(u32)));
+  GA_HIP(pool_malloc(&vb.p, (size_t)total * sizeof(u32)));
+  GA_HIP(pool_malloc(&sort_scratch.p, radix_sort_scratch_bytes(total)));
+  GA_HIP(pool_malloc(&flags.p, ((size_t)total + 1) * sizeof(int)));
+  GA_HIP(pool_malloc(&pos.p, ((size_t)total + 1) * sizeof(int)));
+  GA_HIP(pool_malloc(&tiles.p, scan_scratch_ints((unsigned int)total + 1u) * sizeof(int)));
+  GA_HIP(pool_malloc(&counts.p, 2 * sizeof(int)));
+  GA_HIP(pool_malloc(&g->src.p, (size_t)m * sizeof(int)));
+  GA_HIP(pool_malloc(&g->snk.p, (size_t)m * sizeof(int)));
+  SyncOnExit in_flight(st);
+  GA_HIP(hipMemsetAsync(counts.p, 0, 2 * sizeof(int), st));
+  edit_mc_terminal_kernel<<<grid_for(m), 256, 0, st>>>(g->W.as<double4>(), m, s.prm.foreground_mask_radius * s.prm.foreground_mask_radius,
+                                                       s.prm.background_mask_radius * s.prm.background_mask_radius, s.fg_cap, s.bg_cap, g->src.as<int>(),
+                                                       g->snk.as<int>(), counts.as<int>());
+  edit_mc_key_kernel<<<grid_for(total), 256, 0, st>>>(g->tc.c->neighbors, m, K, ka.as<u64>());
+  GA_HIP(hipGetLastError());
+  int bits = 33;
+  while (((int64_t)1 << (bits - 32)) <= (int64_t)m) bits++;
+  u64* keys = nullptr;
+  u32* vals = nullptr;
+  GA_HIP(radix_sort_pairs(st, total, bits, ka.as<u64>(), va.as<u32>(), kb.as<u64>(), vb.as<u32>(), true, sort_scratch.as<int>(), &keys, &vals));
+  edit_mc_unique_kernel<<<grid_for(total + 1), 256, 0, st>>>(keys, total, m, flags.as<int>());
+  GA_HIP(hipGetLastError());
+  GA_HIP(exclusive_scan_int(st, flags.as<int>(), (unsigned int)total + 1u, tiles.as<int>(), pos.as<int>()));
+  int E = 0, h_counts[2] = {0, 0};
+  GA_HIP(read_back_sync(ctx, st, &E, pos.as<int>() + total, sizeof(int)));
+  GA_HIP(read_back_sync(ctx, st, h_counts, counts.p, sizeof(h_counts)));
+  if (E < 0 || E > total) return GLIM_AMD_ERR_HIP;
+  g->E = E, g->num_fg = h_counts[0], g->num_bg = h_counts[1];
+  // sized by the edge count
+  GA_HIP(pool_malloc(&g->edges.p, (size_t)std::max(E, 1) * sizeof(int2)));
+  GA_HIP(pool_malloc(&g->cap.p, (size_t)std::max(E, 1) * sizeof(int)));
+  edit_mc_edge_kernel<<<grid_for(total), 256, 0, st>>>(keys, flags.as<int>(), pos.as<int>(), total, g->tc.c->pts64, g->Nw.as<double4>(), s.prm.distance_sigma,
+                                                       s.prm.angle_sigma, g->edges.as<int2>(), g->cap.as<int>());
+  GA_HIP(hipGetLastError());
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  g->status = g->num_fg == 0 ? GLIM_AMD_EDIT_NO_SEED : GLIM_AMD_EDIT_OK;
+  return GLIM_AMD_OK;
+}
+
+static void min_cut_counts(const MinCutGraph& g, glim_amd_edit_min_cut_result* out) {
+  out->num_candidates = g.m;
+  out->num_edges = g.E;
+  out->num_foreground = g.num_fg;
+  out->num_background = g.num_bg;
+  out->status = g.status;
 }
 
 }  // namespace edit
@@ -677,6 +868,75 @@ int glim_amd_edit_region_grow(const glim_amd_cloud* const* clouds, int32_t num_c
   in_flight.dismiss();
   out->rounds = last;
   out->status = GLIM_AMD_EDIT_OK;
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_edit_min_cut(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12, const glim_amd_edit_window* window,
+                          const glim_amd_edit_min_cut_params* params, int64_t capacity, int32_t* pairs, glim_amd_edit_min_cut_result* out) {
+  using namespace glim_amd;
+  using namespace glim_amd::edit;
+  if (no_device()) return GLIM_AMD_ERR_NO_DEVICE;
+  if (capacity < 0 || !out || (capacity > 0 && !pairs)) return GLIM_AMD_ERR_INVALID;
+  MinCutSetup setup;
+  GA_TRY(min_cut_setup(clouds, num_clouds, T_world_submap12, window, params, &setup));
+  *out = glim_amd_edit_min_cut_result();
+  out->status = GLIM_AMD_EDIT_EMPTY;
+  if (num_clouds == 0) return GLIM_AMD_OK;
+  MinCutGraph g;  // its transient cloud is destroyed after the lock scope below
+  GA_TRY(min_cut_graph(clouds, num_clouds, T_world_submap12, setup, &g));
+  min_cut_counts(g, out);
+  if (g.status != GLIM_AMD_EDIT_OK) return GLIM_AMD_OK;
+  glim_amd_ctx* ctx = clouds[0]->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  DeviceTemp flags;
+  GA_HIP(pool_malloc(&flags.p, ((size_t)g.m + 1) * sizeof(int)));
+  SyncOnExit in_flight(st);
+  MaxFlowResult r;
+  GA_TRY(max_flow_source_side(ctx, st, g.m, g.E, g.edges.as<int2>(), g.cap.as<int>(), g.src.as<int>(), g.snk.as<int>(), setup.prm.max_rounds, flags.as<int>(), &r));
+  out->flow = r.flow, out->rounds = r.rounds, out->looks = r.looks, out->status = r.status;
+  if (r.status == GLIM_AMD_EDIT_OK) GA_TRY(pick_to_host(ctx, st, flags.as<int>(), g.m, g.sel.pairs.as<int>(), nullptr, capacity, pairs, nullptr, &out->count));
+  in_flight.dismiss();
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_diag_edit_min_cut_graph(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                                     const glim_amd_edit_window* window, const glim_amd_edit_min_cut_params* params, int64_t pair_capacity, int32_t* pairs,
+                                     int32_t* source_cap, int32_t* sink_cap, int64_t edge_capacity, int32_t* edges, int32_t* edge_cap,
+                                     glim_amd_edit_min_cut_result* out) {
+  using namespace glim_amd;
+  using namespace glim_amd::edit;
+  if (no_device()) return GLIM_AMD_ERR_NO_DEVICE;
+  if (pair_capacity < 0 || edge_capacity < 0 || !out || (pair_capacity > 0 && (!pairs || !source_cap || !sink_cap)) ||
+      (edge_capacity > 0 && (!edges || !edge_cap)))
+    return GLIM_AMD_ERR_INVALID;
+  MinCutSetup setup;
+  GA_TRY(min_cut_setup(clouds, num_clouds, T_world_submap12, window, params, &setup));
+  *out = glim_amd_edit_min_cut_result();
+  out->status = GLIM_AMD_EDIT_EMPTY;
+  if (num_clouds == 0) return GLIM_AMD_OK;
+  MinCutGraph g;
+  GA_TRY(min_cut_graph(clouds, num_clouds, T_world_submap12, setup, &g));
+  min_cut_counts(g, out);
+  glim_amd_ctx* ctx = clouds[0]->ctx;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  const size_t np = (size_t)std::min<int64_t>(pair_capacity, g.m);
+  if (np > 0) GA_HIP(hipMemcpyAsync(pairs, g.sel.pairs.p, np * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (g.src.p) {  // the graph was built (status OK or NO_SEED)
+    const size_t ne = (size_t)std::min<int64_t>(edge_capacity, g.E);
+    if (np > 0) {
+      GA_HIP(hipMemcpyAsync(source_cap, g.src.p, np * sizeof(int), hipMemcpyDeviceToHost, st));
+      GA_HIP(hipMemcpyAsync(sink_cap, g.snk.p, np * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    if (ne > 0) {
+      GA_HIP(hipMemcpyAsync(edges, g.edges.p, ne * sizeof(int2), hipMemcpyDeviceToHost, st));
+      GA_HIP(hipMemcpyAsync(edge_cap, g.cap.p, ne * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+  }
+  GA_HIP(hipStreamSynchronize(st));
   return GLIM_AMD_OK;
 }
 

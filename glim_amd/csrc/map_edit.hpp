@@ -2,6 +2,7 @@
 // the kernels of map_edit.hip and for a stand-alone host program (tests/cpp/test_map_edit_host.cpp, plain and under the address /
 // undefined-behaviour sanitizers).  Plain C++ as well as HIP.  Every product and sum is rounded on its own: no FMA contraction, and the
 // operation order is the one include/glim_amd.h "Map editing" states, so that a NumPy restatement reproduces every boolean.
+// Also the edge weights and integer capacities of the min-cut segmentation (tests/cpp/test_min_cut_host.cpp runs them the same way).
 #pragma once
 
 #include <math.h>
@@ -96,6 +97,39 @@ GLIM_AMD_EDIT_HD inline bool edge(const double* a, const double* b, double thr2,
   if (!(sq3(a[0] - b[0], a[1] - b[1], a[2] - b[2]) < thr2)) return false;
   if (!na) return true;
   return fabs((na[0] * nb[0] + na[1] * nb[1]) + na[2] * nb[2]) >= cos_angle;
+}
+
+// ---- min-cut segmentation: edge weights and their integer capacities (include/glim_amd.h "Map editing", min-cut) ----
+constexpr double CAP_SCALE = 65536.0;  // GLIM_AMD_EDIT_CAP_SCALE
+
+// exp(-(dd / (sigma sigma))), dd = (dx dx + dy dy) + dz dz, the denominator rounded once
+GLIM_AMD_EDIT_HD inline double min_cut_distance_weight(const double* a, const double* b, double sigma) {
+#pragma clang fp contract(off)
+  const double dd = sq3(a[0] - b[0], a[1] - b[1], a[2] - b[2]);
+  const double ss = sigma * sigma;
+  return exp(-(dd / ss));
+}
+// exp(-((t t) / (sigma sigma))), t = acos(min(1, |n_i . n_j|)) (estimated normals carry no sign)
+GLIM_AMD_EDIT_HD inline double min_cut_normal_weight(const double* na, const double* nb, double sigma) {
+#pragma clang fp contract(off)
+  const double d = fabs((na[0] * nb[0] + na[1] * nb[1]) + na[2] * nb[2]);
+  const double t = acos(fmin(1.0, d));
+  const double tt = t * t;
+  const double ss = sigma * sigma;
+  return exp(-(tt / ss));
+}
+// floor(w * 65536 + 0.5) as a double: what quantize_capacity casts, and what the parameter check compares with 2^31
+GLIM_AMD_EDIT_HD inline double scaled_weight(double w) {
+#pragma clang fp contract(off)
+  return floor(w * CAP_SCALE + 0.5);
+}
+GLIM_AMD_EDIT_HD inline bool capacity_fits(double w) { return scaled_weight(w) >= 0.0 && scaled_weight(w) < 2147483648.0; }
+GLIM_AMD_EDIT_HD inline int32_t quantize_capacity(double w) { return (int32_t)scaled_weight(w); }
+GLIM_AMD_EDIT_HD inline int32_t min_cut_edge_capacity(const double* a, const double* b, double sigma_d, const double* na, const double* nb, double sigma_a) {
+#pragma clang fp contract(off)
+  double w = min_cut_distance_weight(a, b, sigma_d);
+  if (na) w = w * min_cut_normal_weight(na, nb, sigma_a);
+  return quantize_capacity(w);
 }
 
 }  // namespace edit

@@ -1024,11 +1024,10 @@ int glim_amd_ba_factor_linearize(const glim_amd_ba_factor* factor, const double*
                                  uint32_t* status);
 int glim_amd_ba_factor_destroy(glim_amd_ba_factor* factor);
 
-/* ---- Map editing: point selection, region growing, removal ---------------------------------------------------------------------------
+/* ---- Map editing: point selection, segmentation, removal -------------------------------------------------------------------------------
  * The device side of the reference's map editor (src/glim/viewer/editor/points_selector.cpp): the box / sphere gizmo (:623-674), the
  * radius selection (:677-700), the statistical outliers in a radius (:703-759), region growing (:798-810) and the removal of the selection
- * from the sub-map clouds (:513-562).  Min-cut segmentation (:774-797) is not built: a sequential max-flow whose source is not in the
- * reference tree.
+ * from the sub-map clouds (:513-562), and min-cut segmentation (:774-797), the editor's default segmentation method.
  *
  *   inputs     S device clouds and S matrices M_s (3x4 row-major FP64); point coordinates as for the ball selection above (the exact FP64
  *              points where the cloud keeps them, FP32 widened otherwise).  The transformed point is
@@ -1063,6 +1062,28 @@ int glim_amd_ba_factor_destroy(glim_amd_ba_factor* factor);
  *              unassigned candidate looks for a neighbour of a lower level in a uniform grid; the rounds are enqueued
  *              GLIM_AMD_EDIT_ROUNDS_PER_LOOK at a time and the host reads the rounds' counters between chunks, so a cluster of any
  *              diameter terminates.  `rounds` is the number of growth rounds that assigned a point (= the last level before dilation).
+ *   min-cut    gtsam_points::min_cut is not in the reference tree; these semantics are this project's and are a function of the point set
+ *              alone.  Candidates: WINDOW_BALL around the picked point c with radius background_mask_radius + 1.0, strict (:777-780), m
+ *              of them.  m = 0: status GLIM_AMD_EDIT_EMPTY; m < k_neighbors + 1: GLIM_AMD_EDIT_FEW_POINTS.  Neighbours: the candidates'
+ *              world points go into a transient cloud in pair order as for the outliers (FP32 image e = v - c, the FP64 points beside
+ *              it) and the exact kNN runs with K = k_neighbors + 1; entries equal to the query's own index are dropped wherever they
+ *              stand.  Edges: undirected, {i, j} exists iff j is among i's neighbours or i among j's; duplicates are merged by sorting
+ *              the keys (min << 32 | max) and comparing with the predecessor, so the edge list is in ascending key order and no atomic
+ *              decides anything.  Edge weight, FP64, every product and sum rounded on its own:
+ *                  dd = (dx dx + dy dy) + dz dz  on the FP64 world points;   w = exp(-(dd / (sigma_d sigma_d)))
+ *                  with use_normals:  w = w exp(-((t t) / (sigma_a sigma_a))),  t = acos(min(1, |n_i . n_j|)),  n as in region growing
+ *                  capacity = (int32) floor(w * GLIM_AMD_EDIT_CAP_SCALE + 0.5), the same in both directions; an edge of capacity 0 is
+ *                  kept and carries nothing.
+ *              Terminals: a foreground point (qq < fg fg, strict) is tied to the source with floor(foreground_weight * 65536 + 0.5), a
+ *              background point (qq >= bg bg) to the sink with the background weight quantised the same way; qq is the predicate's.  No
+ *              foreground point: count 0 and status GLIM_AMD_EDIT_NO_SEED.  Result: the points reachable from the source in the
+ *              residual graph of a maximum flow (the two terminals are no points).  This is the minimal source side of a minimum cut,
+ *              the same set for every maximum flow, hence independent of the order of pushes; a foreground point whose terminal arc is
+ *              saturated and which no other residual path reaches is, by this definition, NOT in the set.  Solver: a round-based
+ *              push-relabel without a deciding atomic (csrc/min_cut.hip), run from the background side; push rounds are enqueued
+ *              GLIM_AMD_EDIT_ROUNDS_PER_LOOK at a time, each chunk is followed by an exact relabelling and one look of the host, and the
+ *              call stops when no point with excess reaches absorbing capacity -- or after max_rounds push rounds with status
+ *              GLIM_AMD_EDIT_ROUND_LIMIT, count 0 and no pairs.
  *   removal    a NEW cloud of the points whose index is not listed, in their original order (gtsam_points::sample with the surviving
  *              indices, :561); the input cloud is untouched.  Every per-point array the cloud holds (FP32 / FP64 points, covariances,
  *              normals, times, intensities, the host copy of the times) is gathered bit for bit; has-covariances, has-normals and the
@@ -1076,6 +1097,10 @@ int glim_amd_ba_factor_destroy(glim_amd_ba_factor* factor);
 #define GLIM_AMD_EDIT_WINDOW_BALL 3
 #define GLIM_AMD_EDIT_ROUNDS_PER_LOOK 32 /* growth rounds enqueued between two looks of the host */
 enum { GLIM_AMD_EDIT_OK = 0, GLIM_AMD_EDIT_EMPTY = 1 /* no candidate in the window */, GLIM_AMD_EDIT_FEW_POINTS = 2 /* fewer candidates than k */ };
+/* min-cut segmentation only */
+enum { GLIM_AMD_EDIT_NO_SEED = 3 /* no foreground point */, GLIM_AMD_EDIT_ROUND_LIMIT = 4 /* max_rounds push rounds did not finish the flow */ };
+#define GLIM_AMD_EDIT_CAP_SCALE 65536       /* capacity units per unit of weight */
+#define GLIM_AMD_EDIT_MIN_CUT_MAX_ROUNDS 65536 /* push rounds after which a call gives up (max_rounds = 0) */
 typedef struct glim_amd_edit_window { /* points_selector.cpp:22-23 */
   double center[3];  /* the picked point */
   double resolution; /* map_cell_resolution, 2.0 */
@@ -1125,6 +1150,39 @@ int glim_amd_edit_region_grow(const glim_amd_cloud* const* clouds, int32_t num_c
 /* remove_selected_points (:537-562) for one sub-map.  indices: n entries (NULL with n 0).  *out: a new cloud of the same context, to be
  * destroyed by the caller.  GLIM_AMD_ERR_INVALID: a NULL cloud or output, n < 0, an index outside [0, size). */
 int glim_amd_edit_remove_points(const glim_amd_cloud* cloud, int64_t n, const int32_t* indices, glim_amd_cloud** out);
+/* The defaults marked "recollection" are a recollection of gtsam_points::MinCutParams, which is not in the reference tree. */
+typedef struct glim_amd_edit_min_cut_params {
+  double distance_sigma;         /* 0.25 (recollection) */
+  double angle_sigma;            /* 10 degrees in radians, 0.17453292519943295 (recollection); used only with use_normals */
+  double foreground_mask_radius; /* 0.5 (points_selector.cpp:43) */
+  double background_mask_radius; /* 5.0 (:44) */
+  double foreground_weight;      /* 10.0 (:42) */
+  double background_weight;      /* 0 = the foreground weight */
+  int32_t k_neighbors;           /* 20 (recollection); <= 31 */
+  int32_t use_normals;           /* 0 */
+  int32_t max_rounds;            /* 0 = GLIM_AMD_EDIT_MIN_CUT_MAX_ROUNDS */
+  int32_t reserved;              /* 0 */
+} glim_amd_edit_min_cut_params;
+typedef struct glim_amd_edit_min_cut_result {
+  int64_t count;          /* points of the segment, whatever the capacity */
+  int64_t num_candidates; /* points in the ball */
+  int64_t num_edges;      /* undirected edges of the neighbour graph */
+  int64_t num_foreground; /* points tied to the source */
+  int64_t num_background; /* points tied to the sink */
+  int64_t flow;           /* the maximum flow in capacity units */
+  int32_t rounds;         /* push rounds enqueued */
+  int32_t looks;          /* chunks, i.e. exact relabellings after the first */
+  int32_t status;         /* GLIM_AMD_EDIT_OK / _EMPTY / _FEW_POINTS / _NO_SEED / _ROUND_LIMIT */
+  int32_t reserved;
+} glim_amd_edit_min_cut_result;
+/* select_points_segmentation, min-cut (:774-797).  params NULL = the defaults.  Also GLIM_AMD_ERR_INVALID: a parameter that is not finite,
+ * a sigma <= 0, radii that are not 0 < foreground < background, a foreground weight <= 0, a background weight < 0, k_neighbors < 1,
+ * max_rounds < 0, a weight whose quantised value does not fit 31 bits, more than 2^31 - 257 neighbour entries (candidates x (k + 1));
+ * GLIM_AMD_ERR_UNSUPPORTED: k_neighbors > 31 (the kNN's limit of 32 with the query included); GLIM_AMD_ERR_STATE: use_normals and a cloud
+ * that has points and no normals. */
+int glim_amd_edit_min_cut(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                          const glim_amd_edit_window* window, const glim_amd_edit_min_cut_params* params, int64_t capacity, int32_t* pairs,
+                          glim_amd_edit_min_cut_result* out);
 
 #ifdef __cplusplus
 }

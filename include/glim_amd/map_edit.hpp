@@ -5,9 +5,10 @@
 //   auto ids = glim_amd::select_radius(submaps, poses, picked, 2.0);                            // select_points_radius, :677-700
 //   auto ids = glim_amd::select_outliers(submaps, poses, picked, 2.0);                          // select_outlier_points_radius, :703-759
 //   auto seg = glim_amd::region_growing(submaps, poses, picked, glim_amd::RegionGrowingParams());  // select_points_segmentation, :798-810
+//   auto cut = glim_amd::select_min_cut(submaps, poses, picked, glim_amd::MinCutParams());       // select_points_segmentation, :774-797
 //   auto upd = glim_amd::remove_selected(submaps, seg.ids);                                     // remove_selected_points, :513-562
 //
-// Min-cut segmentation (:774-797) is not built.  No gtsam_points drop-in exists for this tool: points_selector.cpp needs Iridescence.
+// No gtsam_points drop-in exists for this tool: points_selector.cpp needs Iridescence.
 #pragma once
 
 #include <algorithm>
@@ -150,6 +151,38 @@ inline RegionGrowingResult region_growing(const std::vector<PointCloudGPU::Const
         "region_growing");
   r.ids = edit_detail::pack(flat, (std::size_t)r.info.count);
   r.levels.resize((std::size_t)r.info.count);
+  return r;
+}
+
+// The sigmas and k are a recollection of gtsam_points::MinCutParams, which is not in the reference tree; the radii and the weight are the
+// editor's (:42-44).  The semantics (glim_amd.h "Map editing", min-cut) are this project's: the minimal source side of a minimum cut.
+struct MinCutParams {
+  double distance_sigma = 0.25;
+  double angle_sigma = 10.0 * 3.14159265358979323846 / 180.0;  // radians, as the reference's params; used only with use_normals
+  double foreground_mask_radius = 0.5;
+  double background_mask_radius = 5.0;
+  double foreground_weight = 10.0;
+  double background_weight = 0.0;  // 0: the foreground weight
+  int k_neighbors = 20;            // <= 31
+  bool use_normals = false;
+  int max_rounds = 0;  // 0: GLIM_AMD_EDIT_MIN_CUT_MAX_ROUNDS
+};
+struct MinCutResult {
+  std::vector<std::uint64_t> ids;  // the segment, ascending
+  glim_amd_edit_min_cut_result info;
+};
+inline MinCutResult select_min_cut(const std::vector<PointCloudGPU::ConstPtr>& submaps, const std::vector<Isometry3d>& poses,
+                                   const std::array<double, 3>& picked_point, const MinCutParams& params = MinCutParams(),
+                                   double map_cell_resolution = 2.0, int cell_selection_window = 5) {
+  const auto a = edit_detail::args(submaps, poses);
+  const glim_amd_edit_window w = edit_detail::window(picked_point, map_cell_resolution, cell_selection_window);
+  const glim_amd_edit_min_cut_params prm = {params.distance_sigma,    params.angle_sigma,       params.foreground_mask_radius, params.background_mask_radius,
+                                            params.foreground_weight, params.background_weight, params.k_neighbors,            params.use_normals ? 1 : 0,
+                                            params.max_rounds,        0};
+  std::vector<std::int32_t> flat(2 * (std::size_t)a.total + 2);
+  MinCutResult r;
+  check(glim_amd_edit_min_cut(a.handles.data(), (std::int32_t)a.handles.size(), a.M12.data(), &w, &prm, a.total, flat.data(), &r.info), "select_min_cut");
+  r.ids = edit_detail::pack(flat, (std::size_t)r.info.count);
   return r;
 }
 

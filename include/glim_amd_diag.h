@@ -336,6 +336,23 @@ int glim_amd_debug_ba_auto_radius_trace(const glim_amd_cloud* const* clouds, int
 /* the eigen-solver of the plane bundle-adjustment statistics and factors (csrc/eig3_direct.hpp) run by one device thread per matrix:
  * m9: count x 9 row-major symmetric; evals: count x 3 ascending; evecs: count x 9, evecs[3 k + r] = component r of eigenvector k */
 int glim_amd_debug_ba_eigen3(glim_amd_ctx* ctx, int32_t count, const double* m9, double* evals, double* evecs);
+/* test window of the map editor's min-cut segmentation (glim_amd.h): the graph glim_amd_edit_min_cut builds from the same inputs, before any
+ * flow.  pairs: the candidates, pair_capacity x 2; source_cap / sink_cap: pair_capacity entries, the terminal capacity of every candidate (0:
+ * not tied); edges: edge_capacity x 2 candidate indices (i < j) in ascending key order; edge_cap: edge_capacity capacities.  At most the
+ * capacities are written, the first entries; out: the true counts and the status (EMPTY / FEW_POINTS / NO_SEED as for the call, else OK);
+ * count, flow, rounds and looks are 0.  Any array may be NULL with its capacity 0. */
+int glim_amd_diag_edit_min_cut_graph(const glim_amd_cloud* const* clouds, int32_t num_clouds, const double* T_world_submap12,
+                                     const glim_amd_edit_window* window, const glim_amd_edit_min_cut_params* params, int64_t pair_capacity,
+                                     int32_t* pairs, int32_t* source_cap, int32_t* sink_cap, int64_t edge_capacity, int32_t* edges,
+                                     int32_t* edge_cap, glim_amd_edit_min_cut_result* out);
+/* the solver of the min-cut segmentation (csrc/min_cut.hip) alone, on a caller's graph of n nodes: num_edges undirected edges (i, j), i != j,
+ * both in [0, n), parallel edges allowed, with capacities edge_cap >= 0 in both directions; source_cap / sink_cap >= 0 per node.  member: n
+ * flags, 1 iff the node is reachable from the source in the residual graph of a maximum flow.  max_rounds 0 = the default.  status:
+ * GLIM_AMD_EDIT_OK or GLIM_AMD_EDIT_ROUND_LIMIT (every flag 0, flow 0).  GLIM_AMD_ERR_INVALID: a NULL context or output, n < 0 or num_edges < 0
+ * or either above 2^30, an endpoint out of range, a loop, a negative capacity, max_rounds < 0. */
+int glim_amd_diag_max_flow(glim_amd_ctx* ctx, int32_t n, int64_t num_edges, const int32_t* edges, const int32_t* edge_cap,
+                           const int32_t* source_cap, const int32_t* sink_cap, int32_t max_rounds, int32_t* member, int64_t* flow,
+                           int32_t* rounds, int32_t* looks, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -189,6 +189,13 @@ if os.path.exists(me_path):
         f"Device only: region growing in the editor's default window ({sp(rb['num_candidates'])} candidates, cluster {sp(rb['count'])}, {rb['rounds']} rounds in chunks of {me['rounds_per_look']}) {st['region_growing_default_window']['device_ms']:.2f} ms "
         f"({st['region_growing_default_window']['device_ms']*1e3/max(rb['rounds'],1):.0f} µs per round, the selection, sort and read-backs included), removing that cluster from the sub-maps it touches {st['remove_selected']['device_ms']:.2f} ms.  "
         "Every compared step returned the restatement's pairs.  The restatement is single-threaded NumPy (its region growing a dense distance matrix): the figures describe these two programs, nothing was profiled, and no speed-up is claimed.")
+    if 'min_cut' in me:
+        mc=me['min_cut']
+        vals['MAP_EDIT_MEASURED']+=(f"  Min-cut at the editor's defaults (foreground {mc['params']['foreground_mask_radius']:g} m, background {mc['params']['background_mask_radius']:g} m, k {mc['params']['k_neighbors']}) on the same workload, a run of its own: "
+            f"{sp(mc['num_candidates'])} candidates, {sp(mc['num_edges'])} edges, {sp(mc['num_foreground'])} foreground and {sp(mc['num_background'])} background points, flow {sp(mc['flow'])} units, segment {sp(mc['count'])} points, "
+            f"{mc['rounds']} push rounds in {mc['looks']} chunks, status {mc['status']}: the device call {mc['device_ms']:.0f} ms (median of {mc['device_repeats']}; selection, kNN, sorts and every read-back included; {mc['device_ms']/max(mc['looks'],1):.0f} ms per chunk with its relabelling) "
+            f"beside {mc['scipy_maximum_flow_ms']/1e3:.1f} s inside `scipy.sparse.csgraph.maximum_flow` on the graph the device built and downloaded (single-threaded; building its matrix and reading the cut off the residuals not counted); "
+            f"the two results are {'equal' if mc['equal'] else 'NOT equal'} (flow and set).  A description of two programs: the issue set no time target, and no round of this solver has been profiled.")
 else:
     vals['MAP_EDIT_MEASURED']="nothing yet.  `tools/map_edit_time.py` writes `profiles/map_edit/map_edit_time.json` (24 sub-maps of 65 536 points: the four selections, the outliers, region growing and the removal beside the NumPy restatement of the same steps, alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()

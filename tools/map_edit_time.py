@@ -7,7 +7,12 @@ fits, and in the editor's default window, device only), and the removal of the g
 the figures are host wall-clock times around the call, warm-up first, median of the repeats; the clouds are resident before the clock
 starts.  One box, one run; no speed-up beyond these two programs is claimed.
 
-    python tools/map_edit_time.py [--repeats 20] [--out FILE]
+Min-cut segmentation runs at the editor's defaults (foreground 0.5 m, background 5 m, weight 10, k 20) on the same workload: the device call
+beside scipy.sparse.csgraph.maximum_flow on the graph the device built and downloaded (the time inside maximum_flow alone; building the
+matrix and reading the cut off the residuals are not counted), and whether the two agree.  --min-cut-only measures that line alone and
+merges it into the existing file.
+
+    python tools/map_edit_time.py [--repeats 20] [--out FILE] [--min-cut-only]
 """
 import argparse
 import json
@@ -50,18 +55,53 @@ def median_ms(fn, repeats, warmup=2):
     return float(np.median(t))
 
 
+def min_cut_line(api, gpu, poses, center, repeats=3, save=None):
+    """the device call at the editor's defaults beside scipy's maximum flow on the downloaded graph; save: called with the device's half of
+    the line before scipy starts"""
+    import min_cut_restatement as M
+
+    prm = api.MinCutParams()
+    got = api.edit_min_cut(gpu, poses, center, prm)
+    print("min-cut:", {k: v for k, v in got.items() if k != "pairs"}, file=sys.stderr, flush=True)
+    line = {k: got[k] for k in ("count", "num_candidates", "num_edges", "num_foreground", "num_background", "flow", "rounds", "looks", "status")}
+    line.update(device_ms=median_ms(lambda: api.edit_min_cut(gpu, poses, center, prm), repeats, warmup=0), device_repeats=repeats,
+                params={k: getattr(prm, k) for k in ("distance_sigma", "foreground_mask_radius", "background_mask_radius", "foreground_weight", "k_neighbors")})
+    if save:
+        save(line)
+    g = api.diag_edit_min_cut_graph(gpu, poses, center, prm)
+    times = {}
+    flow, flags = M.judge(g["num_candidates"], g["edges"], g["edge_cap"], g["source_cap"], g["sink_cap"], times=times)
+    line.update(scipy_maximum_flow_ms=times["maximum_flow_s"] * 1e3, scipy_flow=flow, scipy_count=int(flags.sum()),
+                equal=bool(got["status"] == "ok" and got["flow"] == flow and np.array_equal(got["pairs"], g["candidates"][flags == 1])))
+    print("min-cut: scipy", flow, int(flags.sum()), times, file=sys.stderr, flush=True)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "map_edit", "map_edit_time.json"))
+    ap.add_argument("--min-cut-only", action="store_true", help="measure the min-cut line alone and merge it into the existing file")
     args = ap.parse_args()
     import map_edit_restatement as R
     from glim_amd import api
-    from oracle import oracle as orc
 
     clouds, poses, center = make_workload()
     ctx = api.Context(0, 1)
     gpu = [api.clone_exact(p, ctx=ctx) for p in clouds]
+    if args.min_cut_only:
+        out = json.load(open(args.out))
+        assert out["submaps"] == len(clouds) and out["points_per_submap"] == len(clouds[0])
+        def save(line):
+            out["min_cut"] = line
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+        save(min_cut_line(api, gpu, poses, center, save=save))
+        print(json.dumps(out["min_cut"]))
+        return
+    from oracle import oracle as orc
+
     model = np.eye(4)
     model[:3, :3] *= 3.0
     model[:3, 3] = center
@@ -99,6 +139,7 @@ def main():
         "region_growing_small_window": {k: grown[k] for k in ("count", "num_candidates", "rounds")},
         "region_growing_default_window": {k: big[k] for k in ("count", "num_candidates", "rounds")},
         "steps": steps, "device_name": ctx.device_info()["name"],
+        "min_cut": min_cut_line(api, gpu, poses, center),
     }
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
