@@ -144,7 +144,8 @@ def gn_step(L, lam=0.0):  # of a record of either size: the rigid (H_ss, b_s) or
     return np.linalg.solve(H + lam * np.eye(len(b)), -b)
 
 
-def _check_record(got, ref):
+def _check_record(got, ref, step=True):
+    """step = False: without the Gauss-Newton step, for a system so short of pairs that the damping decides the step"""
     assert got["num_inliers"] == ref["num_inliers"] > 0
     np.testing.assert_allclose(got["error"], ref["error"], rtol=2e-4)
     Hg, bg = full_system(got)
@@ -153,7 +154,7 @@ def _check_record(got, ref):
     np.testing.assert_allclose(Hg, Hr, rtol=0, atol=2e-4 * scale)
     np.testing.assert_allclose(bg, br, rtol=0, atol=2e-4 * np.abs(br).max() + 1e-6 * scale)
     lam = 1e-6 * np.trace(Hr) / 12
-    assert np.abs(gn_step(got, lam) - gn_step(ref, lam)).max() < POSE_TOL
+    assert not step or np.abs(gn_step(got, lam) - gn_step(ref, lam)).max() < POSE_TOL
 
 
 def _prior(T, T0, prec):

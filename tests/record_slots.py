@@ -28,6 +28,10 @@ gate():  with c64, c32 the two arrays,  S_j = sum c64[:, j],  P_j = sum |c32[:, 
   the last term  the FP64 rotation of the finaliser and its inverse here (sums_of_record): some 30 operations on the entries of one block
 
 Slots whose terms are all integers computed without rounding (the zeros and counts of point-to-point ICP) are exact(): compared with ==.
+
+The continuous-time factor (the last section): the same 28 terms per point, at the pose of the point's time bucket (ct_terms); the 92 entries
+of its record from the bucket sums through the chain rule [D0_k | D1_k] (ct_record); the gate of each entry propagated from the buckets'
+gates with no cancellation assumed (ct_gate); and ct_error_kernel's one term per kept pair with its gate (ct_frozen_terms, error_gate).
 """
 import numpy as np
 
@@ -65,9 +69,11 @@ def perturbed(delta, w=(0.006, -0.005, 0.0062), v=(0.03, -0.028, 0.029)):
 
 
 def transform(T, p):
-    """q = T p in FP64, n x 3"""
-    T = np.asarray(T, dtype=np.float64)
-    return np.asarray(p, dtype=np.float64) @ T[:3, :3].T + T[:3, 3]
+    """q = T p in FP64, n x 3; T: one pose (4 x 4) or one per point (n x 4 x 4)"""
+    T, p = np.asarray(T, dtype=np.float64), np.asarray(p, dtype=np.float64)
+    if T.ndim == 3:
+        return np.einsum("nij,nj->ni", T[:, :3, :3], p) + T[:, :3, 3]
+    return p @ T[:3, :3].T + T[:3, 3]
 
 
 def _terms(M, r, lever):
@@ -196,9 +202,11 @@ def vgicp_plane(p, nrm, coord, mu_rel, AB, T, res, dtype, T_eval=None, w=0.999, 
 
 
 def _source_frame(p, b, T, dt):
-    """the GICP / ICP stages in front of the FP32 algebra: (R in dt, 1 x 3 x 3; r = b - q formed in FP64 and rounded; the lever arm p)"""
+    """the GICP / ICP stages in front of the FP32 algebra: (R in dt, (1 | n) x 3 x 3; r = b - q formed in FP64 and rounded; the lever arm p).
+    T: one pose, or one per point (the continuous-time factor: the pose of the point's bucket)"""
     T = np.asarray(T, dtype=np.float64)
-    return T[None, :3, :3].astype(dt), (np.asarray(b, dtype=np.float64) - transform(T, p)).astype(dt), np.asarray(p).astype(dt)
+    R = T[:, :3, :3] if T.ndim == 3 else T[None, :3, :3]
+    return R.astype(dt), (np.asarray(b, dtype=np.float64) - transform(T, p)).astype(dt), np.asarray(p).astype(dt)
 
 
 def gicp(p, CA, b, CB, T, dtype, transpose=False, axes=0):
@@ -484,3 +492,167 @@ def device_sum(c32, idx, n, ppt):
     assert w.dtype == np.float32
     rows = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
     return rows.astype(np.float64).sum(axis=0)
+
+
+# ---- the continuous-time factor (ct_factor.hpp; ct_gicp_kernel, ct_bucket_kernel, ct_sum_kernel, ct_error_kernel of gicp.hip) -----------------
+CT_ROW = 92  # the record ct_expand_record reads: count, error, the 78 upper entries of the 12 x 12 H (row-major), the 12 of b
+_U12 = np.triu_indices(12)
+CT_NAMES = ["count", "error"] + [f"H{r}_{c}" for r, c in zip(*_U12)] + [f"b{r}" for r in range(12)]
+CT_BLOCK = 256
+
+
+def points_per_thread(n, num_cus=256):
+    """gicp_factor.hpp points_per_thread, restated: the points a thread takes so that the cloud makes at least four blocks of 256 threads per
+    compute unit.  1 up to 262 144 points on a part with 256 compute units; the CT blocks are cut by it (BLOCK * ppt points each)."""
+    target_blocks = max(1, 4 * num_cus)
+    return max(1, min(64, -(-n // (CT_BLOCK * target_blocks))))
+
+
+def ct_matched(scene, corr, bucket):
+    """corr: per source point the index of its target point, or -1; bucket: the time bucket of every source point"""
+    i = np.flatnonzero(np.asarray(corr) >= 0)
+    j = np.asarray(corr)[i]
+    return dict(idx=i, p=scene["sp"][i], CA=scene["sc"][i], b=scene["tp"][j], CB=scene["tc"][j], bucket=np.asarray(bucket)[i], n=len(scene["sp"]),
+                all_buckets=np.asarray(bucket))
+
+
+def ct_terms(scene, m, dtype, poses, axes=0):
+    """ct_gicp_block: the 28 source-frame terms of every matched point -- gicp_point, at the pose T[k] of the point's bucket.  poses: T, nbk x 4 x 4
+    (scene is not read: the matched set carries the points; kept for the signature the other *_terms share)"""
+    return gicp(m["p"], m["CA"], m["b"], m["CB"], np.asarray(poses, dtype=np.float64)[m["bucket"]], dtype, axes=axes)
+
+
+def ct_draws(scene, m, poses):
+    return draws(lambda axes: ct_terms(scene, m, np.float32, poses, axes=axes))
+
+
+def _arrange(S):
+    """the 6 x 6 and the 6 the finalisers make of 28 numbers WITHOUT the sign of b's second half: for gates and absolute sums"""
+    r = record_of_sums(np.abs(S))
+    return r["H_ss"], np.abs(r["b_s"])
+
+
+def bucket_sums(c, bucket, nbk):
+    """nbk x 28: the terms of every bucket added in FP64"""
+    S = np.zeros((nbk, NSLOTS))
+    np.add.at(S, np.asarray(bucket), np.asarray(c, dtype=np.float64))
+    return S
+
+
+def ct_record_of_bucket_sums(S, count, D0, D1):
+    """ct_bucket_block and ct_sum_rows in FP64: per bucket (H_k, b_k) = record_of_sums(S_k) -- the compact record's convention,
+    b = [sums 21..23, -sums 24..26] -- and J_k = [D0_k | D1_k]; the record is sum_k J_k^T H_k J_k, sum_k J_k^T b_k, sum_k S_k[27], the count"""
+    H, b, e = np.zeros((12, 12)), np.zeros(12), 0.0
+    for k in range(len(S)):
+        r = record_of_sums(S[k])
+        J = np.hstack([D0[k], D1[k]])
+        H += J.T @ r["H_ss"] @ J
+        b += J.T @ r["b_s"]
+        e += r["error"]
+    return np.concatenate([[float(count), e], H[_U12], b])
+
+
+def ct_record(c, bucket_of_point, D0, D1):
+    """the 92 entries of the CT record from the terms c (one row per matched point) and the bucket of each of these points"""
+    return ct_record_of_bucket_sums(bucket_sums(c, bucket_of_point, len(D0)), len(c), D0, D1)
+
+
+def ct_record_of(L):
+    """the 92 entries behind a linearisation as the API hands it out (H_00, H_01, H_11, b_0, b_1): ct_expand_record undone"""
+    H = np.block([[L["H_00"], L["H_01"]], [L["H_01"].T, L["H_11"]]])
+    return np.concatenate([[float(L["num_inliers"]), L["error"]], H[_U12], L["b_0"], L["b_1"]])
+
+
+def ct_dict(rec):
+    """ct_expand_record: the API's dict of a 92-entry record"""
+    H = np.zeros((12, 12))
+    H[_U12] = rec[2:80]
+    H = H + np.triu(H, 1).T
+    return dict(num_inliers=int(round(rec[0])), error=float(rec[1]), H_00=H[:6, :6], H_01=H[:6, 6:], H_11=H[6:, 6:], b_0=rec[80:86].copy(), b_1=rec[86:92].copy())
+
+
+def ct_gate(c32_draws, c64, bucket_of_point, D0, D1, s, m=M_DEFAULT):
+    """The gate of each of the 92 entries.  -> dict S (the FP64 record), P, gate (92 each).
+
+    Per bucket k the 28 sums S^k_j have the gate gate^k_j of gate() over that bucket's points (s = additions(1) = 9: a CT block takes one point
+    per thread).  Every record entry is linear in the bucket sums, E = sum_k sum_j a^k_Ej S^k_j with the a made of entries of J_k = [D0_k | D1_k],
+    and no cancellation between buckets or slots is assumed: gate_E = sum_k sum_j |a^k_Ej| gate^k_j -- for H, |J_k|^T G_k |J_k| with G_k the
+    6 x 6 arrangement of the 21 gates; for b, |J_k|^T g_k; for the error, sum_k gate^k_27.  P_E is propagated the same way from the P^k_j.
+    (gate^k_j carries 64 2^-53 of the bucket's block maxima: here it stands for the FP64 additions of the bucket's partial rows, at most 64.)
+
+    On top, the device's own FP64 arithmetic: in ct_bucket_block an entry of W = H_k J_k is a 6-term dot product (6 roundings at most on any
+    term: its product and five additions) and the entry of J_k^T W another one (6 more); ct_sum_rows then adds the nbk bucket rows (at most
+    nbk additions on any term, in whatever grouping).  count = 6 + 6 + nbk roundings, and the gate takes TWICE count 2^-53 of the
+    absolute-value sum sum_k |J_k|^T |H_k| |J_k| (|J_k|^T |b_k|, sum_k |e_k|).  Entry 0, the count, is exact: compared with ==."""
+    c32 = c32_draws[None] if c32_draws.ndim == 2 else c32_draws
+    nbk = len(D0)
+    bucket = np.asarray(bucket_of_point)
+    out = {k: np.zeros(CT_ROW) for k in ("P", "gate", "A")}
+    for k in np.unique(bucket):
+        sel = bucket == k
+        g = gate(c32[:, sel], c64[sel], s, m)
+        aJ = np.abs(np.hstack([D0[k], D1[k]]))
+        for key, v in (("P", g["P"]), ("gate", g["gate"]), ("A", g["S"])):
+            H6, b6 = _arrange(v)
+            out[key][2:80] += (aJ.T @ H6 @ aJ)[_U12]
+            out[key][80:92] += aJ.T @ b6
+            out[key][1] += abs(v[27])
+    fp64 = 2.0 * (6 + 6 + nbk) * 2.0 ** -53 * out["A"]
+    S = ct_record(c64, bucket, D0, D1)
+    return dict(S=S, P=out["P"], gate=out["gate"] + fp64, fp64=fp64)
+
+
+def ct_check(rec, g, label=""):
+    """asserts a device record (92 entries) against a ct_gate() result; returns |rec - S| / P per entry (nan for the count and where P = 0)"""
+    rec = np.asarray(rec, dtype=np.float64)
+    assert rec[0] == g["S"][0], f"{label}: count {rec[0]} != {g['S'][0]}"
+    err = np.abs(rec - g["S"])
+    over = [(CT_NAMES[j], err[j] / g["gate"][j]) for j in range(1, CT_ROW) if not err[j] <= g["gate"][j]]
+    assert not over, f"{label}: entries beyond their gate (name, error / gate): {over}"
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(g["P"] > 0, err / g["P"], np.nan)
+    r[0] = np.nan
+    return r
+
+
+def ct_device_sums(c32, m, ppt=1):
+    """nbk x 28: the FP32 terms added in the shape of the CT factor's reduction -- every bucket's index run cut into blocks of 256 ppt points
+    (device_sum per bucket: FP32 inside a block, FP64 across the blocks of the bucket)"""
+    allb = m["all_buckets"]
+    nbk = int(allb.max()) + 1 if len(allb) else 0
+    S = np.zeros((nbk, NSLOTS))
+    for k in range(nbk):
+        run = np.flatnonzero(allb == k)
+        assert len(run) and np.all(np.diff(run) == 1)  # a bucket is one contiguous index run (the time table never goes back)
+        sel = m["bucket"] == k
+        S[k] = device_sum(c32[sel], m["idx"][sel] - run[0], len(run), ppt)
+    return S
+
+
+def ct_frozen_terms(m, T_lin, T_eval, dtype, axes=0, rotate=True, R_from_eval=False):
+    """ct_error_kernel after a linearising ct_gicp_block: per kept pair e = r . (M r) with M = R A R^T the kept target-frame metric,
+    A = (R^T C_B R + C_A)^-1 by _inv, R the rotation of the LINEARISATION pose of the pair's bucket (FP32 in the FP32 form), and
+    r = b - T_eval,k p formed in FP64 and rounded.  M is formed as the kernel forms it, W = R A and then W R^T, in NumPy's own order of
+    operations.  T_lin, T_eval: nbk x 4 x 4.  -> n values.  (rotate = False: A left in the source frame; R_from_eval: the evaluation pose's
+    rotation in M -- the mutation tests.)"""
+    dt = np.dtype(dtype).type
+    Tl, Te = np.asarray(T_lin, dtype=np.float64)[m["bucket"]], np.asarray(T_eval, dtype=np.float64)[m["bucket"]]
+    R = (Te if R_from_eval else Tl)[:, :3, :3].astype(dt)
+    r = (np.asarray(m["b"], dtype=np.float64) - transform(Te, m["p"])).astype(dt)
+
+    def build(CB, CA, R, r, lever):
+        A = _inv(_t(R) @ CB @ R + CA)
+        return ((R @ A) @ _t(R) if rotate else A), r, lever
+
+    return _finish(axes, build, np.asarray(m["CB"]).astype(dt), np.asarray(m["CA"]).astype(dt), R, r, np.asarray(m["p"]).astype(dt))[:, 27]
+
+
+def ct_frozen_draws(m, T_lin, T_eval):
+    return np.stack([ct_frozen_terms(m, T_lin, T_eval, np.float32, axes=a) for a in range(len(_AXES))])
+
+
+def error_gate(e32_draws, e64, s, m=M_DEFAULT):
+    """slot 27's gate for a kernel that adds one term per pair (ct_error_kernel): dict of the scalars S, P, Q, gate"""
+    pad = lambda e: np.concatenate([np.zeros(e.shape + (NSLOTS - 1,), dtype=e.dtype), e[..., None]], axis=-1)  # noqa: E731
+    g = gate(pad(e32_draws), pad(e64), s, m)
+    return {k: float(g[k][27]) for k in ("S", "P", "Q", "gate")}
