@@ -38,6 +38,37 @@ template <class T>
 inline hipError_t pool_malloc(T** p, size_t bytes) {
   return pool_malloc_impl(reinterpret_cast<void**>(p), bytes);
 }
+// the device's address of a pinned_malloc block; false (and *dev null) where the runtime has none
+template <class T>
+bool host_device_view(T* host, T** dev) {
+  *dev = nullptr;
+  if (hipHostGetDevicePointer(reinterpret_cast<void**>(dev), host, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    *dev = nullptr;
+    return false;
+  }
+  return true;
+}
+
+inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#elif defined(__aarch64__)
+  asm volatile("yield" ::: "memory");
+#endif
+}
+// spin until *word == value (acquire); false after ~200 ms
+inline bool spin_until(const volatile unsigned int* word, unsigned int value) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned long spins = 0;; spins++) {
+    if (*word == value) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      return true;
+    }
+    cpu_relax();
+    if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
+  }
+}
 
 // RAII holder of a pool allocation used as kernel scratch
 struct DeviceTemp {
@@ -287,7 +318,7 @@ struct glim_amd_ctx {
   int priority = 0;  // 1: its streams were created with the device's greatest priority (glim_amd_ctx_create_ex)
   std::vector<FactorPlan*> plan_cache;  // idle factor plans, most recently released first (vgicp.hip; guarded by mu)
   uint64_t plans_built = 0, plans_recycled = 0;  // plans built for new factor lists; how many of them in the buffers of an evicted plan (guarded by mu)
-  // overlap scratch (vgicp.hip), allocated on first use: per-query arrival counters on the device, results + completion word in host-mapped memory
+  // overlap scratch (overlap.hip), allocated on first use: per-query arrival counters on the device, results + completion word in host-mapped memory
   static constexpr int OV_MAX_QUERIES = 1024;
   unsigned long long* ov_counters = nullptr;  // [OV_MAX_QUERIES] packed (arrived blocks << 32 | hits), then the queries-done word
   unsigned int* ov_host = nullptr;            // pinned: [0] completion word, [1 + q] hits of query q
@@ -395,7 +426,7 @@ struct glim_amd_voxelmap {
   int32_t num_voxels = 0;
   uint32_t num_buckets = 0;  // 0 until insert()
   glim_amd::VoxelBucket* buckets = nullptr;
-  // "Plane view" of the same table for factors whose source cloud is plane-form (vgicp.hip, GLIM_AMD_PLANE_SM): same keys, same means, but the
+  // "Plane view" of the same table for factors whose source cloud is plane-form (vgicp.hip accumulate_point): same keys, same means, but the
   // six covariance slots of a record hold A_B = (C_B + I)^-1 (inverted in FP64 from the FP32 record), and one extra, all-zero bucket at index
   // num_buckets that lanes without a correspondence read.  Built on first use (ensure_plane_view), dropped whenever the table is rebuilt.
   glim_amd::VoxelBucket* buckets_sm = nullptr;

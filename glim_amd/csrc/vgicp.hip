@@ -1,7 +1,7 @@
-// vgicp.hip -- the VGICP matching-cost factor on gfx950 (kernels K4 linearise, K5 error, K6 overlap) and the factor-set
-// (NonlinearFactorSetGPU) entry points of the C ABI.
+// vgicp.hip -- the VGICP matching-cost factor on gfx950 (kernels K4 linearise, K5 error) and the factor-set
+// (NonlinearFactorSetGPU) entry points of the C ABI.  (K6, the overlap query, is overlap.hip.)
 //
-// Replaces gtsam_points::IntegratedVGICPFactorGPU::{linearize,error} + NonlinearFactorSetGPU::linearize + overlap_gpu as
+// Replaces gtsam_points::IntegratedVGICPFactorGPU::{linearize,error} + NonlinearFactorSetGPU::linearize as
 // called from src/glim/odometry/odometry_estimation_gpu.cpp:144,161,231,248,383-386, src/glim/mapping/sub_mapping.cpp:252,307
 // and src/glim/mapping/global_mapping.cpp:322,335,448,466,860.  The arithmetic follows the CPU factor
 // (gtsam_points::IntegratedVGICPFactor, the parity oracle: SURVEY.md App. B.5):
@@ -54,35 +54,11 @@ constexpr int NACC = 28;  // FP32 accumulators per thread (see layout below); sl
 // accumulator layout:  0..5  Hww (00 01 02 11 12 22)   6..14 G = hat(p) A (row-major 3x3 = H_wv)   15..20 A (00 01 02 11 12 22)
 //                      21..23 u x p (= b_w)            24..26 u (b_v = -u)                          27 e
 // compact record:      [count, error, 21 upper-triangular H_ss entries row-major, 6 b_s]
-// A/B knobs of round 6's work on the synchronous call (tools/ab_variant.sh <name> -DGLIM_AMD_ROT27=0 ...): one thread per rotated value in the
-// finalisers (rotate_element) / the four-thread form; the resident workers skip the probe of a point no lane has (TAILSKIP) / run it
-#ifndef GLIM_AMD_ROT27
-#define GLIM_AMD_ROT27 1
-#endif
-// the 28 wavefront sums of a row step-major (device_math.hpp wave_sums_to_lane63) / value by value (rounds 1-5)
-#ifndef GLIM_AMD_STEP_MAJOR_SUMS
-#define GLIM_AMD_STEP_MAJOR_SUMS 1
-#endif
-#ifndef GLIM_AMD_RES_TAILSKIP
-#define GLIM_AMD_RES_TAILSKIP 1
-#endif
-// resident workers: the stream data of a lane's second point is loaded before the pose arrives, like the first point's, and a row of exactly two
-// points per lane runs a flat schedule (compute_row) / 0: the second point is loaded behind the pose, every row walks the two-trip pipeline
-#ifndef GLIM_AMD_RES_FLAT2
-#define GLIM_AMD_RES_FLAT2 1
-#endif
 // the four 16-lane ROW sums of every wavefront go to LDS and whoever forms the row's values adds them as (r3 + r2) + (r1 + r0), what the two
-// row_bcast steps left in lane 63 (same bits; 4 instead of 10 instructions per value and wavefront) / 0: the wavefront sums as before
-#ifndef GLIM_AMD_ROW_SUMS_LDS
-#define GLIM_AMD_ROW_SUMS_LDS 1
-#endif
-#if GLIM_AMD_ROW_SUMS_LDS
+// row_bcast steps of a full wavefront sum would leave in lane 63 (same bits; 4 instead of 10 instructions per value and wavefront:
+// profiles/r06/probe/row_sums_through_lds_ab.json)
 constexpr int RED_ROWS = 4;  // s_red[wavefront][16-lane row][value]
-#else
-constexpr int RED_ROWS = 1;  // s_red[wavefront][0][value]
-#endif
 typedef float RedRow[RED_ROWS][glim_amd::PARTIAL_STRIDE];
-__device__ __forceinline__ float4 ld16(const void* p) { return *reinterpret_cast<const float4*>(p); }
 
 enum { MODE_LINEARIZE = 0, MODE_ERROR = 1 };
 
@@ -90,19 +66,11 @@ enum { MODE_LINEARIZE = 0, MODE_ERROR = 1 };
 // space hipcc emits FLAT loads (which tick both vmcnt and lgkmcnt and force vmcnt(0) waits); with it, global_load + counted waits.
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef float v2f_t __attribute__((ext_vector_type(2)));
-typedef float v3f_t __attribute__((ext_vector_type(3)));
 typedef const __attribute__((address_space(1))) v4f_t* gf4_t;
-typedef const __attribute__((address_space(1))) v3f_t* gf3_t;
 typedef const __attribute__((address_space(1))) v2f_t* gf2_t;
 __device__ __forceinline__ float4 gld4(const void* p) {
   const v4f_t v = *reinterpret_cast<gf4_t>(reinterpret_cast<uintptr_t>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-}
-// xyz of a float4 record as ONE 12-byte load: no dead 4th destination register (a dead register gets recycled by the
-// allocator while the load is still in flight, and the write-after-write hazard then stalls the wave on that load)
-__device__ __forceinline__ float4 gld3(const void* p) {
-  const v3f_t v = *reinterpret_cast<gf3_t>(reinterpret_cast<uintptr_t>(p));
-  return make_float4(v.x, v.y, v.z, 1.f);
 }
 __device__ __forceinline__ float2 gld2(const void* p) {
   const v2f_t v = *reinterpret_cast<gf2_t>(reinterpret_cast<uintptr_t>(p));
@@ -265,11 +233,8 @@ __device__ __forceinline__ void finalize_tail(int f, const FinalizeArgs& fa, int
     if (t == 29 && fa.trip_stats && s_sum[29] > 0.0) atomicAdd(&fa.trip_stats[f & 63], (unsigned long long)s_sum[29]);
     __shared__ double s_rot[32];
     if (mode == MODE_LINEARIZE) {
-#if GLIM_AMD_ROT27
-      if (t < RECORD_ROTATED) s_rot[t] = rotate_element(t, s_sum, Tl);  // one thread per rotated value, one path for all of them (rotate_part's bits)
-#else
-      if (t < 4) rotate_part(t, s_sum, Tl, s_rot);  // thread k < 3 rotates block k (Hww, Hwv, Hvv), thread 3 the two vectors
-#endif
+      // one thread per rotated value, one path for all of them (rotate_part's bits; profiles/r06/probe/sync_tailskip_rot27_ab.json)
+      if (t < RECORD_ROTATED) s_rot[t] = rotate_element(t, s_sum, Tl);
       __syncthreads();
     }
     if (tail_stamps) st1 = __builtin_amdgcn_s_memrealtime();
@@ -538,15 +503,7 @@ __device__ __forceinline__ void piece_finalize(const FactorDesc& d, int f, int p
 // Plane-form factors read the "plane view" of the target table (A_B = (C_B + I)^-1 in the covariance slots, voxelmap.hip plane_view_kernel)
 // and form M by Sherman-Morrison instead of building S = C_B + R C_A R^T and inverting it by cofactors: 26 FP32
 // operations instead of 39, same conditioning (the denominator 1 - 0.999 m^T A_B m >= 0.002 carries the cancellation the determinant of S
-// carried).  0: the cofactor form on the plain table (A/B builds: tools/ab_variant.sh sm0 -DGLIM_AMD_PLANE_SM=0).
-#ifndef GLIM_AMD_PLANE_SM
-#define GLIM_AMD_PLANE_SM 1
-#endif
-// key compares of the probe resolution: 1 = every predicate formed once (four 64-bit compares per trip; adopted in round 6: configs[3] kernel
-// 11.11 -> 10.96 ms same box, alternating, -1.4 %; plane-form kernel and synchronous call unchanged: profiles/r06/probe/keycmp4_ab.json), 0 = round 5's form (six)
-#ifndef GLIM_AMD_KEYCMP4
-#define GLIM_AMD_KEYCMP4 1
-#endif
+// carried).  Measured against the cofactor form on the plain table in profiles/r05/probe/k4_sm_ab.txt.
 
 struct Rot32 {  // rotation of the linearisation pose in FP32 (wave-uniform: lives in SGPRs)
   float r00, r01, r02, r10, r11, r12, r20, r21, r22;
@@ -639,21 +596,11 @@ __device__ __forceinline__ Probe<PLANE> probe_point(const FactorDesc& d, const P
 template <int MODE, bool PLANE>
 __device__ __forceinline__ void accumulate_point(float (&acc)[NACC], bool hit, const float4& r0, const float4& r1, float r2c22, const Probe<PLANE>& s,
                                                  const Rot32& R) {
-  // C_t = R C_A R^T, the source covariance in the target frame (symmetric: t00 t01 t02 t11 t12 t22)
-  float t00, t01, t02, t11, t12, t22;
-  if (PLANE) {
-    // C_A = I - (1 - 1e-3) n n^T  =>  C_t = I - (1 - 1e-3) m m^T with m = R n (probe stage): 9 + 9 operations instead of the 45-operation sandwich
-    const float mx = s.c0, my = s.c1, mz = s.c2;
-    const float w = 0.999f, wx = w * mx, wy = w * my;
-    t00 = 1.f - wx * mx; t01 = wx * my; t02 = wx * mz;       // (off-diagonal entries carry the opposite sign: subtracted with one fma below)
-    t11 = 1.f - wy * my; t12 = wy * mz; t22 = 1.f - w * mz * mz;
-  } else {
-    t00 = s.c0; t01 = s.c1; t02 = s.c2; t11 = s.c3; t12 = s.c4; t22 = s.c5;
-  }
   // residual mu - q, both relative to the voxel centre
   const float rx = r0.x - s.qr0, ry = r0.y - s.qr1, rz = r0.z - s.qr2;
   float A00, A01, A02, A11, A12, A22;
-  if (PLANE && GLIM_AMD_PLANE_SM) {
+  if (PLANE) {
+    // C_A = I - (1 - 1e-3) n n^T  =>  C_t = R C_A R^T = I - (1 - 1e-3) m m^T with m = R n (probe stage), and
     // the record holds A_B = (C_B + I)^-1 (plane view of the table).  M = A_B + c w w^T, w = A_B m, c = 0.999 / (1 - 0.999 m.w).  A lane
     // without a match has read the table's all-zero record: w = 0, M = 0, every contribution an exact zero -- no select.
     // Explicit fmaf chains: this function is inlined into four kernels that must return the same bits.
@@ -670,20 +617,13 @@ __device__ __forceinline__ void accumulate_point(float (&acc)[NACC], bool hit, c
     const float cx = c * wx, cy = c * wy, cz = c * wz;
     A00 = fmaf(cx, wx, a00); A01 = fmaf(cx, wy, a01); A02 = fmaf(cx, wz, a02);
     A11 = fmaf(cy, wy, a11); A12 = fmaf(cy, wz, a12); A22 = fmaf(cz, wz, a22);
-    (void)hit; (void)t00; (void)t01; (void)t02; (void)t11; (void)t12; (void)t22;
+    (void)hit;
   } else {
-  // S = C_B + R C_A R^T (symmetric).  A lane without a match has read SOME record of the table -- another voxel's, or the zeros of an empty
-  // way (voxelmap.hip initialises every record) -- so everything up to the determinant is finite for it too; idet = 0 (a select, not a
-  // product) then zeroes its contributions exactly.  No per-coefficient selects.
-  const float S00 = r0.w + t00, S11 = r1.z + t11, S22 = r2c22 + t22;
-  float S01, S02, S12;
-  if (PLANE) {
-    const float mx = s.c0, my = s.c1, mz = s.c2, wx = 0.999f * mx, wy = 0.999f * my;
-    S01 = fmaf(-wx, my, r1.x); S02 = fmaf(-wx, mz, r1.y); S12 = fmaf(-wy, mz, r1.w);
-  } else {
-    S01 = r1.x + t01; S02 = r1.y + t02; S12 = r1.w + t12;
-  }
-  (void)t01; (void)t02; (void)t12;
+  // S = C_B + C_t, C_t = R C_A R^T the source covariance in the target frame (probe stage; symmetric).  A lane without a match has read SOME
+  // record of the table -- another voxel's, or the zeros of an empty way (voxelmap.hip initialises every record) -- so everything up to the
+  // determinant is finite for it too; idet = 0 (a select, not a product) then zeroes its contributions exactly.  No per-coefficient selects.
+  const float S00 = r0.w + s.c0, S11 = r1.z + s.c3, S22 = r2c22 + s.c5;
+  const float S01 = r1.x + s.c1, S02 = r1.y + s.c2, S12 = r1.w + s.c4;
   // M = S^-1 by cofactors (symmetric, called A below)
   const float k00 = S11 * S22 - S12 * S12;
   const float k01 = S02 * S12 - S01 * S22;
@@ -752,7 +692,7 @@ struct PipeCtx {  // wave-uniform context of the pipelined loop
 // i1 / ok1: the point this trip probes (stream data in `nxt`) and whether it exists; i2: the point whose stream loads this trip issues.
 // TAILSKIP (the resident kernels: a wavefront there walks one or two trips and the caller waits for it): the probe and the stream loads of a point that
 // no lane has -- the last trip's steps (2) and (3), ~80 instructions in front of the last algebra -- are skipped behind a scalar branch.  Nothing
-// that is added depends on them: same bits.  (The launch-per-call kernels walk 30-60 trips and stay as they are: their loop sits at its register cap.)
+// that is added depends on them: same bits (profiles/r06/probe/sync_tailskip_rot27_ab.json).  (The launch-per-call kernels walk 30-60 trips and stay as they are: their loop sits at its register cap.)
 struct Resolved {  // a resolved probe: whether this lane / any lane of the wavefront has a correspondence, and the (gathered) record
   bool hit, any_hit;
   float4 r0, r1;
@@ -764,9 +704,9 @@ __device__ __forceinline__ Resolved resolve_probe(const FactorDesc& d, const Pro
   unsigned long long k0 = (unsigned long long)__float_as_uint(cur.head.x) | ((unsigned long long)__float_as_uint(cur.head.y) << 32);
   unsigned long long k1 = (unsigned long long)__float_as_uint(cur.head.z) | ((unsigned long long)__float_as_uint(cur.head.w) << 32);
   unsigned int b = cur.bkt;
-#if GLIM_AMD_KEYCMP4
-  // four 64-bit compares per trip instead of six: each predicate is formed ONCE and reused as a lane mask -- the form below
-  // this #if re-evaluates `k0 == key` / `k1 == key` after the (rare) spill walk because the walk may have changed them
+  // four 64-bit compares per trip: each predicate is formed ONCE and reused as a lane mask; the (rare) spill walk, which
+  // may change k0 / k1, forms them again.  configs[3] kernel 11.11 -> 10.96 ms against six compares, same box, alternating, -1.4 %; plane-form
+  // kernel and synchronous call unchanged: profiles/r06/probe/keycmp4_ab.json
   const bool valid = cur.key != EMPTY_KEY;
   bool eq0 = k0 == cur.key, eq1 = k1 == cur.key;
   if (valid && !eq0 && !eq1 && k1 != EMPTY_KEY) {
@@ -782,19 +722,6 @@ __device__ __forceinline__ Resolved resolve_probe(const FactorDesc& d, const Pro
   }
   const bool in1 = eq1;
   const bool hit = valid && (eq0 || eq1);
-#else
-  if (cur.key != EMPTY_KEY) {
-    // rare spill: both ways of the home bucket hold other keys -> walk to the next bucket (exact compare, table never full)
-    while (k0 != cur.key && k1 != cur.key && k1 != EMPTY_KEY) {
-      b = (b + 1 == d.num_buckets) ? 0u : b + 1;
-      const float4 h = gld4(reinterpret_cast<const char*>(d.buckets) + b * 128u);
-      k0 = (unsigned long long)__float_as_uint(h.x) | ((unsigned long long)__float_as_uint(h.y) << 32);
-      k1 = (unsigned long long)__float_as_uint(h.z) | ((unsigned long long)__float_as_uint(h.w) << 32);
-    }
-  }
-  const bool in1 = (k1 == cur.key);
-  const bool hit = (cur.key != EMPTY_KEY) && (k0 == cur.key || in1);
-#endif
   // A wavefront trip in which no lane has a correspondence skips the record gather and the algebra (its lanes would add exact zeros, so the
   // sums are bit-identical).  In Hilbert order misses come in runs: 17 % of the trips of the 256-submap all-pairs cost (inlier fraction
   // 0.69) have no hit at all; 13.9 -> 12.2 ms for that evaluation (BENCH_r02 `staged`).  General (36 B/pt) kernel only: under the
@@ -805,7 +732,7 @@ __device__ __forceinline__ Resolved resolve_probe(const FactorDesc& d, const Pro
   if (!PLANE) wave_skips += any_hit ? 0 : 1;         // (scalar) trips that skip the record gather and the algebra: reported per run, glim_amd_factor_set_trip_stats
   // every lane reads a record (way 0 of the last bucket when there is no hit) so the wavefront does not diverge
   // (plane view: a lane without a correspondence reads the all-zero record of the extra bucket behind the table, so its M is exactly 0)
-  const unsigned int rec_off = (PLANE && GLIM_AMD_PLANE_SM) ? (hit ? b * 128u + (in1 ? 64u : 16u) : d.num_buckets * 128u + 16u) : b * 128u + (in1 ? 64u : 16u);
+  const unsigned int rec_off = PLANE ? (hit ? b * 128u + (in1 ? 64u : 16u) : d.num_buckets * 128u + 16u) : b * 128u + (in1 ? 64u : 16u);
   const char* rp = reinterpret_cast<const char*>(d.buckets) + rec_off;
   float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
   float r2 = 0.f;
@@ -864,11 +791,11 @@ __device__ __forceinline__ void rotate_priority(int step) {
 // One (factor, chunk) row of a plan, computed by the 256 threads of a block: its lanes walk the factor's points in 256-point hands dealt
 // round robin to the factor's blocks, through the two-trip software pipeline of pipe_trip, with the wave priority rotated every trip; every lane
 // runs the algebra (a lane without a match contributes exact zeros) and the only branch on the hot path is the rare bucket spill.  On return
-// (after a block barrier) s_red[w] holds wavefront w's sums -- as its four 16-lane row sums (GLIM_AMD_ROW_SUMS_LDS; wave_value adds them) -- of
+// (after a block barrier) s_red[w] holds wavefront w's sums -- as its four 16-lane row sums (RED_ROWS; wave_value adds them) -- of
 // accumulator j, [28] its inlier count.
 // first, second: the stream data of this lane's first and second point when the caller has loaded them already (a resident worker does, while it
 // waits for its pose: with one wavefront per SIMD nothing else covers a load issued behind the pose).  With both, a row of exactly two points per
-// lane -- the single chip-wide factor -- leaves the pipeline for a flat schedule (GLIM_AMD_RES_FLAT2 below); the launch-per-call kernels pass
+// lane -- the single chip-wide factor -- leaves the pipeline for a flat schedule (below; profiles/r12/probe/worker_tail_ab.json); the launch-per-call kernels pass
 // neither and compile to the loop alone.
 // cull (CULL only): this block's four pre-cull words (cull_kernel), one per wavefront: bit t set = trip t of that wavefront has no point or cannot
 // find a correspondence.  The wavefront then walks its LIVE trips only, through the same two-trip pipeline: a culled trip costs nothing at all --
@@ -926,7 +853,7 @@ __device__ __forceinline__ void compute_row(const FactorDesc& d, const double* _
         t2 = pop(live);
       }
     } else {
-    if (GLIM_AMD_RES_FLAT2 && first && second && ppt == 2) {
+    if (first && second && ppt == 2) {
       // flat schedule of a resident worker's two points (wave-uniform branch): both key gathers in flight before the first is resolved, both
       // record gathers before the first algebra -- two dependent gathers in front of the sums instead of the pipeline's three (key 0 -> record 0
       // beside key 1 -> record 1), and the FP64 transform of point 1 between key gather 0 and its wait.  Point 0 is added to every accumulator
@@ -953,7 +880,6 @@ __device__ __forceinline__ void compute_row(const FactorDesc& d, const double* _
   if (loop_done_stamp && threadIdx.x == 0) *loop_done_stamp = __builtin_amdgcn_s_memrealtime();  // (device timeline of a resident session: the algebra of the last point is issued)
   // ---- block reduction: DPP wave sums -> LDS ----
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#if GLIM_AMD_ROW_SUMS_LDS
   // every 16-lane row of the wavefront leaves ITS sum (lanes 15 / 31 / 47 / 63); row_value adds the four as the row_bcast steps did.  Values that
   // exist once per wavefront (error-only sum, inlier count, skipped trips) go to row 3, zeros to the others: (v + 0) + (0 + 0) is v.
   const bool row_end = (lane & 15) == 15;
@@ -972,40 +898,12 @@ __device__ __forceinline__ void compute_row(const FactorDesc& d, const double* _
     s_red[wave][rrow][28] = rrow == 3 ? (float)wave_inliers : 0.f;  // <= 64 * ppt: exact in FP32
     s_red[wave][rrow][29] = rrow == 3 ? (float)wave_skips : 0.f;    // <= ppt
   }
-#else
-  if (MODE == MODE_LINEARIZE) {
-#if GLIM_AMD_STEP_MAJOR_SUMS
-    wave_sums_to_lane63<NACC>(acc);  // (step-major: device_math.hpp)
-    if (lane == 63) {
-#pragma unroll
-      for (int j = 0; j < NACC; j++) s_red[wave][0][j] = acc[j];
-    }
-#else
-#pragma unroll
-    for (int j = 0; j < NACC; j++) {
-      const float v = wave_sum_to_lane63(acc[j]);
-      if (lane == 63) s_red[wave][0][j] = v;
-    }
-#endif
-  } else {
-    const float v = wave_sum_to_lane63(acc[27]);
-    if (lane == 63) s_red[wave][0][27] = v;
-  }
-  {
-    if (lane == 63) s_red[wave][0][28] = (float)wave_inliers;  // <= 64 * ppt: exact in FP32
-    if (lane == 63) s_red[wave][0][29] = (float)wave_skips;    // <= ppt
-  }
-#endif
   __syncthreads();
 }
 
 // value j of the block's partial row from the four wavefront sums (the same expression wherever a row is published: same bits)
 __device__ __forceinline__ float wave_value(const RedRow* s_red, int w, int j) {
-#if GLIM_AMD_ROW_SUMS_LDS
   return (s_red[w][3][j] + s_red[w][2][j]) + (s_red[w][1][j] + s_red[w][0][j]);  // lane 63 after row_bcast:15 and row_bcast:31
-#else
-  return s_red[w][0][j];
-#endif
 }
 template <int MODE>
 __device__ __forceinline__ float row_value(const RedRow* s_red, int j) {
@@ -1014,14 +912,10 @@ __device__ __forceinline__ float row_value(const RedRow* s_red, int j) {
 }
 
 // tagged granules (see TAG_PIECES): granule p = values 3p .. 3p + 2 and the call's tag, ONE write-through 16-byte store each.
-// GLIM_AMD_ROW_LANES (default): lane 4p + v of wavefront 0 forms ONE value, 3p + v -- its 16 LDS reads are independent and go out before the first
-// wait --, two quad_perm moves bring the values of lanes 4p + 1 and 4p + 2 into lane 4p, and lane 4p stores the granule.  The row index is made
-// wave-uniform explicitly, so that the buffer descriptor is scalar and the store needs no loop over distinct descriptors.  Same expression per
-// value (row_value), same granule, same store: same bits.
-// 0: thread p < 10 forms the three values of its granule one after the other (48 LDS reads per lane, the last value's as eight dependent round trips).
-#ifndef GLIM_AMD_ROW_LANES
-#define GLIM_AMD_ROW_LANES 1
-#endif
+// Lane 4p + v of wavefront 0 forms ONE value, 3p + v -- its 16 LDS reads are independent and go out before the first wait --, two quad_perm
+// moves bring the values of lanes 4p + 1 and 4p + 2 into lane 4p, and lane 4p stores the granule.  The row index is made wave-uniform
+// explicitly, so that the buffer descriptor is scalar and the store needs no loop over distinct descriptors.  Same expression per value
+// (row_value), same granule, same store: same bits (profiles/r12/probe/worker_tail_ab.json).
 // row_value for a lane-dependent j < PARTIAL_STRIDE with every LDS read issued before the first addition: the same expression, the same bits.
 // (Left to itself the compiler reads two sums, waits, adds, reads the next two: eight dependent LDS round trips on a path the caller waits for.)
 template <int MODE>
@@ -1037,19 +931,12 @@ __device__ __forceinline__ float row_value_batched(const RedRow* s_red, int j) {
     for (int r = 0; r < RED_ROWS; r++) asm volatile("" : "+v"(x[w][r]));  // all of them exist here: the reads are out, the sums follow
   float wv[4];
 #pragma unroll
-  for (int w = 0; w < 4; w++) {
-#if GLIM_AMD_ROW_SUMS_LDS
-    wv[w] = (x[w][3] + x[w][2]) + (x[w][1] + x[w][0]);  // wave_value
-#else
-    wv[w] = x[w][0];
-#endif
-  }
+  for (int w = 0; w < 4; w++) wv[w] = (x[w][3] + x[w][2]) + (x[w][1] + x[w][0]);  // wave_value
   const bool live = (MODE == MODE_LINEARIZE) ? (j <= 29) : (j >= 27 && j <= 29);  // row_value
   return live ? (wv[0] + wv[1]) + (wv[2] + wv[3]) : 0.f;
 }
 template <int MODE>
 __device__ __forceinline__ void publish_row_tagged(const RedRow* s_red, char* rows16, size_t row, unsigned int tag) {
-#if GLIM_AMD_ROW_LANES
   int t = (int)threadIdx.x;
   asm volatile("" : "+v"(t));  // the lane's constants below are formed HERE, three instructions, not kept in registers around a resident session's loop
   if (t < 4 * TAG_PIECES) {  // (lanes 0..39 of wavefront 0: whole quads, so every quad_perm source lane is active)
@@ -1065,15 +952,6 @@ __device__ __forceinline__ void publish_row_tagged(const RedRow* s_red, char* ro
       __builtin_amdgcn_raw_buffer_store_b128(piece, rsrc, p * 16, 0, AUX_SC1);
     }
   }
-#else
-  if (threadIdx.x < TAG_PIECES) {
-    const int j = 3 * (int)threadIdx.x;
-    const v4i_t piece = {__float_as_int(row_value<MODE>(s_red, j)), __float_as_int(row_value<MODE>(s_red, j + 1)), __float_as_int(row_value<MODE>(s_red, j + 2)),
-                         (int)tag};
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(rows16 + row * TAG_ROW_BYTES, 0, TAG_ROW_BYTES, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(piece, rsrc, (int)threadIdx.x * 16, 0, AUX_SC1);
-  }
-#endif
 }
 
 // The fused factor kernel.  MODE: linearise (28 sums) or error only.  FROZEN: residual at a separate evaluation pose with correspondences
@@ -1502,18 +1380,14 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       // everything that does not depend on the pose is fetched BEFORE the wait: the descriptor and this lane's first two points
       const FactorDesc d = ra.descs[bm.x];
       PointIn p0;
-#if GLIM_AMD_RES_FLAT2
       PointIn p1;  // ... and its second (compute_row's own clamp: a lane without one loads the factor's last point and does not use it)
-#endif
       {
         const unsigned int i0 = (unsigned int)min(bm.y * BLOCK + (int)threadIdx.x, max(d.n - 1, 0));
         if (PLANE_ONLY || d.plane) p0 = load_point<true>(d, i0);
         else p0 = load_point<false>(d, i0);
-#if GLIM_AMD_RES_FLAT2
         const unsigned int i1 = (unsigned int)max(min(bm.y * BLOCK + (int)threadIdx.x + d.num_blocks * BLOCK, d.n - 1), 0);
         if (PLANE_ONLY || d.plane) p1 = load_point<true>(d, i1);
         else p1 = load_point<false>(d, i1);
-#endif
       }
       if (bm.x != have) {
         wait_pose(ra, bm.x, last, tag, s_pose, &s_tag);
@@ -1531,13 +1405,9 @@ __global__ __launch_bounds__(BLOCK, PLANE_ONLY ? GLIM_AMD_RES_MINW : 3) void res
       }
       unsigned long long* const tlw = (ra.timeline && r == first_row) ? ra.timeline + TL_WORKER0 + 4 * b : nullptr;
       tl_stamp(tlw, 0);
-#if GLIM_AMD_RES_FLAT2
-      const PointIn* const second = &p1;
-#else
-      const PointIn* const second = nullptr;
-#endif
-      if (PLANE_ONLY || d.plane) compute_row<MODE_LINEARIZE, false, true, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, second);
-      else compute_row<MODE_LINEARIZE, false, false, false, GLIM_AMD_RES_TAILSKIP != 0>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, second);
+      // (TAILSKIP: the probe of a point no lane has is skipped, pipe_trip_at)
+      if (PLANE_ONLY || d.plane) compute_row<MODE_LINEARIZE, false, true, false, true>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, &p1);
+      else compute_row<MODE_LINEARIZE, false, false, false, true>(d, Tl, Tl, bm.y, r / ra.blocks_per_round, s_red, &p0, nullptr, tlw ? tlw + 3 : nullptr, &p1);
       tl_stamp(tlw, 1);
       publish_row_tagged<MODE_LINEARIZE>(s_red, ra.rows16, (size_t)(d.first_block + bm.y), tag);
       tl_stamp(tlw, 2);
@@ -1678,85 +1548,6 @@ __global__ __launch_bounds__(BLOCK) void correspondence_kernel(FactorDesc d, con
   corr[4 * (size_t)i + 3] = hit ? 1 : -1;
 }
 
-struct OverlapTarget {
-  const VoxelBucket* buckets;
-  unsigned int num_buckets;
-  int pad;
-  double inv_res;
-  double T[12];
-};
-// One overlap query = one source cloud against a list of (map, delta) targets (odometry_estimation_gpu.cpp:224-231, :248).
-struct OverlapQuery {
-  const float4* pts;
-  int n;
-  int first_target, num_targets;
-  int first_block, num_blocks;  // blocks [first_block, first_block + num_blocks) of the launch walk this query's points
-  int lanes_shift;              // 2^lanes_shift consecutive lanes share a point and split its targets (overlap_kernel)
-};
-constexpr int OVERLAP_INLINE_TARGETS = 16;
-struct OverlapInline {  // single-query call: everything in the kernel arguments, nothing to upload
-  OverlapQuery q;
-  OverlapTarget t[OVERLAP_INLINE_TARGETS];
-};
-
-// K6: a point counts once if ANY (map_j, delta_j) contains it.  One launch answers any number of queries; completion without a stream
-// synchronise or a read-back copy: every block adds (1 << 32 | its hits) to its query's 64-bit counter with ONE returning atomic, the block
-// that sees all the others' arrivals writes the query's total into host-mapped memory, resets the counter for the next call and -- when it
-// also completes the last query -- publishes the call's sequence number, on which the host spins.
-template <bool INLINE>
-__global__ __launch_bounds__(BLOCK) void overlap_kernel(const OverlapInline in, const OverlapQuery* __restrict__ queries, const OverlapTarget* __restrict__ targets,
-                                                         const int* __restrict__ block_query, int num_queries, unsigned long long* __restrict__ counters,
-                                                         unsigned int* __restrict__ queries_done, unsigned int* __restrict__ h_hits,
-                                                         unsigned int* __restrict__ h_flag, unsigned int seq) {
-  __shared__ int s_tmp[16];
-  const int qi = INLINE ? 0 : block_query[blockIdx.x];
-  const OverlapQuery q = INLINE ? in.q : queries[qi];
-  const OverlapTarget* tg = INLINE ? in.t : targets + q.first_target;
-  // A point's targets are looked up by G = 2^lanes_shift CONSECUTIVE LANES at once (G = 16 for the odometry's 15-keyframe query) instead of one
-  // lane walking them one after the other: a lookup is a dependent chain of memory latencies (key line, perhaps a spill), and fifteen of them in
-  // sequence made the 15-target call of a 10 000-pt frame a 30 us kernel -- latency, not work.  Lane l of a group takes targets l, l + G, ...; the
-  // group's verdict is a slice of the wavefront's ballot; the group's first lane counts the point.  Same count: "any target contains the point".
-  int mine = 0;
-  const int chunk = (int)blockIdx.x - q.first_block;
-  const int shift = q.lanes_shift, G = 1 << shift, sub_lane = (int)threadIdx.x & (G - 1);
-  const int lane = (int)threadIdx.x & 63, group_base = lane & ~(G - 1);
-  const unsigned long long group_mask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << group_base;
-  const long long items = (long long)q.n << shift;  // (point, lane-of-group) pairs
-  const int rounds = (q.num_targets + G - 1) >> shift;
-  for (long long base = (long long)chunk * BLOCK; base < items; base += (long long)q.num_blocks * BLOCK) {  // (block-uniform trip count: ballots stay whole)
-    const long long idx = base + (long long)threadIdx.x;
-    const bool live = idx < items;
-    const int i = live ? (int)(idx >> shift) : 0;
-    const float4 p4 = q.pts[i];
-    bool group_hit = false;
-    for (int r = 0; r < rounds; r++) {
-      const int t = (r << shift) + sub_lane;
-      bool hit = false;
-      if (live && !group_hit && t < q.num_targets) {
-        double qx, qy, qz;
-        transform_point_d(tg[t].T, (double)p4.x, (double)p4.y, (double)p4.z, qx, qy, qz);
-        hit = find_slot(tg[t].buckets, tg[t].num_buckets, voxel_key(qx, qy, qz, tg[t].inv_res)) >= 0;
-      }
-      group_hit = group_hit || (__ballot(hit) & group_mask) != 0ull;
-    }
-    if (live && group_hit && sub_lane == 0) mine++;
-  }
-  const int block_hits = block_reduce_i<2>(mine, s_tmp);
-  if (threadIdx.x == 0) {
-    const unsigned long long prev = atomicAdd(counters + qi, (1ull << 32) | (unsigned long long)(unsigned int)block_hits);
-    if ((int)(prev >> 32) == q.num_blocks - 1) {
-      counters[qi] = 0ull;  // every block of this query has arrived: nobody touches the counter again in this launch
-      h_hits[qi] = (unsigned int)prev + (unsigned int)block_hits;
-      __threadfence_system();
-      const unsigned int done = INLINE ? 0u : atomicAdd(queries_done, 1u);
-      if (INLINE || (int)done == num_queries - 1) {
-        if (!INLINE) *queries_done = 0u;
-        __hip_atomic_store(h_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
-}
-
 }  // namespace
 
 
@@ -1851,17 +1642,6 @@ void plan_free(FactorPlan* p) {
   plan_idle(p);
   plan_release_buffers(p);
   delete p;
-}
-
-template <class T>
-bool host_device_view(T* host, T** dev) {
-  *dev = nullptr;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(dev), host, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    *dev = nullptr;
-    return false;
-  }
-  return true;
 }
 
 }  // namespace
@@ -1974,7 +1754,7 @@ int plan_build(glim_amd_factor_set* set, FactorPlan* plan) {
     }
     d.buckets = e.target->buckets;
     d.num_buckets = e.target->num_buckets;
-    if (GLIM_AMD_PLANE_SM && d.plane) {
+    if (d.plane) {
       glim_amd_voxelmap* tm = const_cast<glim_amd_voxelmap*>(e.target);  // the lazily built view is a cache, not a change of the map
       GA_TRY(ensure_plane_view(tm, set->stream));
       d.buckets = tm->buckets_sm;
@@ -2354,14 +2134,6 @@ void launch_vgicp(glim_amd_factor_set* set, int mode, bool frozen, const Finaliz
   set->plan->last_stream = set->stream;
 }
 
-inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  asm volatile("yield" ::: "memory");
-#endif
-}
-
 bool use_single_dispatch(const glim_amd_factor_set* set, bool poll) {
   const FactorPlan* plan = set->plan;
   return poll && plan->d_rows16 && plan->h_rec16_dev && set->ctx->diag.fuse;
@@ -2491,19 +2263,6 @@ int upload_poses(glim_amd_factor_set* set, const double* T_lin, const double* T_
     if (up != set->stream) GA_HIP(hipStreamWaitEvent(set->stream, plan->pose_events[slot], 0));
   }
   return GLIM_AMD_OK;
-}
-
-// spin until *word == value (acquire); false after ~200 ms
-bool spin_until(const volatile unsigned int* word, unsigned int value) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned long spins = 0;; spins++) {
-    if (*word == value) {
-      std::atomic_thread_fence(std::memory_order_acquire);
-      return true;
-    }
-    cpu_relax();
-    if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
-  }
 }
 
 // ---- resident sessions (host side; kernel: resident_kernel) ------------------------------------------------------------------------------
@@ -3057,48 +2816,6 @@ int run_sync(glim_amd_factor_set* set, int mode, const double* T_lin, const doub
   return GLIM_AMD_OK;
 }
 
-int overlap_scratch(glim_amd_ctx* ctx, hipStream_t st) {
-  if (ctx->ov_counters) return GLIM_AMD_OK;
-  const size_t cbytes = (size_t)glim_amd_ctx::OV_MAX_QUERIES * sizeof(unsigned long long) + 64;
-  GA_HIP(pool_malloc(&ctx->ov_counters, cbytes));
-  GA_HIP(hipMemsetAsync(ctx->ov_counters, 0, cbytes, st));
-  if (ctx->ov_host) return GLIM_AMD_OK;  // (the counters alone are re-made after a failed call: overlap_discard_counters)
-  GA_HIP(pinned_malloc(&ctx->ov_host, (size_t)(1 + glim_amd_ctx::OV_MAX_QUERIES) * sizeof(unsigned int)));
-  memset(ctx->ov_host, 0, (size_t)(1 + glim_amd_ctx::OV_MAX_QUERIES) * sizeof(unsigned int));
-  if (!host_device_view(ctx->ov_host, &ctx->ov_host_dev)) return GLIM_AMD_ERR_HIP;
-  return GLIM_AMD_OK;
-}
-
-// After a failed overlap launch / wait the arrival counters may be left non-zero, which would poison the next call's counts: wait for whatever
-// did get enqueued and drop the block -- overlap_scratch hands the next call a freshly zeroed one.
-void overlap_discard_counters(glim_amd_ctx* ctx, hipStream_t st) {
-  (void)hipStreamSynchronize(st);
-  (void)hipGetLastError();
-  if (ctx->ov_counters) (void)pool_free(ctx->ov_counters);
-  ctx->ov_counters = nullptr;
-}
-
-void fill_overlap_target(OverlapTarget& o, const glim_amd_voxelmap* m, const double* T12) {
-  o.buckets = m->buckets;
-  o.num_buckets = m->num_buckets;
-  o.pad = 0;
-  o.inv_res = m->inv_resolution;
-  memcpy(o.T, T12, 12 * sizeof(double));
-}
-
-// blocks a query's points are spread over: one atomic per block ends the query, so few fat blocks (at most one per CU)
-// lanes that share a point: the smallest power of two >= the number of targets, at most 16 (more targets take further rounds)
-int overlap_lanes_shift(int num_targets) {
-  int s = 0;
-  while ((1 << s) < num_targets && s < 4) s++;
-  return s;
-}
-int overlap_blocks(const glim_amd_ctx* ctx, int64_t n, int lanes_shift) {
-  // two (point, lane) items per thread, at most two blocks per CU: one returning atomic per block ends the query
-  const int64_t items = n << lanes_shift;
-  return (int)std::max<int64_t>(1, std::min<int64_t>((items + 2 * BLOCK - 1) / (2 * BLOCK), 2 * std::max(1, ctx->num_cus)));
-}
-
 }  // namespace
 
 // ---- the batch of the VGICP fine registration (vgicp_batch.hpp) ------------------------------------------------------------------------
@@ -3377,123 +3094,6 @@ int glim_amd_factor_set_profile(glim_amd_factor_set* set, const double* T, int i
   return GLIM_AMD_OK;
 }
 
-// One launch, no allocation, no copy, no stream synchronise: descriptors in the kernel arguments (single query, <= 16 targets) or read by the
-// kernel from a pinned staging block (batches), results and the completion word in host-mapped memory.
-int glim_amd_overlap_batch(glim_amd_ctx* ctx, int32_t num_queries, const int32_t* num_targets, const glim_amd_voxelmap* const* targets,
-                           const double* T, const glim_amd_cloud* const* sources, double* overlaps) {
-  if (!ctx || num_queries <= 0 || !num_targets || !targets || !T || !sources || !overlaps) return GLIM_AMD_ERR_INVALID;
-  if (num_queries > glim_amd_ctx::OV_MAX_QUERIES) return GLIM_AMD_ERR_UNSUPPORTED;
-  int64_t total_targets = 0;
-  for (int q = 0; q < num_queries; q++) {
-    if (num_targets[q] <= 0 || !sources[q] || sources[q]->ctx->device != ctx->device) return GLIM_AMD_ERR_INVALID;
-    for (int t = 0; t < num_targets[q]; t++) {
-      const glim_amd_voxelmap* m = targets[total_targets + t];
-      if (!m || m->ctx->device != ctx->device) return GLIM_AMD_ERR_INVALID;
-      if (!m->buckets) return GLIM_AMD_ERR_STATE;
-    }
-    total_targets += num_targets[q];
-  }
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  GA_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream();
-  for (int64_t t = 0; t < total_targets; t++) GA_TRY(voxelmap_wait_ready(targets[t], st));  // (maps whose build the host has not seen complete)
-  GA_TRY(overlap_scratch(ctx, st));
-  // queries with an empty source are answered here (0.0) and take no part in the launch
-  std::vector<int> live;
-  for (int q = 0; q < num_queries; q++) {
-    overlaps[q] = 0.0;
-    if (sources[q]->n > 0) live.push_back(q);
-  }
-  if (live.empty()) return GLIM_AMD_OK;
-  const unsigned int seq = ++ctx->ov_seq;
-  std::vector<int64_t> first_target((size_t)num_queries);
-  {
-    int64_t acc = 0;
-    for (int q = 0; q < num_queries; q++) {
-      first_target[(size_t)q] = acc;
-      acc += num_targets[q];
-    }
-  }
-  const OverlapInline none{};
-  if (live.size() == 1 && num_targets[live[0]] <= OVERLAP_INLINE_TARGETS) {
-    const int q = live[0];
-    OverlapInline in{};
-    in.q.pts = sources[q]->pts;
-    in.q.n = (int)sources[q]->n;
-    in.q.first_target = 0;
-    in.q.num_targets = num_targets[q];
-    in.q.first_block = 0;
-    in.q.lanes_shift = overlap_lanes_shift(num_targets[q]);
-    in.q.num_blocks = overlap_blocks(ctx, sources[q]->n, in.q.lanes_shift);
-    for (int t = 0; t < num_targets[q]; t++) fill_overlap_target(in.t[t], targets[first_target[(size_t)q] + t], T + 12 * (first_target[(size_t)q] + t));
-    overlap_kernel<true><<<in.q.num_blocks, BLOCK, 0, st>>>(in, nullptr, nullptr, nullptr, 1, ctx->ov_counters, nullptr, ctx->ov_host_dev + 1, ctx->ov_host_dev, seq);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !spin_until(ctx->ov_host, seq)) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-      set_hip_error(e, "overlap");
-      overlap_discard_counters(ctx, st);
-      return GLIM_AMD_ERR_HIP;
-    }
-    overlaps[q] = (double)ctx->ov_host[1] / (double)sources[q]->n;
-    return GLIM_AMD_OK;
-  }
-  // batch: queries, targets and the block -> query table in one pinned block the kernel reads directly
-  int total_blocks = 0;
-  std::vector<OverlapQuery> hq(live.size());
-  int64_t live_targets = 0;
-  long long walking_blocks = 0;
-  for (const int q : live) walking_blocks += overlap_blocks(ctx, sources[q]->n, 0);
-  const bool batch_fills_device = walking_blocks >= (long long)std::max(1, ctx->num_cus);
-  for (size_t i = 0; i < live.size(); i++) {
-    const int q = live[i];
-    hq[i].pts = sources[q]->pts;
-    hq[i].n = (int)sources[q]->n;
-    hq[i].first_target = (int)live_targets;
-    hq[i].num_targets = num_targets[q];
-    hq[i].first_block = total_blocks;
-    // Spreading a point's targets over lanes trades work for latency: every target is looked up, where one lane walking them stops at the first
-    // hit (keyframes overlap: two or three lookups per point on average).  A batch that fills the chip by itself (the 43-query keyframe elimination
-    // loop: 860 blocks) is bound by that work, not by one query's latency -- 55-59 us walking, 92 us spread -- so only batches too small to fill
-    // the device spread.
-    hq[i].lanes_shift = batch_fills_device ? 0 : overlap_lanes_shift(num_targets[q]);
-    hq[i].num_blocks = overlap_blocks(ctx, sources[q]->n, hq[i].lanes_shift);
-    total_blocks += hq[i].num_blocks;
-    live_targets += num_targets[q];
-  }
-  const size_t qbytes = hq.size() * sizeof(OverlapQuery), tbytes = (size_t)live_targets * sizeof(OverlapTarget), bbytes = (size_t)total_blocks * sizeof(int);
-  char* stage = nullptr;
-  GA_HIP(pinned_malloc(&stage, qbytes + tbytes + bbytes));
-  char* stage_dev = nullptr;
-  if (!host_device_view(stage, &stage_dev)) {
-    (void)pinned_free(stage);
-    return GLIM_AMD_ERR_HIP;
-  }
-  memcpy(stage, hq.data(), qbytes);
-  OverlapTarget* ht = reinterpret_cast<OverlapTarget*>(stage + qbytes);
-  int* hb = reinterpret_cast<int*>(stage + qbytes + tbytes);
-  for (size_t i = 0; i < live.size(); i++) {
-    const int q = live[i];
-    for (int t = 0; t < num_targets[q]; t++)
-      fill_overlap_target(ht[hq[i].first_target + t], targets[first_target[(size_t)q] + t], T + 12 * (first_target[(size_t)q] + t));
-    for (int b = 0; b < hq[i].num_blocks; b++) hb[hq[i].first_block + b] = (int)i;
-  }
-  unsigned int* queries_done = reinterpret_cast<unsigned int*>(ctx->ov_counters + glim_amd_ctx::OV_MAX_QUERIES);
-  overlap_kernel<false><<<total_blocks, BLOCK, 0, st>>>(none, reinterpret_cast<const OverlapQuery*>(stage_dev), reinterpret_cast<const OverlapTarget*>(stage_dev + qbytes),
-                                                        reinterpret_cast<const int*>(stage_dev + qbytes + tbytes), (int)live.size(), ctx->ov_counters, queries_done,
-                                                        ctx->ov_host_dev + 1, ctx->ov_host_dev, seq);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && !spin_until(ctx->ov_host, seq)) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    set_hip_error(e, "overlap_batch");
-    overlap_discard_counters(ctx, st);  // (waits for the stream: the kernel reads `stage` directly)
-    (void)pinned_free(stage);
-    return GLIM_AMD_ERR_HIP;
-  }
-  (void)pinned_free(stage);
-  for (size_t i = 0; i < live.size(); i++) overlaps[live[i]] = (double)ctx->ov_host[1 + i] / (double)sources[live[i]]->n;
-  return GLIM_AMD_OK;
-}
-
 int glim_amd_factor_set_profile_fresh(glim_amd_ctx* ctx, int32_t n, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
                                       const uint32_t* flags, const double* T, int iters, float* us_per_iteration) {
   if (!ctx || n <= 0 || !targets || !sources || !T || iters <= 0 || !us_per_iteration) return GLIM_AMD_ERR_INVALID;
@@ -3577,24 +3177,6 @@ int glim_amd_factor_set_profile_fresh_samples(glim_amd_ctx* ctx, int32_t n, cons
     while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count() < gap_us) cpu_relax();  // the optimiser's host work
   }
   return GLIM_AMD_OK;
-}
-
-int glim_amd_overlap_profile(glim_amd_ctx* ctx, int32_t num_queries, const int32_t* num_targets, const glim_amd_voxelmap* const* targets, const double* T,
-                             const glim_amd_cloud* const* sources, int iters, float* us_per_call) {
-  if (!ctx || num_queries <= 0 || iters <= 0 || !us_per_call) return GLIM_AMD_ERR_INVALID;
-  std::vector<double> ov((size_t)num_queries);
-  for (int i = 0; i < 5; i++) GA_TRY(glim_amd_overlap_batch(ctx, num_queries, num_targets, targets, T, sources, ov.data()));
-  const auto t0 = std::chrono::steady_clock::now();
-  for (int i = 0; i < iters; i++) GA_TRY(glim_amd_overlap_batch(ctx, num_queries, num_targets, targets, T, sources, ov.data()));
-  const auto t1 = std::chrono::steady_clock::now();
-  *us_per_call = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
-  return GLIM_AMD_OK;
-}
-
-int glim_amd_overlap(glim_amd_ctx* ctx, int32_t num_targets, const glim_amd_voxelmap* const* targets, const double* T,
-                     const glim_amd_cloud* source, double* overlap) {
-  if (!source || !overlap) return GLIM_AMD_ERR_INVALID;
-  return glim_amd_overlap_batch(ctx, 1, &num_targets, targets, T, &source, overlap);
 }
 
 }  // extern "C"

@@ -1138,7 +1138,7 @@ int glim_amd_voxelmap_insert(glim_amd_voxelmap* m, const glim_amd_cloud* cloud) 
   if (h_stats[1] != 0) return GLIM_AMD_ERR_RANGE;  // (the map is unchanged)
 
   const int num_voxels = h_stats[0];
-  // buckets per voxel (default 6: x-adjacent voxel pairs share a bucket -- device_math.hpp GLIM_AMD_PAIR_SHIFT -- so about 0.1 pairs per
+  // buckets per voxel (default 6: x-adjacent voxel pairs share a bucket -- device_math.hpp PAIR_SHIFT -- so about 0.1 pairs per
   // bucket, and a pair finds its home bucket taken by another pair about 1 % of the time)
   // The table is addressed with 32-bit byte offsets (<= 2^25 buckets = 4 GiB): beyond 5.6 M voxels the factor drops step by step to 2
   // (16.7 M voxels) before the insert is refused -- a sparser table is a speed choice, never a correctness one.

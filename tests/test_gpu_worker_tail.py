@@ -1,4 +1,4 @@
-"""The worker tail of a resident session (vgicp.hip publish_row_tagged with GLIM_AMD_ROW_LANES, compute_row with GLIM_AMD_RES_FLAT2).
+"""The worker tail of a resident session (vgicp.hip publish_row_tagged, one value per lane, and the flat two-point schedule of compute_row).
 
 A row is published one value per lane (lane 4p + v of wavefront 0 forms value 3p + v, two quad_perm moves collect a granule in lane 4p), and a
 resident worker loads the stream data of both points of a lane before the pose arrives and runs a row of exactly two points per lane through a flat
