@@ -212,6 +212,7 @@ class CtAlignTraceEntry(C.Structure):
 
 
 BUNDLE_MAX_POSES, BUNDLE_MAX_FACTORS, BUNDLE_MAX_TERMS = 32, 1024, 1024  # GLIM_AMD_BUNDLE_MAX_* (include/glim_amd.h)
+GRAPH_MAX_POSES, GRAPH_MAX_FACTORS, GRAPH_MAX_TERMS = 256, 32768, 1024  # GLIM_AMD_GRAPH_MAX_* (the global-graph optimisation)
 
 
 class BundlePrior(C.Structure):
@@ -460,6 +461,13 @@ SYMBOLS = {
     "glim_amd_debug_bundle_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
                                                C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
                                                C.POINTER(BundleTraceRound)]),
+    "glim_amd_graph_align_default_params": (_i, [C.POINTER(LMParams)]),
+    "glim_amd_graph_align": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                  C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult)]),
+    "glim_amd_debug_graph_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                              C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
+                                              C.POINTER(BundleTraceRound), _i32]),
+    "glim_amd_debug_graph_solve": (_i, [_vp, _dp, _i32, C.c_double, _dp, C.POINTER(_i32)]),
     "glim_amd_ba_default_params": (_i, [C.POINTER(BaParams)]),
     "glim_amd_ba_ball_select": (_i, [_pp, _i32, _dp, _dp, _d, _i64, _ip, _lp]),
     "glim_amd_ba_ball_stats": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaStats)]),

@@ -861,21 +861,29 @@ class NonlinearFactorSetGPU:
         self.last_error_inliers = inl
         return list(err)
 
+    def _optimize(self, align, name, values, priors, betweens, params):
+        if any(not f.is_binary for f in self.factors):
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU." + name, "a unary factor: the bundle is over binary factors")
+        validation = {f.enable_surface_validation for f in self.factors}
+        if len(validation) > 1:
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU." + name, "surface validation on some factors only")
+        keys = sorted(values)
+        at = {k: i for i, k in enumerate(keys)}
+        res = align([(f.target_voxelmap, f.source, at[f.target_key], at[f.source_key]) for f in self.factors],
+                    [(at[k], P, info) for k, P, info in priors], [(at[i], at[j], D, info) for i, j, D, info in betweens],
+                    [values[k] for k in keys], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx)
+        return {k: res.poses[i] for i, k in enumerate(keys)}, res
+
     def optimize(self, values, priors=(), betweens=(), params=None):
         """The sub-map bundle optimisation over this set's factors, which must all be binary (bundle_align; the loop of sub_mapping.cpp:430-452
         with its PriorFactor and BetweenFactor terms).  values: {key: 4 x 4}; priors: (key, P 4 x 4, information 6 x 6); betweens: (key_i, key_j,
         D 4 x 4, information 6 x 6).  The poses are ordered by sorted key.  Returns ({key: 4 x 4}, BundleResult).  The set itself is untouched."""
-        if any(not f.is_binary for f in self.factors):
-            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize", "a unary factor: the bundle is over binary factors")
-        validation = {f.enable_surface_validation for f in self.factors}
-        if len(validation) > 1:
-            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize", "surface validation on some factors only")
-        keys = sorted(values)
-        at = {k: i for i, k in enumerate(keys)}
-        res = bundle_align([(f.target_voxelmap, f.source, at[f.target_key], at[f.source_key]) for f in self.factors],
-                           [(at[k], P, info) for k, P, info in priors], [(at[i], at[j], D, info) for i, j, D, info in betweens],
-                           [values[k] for k in keys], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx)
-        return {k: res.poses[i] for i, k in enumerate(keys)}, res
+        return self._optimize(bundle_align, "optimize", values, priors, betweens, params)
+
+    def optimize_graph(self, values, priors=(), betweens=(), params=None):
+        """optimize() through the global-graph optimisation (graph_align; global_mapping.cpp:430-484): the same arguments and returns, up to
+        _lib.GRAPH_MAX_POSES poses and _lib.GRAPH_MAX_FACTORS factors."""
+        return self._optimize(graph_align, "optimize_graph", values, priors, betweens, params)
 
     def correspondences(self, index, delta):
         n = self.factors[index].source.size()
@@ -1708,26 +1716,18 @@ def _bundle_args(factors, priors, betweens, X_init, ctx):
     return ctx, (ctx._h, th, sh, _ip(ti), _ip(si), F), (cp, P, cb, Q, _dp(X), N), (ti, si, X)
 
 
-def bundle_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
-    """The sub-map bundle optimisation in one call and one host synchronisation: Levenberg-Marquardt over len(X_init) poses on binary VGICP
-    factors, prior and between terms (sub_mapping.cpp:183-216, 430-452).  factors: (GaussianVoxelMapGPU, PointCloudGPU, target pose index,
-    source pose index), evaluated at X_t^-1 X_s; priors: (pose index, P 4 x 4, information 6 x 6); betweens: (i, j, D 4 x 4, information 6 x 6);
-    flags: 0 or FACTOR_SURFACE_VALIDATION.  Every trial record is what a NonlinearFactorSetGPU of the same pairs returns at the trial's relative
-    poses.  Returns a BundleResult."""
+def _align_poses(entry, factors, priors, betweens, X_init, flags, params, ctx):
+    """glim_amd_bundle_align or glim_amd_graph_align: the same arguments and results"""
     ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
     F, N = fa[-1], ta[-1]
     prm = (params or bundle_align_params())._c()
     X_out, compact, out = np.zeros((N, 12)), np.zeros((F, _lib.COMPACT_DOUBLES)), _lib.BundleResult()
-    check(lib().glim_amd_bundle_align(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out)), "glim_amd_bundle_align")
+    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out)), entry)
     return BundleResult(out, _poses44(X_out), compact)
 
 
-def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True):
-    """Test window (glim_amd_debug_bundle_align_trace): bundle_align's result plus one dict per round run -- round 0 is the initial poses -- with
-    the candidate poses (`X`, N x 4 x 4), the relative poses as the device computed them (`Tf`, F x 12), the `compact` records there (F x 29), the
-    `lam` the step was solved with, the `cost` the evaluation gave, `accepted` and the `status` after the round.  one_thread: the decide step is
-    bundle_lm_step.hpp's step() in one device thread (the cross-check form).  trace=False: the result alone.  Returns (result, rows, the raw
-    trace arrays of all 1 + max_trials rounds: X, Tf, compact, rounds)."""
+def _align_poses_trace(entry, more, factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace):
+    """glim_amd_debug_bundle_align_trace or glim_amd_debug_graph_align_trace (`more`: the arguments behind the trace arrays)"""
     params = params or bundle_align_params()
     ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
     F, N = fa[-1], ta[-1]
@@ -1737,8 +1737,7 @@ def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=
     tX, tTf, trec = np.zeros((rounds, N, 12)), np.zeros((rounds, F, 12)), np.zeros((rounds, F, _lib.COMPACT_DOUBLES))
     tr = (_lib.BundleTraceRound * rounds)()
     targs = (_dp(tX), _dp(tTf), _dp(trec), tr) if trace else (None, None, None, None)
-    check(lib().glim_amd_debug_bundle_align_trace(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), 1 if one_thread else 0, *targs),
-          "glim_amd_debug_bundle_align_trace")
+    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), 1 if one_thread else 0, *targs, *more), entry)
     res = BundleResult(out, _poses44(X_out), compact)
     rows = []
     if trace and N:
@@ -1746,6 +1745,54 @@ def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=
             rows.append({"X": _poses44(tX[k]), "Tf": tTf[k].copy(), "compact": trec[k].copy(), "lam": tr[k].lam, "cost": tr[k].cost,
                          "accepted": bool(tr[k].accepted), "status": tr[k].status})
     return res, rows, (tX, tTf, trec, tr)
+
+
+def bundle_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
+    """The sub-map bundle optimisation in one call and one host synchronisation: Levenberg-Marquardt over len(X_init) poses on binary VGICP
+    factors, prior and between terms (sub_mapping.cpp:183-216, 430-452).  factors: (GaussianVoxelMapGPU, PointCloudGPU, target pose index,
+    source pose index), evaluated at X_t^-1 X_s; priors: (pose index, P 4 x 4, information 6 x 6); betweens: (i, j, D 4 x 4, information 6 x 6);
+    flags: 0 or FACTOR_SURFACE_VALIDATION.  Every trial record is what a NonlinearFactorSetGPU of the same pairs returns at the trial's relative
+    poses.  Returns a BundleResult."""
+    return _align_poses("glim_amd_bundle_align", factors, priors, betweens, X_init, flags, params, ctx)
+
+
+def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True):
+    """Test window (glim_amd_debug_bundle_align_trace): bundle_align's result plus one dict per round run -- round 0 is the initial poses -- with
+    the candidate poses (`X`, N x 4 x 4), the relative poses as the device computed them (`Tf`, F x 12), the `compact` records there (F x 29), the
+    `lam` the step was solved with, the `cost` the evaluation gave, `accepted` and the `status` after the round.  one_thread: the decide step is
+    bundle_lm_step.hpp's step() in one device thread (the cross-check form).  trace=False: the result alone.  Returns (result, rows, the raw
+    trace arrays of all 1 + max_trials rounds: X, Tf, compact, rounds)."""
+    return _align_poses_trace("glim_amd_debug_bundle_align_trace", (), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace)
+
+
+def graph_align_params(**kw):
+    """LMParams with the global-graph optimisation's values (glim_amd_graph_align_default_params): the bundle's."""
+    return bundle_align_params(**kw)
+
+
+def graph_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
+    """The global-graph optimisation (glim_amd_graph_align; global_mapping.cpp:430-484 and that file's between factors): bundle_align's
+    arguments, rule and BundleResult at up to _lib.GRAPH_MAX_POSES poses and _lib.GRAPH_MAX_FACTORS factors.  The systems live in device
+    memory and a round is a sequence of launches; within the bundle's caps the result is bundle_align's, bit for bit."""
+    return _align_poses("glim_amd_graph_align", factors, priors, betweens, X_init, flags, params, ctx)
+
+
+def graph_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True, rounds_per_chunk=0):
+    """Test window (glim_amd_debug_graph_align_trace): bundle_align_debug_trace's returns for graph_align.  one_thread: every round is
+    bundle_lm_step.hpp's step() in one device thread with its system in device memory (the cross-check form; seconds beyond a few dozen poses).
+    rounds_per_chunk: rounds enqueued between two looks at the status (0: the default); it moves no bit."""
+    return _align_poses_trace("glim_amd_debug_graph_align_trace", (int(rounds_per_chunk),), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace)
+
+
+def graph_solve_debug(S, n, lam, ctx=None):
+    """Test window (glim_amd_debug_graph_solve): the device's blocked solve of (H + lam I) delta = -b on a packed system S (the lower triangle of
+    H by rows, then b).  Returns (ok, delta)."""
+    ctx = ctx or default_context()
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    assert S.size == n * (n + 1) // 2 + n
+    delta, ok = np.full(n, np.nan), C.c_int32(-1)
+    check(lib().glim_amd_debug_graph_solve(ctx._h, _dp(S), int(n), float(lam), _dp(delta), C.byref(ok)), "glim_amd_debug_graph_solve")
+    return bool(ok.value), delta
 
 
 def ct_align_params(**kw):

@@ -35,6 +35,11 @@
 // decide kernel: one workgroup that expands the records, assembles the dense 6N x 6N system, factorises it in LDS, retracts the poses and
 // writes the next round's relative poses, every value by the item functions of bundle_lm_step.hpp.
 //
+// The global-graph optimisation (include/glim_amd.h "Global-graph optimisation") is the bundle at up to 256 poses: the same host scaffold, the
+// same factors' round and the same item functions, but the systems live in device memory and the decide step is a sequence of launches
+// (graph_round below; the blocked solve's launches are graph_align.hip's, graph_solve.hpp).  Its rounds are enqueued a few at a time, as the
+// ICP loop's are.
+//
 // The scan-to-keyframes VGICP registration (include/glim_amd.h "Scan-to-keyframes VGICP registration") is the same scheme over ONE pose per
 // problem and M unary VGICP factors with fixed target poses: a round is vgicp_batch_round over the F factors of all problems at T_f = P_f^-1 X,
 // each behind a status word of its own, and the keyframe decide kernel: one wavefront per problem that sums the problem's M records in
@@ -52,6 +57,7 @@
 #include "ct_lm_step.hpp"
 #include "device_math.hpp"
 #include "gicp_factor.hpp"
+#include "graph_solve.hpp"
 #include "icp_factor.hpp"
 #include "internal.hpp"
 #include "ivox_map.hpp"
@@ -569,6 +575,233 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(const bun
   }
 }
 
+// ---- the global-graph optimisation ----
+// bundle_lm::step once more, at up to GLIM_AMD_GRAPH_MAX_POSES poses: the same item functions, one owner per item, but as a sequence of ordinary
+// launches with the systems in device memory.  A kernel boundary on the one stream is the only ordering; what a later kernel of the round has to
+// know of an earlier one's outcome (the decision, a non-finite value, a failed pivot) it reads in device memory: the problem's Scalars and
+// GraphWords.  The solve's matrix is graph_solve.hpp's and its launches are graph_align.hip's.
+static_assert(GLIM_AMD_GRAPH_MAX_POSES * 6 == graph_solve::MAX_DIM, "the caps");
+static_assert(GLIM_AMD_GRAPH_MAX_FACTORS >= GLIM_AMD_GRAPH_MAX_POSES * (GLIM_AMD_GRAPH_MAX_POSES - 1) / 2, "every pair of the poses");
+constexpr int GRAPH_THREADS = 256;
+constexpr int GRAPH_SUM_CHUNK = 512;
+constexpr int GRAPH_ROUNDS_PER_CHUNK = 4;
+
+struct GraphWords {
+  double lambda_before;  // of the round: what its trace entry reports
+  int bad_in;            // a record, a candidate or an assembled entry of the round is not finite
+  int bad_out;           // a next candidate is not finite
+  int keep;              // the round's decision: the candidate is kept
+  int fail;              // the round's solve met a pivot that is not > 0
+};
+
+struct GraphScratch {
+  double* E;  // system_doubles(n): the evaluated system, packed as the rule has it (Problem::W)
+  double* M;  // graph_solve::matrix_doubles(n): the solve's matrix, column-major
+  GraphWords* words;
+};
+size_t graph_scratch_doubles(int n) { return (size_t)bundle_lm::system_doubles(n) + graph_solve::matrix_doubles(n) + sizeof(GraphWords) / sizeof(double); }
+GraphScratch graph_scratch_at(double* d, int n) {
+  GraphScratch g;
+  g.E = d;
+  g.M = g.E + bundle_lm::system_doubles(n);
+  g.words = reinterpret_cast<GraphWords*>(g.M + graph_solve::matrix_doubles(n));
+  return g;
+}
+static_assert(sizeof(GraphWords) % sizeof(double) == 0, "the words follow the matrix");
+
+__device__ __forceinline__ int graph_thread() { return (int)((blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x); }
+__device__ __forceinline__ int graph_threads() { return (int)(gridDim.y * gridDim.x * blockDim.x); }
+
+__device__ __forceinline__ void graph_trace_round(const bundle_lm::Problem& pr, const GraphWords* w, const BundleTrace& tr, int round) {
+  if (!tr.rounds) return;
+  glim_amd_bundle_trace_round e;
+  e.lambda = w->lambda_before;
+  e.cost = pr.s->trial_cost;
+  e.accepted = pr.s->accepted;
+  e.status = pr.s->status;
+  tr.rounds[round] = e;
+}
+
+// the items of a round: a factor's blocks, a term's contribution (a thread each); the finite check of what the round was given; the trace's
+// copies of it
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_items_kernel(const bundle_lm::Problem pr, GraphWords* w, const double* __restrict__ recs, const BundleTrace tr,
+                                                                    int round) {
+  using namespace bundle_lm;
+  if (pr.s->status != lm::RUNNING) return;  // the same for every thread of the grid
+  const Graph& g = pr.g;
+  const int N = g.N, F = g.F, t = graph_thread(), T = graph_threads();
+  if (tr.rounds) {
+    for (int u = t; u < 12 * N; u += T) tr.X[(size_t)round * 12 * N + u] = pr.cand[u];
+    for (int u = t; u < 12 * F; u += T) tr.Tf[(size_t)round * 12 * F + u] = pr.Tf[u];
+    for (int u = t; u < lm::RECORD * F; u += T) tr.rec[(size_t)round * lm::RECORD * F + u] = recs[u];
+  }
+  bool bad = false;
+  for (int u = t; u < lm::RECORD * F; u += T) bad = bad || !lm::finite(recs[u]);
+  for (int u = t; u < 12 * N; u += T) bad = bad || !lm::finite(pr.cand[u]);
+  if (bad) w->bad_in = 1;
+  for (int i = t; i < F + g.P + g.Q; i += T) {
+    if (i < F) expand_factor(recs, pr.Tf, i, pr.lin);
+    else if (i < F + g.P) prior_term(g, pr.cand, i - F, pr.pc);
+    else between_term(g, pr.cand, i - F - g.P, pr.bc);
+  }
+}
+
+// the evaluated system: blockIdx.y is the row (row n: b), the threads run along the columns; an entry is its list's sum
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_assemble_kernel(const bundle_lm::Problem pr, GraphWords* w) {
+  using namespace bundle_lm;
+  if (pr.s->status != lm::RUNNING) return;
+  const int n = 6 * pr.g.N, r = (int)blockIdx.y, c = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
+  if (c >= n || (r < n && c > r)) return;
+  const double v = r < n ? assemble_entry(pr.g, pr.lin, pr.pc, pr.bc, r, c) : assemble_rhs(pr.g, pr.lin, pr.pc, pr.bc, c);
+  pr.W[tri(r) + c] = v;
+  if (!lm::finite(v)) w->bad_in = 1;
+}
+
+// One small workgroup: the four ascending sums (a wavefront's first thread each, over values the workgroup stages in LDS chunk by chunk)
+// and bundle_lm::decide.  The decision goes into the problem's Scalars and words, where the later kernels of the round read it
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_decide_kernel(const bundle_lm::Problem pr, const lm::Params prm, GraphWords* w, const double* __restrict__ recs,
+                                                                     const BundleTrace tr, int round) {
+#pragma clang fp contract(off)
+  using namespace bundle_lm;
+  __shared__ double s_v[4][GRAPH_SUM_CHUNK];
+  __shared__ double s_sums[4];
+  const int t = threadIdx.x;
+  if (pr.s->status != lm::RUNNING) {  // the same for every thread
+    if (t == 0) w->keep = 0;
+    return;
+  }
+  const Graph& g = pr.g;
+  const int F = g.F, most = max(F, max(g.P, g.Q));
+  double sum = 0.0;  // of the thread that owns a sum: sum_ascending over the chunks
+  for (int base = 0; base < most; base += GRAPH_SUM_CHUNK) {
+    for (int u = t; u < GRAPH_SUM_CHUNK; u += GRAPH_THREADS) {
+      const int i = base + u;
+      if (i < F) {
+        s_v[0][u] = recs[(size_t)lm::RECORD * i + 1];
+        s_v[1][u] = recs[(size_t)lm::RECORD * i];
+      }
+      if (i < g.P) s_v[2][u] = pr.pc[(size_t)PRIOR_STRIDE * i + 42];
+      if (i < g.Q) s_v[3][u] = pr.bc[(size_t)BETWEEN_STRIDE * i + 156];
+    }
+    __syncthreads();
+    if (t % 64 == 0) {
+      const int a = t / 64, count = a < 2 ? F : a == 2 ? g.P : g.Q, end = min(GRAPH_SUM_CHUNK, count - base);
+      for (int u = 0; u < end; u++) sum += s_v[a][u];
+    }
+    __syncthreads();
+  }
+  if (t % 64 == 0) s_sums[t / 64] = sum;
+  __syncthreads();
+  if (t != 0) return;
+  Scalars sc = *pr.s;
+  sc.accepted = 0;
+  w->lambda_before = sc.lambda;
+  const double cost = (s_sums[0] + s_sums[2]) + s_sums[3];
+  int keep = 0;
+  if (w->bad_in || !lm::finite(cost)) sc.status = lm::NUMERIC;
+  else keep = decide(prm, F, sc, cost, s_sums[0], s_sums[2], s_sums[3], s_sums[1]) ? 1 : 0;
+  *pr.s = sc;
+  w->keep = keep;
+  w->bad_in = w->bad_out = 0;
+  if (sc.status != lm::RUNNING) graph_trace_round(pr, w, tr, round);  // the round ends here
+}
+
+// entry (i, j) of the solve's matrix from a packed system
+__device__ __forceinline__ void graph_load_entry(const double* S, int n, double lambda, int i, int j, double* M) {
+  const int u = bundle_lm::tri(i) + j;
+  M[(size_t)j * graph_solve::leading(n) + i] = bundle_lm::solve_load(S, n, lambda, u, i, j);
+}
+
+// a kept candidate: its poses, records and system become the kept ones; while the loop runs: the solve's matrix from the kept system
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_keep_load_kernel(const bundle_lm::Problem pr, const GraphWords* __restrict__ w, const double* __restrict__ recs,
+                                                                        double* M) {
+  using namespace bundle_lm;
+  const bool keep = w->keep > 0, running = pr.s->status == lm::RUNNING;
+  if (!keep && !running) return;
+  const int N = pr.g.N, F = pr.g.F, n = 6 * N;
+  if (keep) {
+    const int t = graph_thread(), T = graph_threads();
+    for (int u = t; u < 12 * N; u += T) pr.X[u] = pr.cand[u];
+    for (int u = t; u < lm::RECORD * F; u += T) pr.rec[u] = recs[u];
+  }
+  const int i = (int)blockIdx.y, j = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
+  if (j >= n || (i < n && j > i)) return;
+  const int u = tri(i) + j;
+  if (keep) pr.S[u] = pr.W[u];
+  if (running) graph_load_entry(keep ? pr.W : pr.S, n, pr.s->lambda, i, j, M);
+}
+
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_load_kernel(const double* __restrict__ S, int n, double lambda, double* M) {
+  const int i = (int)blockIdx.y, j = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
+  if (j >= n || (i < n && j > i)) return;
+  graph_load_entry(S, n, lambda, i, j, M);
+}
+
+// the next candidates: a pose each.  After a failed solve they are the kept poses (the solve has left delta at +0.0)
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_retract_kernel(const bundle_lm::Problem pr, GraphWords* w) {
+  if (pr.s->status != lm::RUNNING) return;
+  const int k = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
+  if (k >= pr.g.N) return;
+  if (!w->fail) {
+    lm::retract(pr.X + 12 * k, pr.delta + 6 * k, pr.cand + 12 * k);
+  } else {
+    for (int i = 0; i < 12; i++) pr.cand[12 * k + i] = pr.X[12 * k + i];
+  }
+  if (!lm::all_finite(pr.cand + 12 * k, 12)) w->bad_out = 1;
+}
+
+// the next round's T_f, a factor each, and the end of the round's bookkeeping (the first thread)
+__global__ __launch_bounds__(GRAPH_THREADS) void graph_next_kernel(const bundle_lm::Problem pr, const GraphWords* w, const BundleTrace tr, int round) {
+  // (the first thread may set NUMERIC below while another workgroup starts: that workgroup has nothing to do either way)
+  if (pr.s->status != lm::RUNNING) return;
+  const int bad = w->bad_out, f = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
+  if (!bad && f < pr.g.F) bundle_lm::relative_pose(pr.cand, pr.g.ft, pr.g.fs, f, pr.Tf);
+  if (f == 0) {
+    pr.s->solve_ok = w->fail ? 0 : 1;
+    if (bad) pr.s->status = lm::NUMERIC;
+    graph_trace_round(pr, w, tr, round);
+  }
+}
+
+// the cross-check variant: one thread runs step() as it stands, with W in device memory
+__global__ __launch_bounds__(64) void graph_one_thread_kernel(const bundle_lm::Problem pr, const lm::Params prm, GraphWords* w, const double* __restrict__ recs,
+                                                              const BundleTrace tr, int round) {
+  using namespace bundle_lm;
+  if (pr.s->status != lm::RUNNING) return;
+  const int t = threadIdx.x, N = pr.g.N, F = pr.g.F;
+  if (tr.rounds) {
+    for (int u = t; u < 12 * N; u += 64) tr.X[(size_t)round * 12 * N + u] = pr.cand[u];
+    for (int u = t; u < 12 * F; u += 64) tr.Tf[(size_t)round * 12 * F + u] = pr.Tf[u];
+    for (int u = t; u < lm::RECORD * F; u += 64) tr.rec[(size_t)round * lm::RECORD * F + u] = recs[u];
+  }
+  if (t != 0) return;
+  w->lambda_before = pr.s->lambda;
+  Problem q = pr;
+  step(prm, q, recs);
+  graph_trace_round(pr, w, tr, round);
+}
+
+// the launches of one round behind the factors' evaluation
+int graph_round(const bundle_lm::Problem& pr, const GraphScratch& gs, const lm::Params& prm, const double* d_recs, const int* d_status, const BundleTrace& tr, int round,
+                int one_thread, hipStream_t st) {
+  const bundle_lm::Graph& g = pr.g;
+  if (one_thread) {
+    graph_one_thread_kernel<<<1, 64, 0, st>>>(pr, prm, gs.words, d_recs, tr, round);
+    return GLIM_AMD_OK;
+  }
+  const int n = 6 * g.N;
+  auto blocks = [](int count) { return std::max(1, (count + GRAPH_THREADS - 1) / GRAPH_THREADS); };
+  const dim3 square(blocks(n), n + 1);
+  graph_items_kernel<<<blocks(g.F + g.P + g.Q), GRAPH_THREADS, 0, st>>>(pr, gs.words, d_recs, tr, round);
+  graph_assemble_kernel<<<square, GRAPH_THREADS, 0, st>>>(pr, gs.words);
+  graph_decide_kernel<<<1, GRAPH_THREADS, 0, st>>>(pr, prm, gs.words, d_recs, tr, round);
+  graph_keep_load_kernel<<<square, GRAPH_THREADS, 0, st>>>(pr, gs.words, d_recs, gs.M);
+  GA_HIP(graph_solve_enqueue(st, gs.M, n, pr.delta, &gs.words->fail, d_status));
+  graph_retract_kernel<<<blocks(g.N), GRAPH_THREADS, 0, st>>>(pr, gs.words);
+  graph_next_kernel<<<blocks(g.F), GRAPH_THREADS, 0, st>>>(pr, gs.words, tr, round);
+  return GLIM_AMD_OK;
+}
+
 bool lm_params_ok(const glim_amd_lm_params& p) {
   const double v[] = {p.lambda_initial, p.lambda_factor, p.lambda_upper_bound, p.lambda_lower_bound, p.relative_error_tol, p.absolute_error_tol, p.error_scale};
   for (double x : v)
@@ -973,25 +1206,24 @@ int run_keyframe_align(const glim_amd_cloud* const* sources, const int32_t* firs
   return GLIM_AMD_OK;
 }
 
-// The sub-map bundle optimisation.  One block of doubles and one of ints hold the graph, the state and the scratch of the problem, laid out
-// the same on host and device; a round is vgicp_batch_round over the F factors, all behind the problem's ONE status word (stride 0), and the
-// bundle decide kernel, which leaves the next round's T_f in the batch's pose buffer.  trace: the four arrays of the diag entry, or all null.
-int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+// ---- the host scaffold of the two N-pose loops (the sub-map bundle, the global graph) ----
+struct GraphCaps {
+  int poses, factors, terms;
+};
+
+// the refusals of glim_amd_bundle_align with a loop's caps: everything that is answered before a handle or the context is used, then the pairs.
+// GLIM_AMD_OK with N == 0 is the caller's to answer first
+int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
                      const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
-                     int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
-                     glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host) {
-  using namespace bundle_lm;
-  if (N < 0 || F < 0 || P < 0 || Q < 0) return GLIM_AMD_ERR_INVALID;
-  if (N == 0) return GLIM_AMD_OK;
+                     int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, const double* X_out12, const glim_amd_bundle_result* result,
+                     const GraphCaps& caps, lm::Params* prm, int* rounds) {
   if (!ctx || !X_init12 || !X_out12 || !result) return GLIM_AMD_ERR_INVALID;
   if (F > 0 && (!targets || !sources || !target_pose || !source_pose)) return GLIM_AMD_ERR_INVALID;
   if ((P > 0 && !priors) || (Q > 0 && !betweens)) return GLIM_AMD_ERR_INVALID;
   if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;
   if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: every factor here is binary
-  lm::Params prm;
-  int rounds;
-  GA_TRY(resolve_params(params, bundle_default_params, &prm, &rounds));
-  if (N > MAX_POSES || F > MAX_FACTORS || P > MAX_TERMS || Q > MAX_TERMS) return GLIM_AMD_ERR_UNSUPPORTED;
+  GA_TRY(resolve_params(params, bundle_default_params, prm, rounds));
+  if (N > caps.poses || F > caps.factors || P > caps.terms || Q > caps.terms) return GLIM_AMD_ERR_UNSUPPORTED;
   if (!one_context(targets, sources, F, ctx)) return GLIM_AMD_ERR_INVALID;
   for (int f = 0; f < F; f++)
     if (target_pose[f] < 0 || target_pose[f] >= N || source_pose[f] < 0 || source_pose[f] >= N || target_pose[f] == source_pose[f]) return GLIM_AMD_ERR_INVALID;
@@ -1005,43 +1237,21 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     if (!all_finite_host(b.T, 12) || !all_finite_host(b.information, 36)) return GLIM_AMD_ERR_INVALID;
   }
   if (!all_finite_host(X_init12, 12 * N)) return GLIM_AMD_ERR_INVALID;
-  GA_TRY(vgicp_pairs_ok(targets, sources, F));
+  return vgicp_pairs_ok(targets, sources, F);
+}
 
-  // the two blocks: offsets in doubles / ints
-  const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q);
-  size_t at = 0;
-  auto take = [&](size_t count) {
-    const size_t o = at;
-    at += count;
-    return o;
-  };
-  const size_t o_X = take(12 * (size_t)N), o_cand = take(12 * (size_t)N), o_delta = take(n), o_rec = take((size_t)lm::RECORD * F), o_S = take(nsys),
-               o_pT = take(12 * (size_t)P), o_pL = take(36 * (size_t)P), o_bT = take(12 * (size_t)Q), o_bL = take(36 * (size_t)Q),
-               o_scal = take(sizeof(Scalars) / sizeof(double));
-  const size_t upload_doubles = at;  // what the host fills; the scratch below is written before it is read
-  const size_t o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
-  const size_t total_doubles = at;
-  at = 0;
-  const size_t i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_first = take(tri(N) + 1), i_items = take(nlist);
-  const size_t total_ints = at;
-  std::vector<double> hd(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q, 0.0);
-  std::vector<int> hi(total_ints + (size_t)tri(N), 0);  // (the tail: build_lists' cursors)
-  for (int f = 0; f < F; f++) {
-    hi[i_ft + f] = target_pose[f];
-    hi[i_fs + f] = source_pose[f];
-  }
-  for (int p = 0; p < P; p++) {
-    hi[i_pk + p] = priors[p].pose;
-    memcpy(&hd[o_pT + 12 * (size_t)p], priors[p].T, 12 * sizeof(double));
-    memcpy(&hd[o_pL + 36 * (size_t)p], priors[p].information, 36 * sizeof(double));
-  }
-  for (int q = 0; q < Q; q++) {
-    hi[i_bi + q] = betweens[q].pose_i;
-    hi[i_bj + q] = betweens[q].pose_j;
-    memcpy(&hd[o_bT + 12 * (size_t)q], betweens[q].T, 12 * sizeof(double));
-    memcpy(&hd[o_bL + 36 * (size_t)q], betweens[q].information, 36 * sizeof(double));
-  }
-  auto problem_at = [&](double* d, int* i, double* Tf) {
+// One block of doubles and one of ints hold the graph, the state and the scratch of a problem, laid out the same on host and device: the
+// offsets in doubles / ints, and the host's copy with the graph, its lists and the state before round 0.  `extra`: doubles of further
+// scratch behind the problem's own (o_extra)
+struct GraphBlocks {
+  size_t o_X, o_cand, o_delta, o_rec, o_S, o_pT, o_pL, o_bT, o_bL, o_scal, upload_doubles, o_pc, o_bc, o_lin, o_Tf0, o_extra, total_doubles;
+  size_t i_ft, i_fs, i_pk, i_bi, i_bj, i_first, i_items, total_ints;
+  int N, F, P, Q;
+  std::vector<double> hd;
+  std::vector<int> hi;
+
+  bundle_lm::Problem problem_at(double* d, int* i, double* Tf) const {
+    using namespace bundle_lm;
     Problem pr;
     memset(&pr, 0, sizeof(pr));
     pr.g = Graph{N, F, P, Q, i + i_ft, i + i_fs, i + i_pk, d + o_pT, d + o_pL, i + i_bi, i + i_bj, d + o_bT, d + o_bL, i + i_first, i + i_items};
@@ -1054,15 +1264,86 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     pr.lin = reinterpret_cast<glim_amd_linearized6*>(d + o_lin);
     pr.pc = d + o_pc;
     pr.bc = d + o_bc;
-    pr.W = nullptr;  // the kernel's LDS
+    pr.W = nullptr;  // the bundle kernel's LDS; the graph's scratch
     pr.s = reinterpret_cast<Scalars*>(d + o_scal);
     return pr;
-  };
-  {
+  }
+
+  GraphBlocks(int N_, int F_, int P_, int Q_, const int32_t* target_pose, const int32_t* source_pose, const glim_amd_bundle_prior* priors,
+              const glim_amd_bundle_between* betweens, const double* X_init12, const lm::Params& prm, size_t extra)
+      : N(N_), F(F_), P(P_), Q(Q_) {
+    using namespace bundle_lm;
+    const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q);
+    size_t at = 0;
+    auto take = [&](size_t count) {
+      const size_t o = at;
+      at += count;
+      return o;
+    };
+    o_X = take(12 * (size_t)N), o_cand = take(12 * (size_t)N), o_delta = take(n), o_rec = take((size_t)lm::RECORD * F), o_S = take(nsys);
+    o_pT = take(12 * (size_t)P), o_pL = take(36 * (size_t)P), o_bT = take(12 * (size_t)Q), o_bL = take(36 * (size_t)Q);
+    o_scal = take(sizeof(Scalars) / sizeof(double));
+    upload_doubles = at;  // what the host fills; the scratch below is written before it is read
+    o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
+    o_extra = take(extra);
+    total_doubles = at;
+    at = 0;
+    i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_first = take(tri(N) + 1), i_items = take(nlist);
+    total_ints = at;
+    hd.assign(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q, 0.0);
+    hi.assign(total_ints + (size_t)tri(N), 0);  // (the tail: build_lists' cursors)
+    for (int f = 0; f < F; f++) {
+      hi[i_ft + f] = target_pose[f];
+      hi[i_fs + f] = source_pose[f];
+    }
+    for (int p = 0; p < P; p++) {
+      hi[i_pk + p] = priors[p].pose;
+      memcpy(&hd[o_pT + 12 * (size_t)p], priors[p].T, 12 * sizeof(double));
+      memcpy(&hd[o_pL + 36 * (size_t)p], priors[p].information, 36 * sizeof(double));
+    }
+    for (int q = 0; q < Q; q++) {
+      hi[i_bi + q] = betweens[q].pose_i;
+      hi[i_bj + q] = betweens[q].pose_j;
+      memcpy(&hd[o_bT + 12 * (size_t)q], betweens[q].T, 12 * sizeof(double));
+      memcpy(&hd[o_bL + 36 * (size_t)q], betweens[q].information, 36 * sizeof(double));
+    }
     Problem host = problem_at(hd.data(), hi.data(), nullptr);
     build_lists(host.g, hi.data() + i_first, hi.data() + i_items, hi.data() + total_ints);
     init(prm, X_init12, host);
   }
+};
+
+void graph_result(const bundle_lm::Scalars& sc, glim_amd_bundle_result* result) {
+  memset(result, 0, sizeof(*result));
+  result->cost = sc.cost;
+  result->factor_cost = sc.fcost;
+  result->prior_cost = sc.pcost;
+  result->between_cost = sc.bcost;
+  result->num_inliers = (int64_t)llround(sc.inliers);
+  result->iterations = sc.iterations;
+  result->trials = sc.trials;
+  result->status = sc.status;
+  result->lambda = sc.lambda;
+}
+
+// The sub-map bundle optimisation and the global-graph optimisation: one host scaffold.  A round is vgicp_batch_round over the F factors, all
+// behind the problem's ONE status word (stride 0), and then either the bundle decide kernel (one workgroup, the system in LDS) or the graph's
+// launches (graph_round: the system in device memory); both leave the next round's T_f in the batch's pose buffer.  trace: the four arrays of
+// the diag entry, or all null.  chunk: rounds enqueued between two looks at the status; 0: all of them up front and ONE synchronisation.  The
+// state lives on the device: the chunk length moves no bit of a result.
+int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                     const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
+                     int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
+                     glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host, bool graph = false, int chunk = 0) {
+  using namespace bundle_lm;
+  if (N < 0 || F < 0 || P < 0 || Q < 0) return GLIM_AMD_ERR_INVALID;
+  if (N == 0) return GLIM_AMD_OK;
+  lm::Params prm;
+  int rounds;
+  const GraphCaps caps = graph ? GraphCaps{GLIM_AMD_GRAPH_MAX_POSES, GLIM_AMD_GRAPH_MAX_FACTORS, GLIM_AMD_GRAPH_MAX_TERMS} : GraphCaps{MAX_POSES, MAX_FACTORS, MAX_TERMS};
+  GA_TRY(check_graph_args(ctx, targets, sources, target_pose, source_pose, F, flags, priors, P, betweens, Q, X_init12, N, params, X_out12, result, caps, &prm,
+                          &rounds));
+  const GraphBlocks blk(N, F, P, Q, target_pose, source_pose, priors, betweens, X_init12, prm, graph ? graph_scratch_doubles(6 * N) : 0);
 
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the call
   GA_HIP(hipSetDevice(ctx->device));
@@ -1075,8 +1356,8 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     st = batch.stream();
   }
   SyncOnExit in_flight(st);  // an error exit after the launches waits for the stream before the scratch goes back to the pool
-  GA_HIP(pool_malloc(&d_d.p, std::max<size_t>(1, total_doubles) * sizeof(double)));
-  GA_HIP(pool_malloc(&d_i.p, std::max<size_t>(1, total_ints) * sizeof(int)));
+  GA_HIP(pool_malloc(&d_d.p, std::max<size_t>(1, blk.total_doubles) * sizeof(double)));
+  GA_HIP(pool_malloc(&d_i.p, std::max<size_t>(1, blk.total_ints) * sizeof(int)));
   if (trace_host.rounds) {  // (the entry point has seen to it that the arrays the graph needs come together)
     GA_TRY(tX.open(trace_host.X, (size_t)rounds * 12 * N * sizeof(double), st));
     GA_TRY(tTf.open(trace_host.Tf, (size_t)rounds * 12 * F * sizeof(double), st));
@@ -1084,22 +1365,33 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     GA_TRY(trounds.open(trace_host.rounds, (size_t)rounds * sizeof(glim_amd_bundle_trace_round), st));
   }
   const BundleTrace tr{tX.d.as<double>(), tTf.d.as<double>(), trec.d.as<double>(), trounds.d.as<glim_amd_bundle_trace_round>()};
-  GA_HIP(hipMemcpyAsync(d_d.p, hd.data(), upload_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  if (total_ints) GA_HIP(hipMemcpyAsync(d_i.p, hi.data(), total_ints * sizeof(int), hipMemcpyHostToDevice, st));
-  const Problem pr = problem_at(d_d.as<double>(), d_i.as<int>(), F > 0 ? batch.poses() : d_d.as<double>() + o_Tf0);
+  GA_HIP(hipMemcpyAsync(d_d.p, blk.hd.data(), blk.upload_doubles * sizeof(double), hipMemcpyHostToDevice, st));
+  if (blk.total_ints) GA_HIP(hipMemcpyAsync(d_i.p, blk.hi.data(), blk.total_ints * sizeof(int), hipMemcpyHostToDevice, st));
+  Problem pr = blk.problem_at(d_d.as<double>(), d_i.as<int>(), F > 0 ? batch.poses() : d_d.as<double>() + blk.o_Tf0);
+  const GraphScratch gs = graph_scratch_at(d_d.as<double>() + blk.o_extra, 6 * N);
+  if (graph) {
+    pr.W = gs.E;
+    GA_HIP(hipMemsetAsync(gs.words, 0, sizeof(GraphWords), st));
+  }
   const int* d_status = reinterpret_cast<const int*>(reinterpret_cast<const char*>(pr.s) + offsetof(Scalars, status));
   const double* d_recs = F > 0 ? batch.records() : pr.rec;
   if (F > 0) bundle_pose_kernel<<<1, 256, 0, st>>>(pr);
-  for (int r = 0; r < rounds; r++) {
-    if (F > 0) GA_TRY(vgicp_batch_round(&batch, d_status, 0));
-    bundle_decide_kernel<<<1, BUNDLE_THREADS, 0, st>>>(pr, prm, d_recs, tr, r, one_thread);
-  }
-  GA_HIP(hipGetLastError());
   Scalars sc;
+  for (int r = 0;;) {
+    for (const int end = chunk > 0 ? std::min(rounds, r + chunk) : rounds; r < end; r++) {
+      if (F > 0) GA_TRY(vgicp_batch_round(&batch, d_status, 0));
+      if (graph) GA_TRY(graph_round(pr, gs, prm, d_recs, d_status, tr, r, one_thread, st));
+      else bundle_decide_kernel<<<1, BUNDLE_THREADS, 0, st>>>(pr, prm, d_recs, tr, r, one_thread);
+    }
+    GA_HIP(hipGetLastError());
+    GA_HIP(hipMemcpyAsync(&sc, pr.s, sizeof(sc), hipMemcpyDeviceToHost, st));
+    if (r == rounds) break;
+    GA_HIP(hipStreamSynchronize(st));  // a chunk's end: the loop stops enqueueing when the problem has finished
+    if (sc.status != lm::RUNNING) break;
+  }
   std::vector<double> rec_host((size_t)lm::RECORD * F);
   GA_HIP(hipMemcpyAsync(X_out12, pr.X, 12 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
   if (F > 0) GA_HIP(hipMemcpyAsync(rec_host.data(), pr.rec, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  GA_HIP(hipMemcpyAsync(&sc, pr.s, sizeof(sc), hipMemcpyDeviceToHost, st));
   GA_TRY(tX.fetch(st));
   GA_TRY(tTf.fetch(st));  // (nothing without factors: no bytes)
   GA_TRY(trec.fetch(st));
@@ -1108,16 +1400,7 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   in_flight.dismiss();
   if (F > 0) batch.seen_complete();
   if (compact_out && F > 0) memcpy(compact_out, rec_host.data(), rec_host.size() * sizeof(double));
-  memset(result, 0, sizeof(*result));
-  result->cost = sc.cost;
-  result->factor_cost = sc.fcost;
-  result->prior_cost = sc.pcost;
-  result->between_cost = sc.bcost;
-  result->num_inliers = (int64_t)llround(sc.inliers);
-  result->iterations = sc.iterations;
-  result->trials = sc.trials;
-  result->status = sc.status;
-  result->lambda = sc.lambda;
+  graph_result(sc, result);
   return GLIM_AMD_OK;
 }
 
@@ -1149,6 +1432,54 @@ int glim_amd_debug_bundle_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap
   if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
   return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
                           params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds});
+}
+
+int glim_amd_graph_align_default_params(glim_amd_lm_params* params) { return glim_amd_bundle_align_default_params(params); }
+
+int glim_amd_graph_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                         const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                         const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                         const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result) {
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, 0, BundleTrace{nullptr, nullptr, nullptr, nullptr}, true, GRAPH_ROUNDS_PER_CHUNK);
+}
+
+int glim_amd_debug_graph_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                     const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                     const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                     int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                     double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
+                                     double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk) {
+  const bool any = X_trace || Tf_trace || compact_trace || rounds;
+  if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
+  if (rounds_per_chunk < 0) return GLIM_AMD_ERR_INVALID;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, true,
+                          rounds_per_chunk > 0 ? rounds_per_chunk : GRAPH_ROUNDS_PER_CHUNK);
+}
+
+int glim_amd_debug_graph_solve(glim_amd_ctx* ctx, const double* S, int32_t n, double lambda, double* delta_out, int32_t* ok_out) {
+  if (!ctx || !S || !delta_out || !ok_out || n < 1 || n > graph_solve::MAX_DIM || !std::isfinite(lambda)) return GLIM_AMD_ERR_INVALID;
+  const size_t nsys = (size_t)bundle_lm::system_doubles(n), nm = graph_solve::matrix_doubles(n);
+  std::unique_lock<std::mutex> held(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  DeviceTemp d;  // the system, the matrix, delta, then the two words (fail, a status that stays 0)
+  SyncOnExit in_flight(st);
+  GA_HIP(pool_malloc(&d.p, (nsys + nm + n + 1) * sizeof(double)));
+  double *d_S = d.as<double>(), *d_M = d_S + nsys, *d_delta = d_M + nm;
+  int* d_words = reinterpret_cast<int*>(d_delta + n);
+  GA_HIP(hipMemcpyAsync(d_S, S, nsys * sizeof(double), hipMemcpyHostToDevice, st));
+  GA_HIP(hipMemsetAsync(d_words, 0, 2 * sizeof(int), st));
+  graph_load_kernel<<<dim3((n + GRAPH_THREADS - 1) / GRAPH_THREADS, n + 1), GRAPH_THREADS, 0, st>>>(d_S, n, lambda, d_M);
+  GA_HIP(graph_solve_enqueue(st, d_M, n, d_delta, d_words, d_words + 1));
+  int fail = 0;
+  GA_HIP(hipMemcpyAsync(delta_out, d_delta, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipMemcpyAsync(&fail, d_words, sizeof(int), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  *ok_out = fail ? 0 : 1;
+  return GLIM_AMD_OK;
 }
 
 int glim_amd_vgicp_align_default_params(glim_amd_lm_params* params) {

@@ -868,6 +868,40 @@ int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* tar
                           const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
                           const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result);
 
+/* ---- Global-graph optimisation: the sub-map bundle optimisation above at the size of GLIM's global graph (src/glim/mapping/global_mapping.cpp:
+ *      430-484, the pairwise IntegratedVGICPFactorGPU between sub-maps, plus that file's pose-only BetweenFactor<Pose3>): the same graph
+ *      description, the same rule (glim_amd/csrc/bundle_lm_step.hpp, whose item functions take N from the graph, not from a cap), larger caps.
+ *      N poses over F binary factors, P priors and Q betweens; 6N DoF, the bundle's tangent order and perturbation; FP64, contraction off.
+ *   record     the bundle's, word for word: every trial record is the bits of a caller's set of the same pairs at the candidate's T_f.
+ *   blocks     the bundle's.  The factors' blocks live in device memory (976 B each, 32 MB at the cap).
+ *   terms      the bundle's.
+ *   system     the bundle's: the same entries, the same order of every sum.  Both systems (the evaluated one, the kept one) live in device
+ *              memory as packed lower triangles.
+ *   solve      the bundle's: every entry of L, of y and of delta receives the same FP64 operations in the same order.  The factorisation walks
+ *              block columns of 64-wide tiles in ascending order and, inside each, ascending k (glim_amd/csrc/graph_solve.hpp);
+ *              the back substitution walks them in descending order.  The solve's matrix is column-major in device memory; the layout is not
+ *              part of the rule.  A failed pivot is the bundle's failed solve.
+ *   retract    the bundle's.
+ *   the rest   the bundle's (lm::decide, called).  A round is a sequence of ordinary launches on the context's first stream; a kernel boundary
+ *              is the only ordering.  No kernel waits for another workgroup and none declares more than 64 KiB of LDS.  The rounds are
+ *              enqueued a few at a time; between two chunks the host reads the status and stops enqueueing when the loop has finished.  The
+ *              state lives on the device: the chunk length moves no bit of a result.
+ * With the same arguments within the bundle's caps, glim_amd_graph_align returns what glim_amd_bundle_align returns, bit for bit.
+ * Out of scope: ISAM2 (GLIM's global mapping is incremental; this is one batch optimisation over the poses), IMU variables, LinearDampingFactor,
+ * robust kernels, several devices, translating a gtsam::NonlinearFactorGraph.
+ * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
+ * resident session of the context are not touched. */
+#define GLIM_AMD_GRAPH_MAX_POSES 256     /* 1536 x 1536 */
+#define GLIM_AMD_GRAPH_MAX_FACTORS 32768 /* every pair i < j of 256 poses is 32 640 */
+#define GLIM_AMD_GRAPH_MAX_TERMS 1024    /* priors; and betweens */
+/* the defaults of glim_amd_bundle_align_default_params */
+int glim_amd_graph_align_default_params(glim_amd_lm_params* params);
+/* The arguments, the results and the refusals of glim_amd_bundle_align, with the caps above.  Nothing is launched when an argument is refused. */
+int glim_amd_graph_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                         const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                         const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                         const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result);
+
 /* ---- Scan-to-keyframes VGICP registration: the LiDAR part of GLIM's frame-to-keyframes matching cost
  *      (src/glim/odometry/odometry_estimation_gpu.cpp:150-165, 183-203): one unary IntegratedVGICPFactorGPU(fixed_target_pose, X(current),
  *      voxelmap, frame) per keyframe and per voxel-map level, ALL on the same pose variable -- as a batch of `count` independent problems, each

@@ -73,7 +73,10 @@ struct BundleResult {
   glim_amd_bundle_result raw{};
 };
 
-inline BundleResult optimize_bundle(const BundleGraph& g, const std::vector<Isometry3d>& initial, const LMParams& params = bundle_params()) {
+namespace detail {
+// entry: glim_amd_bundle_align, or an entry point with its arguments (graph_align.hpp)
+template <class Entry>
+inline BundleResult optimize_poses(Entry entry, const char* what, const BundleGraph& g, const std::vector<Isometry3d>& initial, const LMParams& params) {
   BundleResult r;
   const std::size_t N = initial.size(), F = g.targets.size();
   if (N == 0) return r;  // answered before any device call
@@ -83,10 +86,10 @@ inline BundleResult optimize_bundle(const BundleGraph& g, const std::vector<Isom
   r.compact.resize(GLIM_AMD_COMPACT_DOUBLES * F);
   const glim_amd_lm_params p = params.c();
   const Context ctx = g.ctx ? g.ctx : StreamTempBufferRoundRobin::default_instance();
-  check(glim_amd_bundle_align(ctx->context(), g.targets.data(), g.sources.data(), g.target_pose.data(), g.source_pose.data(), (std::int32_t)F,
-                              g.surface_validation ? GLIM_AMD_FACTOR_SURFACE_VALIDATION : 0u, g.priors.data(), (std::int32_t)g.priors.size(), g.betweens.data(),
-                              (std::int32_t)g.betweens.size(), X.data(), (std::int32_t)N, &p, out.data(), F ? r.compact.data() : nullptr, &r.raw),
-        "optimize_bundle");
+  check(entry(ctx->context(), g.targets.data(), g.sources.data(), g.target_pose.data(), g.source_pose.data(), (std::int32_t)F,
+              g.surface_validation ? GLIM_AMD_FACTOR_SURFACE_VALIDATION : 0u, g.priors.data(), (std::int32_t)g.priors.size(), g.betweens.data(),
+              (std::int32_t)g.betweens.size(), X.data(), (std::int32_t)N, &p, out.data(), F ? r.compact.data() : nullptr, &r.raw),
+        what);
   r.poses.resize(N);
   for (std::size_t k = 0; k < N; k++)
     for (int u = 0; u < 12; u++) r.poses[k].m[u] = out[12 * k + u];
@@ -99,6 +102,11 @@ inline BundleResult optimize_bundle(const BundleGraph& g, const std::vector<Isom
   r.trials = r.raw.trials;
   r.status = r.raw.status;
   return r;
+}
+}  // namespace detail
+
+inline BundleResult optimize_bundle(const BundleGraph& g, const std::vector<Isometry3d>& initial, const LMParams& params = bundle_params()) {
+  return detail::optimize_poses([](auto... a) { return glim_amd_bundle_align(a...); }, "optimize_bundle", g, initial, params);
 }
 
 }  // namespace glim_amd

@@ -302,6 +302,21 @@ int glim_amd_debug_bundle_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap
                                       int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
                                       double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
                                       double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds);
+/* test window of the global-graph optimisation (glim_amd.h): glim_amd_graph_align with the same arguments and results and the trace arrays of
+ * glim_amd_debug_bundle_align_trace, plus two arguments.  rounds_per_chunk: how many rounds are enqueued between two looks at the status (0: the
+ * default; it moves no bit of a result).  one_thread != 0: every round is bundle_lm_step.hpp's step() as it stands, run by ONE device thread with
+ * its working system in device memory -- the cross-check of the launches (same bits); it is no production path and takes seconds beyond a few
+ * dozen poses. */
+int glim_amd_debug_graph_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                     const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                     const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                     int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                     double* X_out12, double* compact_out, glim_amd_bundle_result* result, int32_t one_thread, double* X_trace,
+                                     double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk);
+/* the device's blocked solve alone (glim_amd/csrc/graph_solve.hpp) on a caller's system: S is the packed lower triangle of H by rows (row i at
+ * i (i + 1) / 2), then b; 1 <= n <= 6 GLIM_AMD_GRAPH_MAX_POSES.  Solves (H + lambda I) delta = -b.  delta_out: n doubles, +0.0 after a failed
+ * pivot; *ok_out: 1, or 0 after a failed pivot. */
+int glim_amd_debug_graph_solve(glim_amd_ctx* ctx, const double* S, int32_t n, double lambda, double* delta_out, int32_t* ok_out);
 /* test window of the scan-to-keyframes VGICP registration (glim_amd.h): glim_amd_keyframe_align_batch with the same arguments and results,
  * plus, with R = 1 + max_trials rounds (max_trials as resolved; round 0 is the initial pose; valid for r <= out[i].trials, the rest are zero):
  * per problem i and round r, rounds[i * R + r] -- T_candidate: the X the round evaluated, lambda: the one its step was solved with, compact:
