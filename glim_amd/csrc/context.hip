@@ -38,14 +38,11 @@ struct DiagKey {
   const char* const* words;  // value words (index = value), or null for a plain integer
   int lo, hi;
 };
-const char* const kPathWords[] = {"auto", "grid", "chunks", "brute", nullptr};
-const char* const kKernelWords[] = {"auto", "wave64", "pair", "qgroup", nullptr};
+const char* const kPathWords[] = {"auto", "brute", nullptr};
 const char* const kResidentWords[] = {"0", "1", "auto", nullptr};
 const char* const kResidentPostWords[] = {"lines", "direct", "auto", nullptr};
 const DiagKey kDiagKeys[] = {
-  {"knn_path", &Diag::knn_path, kPathWords, 0, 3},
-  {"knn_kernel", &Diag::knn_kernel, kKernelWords, 0, 3},
-  {"knn_select", &Diag::knn_select, nullptr, 0, 1},
+  {"knn_path", &Diag::knn_path, kPathWords, 0, 1},
   {"plane", &Diag::plane, nullptr, 0, 1},
   {"curve_order", &Diag::curve_order, nullptr, 0, 1},
   {"ppt", &Diag::ppt, nullptr, 0, 256},

@@ -148,9 +148,7 @@ int detect_plane_form(::glim_amd_cloud* c, hipStream_t st);
 // GLIM_AMD_DIAG="key=value,key=value", parsed once per process -- and changed per context with glim_amd_ctx_set_diag (same syntax).
 // No other getenv exists in the library.
 struct Diag {
-  int knn_path = 0;       // knn_path=auto|grid|chunks|brute     which kNN implementation answers glim_amd_cloud_find_neighbors
-  int knn_kernel = 0;     // knn_kernel=auto|wave64|pair         64-query or pair-lane chunk kernel
-  int knn_select = 1;     // knn_select=0|1                      per-lane threshold selection of the chunk kernels (k <= 10)
+  int knn_path = 0;       // knn_path=auto|brute                 brute: the exhaustive kernel answers glim_amd_cloud_find_neighbors at every size (cross-check)
   int plane = 1;          // plane=0|1                           plane-form (24 B/pt) factor kernel for plane-form clouds
   int curve_order = 1;    // curve_order=0|1                     factor streams in the Hilbert order of the cloud
   int ppt = 0;            // ppt=<n>                             points per thread of the factor kernel (0: one resident set of blocks)
@@ -182,12 +180,11 @@ struct Diag {
   int multi_host_gather = 0;  // multi_host_gather=0|1           glim_amd_multi: allow a host gather when librccl cannot be loaded (tests)
   int multi_virtual = 0;  // multi_virtual=0|1                   glim_amd_multi_create accepts one physical device several times ("virtual devices": the N > 1
                           //                                    code path on a one-GPU box; the exchange is a same-device stand-in for ncclAllGather)
-  char knn_debug[256] = "";   // knn_debug=<file>                dump per-wavefront work counters of the 64-query chunk kernel
+  char knn_debug[256] = "";   // knn_debug=<file>                dump the query-group kNN kernel's work counters (8 ints: wavefronts, chunk scans, exact evaluations, insertions, chunk-test rounds, 0, 0, 0)
 };
 enum { RESIDENT_OFF = 0, RESIDENT_ON = 1, RESIDENT_AUTO = 2 };
 enum { RESIDENT_POST_LINES = 0, RESIDENT_POST_DIRECT = 1, RESIDENT_POST_AUTO = 2 };
-enum { KNN_PATH_AUTO = 0, KNN_PATH_GRID = 1, KNN_PATH_CHUNKS = 2, KNN_PATH_BRUTE = 3 };
-enum { KNN_KERNEL_AUTO = 0, KNN_KERNEL_WAVE64 = 1, KNN_KERNEL_PAIR = 2 };
+enum { KNN_PATH_AUTO = 0, KNN_PATH_BRUTE = 1 };
 const Diag& process_diag();                        // GLIM_AMD_DIAG, parsed once
 int diag_parse(Diag& d, const char* key_values);   // GLIM_AMD_OK or GLIM_AMD_ERR_INVALID (unknown key / bad value); d untouched on error
 int diag_print(const Diag& d, char* buf, size_t len);

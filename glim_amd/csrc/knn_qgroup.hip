@@ -1,20 +1,52 @@
 // knn_qgroup.hip -- kernel group K2, the query-group Hilbert-chunk kernel (see knn.hip for the method and the host side).
 //
-// The 64-query kernel (knn_chunks.hip) and the pair-lane kernel (knn_pairs.hip) give every LANE a query: a wavefront is a lock-step chain of
-// (candidate chunks scanned) x 64 candidate steps + (insertion rounds of its slowest lane), all wavefronts are resident at once and the launch
-// lasts as long as the slowest of them -- twice the mean at 131 072 points -- while a 10 000-point cloud fills 313 of the chip's 1 024 SIMDs with one
-// such chain each.  Here the lanes are the CANDIDATES: a wavefront answers Q (1 or 2) consecutive queries of the curve order, a scanned chunk is ONE
-// coalesced load (lane j holds candidate j), the Q distances per lane are the oracle's FP64 expression directly (no FP32 pre-pass to undo),
-// v_cmp against the query's k-th best IS the ballot of candidates that enter, and each query's list lives in lanes 0..K-1 (lane j = j-th best),
-// so an insertion is a vote, a population count and a one-lane shift.  A cloud of n points is n / Q short independent work items: no tail, and
-// small clouds fill the chip.  The first chunk (the query's own) is sorted by a 64-lane bitonic network instead of 64 insertions.
-// Lists are bit-identical to the other kernels and to the oracle: same FP64 distance expression, ties by original index, every point of every
-// chunk that can hold a better candidate is offered (the chunk test below is conservative).
+// The lanes are the CANDIDATES: a wavefront answers Q (1 or 2) consecutive queries of the curve order, a scanned chunk is ONE coalesced load
+// (lane j holds candidate j), the Q distances per lane are the oracle's FP64 expression directly (no FP32 pre-pass to undo), v_cmp against the
+// query's k-th best IS the ballot of candidates that enter, and each query's list lives in lanes 0..K-1 (lane j = j-th best), so an insertion is
+// a vote, a population count and a one-lane shift.  A cloud of n points is n / Q short independent work items: no tail, and small clouds fill
+// the chip.  The first chunk (the query's own) is sorted by a 64-lane bitonic network instead of 64 insertions.
+// Lists are bit-identical to the exhaustive kernel's and to the oracle's: same FP64 distance expression, ties by original index, every point of
+// every chunk that can hold a better candidate is offered (the chunk test below is conservative).
+// (The retired kernels that gave every LANE a query were lock-step chains as long as their slowest lane: knn.hip, "measured and retired".)
 #include "knn_common.hpp"
 
 using namespace glim_amd;
 
 namespace {
+
+// Boxes of the groups of 64 chunks, stored behind the chunk boxes (box[6 * (C + g) ...]).  A query chunk tests the (<= 256) group boxes
+// against its search radius after the first three scans and walks only the groups that pass -- 3.0 of 32 on average for a 131 072-pt scan --
+// where the walk over all groups used to be most of the ~47 us every wavefront paid whatever it scanned.  A group box contains its chunk
+// boxes and the radius only shrinks, so no chunk that the full walk would have scanned is lost.
+__global__ __launch_bounds__(256) void group_box_kernel(int C, float* __restrict__ box /* [C + G][6] */) {
+  const int g = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const int G = (C + CHUNK - 1) / CHUNK;
+  if (g >= G) return;
+  const int cc = g * CHUNK + lane;
+  const float inf = __int_as_float(0x7f800000);
+  float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+  if (cc < C) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      lo[a] = box[6 * (size_t)cc + a];
+      hi[a] = box[6 * (size_t)cc + 3 + a];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64));
+      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
+    }
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      box[6 * (size_t)(C + g) + a] = lo[a];
+      box[6 * (size_t)(C + g) + 3 + a] = hi[a];
+    }
+  }
+}
 
 __device__ __forceinline__ double uniform_d(double v) {  // a wave-uniform double, moved to scalar registers
   const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
@@ -83,7 +115,7 @@ __global__ __launch_bounds__(256) void knn_qgroup_kernel(int n, int C, const flo
   const int gq = __builtin_amdgcn_readfirstlane(wg * 4 + (threadIdx.x >> 6));
   const int c = gq / GPC, sub = gq % GPC;
   if (c >= C) return;       // whole wavefront
-  if (*guard != 0) return;  // see knn_chunk_kernel
+  if (*guard != 0) return;  // the cloud's extent is not finite or beyond the FP32 chunk test's range (knn.hip: curve_key_kernel): the caller answers otherwise
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
 
   // the Q queries (wave-uniform).  Padding queries at the end of the last chunk repeat the group's first query (they never widen the search)
@@ -301,6 +333,8 @@ void launch_qgroup(hipStream_t st, int n, int C, const float4* sorted, const flo
 }  // namespace
 
 namespace glim_amd {
+
+void knn_launch_group_boxes(hipStream_t st, int C, float* box) { group_box_kernel<<<((C + CHUNK - 1) / CHUNK + 3) / 4, 256, 0, st>>>(C, box); }
 
 void knn_launch_qgroup(hipStream_t st, int n, int C, const float4* sorted, float* box, int k, int32_t* out, const int* guard, int queries_per_wave, int* dbg) {
   knn_launch_group_boxes(st, C, box);

@@ -19,8 +19,8 @@ extern "C" {
 /* ---- diagnostic / tuning switches ------------------------------------------------------------------------------ */
 /* Diagnostic / tuning switches of a context (no counterpart in the reference; none is needed in production).  key_values:
  * "key=value,key=value"; NULL or "" restores the process defaults, which come from the ONE environment variable the library reads,
- * GLIM_AMD_DIAG (same syntax, parsed once per process).  Keys: knn_path=auto|grid|chunks|brute, knn_kernel=auto|wave64|pair|qgroup,
- * knn_select=0|1, plane=0|1, curve_order=0|1, ppt=<n>, poll=0|1, inline_pose=0|1, bucket_factor=<n>, plan_cache=0|1, plan_recycle=0|1, host_poses=0|1, host_pack=0|1, pull_gated=0|1, frame_fused=0|1,
+ * GLIM_AMD_DIAG (same syntax, parsed once per process).  Keys: knn_path=auto|brute (brute: the exhaustive kNN kernel answers
+ * at every size), plane=0|1, curve_order=0|1, ppt=<n>, poll=0|1, inline_pose=0|1, bucket_factor=<n>, plan_cache=0|1, plan_recycle=0|1, host_poses=0|1, host_pack=0|1, pull_gated=0|1, frame_fused=0|1,
  * view_fused=0|1 (a voxel map built from a plane-form cloud gets its plane view -- the (C_B + I)^-1 records the plane-form factor kernel reads --
  * from the map's own finalise kernel; 0: on the first factor that needs it),
  * fuse=0|1 (small synchronous sets in ONE dispatch), host_rotate=0|1 (linearisations of the smallest such sets, and of a resident session's, return
@@ -126,7 +126,7 @@ int glim_amd_factor_set_profile_fresh_samples(glim_amd_ctx* ctx, int32_t n, cons
 int glim_amd_factor_set_profile_lm(glim_amd_factor_set* set, const double* T_target_source, int iters, float* ms_linearize, float* ms_error);
 /* timing aid: `iters` calls of glim_amd_cloud_find_neighbors with this k; wall milliseconds per call, and the HIP-event duration (events on the call's own
  * stream) of the query-group kernel inside it -- the dominant kernel of the kNN-led workloads, whose roofline bench.py quotes (0 when another kernel
- * answered: clouds <= 2 048 points, forced knn_path / knn_kernel). */
+ * answered: clouds <= 2 048 points, knn_path=brute). */
 int glim_amd_cloud_profile_neighbors(glim_amd_cloud* cloud, int k, int iters, float* ms_per_call, float* ms_qgroup_kernel);
 /* timing aid: `iters` back-to-back glim_amd_overlap_batch calls with these arguments; microseconds per call, measured inside the library. */
 int glim_amd_overlap_profile(glim_amd_ctx* ctx, int32_t num_queries, const int32_t* num_targets, const glim_amd_voxelmap* const* targets,

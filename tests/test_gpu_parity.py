@@ -647,32 +647,55 @@ def test_plane_view_written_with_the_map_equals_the_one_built_on_first_use(api, 
     assert np.abs(gn_step(Lg) - gn_step(Lc)).max() < 1e-6
 
 
-def test_knn_chunk_and_grid_paths_agree(api, ctx, orc):
-    """The two device kNN implementations (Hilbert-ordered chunks, hashed grid) and the oracle give identical lists, also on a cloud
-    with a strongly non-uniform density, exact duplicates and a size that is not a multiple of the chunk length."""
-    rng = np.random.default_rng(11)
-    dense = rng.normal(size=(20000, 3)) * [0.05, 0.05, 0.02]
-    sparse = rng.uniform(-30, 30, size=(9000, 3)) * [1, 1, 0.1]
-    line = np.c_[np.linspace(0, 40, 2937), np.zeros(2937), np.zeros(2937)]
-    pts = np.vstack([dense, sparse, line, dense[:500]]).astype(np.float32)  # the last 500 duplicate earlier points exactly
+def _knn_mixture(rng, dense_n, sparse_n, line_n, dup_n):
+    """Strongly non-uniform density: a dense blob, a sparse slab, a line, and exact duplicates of the blob's first points."""
+    dense = rng.normal(size=(dense_n, 3)) * [0.05, 0.05, 0.02]
+    sparse = rng.uniform(-30, 30, size=(sparse_n, 3)) * [1, 1, 0.1]
+    line = np.c_[np.linspace(0, 40, line_n), np.zeros(line_n), np.zeros(line_n)]
+    return np.vstack([dense, sparse, line, dense[:dup_n]]).astype(np.float32)
+
+
+def test_knn_default_and_exhaustive_paths_agree(api, ctx, orc):
+    """The two device kNN implementations (Hilbert-ordered chunks with the query-group kernel, the exhaustive kernel) and the oracle give
+    identical lists, also on a cloud with a strongly non-uniform density, exact duplicates and a size that is not a multiple of the chunk length."""
+    pts = _knn_mixture(np.random.default_rng(11), 20000, 9000, 2937, 500)  # 32 437 points; the last 500 duplicate earlier points exactly
     ref = orc.knn(pts.astype(np.float64), 10)
     g = api.PointCloudGPU.clone(pts, ctx=ctx)
-    got_chunk = g.find_neighbors(10)  # the default: the query-group kernel (knn_qgroup.hip), 2 queries per wavefront at this size
-    for variant in ("wave64", "pair"):  # the lane-per-query kernels
-        with ctx.diag(f"knn_kernel={variant}"):
-            np.testing.assert_array_equal(g.find_neighbors(10), ref)
-    with ctx.diag("knn_path=grid"):
-        got_grid = g.find_neighbors(10)
-    np.testing.assert_array_equal(got_chunk, ref)
-    np.testing.assert_array_equal(got_grid, ref)
+    got_default = g.find_neighbors(10)  # the default: the query-group kernel (knn_qgroup.hip), ONE query per wavefront at this size (< 49 152)
+    with ctx.diag("knn_path=brute"):
+        got_brute = g.find_neighbors(10)
+    np.testing.assert_array_equal(got_default, ref)
+    np.testing.assert_array_equal(got_brute, ref)
     for k in (1, 5, 16, 32):
-        np.testing.assert_array_equal(g.find_neighbors(k), orc.knn(pts.astype(np.float64), k))
-    # small clouds default to the grid path; the chunk path must agree there too (last chunk partially filled)
+        ref_k = orc.knn(pts.astype(np.float64), k)
+        np.testing.assert_array_equal(g.find_neighbors(k), ref_k)
+        if k == 32:
+            with ctx.diag("knn_path=brute"):
+                np.testing.assert_array_equal(g.find_neighbors(k), ref_k)
+    # a small cloud (4 634 points: still above the exhaustive kernel's 2 048, so the default is the query-group kernel; last chunk partially filled)
     small = api.PointCloudGPU.clone(pts[::7], ctx=ctx)
     ref_small = orc.knn(pts[::7].astype(np.float64), 10)
     np.testing.assert_array_equal(small.find_neighbors(10), ref_small)
-    with ctx.diag("knn_path=chunks"):
+    with ctx.diag("knn_path=brute"):
         np.testing.assert_array_equal(small.find_neighbors(10), ref_small)
+
+
+@pytest.mark.parametrize("n", [2049, 2112, 4097, 32768 + 5, 49152 + 37])
+def test_knn_curve_branches_agree_with_the_exhaustive_kernel(api, ctx, orc, n):
+    """The branches of knn_curve at their edges, default == exhaustive kernel == oracle: just above the exhaustive kernel's 2 048 points with a
+    last chunk of 1 (2 049), 64 (2 112) and 1 (4 097) points; 13 Hilbert bits and still one query per wavefront (32 773); two queries per
+    wavefront, an odd count and a partial last chunk (49 189)."""
+    sparse_n, line_n, dup_n = n // 4, n // 11, n // 64
+    pts = _knn_mixture(np.random.default_rng(n), n - sparse_n - line_n - dup_n, sparse_n, line_n, dup_n)
+    assert len(pts) == n
+    ref = orc.knn(pts.astype(np.float64), 10)
+    g = api.PointCloudGPU.clone(pts, ctx=ctx)
+    got_default = g.find_neighbors(10)
+    with ctx.diag("knn_path=brute"):
+        got_brute = g.find_neighbors(10)
+    np.testing.assert_array_equal(got_brute, ref)
+    np.testing.assert_array_equal(got_default, ref)
+    np.testing.assert_array_equal(got_default, got_brute)
 
 
 @pytest.mark.parametrize("name", ["lattice", "identical", "offset", "two_scales", "astronomic"])
@@ -691,23 +714,18 @@ def test_knn_exact_on_degenerate_distributions(api, ctx, orc, name):
     else:
         pts = np.vstack([rng.normal(size=(4000, 3)) * 0.01, rng.uniform(-50, 50, (3000, 3))])
     pts = pts.astype(np.float32)
-    ref = orc.knn(pts.astype(np.float64), 10, method="brute")
     g = api.PointCloudGPU.clone(pts, ctx=ctx)
-    for variant in ("wave64", "pair", "qgroup"):  # 64 queries per wavefront / 32 queries with two lanes each / lanes = candidates
-        with ctx.diag(f"knn_path=chunks,knn_kernel={variant}"):
-            np.testing.assert_array_equal(g.find_neighbors(10), ref)
-            for k in (3, 16, 32):
-                np.testing.assert_array_equal(g.find_neighbors(k), orc.knn(pts.astype(np.float64), k, method="brute"))
-    if name == "astronomic":
-        return
-    with ctx.diag("knn_path=grid"):
-        np.testing.assert_array_equal(g.find_neighbors(10), ref)
+    for k in (10, 3, 16, 32):
+        ref = orc.knn(pts.astype(np.float64), k, method="brute")
+        np.testing.assert_array_equal(g.find_neighbors(k), ref)  # default: the query-group kernel ("astronomic": its hand-over)
+        with ctx.diag("knn_path=brute"):
+            np.testing.assert_array_equal(g.find_neighbors(k), ref)
 
 
 @pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
 def test_knn_refuses_non_finite_points_and_the_context_survives(api, ctx, orc, bad):
-    """A non-finite coordinate is an error (GLIM_AMD_ERR_RANGE), found on the device: the bounding box never travels to the host, the chunk
-    kernels stand down behind their guard word.  The next call on the same context answers as usual."""
+    """A non-finite coordinate is an error (GLIM_AMD_ERR_RANGE), found on the device: the bounding box never travels to the host, the
+    query-group kernel stands down behind its guard word.  The next call on the same context answers as usual."""
     from glim_amd._lib import GlimAmdError
 
     rng = np.random.default_rng(11)
@@ -715,18 +733,15 @@ def test_knn_refuses_non_finite_points_and_the_context_survives(api, ctx, orc, b
     ref = orc.knn(pts.astype(np.float64), 10, method="brute")
     broken = pts.copy()
     broken[1234, 1] = bad
-    for variant in ("wave64", "pair", "qgroup"):
-        with ctx.diag(f"knn_path=chunks,knn_kernel={variant}"):
-            with pytest.raises(GlimAmdError) as err:
-                api.PointCloudGPU.clone(broken, ctx=ctx).find_neighbors(10)
-            assert err.value.code == -4
-            np.testing.assert_array_equal(api.PointCloudGPU.clone(pts, ctx=ctx).find_neighbors(10), ref)
+    with pytest.raises(GlimAmdError) as err:
+        api.PointCloudGPU.clone(broken, ctx=ctx).find_neighbors(10)
+    assert err.value.code == -4
+    np.testing.assert_array_equal(api.PointCloudGPU.clone(pts, ctx=ctx).find_neighbors(10), ref)
 
 
-def test_knn_threshold_selection_is_exact(api, ctx, orc):
-    """The per-lane threshold selection of the chunk kernels (knn_chunks.hip; the default for k <= 10) must leave every neighbour list
-    bit-identical: both kernels (64 queries per wavefront / pair lanes), k = 10 and k = 5 (the two list sizes it is instantiated for), with the
-    selection on (default) and off (diag knn_select=0), on ties, duplicates, a far offset, two scales and a real scan."""
+def test_knn_is_exact_on_ties_duplicates_offsets_and_a_scan(api, ctx, orc):
+    """Default path == exhaustive kernel == oracle, bit-identical lists for k = 10 and k = 5, on ties, duplicates, a far offset, two scales and
+    a real scan (the six clouds the retired per-lane threshold selection was held to)."""
     from glim_amd import synth
 
     rng = np.random.default_rng(5)
@@ -743,25 +758,28 @@ def test_knn_threshold_selection_is_exact(api, ctx, orc):
         g = api.PointCloudGPU.clone(pts, ctx=ctx)
         for k in (10, 5):
             ref = orc.knn(pts.astype(np.float64), k, method="brute")
-            for select in (1, 0):
-                for variant in ("wave64", "pair", "qgroup"):
-                    with ctx.diag(f"knn_path=chunks,knn_kernel={variant},knn_select={select}"):
-                        np.testing.assert_array_equal(g.find_neighbors(k), ref, err_msg=f"{name} k={k} {variant} select={select}")
+            np.testing.assert_array_equal(g.find_neighbors(k), ref, err_msg=f"{name} k={k} default")
+            with ctx.diag("knn_path=brute"):
+                np.testing.assert_array_equal(g.find_neighbors(k), ref, err_msg=f"{name} k={k} exhaustive")
 
 
 def test_diag_switches_parse_and_reject(api, ctx):
     """glim_amd_ctx_set_diag: known keys change the context's switches, unknown keys / bad values change nothing; "" restores the defaults."""
     base = ctx.get_diag()
-    assert base["knn_path"] == "auto" and base["plane"] == "1" and base["knn_select"] == "1" and base["resident"] == "auto"
-    with ctx.diag("knn_path=grid,ppt=3"):
-        assert ctx.get_diag()["knn_path"] == "grid" and ctx.get_diag()["ppt"] == "3"
+    assert base["knn_path"] == "auto" and base["plane"] == "1" and base["resident"] == "auto"
+    with ctx.diag("knn_path=brute,ppt=3"):
+        assert ctx.get_diag()["knn_path"] == "brute" and ctx.get_diag()["ppt"] == "3"
         ctx.set_diag("plane=0")  # set_diag ADDS to the switches in force
-        assert ctx.get_diag()["knn_path"] == "grid" and ctx.get_diag()["plane"] == "0"
-        # pool / multi_rccl / multi_host_gather are process-wide (GLIM_AMD_DIAG only): a context refuses them instead of accepting a no-op
-        for bad in ("no_such_key=1", "knn_path=fast", "ppt=-1", "plane", "pool=0", "plane=0,multi_rccl=0", "multi_host_gather=1", "resident=2"):
+        assert ctx.get_diag()["knn_path"] == "brute" and ctx.get_diag()["plane"] == "0"
+        in_force = ctx.get_diag()
+        # pool / multi_rccl / multi_host_gather are process-wide (GLIM_AMD_DIAG only): a context refuses them instead of accepting a no-op;
+        # knn_kernel, knn_select and the knn_path words grid / chunks belonged to the retired kNN kernels
+        for bad in ("no_such_key=1", "knn_path=fast", "ppt=-1", "plane", "pool=0", "plane=0,multi_rccl=0", "multi_host_gather=1", "resident=2",
+                    "knn_kernel=pair", "knn_select=0", "knn_path=grid", "knn_path=chunks"):
             with pytest.raises(api.GlimAmdError):
                 ctx.set_diag(bad)
-            assert ctx.get_diag()["knn_path"] == "grid"
+            assert ctx.get_diag()["knn_path"] == "brute"
+            assert ctx.get_diag() == in_force
     assert ctx.get_diag() == base  # the scope restores the process defaults
     with pytest.raises(RuntimeError):
         with ctx.diag("plane=0"):

@@ -1,7 +1,7 @@
-"""CPU model of the pair-lane kNN kernel (glim_amd/csrc/knn_pairs.hip): 32 queries per wavefront, two lanes per query with separate top-k lists over
-disjoint candidates and a shared pruning bound, lists merged at the end.  Like tools/knn_model.py it follows the kernel step by step and counts the
-lock-step insertion rounds; it exists to check, without a GPU, that the per-lane threshold selection of the chunk kernels leaves the merged
-lists exact in THIS kernel too (a lane selects over its own list only) and to price it.  A design tool, not an oracle.
+"""CPU model of the retired pair-lane kNN kernel (glim_amd/csrc/knn.hip, "measured and retired"; git log has the kernel): 32 queries per wavefront, two
+lanes per query with separate top-k lists over disjoint candidates and a shared pruning bound, lists merged at the end.  It follows that kernel step
+by step and counts the lock-step insertion rounds; it was written to check, without a GPU, that the per-lane threshold selection of the lane-per-query
+kernels leaves the merged lists exact (a lane selects over its own list only) and to price it.  A design tool, not an oracle.
 
   python tools/knn_pair_model.py        # 65 536-pt scan: rounds with / without the selection, lists compared with the exhaustive answer
 """
@@ -12,7 +12,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from knn_model import hilbert_keys  # noqa: E402
+from knn_qgroup_model import hilbert_keys  # noqa: E402  (curve_key_kernel's keys)
 
 Q, K = 32, 10
 f32 = np.float32

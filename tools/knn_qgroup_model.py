@@ -14,11 +14,48 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from knn_model import hilbert_keys  # noqa: E402  (tools/knn_model.py: curve_key_kernel's keys)
 
 CHUNK = 64
 F32 = np.float32
 INF32 = F32(np.inf)
+
+
+def hilbert_keys(pts, bits=13):
+    """curve_key_kernel: quantise to `bits` per axis over the bounding box (largest extent), Skilling's transform, interleave."""
+    p = pts.astype(np.float32)
+    lo = p.min(axis=0)
+    ext = np.float32((p.max(axis=0) - lo).max())
+    qmax = np.uint32((1 << bits) - 1)
+    scale = np.float32(qmax) / ext if ext > 0 else np.float32(0)
+    X = [np.minimum(qmax, np.maximum(np.float32(0), (p[:, a] - lo[a]) * scale).astype(np.uint32)) for a in range(3)]
+    M = np.uint32(1 << (bits - 1))
+    Q = M
+    while Q > 1:
+        P = np.uint32(Q - 1)
+        for a in range(3):
+            hit = (X[a] & Q) != 0
+            t = np.where(hit, np.uint32(0), (X[0] ^ X[a]) & P)
+            X[0] = np.where(hit, X[0] ^ P, X[0] ^ t)
+            if a != 0:
+                X[a] = X[a] ^ t
+        Q = np.uint32(Q >> 1)
+    X[1] ^= X[0]
+    X[2] ^= X[1]
+    t = np.zeros_like(X[0])
+    Q = M
+    while Q > 1:
+        t = np.where((X[2] & Q) != 0, t ^ np.uint32(Q - 1), t)
+        Q = np.uint32(Q >> 1)
+    X = [x ^ t for x in X]
+
+    def spread3(v):
+        out = np.zeros(len(v), dtype=np.uint64)
+        v = v.astype(np.uint64)
+        for b in range(bits):
+            out |= ((v >> np.uint64(b)) & np.uint64(1)) << np.uint64(3 * b)
+        return out
+
+    return spread3(X[2]) | (spread3(X[1]) << np.uint64(1)) | (spread3(X[0]) << np.uint64(2))
 
 
 def _fma32(a, b, c):

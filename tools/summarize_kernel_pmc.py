@@ -1,4 +1,4 @@
-"""Per-kernel averages of rocprofv3 --pmc passes (tools/round_evidence_r06.sh) for ONE kernel picked by a name fragment: writes a small JSON.
+"""Per-kernel averages of rocprofv3 --pmc passes (one run per counter group, a kernel-trace run beside them) for ONE kernel picked by a name fragment: writes a small JSON.
 
   python tools/summarize_kernel_pmc.py <prof dir with pass sub-directories> <kernel name fragment> <out.json> [key=value ...]
 
@@ -32,7 +32,7 @@ key = max(counters, key=lambda k: sum(durations.get(k, [0.0])) or len(next(iter(
 avg = {c: sum(v) / len(v) for c, v in counters[key].items()}
 out = {"kernel": key[0][:200], "grid": key[1], "dispatches_per_counter": {c: len(v) for c, v in counters[key].items()}, "counters_avg_per_dispatch": avg,
        "kernel_avg_us_rocprof": (sum(durations[key]) / len(durations[key])) if durations.get(key) else None,
-       "source": "rocprofv3 --pmc passes, one run per counter group (tools/round_evidence_r06.sh), averages over the dispatches of this kernel / grid"}
+       "source": "rocprofv3 --pmc passes, one run per counter group with no tracing option, averages over the dispatches of this kernel / grid"}
 out.update(extra)
 if "TCC_EA0_RDREQ_128B_sum" in avg:
     read = 32.0 * avg.get("TCC_EA0_RDREQ_32B_sum", 0.0) + 64.0 * avg.get("TCC_EA0_RDREQ_64B_sum", 0.0) + 128.0 * avg["TCC_EA0_RDREQ_128B_sum"]
