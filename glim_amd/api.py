@@ -893,13 +893,9 @@ class NonlinearFactorSetGPU:
         return corr
 
     def cull_stats(self, reset=False):
-        """(trips culled by the pre-pass, trips that hold points) since the last reset, or None when the plan has no pre-cull (glim_amd_factor_set_cull_stats)."""
-        a, b = C.c_uint64(), C.c_uint64()
-        rc = lib().glim_amd_factor_set_cull_stats(self._h, C.byref(a), C.byref(b), int(bool(reset)))
-        if rc == -6:
-            return None
-        check(rc, "glim_amd_factor_set_cull_stats")
-        return a.value, b.value
+        """Always None: the pre-cull of the general-form factor kernel is retired (measured on the global-map workload the pre-pass cost more than the
+        walk it saved: profiles/r06/probe/precull_ab_take1_thread_per_row.json, precull_ab_take2_lane_per_trip.json).  Kept because bench.py asks."""
+        return None
 
     def linearize_device_async(self, T_target_source, out_device_ptr, row_offset=0):
         T = T_target_source

@@ -63,7 +63,6 @@ const DiagKey kDiagKeys[] = {
   {"resident", &Diag::resident, kResidentWords, 0, 2},
   {"resident_idle_us", &Diag::resident_idle_us, nullptr, 100, 1000000},
   {"resident_post", &Diag::resident_post, kResidentPostWords, 0, 2},
-  {"cull", &Diag::cull, nullptr, 0, 2},
   {"small_rows", &Diag::small_rows, nullptr, 0, 4096},
   {"pool", &Diag::pool, nullptr, 0, 1},
   {"multi_rccl", &Diag::multi_rccl, nullptr, 0, 1},

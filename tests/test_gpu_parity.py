@@ -767,17 +767,19 @@ def test_diag_switches_parse_and_reject(api, ctx):
     """glim_amd_ctx_set_diag: known keys change the context's switches, unknown keys / bad values change nothing; "" restores the defaults."""
     base = ctx.get_diag()
     assert base["knn_path"] == "auto" and base["plane"] == "1" and base["resident"] == "auto"
+    assert not any("cull" in k or "cull" in v for k, v in base.items())  # (get_diag returns the string of glim_amd_ctx_get_diag, split)
     with ctx.diag("knn_path=brute,ppt=3"):
         assert ctx.get_diag()["knn_path"] == "brute" and ctx.get_diag()["ppt"] == "3"
         ctx.set_diag("plane=0")  # set_diag ADDS to the switches in force
         assert ctx.get_diag()["knn_path"] == "brute" and ctx.get_diag()["plane"] == "0"
         in_force = ctx.get_diag()
         # pool / multi_rccl / multi_host_gather are process-wide (GLIM_AMD_DIAG only): a context refuses them instead of accepting a no-op;
-        # knn_kernel, knn_select and the knn_path words grid / chunks belonged to the retired kNN kernels
+        # knn_kernel, knn_select and the knn_path words grid / chunks belonged to the retired kNN kernels, cull to the retired pre-cull
         for bad in ("no_such_key=1", "knn_path=fast", "ppt=-1", "plane", "pool=0", "plane=0,multi_rccl=0", "multi_host_gather=1", "resident=2",
-                    "knn_kernel=pair", "knn_select=0", "knn_path=grid", "knn_path=chunks"):
-            with pytest.raises(api.GlimAmdError):
+                    "knn_kernel=pair", "knn_select=0", "knn_path=grid", "knn_path=chunks", "cull=0", "cull=1", "cull=2"):
+            with pytest.raises(api.GlimAmdError) as refused:
                 ctx.set_diag(bad)
+            assert refused.value.code == -1  # GLIM_AMD_ERR_INVALID
             assert ctx.get_diag()["knn_path"] == "brute"
             assert ctx.get_diag() == in_force
     assert ctx.get_diag() == base  # the scope restores the process defaults

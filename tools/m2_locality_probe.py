@@ -2,7 +2,7 @@
 """What bounds the general-form factor kernel on configs[3] -- vector-ALU issue or the memory system?  
 
 The all-pairs cost streams 256 clouds / maps (0.7 GB) through 32 MiB of L2 and the 256 MiB Infinity Cache; the instruction-mix model of DESIGN 4.1
-fits its absolute time but has over-predicted every instruction-count saving (FP32 transform, packed FP32, pre-cull).  This probe runs the SAME
+fits its absolute time but has over-predicted every instruction-count saving (FP32 transform, packed FP32, the pre-cull of round 6 -- since deleted).  This probe runs the SAME
 kernel, the SAME number of factors and (to within sampling) the same mix of inlier fractions over working sets of different size:
 
   all_pairs          the 32 640 pairs of 256 submaps, source-major (bench.py's configs[3])
