@@ -250,6 +250,18 @@ class BundleTraceRound(C.Structure):
     _fields_ = [("lam", C.c_double), ("cost", C.c_double), ("accepted", C.c_int32), ("status", C.c_int32)]
 
 
+class GraphDamping(C.Structure):
+    """glim_amd_graph_damping (include/glim_amd.h "Damping terms and Huber between terms")"""
+
+    _fields_ = [("pose", C.c_int32), ("reserved", C.c_int32), ("diagonal", C.c_double * 6)]
+
+
+class GraphTerms(C.Structure):
+    """glim_amd_graph_terms"""
+
+    _fields_ = [("dampings", C.POINTER(GraphDamping)), ("num_dampings", C.c_int32), ("reserved", C.c_int32), ("between_huber_width", C.POINTER(C.c_double))]
+
+
 class BaParams(C.Structure):
     """glim_amd_ba_params (include/glim_amd.h "Plane / edge bundle-adjustment factors and ball selection")"""
 
@@ -464,6 +476,16 @@ SYMBOLS = {
     "glim_amd_graph_align_default_params": (_i, [C.POINTER(LMParams)]),
     "glim_amd_graph_align": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
                                   C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult)]),
+    "glim_amd_bundle_align_terms": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                         C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), C.POINTER(GraphTerms), _dp]),
+    "glim_amd_graph_align_terms": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                        C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), C.POINTER(GraphTerms), _dp]),
+    "glim_amd_debug_bundle_align_terms_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp,
+                                                     _i32, C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), C.POINTER(GraphTerms), _dp, _i32, _dp, _dp,
+                                                     _dp, C.POINTER(BundleTraceRound)]),
+    "glim_amd_debug_graph_align_terms_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp,
+                                                    _i32, C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), C.POINTER(GraphTerms), _dp, _i32, _dp, _dp,
+                                                    _dp, C.POINTER(BundleTraceRound), _i32]),
     "glim_amd_debug_graph_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
                                               C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
                                               C.POINTER(BundleTraceRound), _i32]),

@@ -861,7 +861,7 @@ class NonlinearFactorSetGPU:
         self.last_error_inliers = inl
         return list(err)
 
-    def _optimize(self, align, name, values, priors, betweens, params):
+    def _optimize(self, align, name, values, priors, betweens, params, dampings=()):
         if any(not f.is_binary for f in self.factors):
             raise GlimAmdError(-1, "NonlinearFactorSetGPU." + name, "a unary factor: the bundle is over binary factors")
         validation = {f.enable_surface_validation for f in self.factors}
@@ -870,20 +870,22 @@ class NonlinearFactorSetGPU:
         keys = sorted(values)
         at = {k: i for i, k in enumerate(keys)}
         res = align([(f.target_voxelmap, f.source, at[f.target_key], at[f.source_key]) for f in self.factors],
-                    [(at[k], P, info) for k, P, info in priors], [(at[i], at[j], D, info) for i, j, D, info in betweens],
-                    [values[k] for k in keys], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx)
+                    [(at[k], P, info) for k, P, info in priors], [(at[b[0]], at[b[1]]) + tuple(b[2:]) for b in betweens],
+                    [values[k] for k in keys], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx,
+                    dampings=[(at[k], d) for k, d in dampings])
         return {k: res.poses[i] for i, k in enumerate(keys)}, res
 
-    def optimize(self, values, priors=(), betweens=(), params=None):
+    def optimize(self, values, priors=(), betweens=(), params=None, dampings=()):
         """The sub-map bundle optimisation over this set's factors, which must all be binary (bundle_align; the loop of sub_mapping.cpp:430-452
         with its PriorFactor and BetweenFactor terms).  values: {key: 4 x 4}; priors: (key, P 4 x 4, information 6 x 6); betweens: (key_i, key_j,
-        D 4 x 4, information 6 x 6).  The poses are ordered by sorted key.  Returns ({key: 4 x 4}, BundleResult).  The set itself is untouched."""
-        return self._optimize(bundle_align, "optimize", values, priors, betweens, params)
+        D 4 x 4, information 6 x 6[, Huber width]); dampings: (key, scale or 6 values), as bundle_align has them.  The poses are ordered by sorted
+        key.  Returns ({key: 4 x 4}, BundleResult).  The set itself is untouched."""
+        return self._optimize(bundle_align, "optimize", values, priors, betweens, params, dampings)
 
-    def optimize_graph(self, values, priors=(), betweens=(), params=None):
+    def optimize_graph(self, values, priors=(), betweens=(), params=None, dampings=()):
         """optimize() through the global-graph optimisation (graph_align; global_mapping.cpp:430-484): the same arguments and returns, up to
         _lib.GRAPH_MAX_POSES poses and _lib.GRAPH_MAX_FACTORS factors."""
-        return self._optimize(graph_align, "optimize_graph", values, priors, betweens, params)
+        return self._optimize(graph_align, "optimize_graph", values, priors, betweens, params, dampings)
 
     def correspondences(self, index, delta):
         n = self.factors[index].source.size()
@@ -1668,10 +1670,12 @@ def bundle_align_params(**kw):
 
 class BundleResult:
     """glim_amd_bundle_align's answer: the last kept poses (N x 4 x 4), the cost there and its three parts, the factors' inliers, the counts,
-    the status (ALIGN_STATUS), the lambda after the last trial and the F compact records at the poses."""
+    the status (ALIGN_STATUS), the lambda after the last trial and the F compact records at the poses.  between_weights: the Q Huber weights of
+    the evaluation at the poses (glim_amd_*_align_terms), or None from a call without damping terms and Huber widths."""
 
-    def __init__(self, c, X, compact):
+    def __init__(self, c, X, compact, between_weights=None):
         self.poses = X
+        self.between_weights = between_weights
         self.cost, self.factor_cost, self.prior_cost, self.between_cost = c.cost, c.factor_cost, c.prior_cost, c.between_cost
         self.num_inliers = c.num_inliers
         self.iterations, self.trials, self.status = c.iterations, c.trials, c.status
@@ -1712,19 +1716,44 @@ def _bundle_args(factors, priors, betweens, X_init, ctx):
     return ctx, (ctx._h, th, sh, _ip(ti), _ip(si), F), (cp, P, cb, Q, _dp(X), N), (ti, si, X)
 
 
-def _align_poses(entry, factors, priors, betweens, X_init, flags, params, ctx):
-    """glim_amd_bundle_align or glim_amd_graph_align: the same arguments and results"""
+def _graph_terms(betweens, dampings):
+    """The damping terms and the Huber widths (a between's fifth element) of a call -> (the betweens without widths, the arguments behind
+    `result` of a glim_amd_*_align_terms entry, the weights' array, what must stay alive); all None but the betweens when the call has neither:
+    the entry point without `_terms` is then called as it always was."""
+    betweens, dampings = list(betweens), list(dampings)
+    if not dampings and not any(len(b) > 4 for b in betweens):
+        return betweens, None, None, None
+    D, Q = len(dampings), len(betweens)
+    cd = (_lib.GraphDamping * max(D, 1))()
+    for c, (k, d) in zip(cd, dampings):
+        c.pose = int(k)
+        c.diagonal[:] = list(np.broadcast_to(np.asarray(d, dtype=np.float64).reshape(-1), (6,)))
+    widths = np.array([float(b[4]) if len(b) > 4 else 0.0 for b in betweens], dtype=np.float64).reshape(Q)
+    terms = _lib.GraphTerms(C.cast(cd, C.POINTER(_lib.GraphDamping)), D, 0, _dp(widths) if any(len(b) > 4 for b in betweens) else None)
+    weights = np.zeros(Q)
+    return [tuple(b[:4]) for b in betweens], (C.byref(terms), _dp(weights)), weights, (cd, widths, terms)
+
+
+def _align_poses(entry, factors, priors, betweens, X_init, flags, params, ctx, dampings=()):
+    """glim_amd_bundle_align or glim_amd_graph_align, or their `_terms` forms: the same arguments and results"""
+    betweens, terms, weights, alive = _graph_terms(betweens, dampings)
     ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
     F, N = fa[-1], ta[-1]
     prm = (params or bundle_align_params())._c()
     X_out, compact, out = np.zeros((N, 12)), np.zeros((F, _lib.COMPACT_DOUBLES)), _lib.BundleResult()
-    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out)), entry)
-    return BundleResult(out, _poses44(X_out), compact)
+    if terms:
+        entry += "_terms"
+    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), *(terms or ())), entry)
+    return BundleResult(out, _poses44(X_out), compact, weights)
 
 
-def _align_poses_trace(entry, more, factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace):
-    """glim_amd_debug_bundle_align_trace or glim_amd_debug_graph_align_trace (`more`: the arguments behind the trace arrays)"""
+def _align_poses_trace(entry, more, factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace, dampings=()):
+    """glim_amd_debug_bundle_align_trace or glim_amd_debug_graph_align_trace, or their `_terms` forms (`more`: the arguments behind the trace
+    arrays)"""
     params = params or bundle_align_params()
+    betweens, terms, weights, alive = _graph_terms(betweens, dampings)
+    if terms:
+        entry = entry.replace("_trace", "_terms_trace")
     ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, X_init, ctx)
     F, N = fa[-1], ta[-1]
     rounds = 1 + params.resolved_max_trials()
@@ -1733,8 +1762,9 @@ def _align_poses_trace(entry, more, factors, priors, betweens, X_init, flags, pa
     tX, tTf, trec = np.zeros((rounds, N, 12)), np.zeros((rounds, F, 12)), np.zeros((rounds, F, _lib.COMPACT_DOUBLES))
     tr = (_lib.BundleTraceRound * rounds)()
     targs = (_dp(tX), _dp(tTf), _dp(trec), tr) if trace else (None, None, None, None)
-    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), 1 if one_thread else 0, *targs, *more), entry)
-    res = BundleResult(out, _poses44(X_out), compact)
+    check(getattr(lib(), entry)(*fa, int(flags), *ta, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), *(terms or ()), 1 if one_thread else 0, *targs,
+                                *more), entry)
+    res = BundleResult(out, _poses44(X_out), compact, weights)
     rows = []
     if trace and N:
         for k in range(min(rounds, res.trials + 1)):
@@ -1743,22 +1773,23 @@ def _align_poses_trace(entry, more, factors, priors, betweens, X_init, flags, pa
     return res, rows, (tX, tTf, trec, tr)
 
 
-def bundle_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
+def bundle_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, dampings=()):
     """The sub-map bundle optimisation in one call and one host synchronisation: Levenberg-Marquardt over len(X_init) poses on binary VGICP
     factors, prior and between terms (sub_mapping.cpp:183-216, 430-452).  factors: (GaussianVoxelMapGPU, PointCloudGPU, target pose index,
     source pose index), evaluated at X_t^-1 X_s; priors: (pose index, P 4 x 4, information 6 x 6); betweens: (i, j, D 4 x 4, information 6 x 6);
     flags: 0 or FACTOR_SURFACE_VALIDATION.  Every trial record is what a NonlinearFactorSetGPU of the same pairs returns at the trial's relative
-    poses.  Returns a BundleResult."""
-    return _align_poses("glim_amd_bundle_align", factors, priors, betweens, X_init, flags, params, ctx)
+    poses.  A between may carry a fifth element, its Huber width (0: Gaussian); dampings: (pose index, scale or 6 diagonal values), the
+    LinearDampingFactor.  With either, glim_amd_bundle_align_terms is called and the result has between_weights.  Returns a BundleResult."""
+    return _align_poses("glim_amd_bundle_align", factors, priors, betweens, X_init, flags, params, ctx, dampings)
 
 
-def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True):
+def bundle_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True, dampings=()):
     """Test window (glim_amd_debug_bundle_align_trace): bundle_align's result plus one dict per round run -- round 0 is the initial poses -- with
     the candidate poses (`X`, N x 4 x 4), the relative poses as the device computed them (`Tf`, F x 12), the `compact` records there (F x 29), the
     `lam` the step was solved with, the `cost` the evaluation gave, `accepted` and the `status` after the round.  one_thread: the decide step is
     bundle_lm_step.hpp's step() in one device thread (the cross-check form).  trace=False: the result alone.  Returns (result, rows, the raw
     trace arrays of all 1 + max_trials rounds: X, Tf, compact, rounds)."""
-    return _align_poses_trace("glim_amd_debug_bundle_align_trace", (), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace)
+    return _align_poses_trace("glim_amd_debug_bundle_align_trace", (), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace, dampings)
 
 
 def graph_align_params(**kw):
@@ -1766,18 +1797,19 @@ def graph_align_params(**kw):
     return bundle_align_params(**kw)
 
 
-def graph_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None):
+def graph_align(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, dampings=()):
     """The global-graph optimisation (glim_amd_graph_align; global_mapping.cpp:430-484 and that file's between factors): bundle_align's
     arguments, rule and BundleResult at up to _lib.GRAPH_MAX_POSES poses and _lib.GRAPH_MAX_FACTORS factors.  The systems live in device
     memory and a round is a sequence of launches; within the bundle's caps the result is bundle_align's, bit for bit."""
-    return _align_poses("glim_amd_graph_align", factors, priors, betweens, X_init, flags, params, ctx)
+    return _align_poses("glim_amd_graph_align", factors, priors, betweens, X_init, flags, params, ctx, dampings)
 
 
-def graph_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True, rounds_per_chunk=0):
+def graph_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=None, ctx=None, one_thread=False, trace=True, rounds_per_chunk=0, dampings=()):
     """Test window (glim_amd_debug_graph_align_trace): bundle_align_debug_trace's returns for graph_align.  one_thread: every round is
     bundle_lm_step.hpp's step() in one device thread with its system in device memory (the cross-check form; seconds beyond a few dozen poses).
     rounds_per_chunk: rounds enqueued between two looks at the status (0: the default); it moves no bit."""
-    return _align_poses_trace("glim_amd_debug_graph_align_trace", (int(rounds_per_chunk),), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace)
+    return _align_poses_trace("glim_amd_debug_graph_align_trace", (int(rounds_per_chunk),), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace,
+                              dampings)
 
 
 def graph_solve_debug(S, n, lam, ctx=None):

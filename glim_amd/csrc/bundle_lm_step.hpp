@@ -14,10 +14,20 @@
 //   terms      prior: r = Log(P^-1 X), J = J_r(r)^-1.  between: r = Log(D^-1 X_i^-1 X_j), J = [-J_r(r)^-1 Ad((X_i^-1 X_j)^-1) | J_r(r)^-1].  Each
 //              adds J^T L J to H, J^T L r to b and r^T L r to the cost (term_products; L = the information, of which only the upper triangle
 //              is read; L r and L J are formed first, sums ascending from +0.0).
+//   huber      a between q may carry a width k_q >= 0 (Graph::bw; 0 or no array: the Gaussian between above, its bits untouched).  After
+//              term_products: s = sqrt(c), c = r^T L r.  The between is down-weighted iff k_q > 0 and s > k_q (false for a NaN): then
+//              w = k_q / s, each of the 144 + 12 stored values is multiplied once by w and the stored cost becomes k_q ((s + s) - k_q);
+//              otherwise w = 1.0 and nothing stored is touched.  This is gtsam's noiseModel::Robust::WhitenSystem and mEstimator::Huber::loss
+//              in this header's cost convention (cost = r^T L r, twice gtsam's error).  The weights of the last KEPT evaluation are kept with
+//              the kept system (Problem::wk, copied from Problem::wt on accept).
+//   damping    a term (pose k, d[6]) is gtsam_points::LinearDampingFactor: from upstream recall its error() is 0 and its linearize() a
+//              Hessian factor with G = diag(d), g = 0, f = 0 (the factor's source is not in the reference tree).  It adds d[m]
+//              to entry (6k + m, 6k + m) of H and nothing to any other entry, to b or to the cost.  Several on one pose are allowed; a pose
+//              touched only by dampings has the block diag(sum d) + lambda I, the right-hand side +0.0 and a zero step.
 //   system     H dense symmetric 6N x 6N, kept as its lower triangle in packed rows (row i at i (i + 1) / 2), then b as row 6N.  Every entry is a
-//              sum from +0.0 over the items of its pose block in this order: factors by ascending index, then priors, then betweens
-//              (assemble_entry, assemble_rhs over the lists build_lists makes).  cost = ((sum_f e_f) + sum priors) + sum betweens, each
-//              ascending from +0.0.  "The cost at a candidate" comes from the LINEARISING evaluation: a trial is one evaluation.
+//              sum from +0.0 over the items of its pose block in this order: factors by ascending index, then priors, then betweens, then
+//              dampings (assemble_entry, assemble_rhs over the lists build_lists makes).  cost = ((sum_f e_f) + sum priors) + sum betweens,
+//              each ascending from +0.0.  "The cost at a candidate" comes from the LINEARISING evaluation: a trial is one evaluation.
 //   solve      (H + lambda I) delta = -b.  L[i][j] = (A[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j], the subtractions one at a time in ascending
 //              k (chol_pivot, chol_entry).  -b is carried as row 6N of A, so y = L^-1 (-b) is that row of L.  A pivot that is not > 0 or not
 //              finite is a FAILED solve: the candidate is then the kept poses and the trial is rejected.  Back substitution by columns:
@@ -51,7 +61,7 @@ namespace bundle_lm {
 
 constexpr int MAX_POSES = 32;
 constexpr int MAX_FACTORS = 1024;
-constexpr int MAX_TERMS = 1024;  // priors; and betweens
+constexpr int MAX_TERMS = 1024;  // priors; and betweens; and dampings
 constexpr int MAX_DIM = 6 * MAX_POSES;
 constexpr int PRIOR_STRIDE = 36 + 6 + 1;       // doubles of a prior's contribution: H (6 x 6), b, cost
 constexpr int BETWEEN_STRIDE = 144 + 12 + 1;   // of a between's: H (12 x 12, [i | j]), b, cost
@@ -60,7 +70,7 @@ GLIM_AMD_LM_HD inline int system_doubles(int n) { return tri(n) + n; }  // the p
 constexpr int MAX_SYSTEM = MAX_DIM * (MAX_DIM + 1) / 2 + MAX_DIM;
 
 // what an item of a pose block's list adds to the block (rows of pose hi, columns of pose lo, lo <= hi)
-enum { F_TT = 0, F_SS = 1, F_ST = 2, F_TS = 3, PRIOR = 4, B_II = 5, B_JJ = 6, B_JI = 7, B_IJ = 8 };
+enum { F_TT = 0, F_SS = 1, F_ST = 2, F_TS = 3, PRIOR = 4, B_II = 5, B_JJ = 6, B_JI = 7, B_IJ = 8, DAMP = 9 };
 
 struct Graph {
   int N, F, P, Q;
@@ -70,8 +80,13 @@ struct Graph {
   const int *bi, *bj;          // Q: poses of a between
   const double *bT, *bL;       //    its measurement (12) and information (36)
   const int *first, *items;    // lists: block (lo, hi) is entry tri(hi) + lo; its items are items[first[e] .. first[e + 1]), item = index << 4 | kind
+  int D = 0;                   // dampings
+  const int* dk = nullptr;     // D: pose of a damping
+  const double* dd = nullptr;  //    its diagonal (6)
+  const double* bw = nullptr;  // Q: Huber width of a between (0: Gaussian), or null: every between is Gaussian
 };
 GLIM_AMD_LM_HD inline int list_items(int F, int P, int Q) { return 3 * F + P + 3 * Q; }
+GLIM_AMD_LM_HD inline int list_items(int F, int P, int Q, int D) { return list_items(F, P, Q) + D; }
 
 // the lists, in the order of the sums.  first: tri(N) + 1 ints, items: list_items ints, cursor: tri(N) ints of workspace.  Host only.
 inline void build_lists(const Graph& g, int* first, int* items, int* cursor) {
@@ -108,6 +123,7 @@ inline void build_lists(const Graph& g, int* first, int* items, int* cursor) {
       if (i < j) put(i, j, q, B_JI);
       else put(j, i, q, B_IJ);
     }
+    for (int d = 0; d < g.D; d++) put(g.dk[d], g.dk[d], d, DAMP);
   }
 }
 
@@ -134,6 +150,8 @@ struct Problem {
   double* bc;     // BETWEEN_STRIDE Q: scratch
   double* W;      // system_doubles(6 N): scratch, the evaluated system and then the solve
   Scalars* s;
+  double* wt = nullptr;  // Q: scratch, the betweens' weights at the evaluation; or null: not recorded
+  double* wk = nullptr;  // Q: the weights of the kept evaluation; or null
 };
 
 // ---- items ------------------------------------------------------------------------------------------------------------------------------------
@@ -186,11 +204,28 @@ GLIM_AMD_BUNDLE_ITEM void prior_term(const Graph& g, const double* X, int p, dou
   term_products(Ji.m, 6, g.pL + 36 * p, r, pc + PRIOR_STRIDE * p);
 }
 
-GLIM_AMD_BUNDLE_ITEM void between_term(const Graph& g, const double* X, int q, double* bc) {
+// wt: the between's weight goes to wt[q] (1.0 unless down-weighted), or null
+GLIM_AMD_BUNDLE_ITEM void between_term(const Graph& g, const double* X, int q, double* bc, double* wt) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   double r[6], J[72];
+  double* out = bc + BETWEEN_STRIDE * q;
   ct_se3::between_residual(g.bT + 12 * q, X + 12 * g.bi[q], X + 12 * g.bj[q], r, J);
-  term_products(J, 12, g.bL + 36 * q, r, bc + BETWEEN_STRIDE * q);
+  term_products(J, 12, g.bL + 36 * q, r, out);
+  double w = 1.0;
+  const double k = g.bw ? g.bw[q] : 0.0;
+  if (k > 0.0) {
+    const double s = sqrt(out[156]);
+    if (s > k) {
+      w = k / s;
+      for (int u = 0; u < 156; u++) out[u] *= w;
+      out[156] = k * ((s + s) - k);
+    }
+  }
+  if (wt) wt[q] = w;
 }
+GLIM_AMD_LM_HD inline void between_term(const Graph& g, const double* X, int q, double* bc) { between_term(g, X, q, bc, nullptr); }
 
 // v[0] + v[stride] + ... (n values), ascending from +0.0
 GLIM_AMD_LM_HD inline double sum_ascending(const double* v, int n, int stride) {
@@ -216,7 +251,11 @@ GLIM_AMD_LM_HD inline double assemble_entry(const Graph& g, const glim_amd_linea
       case B_II: v = bc[BETWEEN_STRIDE * k + 12 * rr + cc]; break;
       case B_JJ: v = bc[BETWEEN_STRIDE * k + 12 * (rr + 6) + cc + 6]; break;
       case B_JI: v = bc[BETWEEN_STRIDE * k + 12 * (rr + 6) + cc]; break;
-      default: v = bc[BETWEEN_STRIDE * k + 12 * rr + cc + 6]; break;  // B_IJ
+      case B_IJ: v = bc[BETWEEN_STRIDE * k + 12 * rr + cc + 6]; break;
+      default:  // DAMP: the diagonal, and no other entry of the block
+        if (rr != cc) continue;
+        v = g.dd[6 * k + rr];
+        break;
     }
     s += v;
   }
@@ -236,7 +275,8 @@ GLIM_AMD_LM_HD inline double assemble_rhs(const Graph& g, const glim_amd_lineari
       case F_SS: v = lin[k].b_s[rr]; break;
       case PRIOR: v = pc[PRIOR_STRIDE * k + 36 + rr]; break;
       case B_II: v = bc[BETWEEN_STRIDE * k + 144 + rr]; break;
-      default: v = bc[BETWEEN_STRIDE * k + 144 + 6 + rr]; break;  // B_JJ
+      case B_JJ: v = bc[BETWEEN_STRIDE * k + 144 + 6 + rr]; break;
+      default: continue;  // DAMP: nothing
     }
     s += v;
   }
@@ -319,6 +359,8 @@ GLIM_AMD_LM_HD inline void init(const lm::Params& p, const double* X_init, Probl
   for (int i = 0; i < 6 * pr.g.N; i++) pr.delta[i] = 0.0;
   for (int i = 0; i < lm::RECORD * pr.g.F; i++) pr.rec[i] = 0.0;
   for (int i = 0; i < system_doubles(6 * pr.g.N); i++) pr.S[i] = 0.0;
+  if (pr.wk)
+    for (int q = 0; q < pr.g.Q; q++) pr.wk[q] = 1.0;
   Scalars& s = *pr.s;
   s.lambda = p.lambda_initial;
   s.cost = s.fcost = s.pcost = s.bcost = s.inliers = s.trial_cost = 0.0;
@@ -341,7 +383,7 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, Problem& pr, const double* 
   }
   for (int f = 0; f < g.F; f++) expand_factor(recs, pr.Tf, f, pr.lin);
   for (int q = 0; q < g.P; q++) prior_term(g, pr.cand, q, pr.pc);
-  for (int q = 0; q < g.Q; q++) between_term(g, pr.cand, q, pr.bc);
+  for (int q = 0; q < g.Q; q++) between_term(g, pr.cand, q, pr.bc, pr.wt);
   const double fcost = sum_ascending(recs + 1, g.F, lm::RECORD), inliers = sum_ascending(recs, g.F, lm::RECORD);
   const double pcost = sum_ascending(pr.pc + 42, g.P, PRIOR_STRIDE), bcost = sum_ascending(pr.bc + 156, g.Q, BETWEEN_STRIDE);
   const double cost = (fcost + pcost) + bcost;
@@ -356,6 +398,8 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, Problem& pr, const double* 
     for (int i = 0; i < 12 * g.N; i++) pr.X[i] = pr.cand[i];
     for (int i = 0; i < lm::RECORD * g.F; i++) pr.rec[i] = recs[i];
     for (int i = 0; i < nsys; i++) pr.S[i] = pr.W[i];
+    if (pr.wt && pr.wk)
+      for (int q = 0; q < g.Q; q++) pr.wk[q] = pr.wt[q];
   }
   if (s.status != lm::RUNNING) return;
   for (int i = 0; i <= n; i++)

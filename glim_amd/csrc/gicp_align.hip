@@ -40,6 +40,10 @@
 // (graph_round below; the blocked solve's launches are graph_align.hip's, graph_solve.hpp).  Its rounds are enqueued a few at a time, as the
 // ICP loop's are.
 //
+// Both take damping terms and Huber widths of the between terms (include/glim_amd.h "Damping terms and Huber between terms") through the same
+// item functions: the two arrays live in device memory beside the graph, and so do the betweens' weights -- those of a round's evaluation, and
+// those of the kept evaluation, which the kernel that keeps a candidate's poses and records copies with them.
+//
 // The scan-to-keyframes VGICP registration (include/glim_amd.h "Scan-to-keyframes VGICP registration") is the same scheme over ONE pose per
 // problem and M unary VGICP factors with fixed target poses: a round is vgicp_batch_round over the F factors of all problems at T_f = P_f^-1 X,
 // each behind a status word of its own, and the keyframe decide kernel: one wavefront per problem that sums the problem's M records in
@@ -470,7 +474,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(const bun
   for (int w = t; w < F + g.P + g.Q; w += BUNDLE_THREADS) {
     if (w < F) expand_factor(recs, pr.Tf, w, pr.lin);
     else if (w < F + g.P) prior_term(g, pr.cand, w - F, pr.pc);
-    else between_term(g, pr.cand, w - F - g.P, pr.bc);
+    else between_term(g, pr.cand, w - F - g.P, pr.bc, pr.wt);
   }
   for (int f = t; f < F; f += BUNDLE_THREADS) {
     s_W[f] = recs[lm::RECORD * f + 1];
@@ -509,6 +513,7 @@ __global__ __launch_bounds__(BUNDLE_THREADS) void bundle_decide_kernel(const bun
   if (keep > 0) {
     for (int u = t; u < 12 * N; u += BUNDLE_THREADS) pr.X[u] = pr.cand[u];
     for (int u = t; u < lm::RECORD * F; u += BUNDLE_THREADS) pr.rec[u] = recs[u];
+    for (int u = t; u < g.Q; u += BUNDLE_THREADS) pr.wk[u] = pr.wt[u];  // the weights of the kept evaluation (its thread wrote wt[u] before the barriers)
   }
   if (keep > 0 || running) {  // the kept system goes out, the solve's matrix comes in; a thread owns the same entries in both
     const double lambda = s_sc.lambda;
@@ -642,7 +647,7 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_items_kernel(const bundle
   for (int i = t; i < F + g.P + g.Q; i += T) {
     if (i < F) expand_factor(recs, pr.Tf, i, pr.lin);
     else if (i < F + g.P) prior_term(g, pr.cand, i - F, pr.pc);
-    else between_term(g, pr.cand, i - F - g.P, pr.bc);
+    else between_term(g, pr.cand, i - F - g.P, pr.bc, pr.wt);
   }
 }
 
@@ -723,6 +728,7 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_keep_load_kernel(const bu
     const int t = graph_thread(), T = graph_threads();
     for (int u = t; u < 12 * N; u += T) pr.X[u] = pr.cand[u];
     for (int u = t; u < lm::RECORD * F; u += T) pr.rec[u] = recs[u];
+    for (int u = t; u < pr.g.Q; u += T) pr.wk[u] = pr.wt[u];
   }
   const int i = (int)blockIdx.y, j = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
   if (j >= n || (i < n && j > i)) return;
@@ -1216,14 +1222,16 @@ struct GraphCaps {
 int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
                      const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
                      int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, const double* X_out12, const glim_amd_bundle_result* result,
-                     const GraphCaps& caps, lm::Params* prm, int* rounds) {
+                     const GraphCaps& caps, lm::Params* prm, int* rounds, const glim_amd_graph_terms* more) {
   if (!ctx || !X_init12 || !X_out12 || !result) return GLIM_AMD_ERR_INVALID;
   if (F > 0 && (!targets || !sources || !target_pose || !source_pose)) return GLIM_AMD_ERR_INVALID;
   if ((P > 0 && !priors) || (Q > 0 && !betweens)) return GLIM_AMD_ERR_INVALID;
-  if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;
+  const int D = more ? more->num_dampings : 0;
+  if (D < 0 || (D > 0 && !more->dampings)) return GLIM_AMD_ERR_INVALID;
+  if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;  // (dampings alone too: there is nothing to optimise over)
   if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: every factor here is binary
   GA_TRY(resolve_params(params, bundle_default_params, prm, rounds));
-  if (N > caps.poses || F > caps.factors || P > caps.terms || Q > caps.terms) return GLIM_AMD_ERR_UNSUPPORTED;
+  if (N > caps.poses || F > caps.factors || P > caps.terms || Q > caps.terms || D > caps.terms) return GLIM_AMD_ERR_UNSUPPORTED;
   if (!one_context(targets, sources, F, ctx)) return GLIM_AMD_ERR_INVALID;
   for (int f = 0; f < F; f++)
     if (target_pose[f] < 0 || target_pose[f] >= N || source_pose[f] < 0 || source_pose[f] >= N || target_pose[f] == source_pose[f]) return GLIM_AMD_ERR_INVALID;
@@ -1236,6 +1244,15 @@ int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     if (b.pose_i < 0 || b.pose_i >= N || b.pose_j < 0 || b.pose_j >= N || b.pose_i == b.pose_j) return GLIM_AMD_ERR_INVALID;
     if (!all_finite_host(b.T, 12) || !all_finite_host(b.information, 36)) return GLIM_AMD_ERR_INVALID;
   }
+  for (int d = 0; d < D; d++) {
+    const glim_amd_graph_damping& e = more->dampings[d];
+    if (e.pose < 0 || e.pose >= N) return GLIM_AMD_ERR_INVALID;
+    for (double v : e.diagonal)
+      if (!(v >= 0.0) || !std::isfinite(v)) return GLIM_AMD_ERR_INVALID;
+  }
+  if (more && more->between_huber_width)
+    for (int q = 0; q < Q; q++)
+      if (!(more->between_huber_width[q] >= 0.0) || !std::isfinite(more->between_huber_width[q])) return GLIM_AMD_ERR_INVALID;
   if (!all_finite_host(X_init12, 12 * N)) return GLIM_AMD_ERR_INVALID;
   return vgicp_pairs_ok(targets, sources, F);
 }
@@ -1244,17 +1261,18 @@ int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
 // offsets in doubles / ints, and the host's copy with the graph, its lists and the state before round 0.  `extra`: doubles of further
 // scratch behind the problem's own (o_extra)
 struct GraphBlocks {
-  size_t o_X, o_cand, o_delta, o_rec, o_S, o_pT, o_pL, o_bT, o_bL, o_scal, upload_doubles, o_pc, o_bc, o_lin, o_Tf0, o_extra, total_doubles;
-  size_t i_ft, i_fs, i_pk, i_bi, i_bj, i_first, i_items, total_ints;
-  int N, F, P, Q;
+  size_t o_X, o_cand, o_delta, o_rec, o_S, o_pT, o_pL, o_bT, o_bL, o_dd, o_bw, o_wk, o_scal, upload_doubles, o_pc, o_bc, o_wt, o_lin, o_Tf0, o_extra, total_doubles;
+  size_t i_ft, i_fs, i_pk, i_bi, i_bj, i_dk, i_first, i_items, total_ints;
+  int N, F, P, Q, D;
+  bool widths;  // the betweens carry Huber widths
   std::vector<double> hd;
   std::vector<int> hi;
 
   bundle_lm::Problem problem_at(double* d, int* i, double* Tf) const {
     using namespace bundle_lm;
-    Problem pr;
-    memset(&pr, 0, sizeof(pr));
-    pr.g = Graph{N, F, P, Q, i + i_ft, i + i_fs, i + i_pk, d + o_pT, d + o_pL, i + i_bi, i + i_bj, d + o_bT, d + o_bL, i + i_first, i + i_items};
+    Problem pr{};
+    pr.g = Graph{N, F, P, Q, i + i_ft, i + i_fs, i + i_pk, d + o_pT, d + o_pL, i + i_bi, i + i_bj, d + o_bT, d + o_bL, i + i_first, i + i_items,
+                 D, i + i_dk, d + o_dd, widths ? d + o_bw : nullptr};
     pr.X = d + o_X;
     pr.cand = d + o_cand;
     pr.delta = d + o_delta;
@@ -1266,14 +1284,16 @@ struct GraphBlocks {
     pr.bc = d + o_bc;
     pr.W = nullptr;  // the bundle kernel's LDS; the graph's scratch
     pr.s = reinterpret_cast<Scalars*>(d + o_scal);
+    pr.wt = d + o_wt;
+    pr.wk = d + o_wk;
     return pr;
   }
 
   GraphBlocks(int N_, int F_, int P_, int Q_, const int32_t* target_pose, const int32_t* source_pose, const glim_amd_bundle_prior* priors,
-              const glim_amd_bundle_between* betweens, const double* X_init12, const lm::Params& prm, size_t extra)
-      : N(N_), F(F_), P(P_), Q(Q_) {
+              const glim_amd_bundle_between* betweens, const glim_amd_graph_terms* more, const double* X_init12, const lm::Params& prm, size_t extra)
+      : N(N_), F(F_), P(P_), Q(Q_), D(more ? more->num_dampings : 0), widths(more && more->between_huber_width && Q_ > 0) {
     using namespace bundle_lm;
-    const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q);
+    const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q, D);
     size_t at = 0;
     auto take = [&](size_t count) {
       const size_t o = at;
@@ -1282,15 +1302,16 @@ struct GraphBlocks {
     };
     o_X = take(12 * (size_t)N), o_cand = take(12 * (size_t)N), o_delta = take(n), o_rec = take((size_t)lm::RECORD * F), o_S = take(nsys);
     o_pT = take(12 * (size_t)P), o_pL = take(36 * (size_t)P), o_bT = take(12 * (size_t)Q), o_bL = take(36 * (size_t)Q);
+    o_dd = take(6 * (size_t)D), o_bw = take(widths ? (size_t)Q : 0), o_wk = take(Q);
     o_scal = take(sizeof(Scalars) / sizeof(double));
     upload_doubles = at;  // what the host fills; the scratch below is written before it is read
-    o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
+    o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_wt = take(Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
     o_extra = take(extra);
     total_doubles = at;
     at = 0;
-    i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_first = take(tri(N) + 1), i_items = take(nlist);
+    i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_dk = take(D), i_first = take(tri(N) + 1), i_items = take(nlist);
     total_ints = at;
-    hd.assign(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q, 0.0);
+    hd.assign(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q + (size_t)Q, 0.0);
     hi.assign(total_ints + (size_t)tri(N), 0);  // (the tail: build_lists' cursors)
     for (int f = 0; f < F; f++) {
       hi[i_ft + f] = target_pose[f];
@@ -1306,6 +1327,11 @@ struct GraphBlocks {
       hi[i_bj + q] = betweens[q].pose_j;
       memcpy(&hd[o_bT + 12 * (size_t)q], betweens[q].T, 12 * sizeof(double));
       memcpy(&hd[o_bL + 36 * (size_t)q], betweens[q].information, 36 * sizeof(double));
+      if (widths) hd[o_bw + q] = more->between_huber_width[q];
+    }
+    for (int d = 0; d < D; d++) {
+      hi[i_dk + d] = more->dampings[d].pose;
+      memcpy(&hd[o_dd + 6 * (size_t)d], more->dampings[d].diagonal, 6 * sizeof(double));
     }
     Problem host = problem_at(hd.data(), hi.data(), nullptr);
     build_lists(host.g, hi.data() + i_first, hi.data() + i_items, hi.data() + total_ints);
@@ -1334,7 +1360,8 @@ void graph_result(const bundle_lm::Scalars& sc, glim_amd_bundle_result* result) 
 int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
                      const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
                      int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
-                     glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host, bool graph = false, int chunk = 0) {
+                     glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host, bool graph = false, int chunk = 0,
+                     const glim_amd_graph_terms* more = nullptr, double* between_weight_out = nullptr) {
   using namespace bundle_lm;
   if (N < 0 || F < 0 || P < 0 || Q < 0) return GLIM_AMD_ERR_INVALID;
   if (N == 0) return GLIM_AMD_OK;
@@ -1342,8 +1369,8 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   int rounds;
   const GraphCaps caps = graph ? GraphCaps{GLIM_AMD_GRAPH_MAX_POSES, GLIM_AMD_GRAPH_MAX_FACTORS, GLIM_AMD_GRAPH_MAX_TERMS} : GraphCaps{MAX_POSES, MAX_FACTORS, MAX_TERMS};
   GA_TRY(check_graph_args(ctx, targets, sources, target_pose, source_pose, F, flags, priors, P, betweens, Q, X_init12, N, params, X_out12, result, caps, &prm,
-                          &rounds));
-  const GraphBlocks blk(N, F, P, Q, target_pose, source_pose, priors, betweens, X_init12, prm, graph ? graph_scratch_doubles(6 * N) : 0);
+                          &rounds, more));
+  const GraphBlocks blk(N, F, P, Q, target_pose, source_pose, priors, betweens, more, X_init12, prm, graph ? graph_scratch_doubles(6 * N) : 0);
 
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the call
   GA_HIP(hipSetDevice(ctx->device));
@@ -1392,6 +1419,7 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   std::vector<double> rec_host((size_t)lm::RECORD * F);
   GA_HIP(hipMemcpyAsync(X_out12, pr.X, 12 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
   if (F > 0) GA_HIP(hipMemcpyAsync(rec_host.data(), pr.rec, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (between_weight_out && Q > 0) GA_HIP(hipMemcpyAsync(between_weight_out, pr.wk, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
   GA_TRY(tX.fetch(st));
   GA_TRY(tTf.fetch(st));  // (nothing without factors: no bytes)
   GA_TRY(trec.fetch(st));
@@ -1456,6 +1484,55 @@ int glim_amd_debug_graph_align_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap*
   return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
                           params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, true,
                           rounds_per_chunk > 0 ? rounds_per_chunk : GRAPH_ROUNDS_PER_CHUNK);
+}
+
+// the two loops with damping terms and Huber widths: the same scaffold, the terms behind the graph
+int glim_amd_bundle_align_terms(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                                const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                                const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                                const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result,
+                                const glim_amd_graph_terms* more, double* between_weight_out) {
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, 0, BundleTrace{nullptr, nullptr, nullptr, nullptr}, false, 0, more, between_weight_out);
+}
+
+int glim_amd_debug_bundle_align_terms_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                            const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                            const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                            int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                            double* X_out12, double* compact_out, glim_amd_bundle_result* result, const glim_amd_graph_terms* more,
+                                            double* between_weight_out, int32_t one_thread, double* X_trace, double* Tf_trace, double* compact_trace,
+                                            glim_amd_bundle_trace_round* rounds) {
+  const bool any = X_trace || Tf_trace || compact_trace || rounds;
+  if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, false, 0, more,
+                          between_weight_out);
+}
+
+int glim_amd_graph_align_terms(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                               const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                               const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                               const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result,
+                               const glim_amd_graph_terms* more, double* between_weight_out) {
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, 0, BundleTrace{nullptr, nullptr, nullptr, nullptr}, true, GRAPH_ROUNDS_PER_CHUNK, more,
+                          between_weight_out);
+}
+
+int glim_amd_debug_graph_align_terms_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                           const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                           const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                           int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                           double* X_out12, double* compact_out, glim_amd_bundle_result* result, const glim_amd_graph_terms* more,
+                                           double* between_weight_out, int32_t one_thread, double* X_trace, double* Tf_trace, double* compact_trace,
+                                           glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk) {
+  const bool any = X_trace || Tf_trace || compact_trace || rounds;
+  if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
+  if (rounds_per_chunk < 0) return GLIM_AMD_ERR_INVALID;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, true,
+                          rounds_per_chunk > 0 ? rounds_per_chunk : GRAPH_ROUNDS_PER_CHUNK, more, between_weight_out);
 }
 
 int glim_amd_debug_graph_solve(glim_amd_ctx* ctx, const double* S, int32_t n, double lambda, double* delta_out, int32_t* ok_out) {

@@ -824,12 +824,14 @@ int glim_amd_ct_align(glim_amd_ct_gicp_factor* factor, const double* X_init12, c
  *              GICP fine registration, with "the error" read as the cost and "inliers" as the sum of the factors' inlier counts (with F = 0
  *              there are none to ask for).  glim_amd_lm_params is reused unchanged.
  * The system lives in one workgroup's LDS (160 KiB on gfx950), which sets GLIM_AMD_BUNDLE_MAX_POSES; the factors' blocks live in device memory.
- * Out of scope: IMU graphs (V, B variables, ImuFactor), ISAM2, translating a gtsam::NonlinearFactorGraph, several devices.
+ * Damping terms and Huber between terms: glim_amd_bundle_align_terms below ("Damping terms and Huber between terms").
+ * Out of scope: IMU graphs (V, B variables, ImuFactor), ISAM2, pose marginals, robust priors, M-estimators other than Huber, translating a
+ * gtsam::NonlinearFactorGraph, several devices.
  * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
  * resident session of the context are not touched. */
 #define GLIM_AMD_BUNDLE_MAX_POSES 32     /* 192 x 192: 149 760 B of packed triangle and right-hand side in LDS */
 #define GLIM_AMD_BUNDLE_MAX_FACTORS 1024 /* every ordered pair of 32 poses is 992 */
-#define GLIM_AMD_BUNDLE_MAX_TERMS 1024   /* priors; and betweens */
+#define GLIM_AMD_BUNDLE_MAX_TERMS 1024   /* priors; and betweens; and dampings */
 typedef struct {
   int32_t pose;
   int32_t reserved;
@@ -887,13 +889,14 @@ int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* tar
  *              enqueued a few at a time; between two chunks the host reads the status and stops enqueueing when the loop has finished.  The
  *              state lives on the device: the chunk length moves no bit of a result.
  * With the same arguments within the bundle's caps, glim_amd_graph_align returns what glim_amd_bundle_align returns, bit for bit.
- * Out of scope: ISAM2 (GLIM's global mapping is incremental; this is one batch optimisation over the poses), IMU variables, LinearDampingFactor,
- * robust kernels, several devices, translating a gtsam::NonlinearFactorGraph.
+ * Damping terms (LinearDampingFactor) and Huber between terms: glim_amd_graph_align_terms below.
+ * Out of scope: ISAM2 (GLIM's global mapping is incremental; this is one batch optimisation over the poses), IMU variables, pose marginals,
+ * robust priors, M-estimators other than Huber, several devices, translating a gtsam::NonlinearFactorGraph.
  * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
  * resident session of the context are not touched. */
 #define GLIM_AMD_GRAPH_MAX_POSES 256     /* 1536 x 1536 */
 #define GLIM_AMD_GRAPH_MAX_FACTORS 32768 /* every pair i < j of 256 poses is 32 640 */
-#define GLIM_AMD_GRAPH_MAX_TERMS 1024    /* priors; and betweens */
+#define GLIM_AMD_GRAPH_MAX_TERMS 1024    /* priors; and betweens; and dampings */
 /* the defaults of glim_amd_bundle_align_default_params */
 int glim_amd_graph_align_default_params(glim_amd_lm_params* params);
 /* The arguments, the results and the refusals of glim_amd_bundle_align, with the caps above.  Nothing is launched when an argument is refused. */
@@ -901,6 +904,49 @@ int glim_amd_graph_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targ
                          const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
                          const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
                          const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_bundle_result* result);
+
+/* ---- Damping terms and Huber between terms: the two terms GLIM's global mapping graphs are made of beside factors, priors and Gaussian
+ *      betweens, for both optimisations above.  The rule is theirs (glim_amd/csrc/bundle_lm_step.hpp) with two additions:
+ *   damping    (pose k, diagonal d[6]) is gtsam_points::LinearDampingFactor (global_mapping.cpp:162, 960,
+ *              global_mapping_pose_graph.cpp:136: LinearDampingFactor(X(0), 6, init_pose_damping_scale), d = the scale six times;
+ *              global_mapping.cpp:523: (key, 6, 1e3) beside an indeterminate pose; loose_initial_state_estimation.cpp:124: the per-axis form).  From upstream recall its error() is 0 and its linearize() a Hessian
+ *              factor with G = diag(d), g = 0, f = 0; the factor's source is not in the reference tree.  It adds d[m] to entry
+ *              (6k + m, 6k + m) of H and nothing to any other entry, to b or to the cost.  In every sum it comes after the betweens, by
+ *              ascending index.  Several dampings on one pose are allowed.  A pose touched only by dampings has the block diag(sum d) +
+ *              lambda I, the right-hand side +0.0 and a zero step.
+ *   huber      between q may carry a width k_q >= 0 (0: the Gaussian between): noiseModel::Robust(Huber(k_q), information), as
+ *              global_mapping_pose_graph.cpp:465-468 gives every loop factor.  With c = r^T L r and s = sqrt(c), the between is down-weighted
+ *              iff k_q > 0 and s > k_q: then w = k_q / s, its J^T L J and J^T L r are multiplied entry by entry by w and its cost becomes
+ *              k_q ((s + s) - k_q); otherwise w = 1.0 and its contribution keeps the Gaussian between's bits.  This is gtsam's
+ *              Robust::WhitenSystem and Huber loss in the cost convention here (cost = r^T L r, twice gtsam's error).
+ * glim_amd_bundle_result is reused: between_cost is the sum of the robust costs.  between_weight_out: NULL, or num_betweens doubles, the weights
+ * w of the evaluation at the returned poses (kept on the device with the kept system; 1.0 for a Gaussian between).
+ * more == NULL, or no damping and no width that is not 0, returns what the entry point without `_terms` returns, bit for bit.  The refusals are
+ * those of that entry point, and, also before anything is launched: GLIM_AMD_ERR_INVALID: a negative num_dampings, NULL dampings with a
+ * positive count, a damping's pose out of range, a diagonal entry or a width that is negative or not finite, a graph with dampings but no
+ * factor, prior or between (there is nothing to optimise over); GLIM_AMD_ERR_UNSUPPORTED: more dampings than *_MAX_TERMS.
+ * Out of scope: ISAM2, IMU variables, pose marginals, robust priors, other M-estimators, several devices. */
+typedef struct {
+  int32_t pose;
+  int32_t reserved;
+  double diagonal[6];      /* (omega, v) order; each >= 0 and finite */
+} glim_amd_graph_damping;
+typedef struct {
+  const glim_amd_graph_damping* dampings;
+  int32_t num_dampings;
+  int32_t reserved;
+  const double* between_huber_width; /* NULL, or num_betweens values; 0 = Gaussian */
+} glim_amd_graph_terms;
+int glim_amd_bundle_align_terms(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens, int32_t num_betweens,
+                                const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
+                                glim_amd_bundle_result* result, const glim_amd_graph_terms* more, double* between_weight_out);
+int glim_amd_graph_align_terms(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                               const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                               const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens, int32_t num_betweens,
+                               const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
+                               glim_amd_bundle_result* result, const glim_amd_graph_terms* more, double* between_weight_out);
 
 /* ---- Scan-to-keyframes VGICP registration: the LiDAR part of GLIM's frame-to-keyframes matching cost
  *      (src/glim/odometry/odometry_estimation_gpu.cpp:150-165, 183-203): one unary IntegratedVGICPFactorGPU(fixed_target_pose, X(current),
