@@ -496,6 +496,7 @@ SYMBOLS = {
     "glim_amd_ba_auto_radius": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaParams), C.POINTER(BaRadiusResult)]),
     "glim_amd_debug_ba_auto_radius_trace": (_i, [_pp, _i32, _dp, _dp, _d, C.POINTER(BaParams), C.POINTER(BaRadiusResult), C.POINTER(BaTraceEntry), _ip]),
     "glim_amd_debug_ba_eigen3": (_i, [_vp, _i32, _dp, _dp, _dp]),
+    "glim_amd_debug_se3_eval": (_i, [_vp, _i32, _i32, _dp, _dp]),
     "glim_amd_ba_factor_create": (_i, [_vp, _i32, _i64, _dp, _ip, _i32, _pp]),
     "glim_amd_ba_factor_create_from_ball": (_i, [_pp, _i32, _dp, _dp, _d, _i32, _pp]),
     "glim_amd_ba_factor_info": (_i, [_vp, _ip, _lp, _ip, _ip, _dp]),

@@ -1823,6 +1823,21 @@ def graph_solve_debug(S, n, lam, ctx=None):
     return bool(ok.value), delta
 
 
+SE3_DEBUG_OPS = {"exp": (0, 6, 12), "log": (1, 12, 6), "jr": (2, 6, 36), "jr_inv": (3, 6, 36), "ad": (4, 12, 36), "prior": (5, 24, 42), "between": (6, 36, 78),
+                 "ct": (7, 25, 84)}  # name -> op, doubles in, doubles out (include/glim_amd_diag.h)
+
+
+def se3_debug_eval(op, x, ctx=None):
+    """Test window (glim_amd_debug_se3_eval): one routine of csrc/ct_se3.hpp on the device, one thread per row of x (cases x IN doubles).
+    op: a name of SE3_DEBUG_OPS.  Returns cases x OUT doubles."""
+    ctx = ctx or default_context()
+    code, n_in, n_out = SE3_DEBUG_OPS[op]
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n_in)
+    out = np.full((len(x), n_out), np.nan)
+    check(lib().glim_amd_debug_se3_eval(ctx._h, code, len(x), _dp(x), _dp(out)), "glim_amd_debug_se3_eval")
+    return out
+
+
 def ct_align_params(**kw):
     """LMParams with GLIM's continuous-time odometry values (glim_amd_ct_align_default_params): lambda_initial 1e-10, absolute_error_tol 1e-2,
     max_iterations 8 (odometry_estimation_ct.cpp:176-183)."""

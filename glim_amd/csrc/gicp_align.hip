@@ -331,6 +331,14 @@ __global__ __launch_bounds__(CT_POSE_THREADS) void ct_align_poses_kernel(const c
   for (int k = threadIdx.x; k < nbk; k += CT_POSE_THREADS) ct_se3::ct_pose_bucket(s_X, s_shared, table[k], poses + (size_t)k * CT_POSE_STRIDE);
 }
 
+// the test window of ct_se3.hpp (glim_amd_debug_se3_eval): one thread per case runs ct_se3::se3_eval on its own slice and nothing else
+constexpr int SE3_EVAL_THREADS = 64;
+__global__ __launch_bounds__(SE3_EVAL_THREADS) void se3_eval_kernel(int op, int count, const double* __restrict__ in, double* __restrict__ out) {
+  const int i = blockIdx.x * SE3_EVAL_THREADS + threadIdx.x;
+  if (i >= count) return;
+  ct_se3::se3_eval(op, in + (size_t)i * ct_se3::se3_eval_in(op), out + (size_t)i * ct_se3::se3_eval_out(op));
+}
+
 // ct_gicp_kernel<true> and ct_bucket_kernel behind the status check (no keep_* pointers: what the factor keeps for error() stays as it was)
 template <class NN>
 __global__ __launch_bounds__(BLOCK) void ct_align_linearize_kernel(const GicpArgs a, const CtArgs c, const ct_lm::State* __restrict__ state,
@@ -1556,6 +1564,26 @@ int glim_amd_debug_graph_solve(glim_amd_ctx* ctx, const double* S, int32_t n, do
   GA_HIP(hipStreamSynchronize(st));
   in_flight.dismiss();
   *ok_out = fail ? 0 : 1;
+  return GLIM_AMD_OK;
+}
+
+int glim_amd_debug_se3_eval(glim_amd_ctx* ctx, int32_t op, int32_t count, const double* in, double* out) {
+  if (!ctx || !in || !out || count < 0 || op < 0 || op >= ct_se3::SE3_EVAL_OPS) return GLIM_AMD_ERR_INVALID;
+  if (count == 0) return GLIM_AMD_OK;
+  const size_t ni = (size_t)count * ct_se3::se3_eval_in(op), no = (size_t)count * ct_se3::se3_eval_out(op);
+  std::unique_lock<std::mutex> held(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  DeviceTemp d;  // the inputs, then the outputs
+  SyncOnExit in_flight(st);
+  GA_HIP(pool_malloc(&d.p, (ni + no) * sizeof(double)));
+  double *d_in = d.as<double>(), *d_out = d_in + ni;
+  GA_HIP(hipMemcpyAsync(d_in, in, ni * sizeof(double), hipMemcpyHostToDevice, st));
+  se3_eval_kernel<<<(count + SE3_EVAL_THREADS - 1) / SE3_EVAL_THREADS, SE3_EVAL_THREADS, 0, st>>>(op, count, d_in, d_out);
+  GA_HIP(hipGetLastError());
+  GA_HIP(hipMemcpyAsync(out, d_out, no * sizeof(double), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
   return GLIM_AMD_OK;
 }
 

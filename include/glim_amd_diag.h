@@ -359,6 +359,18 @@ int glim_amd_debug_ba_auto_radius_trace(const glim_amd_cloud* const* clouds, int
 /* the eigen-solver of the plane bundle-adjustment statistics and factors (csrc/eig3_direct.hpp) run by one device thread per matrix:
  * m9: count x 9 row-major symmetric; evals: count x 3 ascending; evecs: count x 9, evecs[3 k + r] = component r of eigenvector k */
 int glim_amd_debug_ba_eigen3(glim_amd_ctx* ctx, int32_t count, const double* m9, double* evals, double* evecs);
+/* the SE(3) maps and pose-graph terms every on-device optimiser is built from (csrc/ct_se3.hpp), one routine at a time, one device thread per
+ * case (blocks of 64): in: count x IN doubles, out: count x OUT doubles.  Poses are row-major 3 x 4, tangents (omega, v), 6 x 6 row-major.
+ *   op 0 exp              IN  6 xi              OUT 12 T
+ *   op 1 log              IN 12 T               OUT  6 xi
+ *   op 2 jr               IN  6 xi              OUT 36 J_r(xi)
+ *   op 3 jr_inv           IN  6 xi              OUT 36 J_r(xi)^-1
+ *   op 4 ad               IN 12 T               OUT 36 Ad(T)
+ *   op 5 prior_residual   IN 24 P | X           OUT 42 r = Log(P^-1 X) | d r / d X (6 x 6)
+ *   op 6 between_residual IN 36 D | X | Y       OUT 78 r = Log(D^-1 X^-1 Y) | [d r / d X | d r / d Y] (6 x 12)
+ *   op 7 ct_pose_bucket   IN 25 X | Y | t_k     OUT 84 T_k | D0_k | D1_k
+ * GLIM_AMD_ERR_INVALID: a NULL context or array, count < 0, any other op.  count == 0: GLIM_AMD_OK, nothing is launched. */
+int glim_amd_debug_se3_eval(glim_amd_ctx* ctx, int32_t op, int32_t count, const double* in, double* out);
 /* test window of the map editor's min-cut segmentation (glim_amd.h): the graph glim_amd_edit_min_cut builds from the same inputs, before any
  * flow.  pairs: the candidates, pair_capacity x 2; source_cap / sink_cap: pair_capacity entries, the terminal capacity of every candidate (0:
  * not tied); edges: edge_capacity x 2 candidate indices (i < j) in ascending key order; edge_cap: edge_capacity capacities.  At most the

@@ -6,6 +6,7 @@ import numpy as np
 
 POSE_TOL = 1e-4
 SERIES = 0.02
+Q_SERIES = 1.0  # csrc/ct_se3.hpp CT_Q_SERIES: the coefficients of Q are their series below this
 
 
 
@@ -17,6 +18,14 @@ def so3_coeffs(th):
     if th < SERIES:
         return 0.5 - th**2 / 24 + th**4 / 720, 1 / 6 - th**2 / 120 + th**4 / 5040
     return (1 - np.cos(th)) / th**2, (th - np.sin(th)) / th**3
+
+
+def alt_series(t2, k0):
+    """sum_k (-1)^k t2^k / (2 k + k0)!, ten terms nested (csrc/ct_se3.hpp alt_series)"""
+    s = 1.0
+    for k in range(9, 0, -1):
+        s = 1.0 - s * t2 / ((2 * k + k0 - 1) * (2 * k + k0))
+    return s / float(np.prod(np.arange(2, k0 + 1)))
 
 
 def expmap(xi):
@@ -52,9 +61,9 @@ def expmap_derivative(xi):
     W, V = hat(w), hat(rho)
     b, c = so3_coeffs(th)
     Jw = np.eye(3) - b * W + c * W @ W
-    if th < SERIES:
-        ca, cb = 1 / 6 - th**2 / 120 + th**4 / 5040, -1 / 24 + th**2 / 720 - th**4 / 40320
-        cc = -0.5 * (cb - 3 * (-1 / 120 + th**2 / 5040 - th**4 / 362880))
+    if th < Q_SERIES:
+        ca, cb = alt_series(th**2, 3), -alt_series(th**2, 4)
+        cc = -0.5 * (cb + 3 * alt_series(th**2, 5))
     else:
         ca, cb = (th - np.sin(th)) / th**3, (1 - th**2 / 2 - np.cos(th)) / th**4
         cc = -0.5 * (cb - 3 * (th - np.sin(th) - th**3 / 6) / th**5)

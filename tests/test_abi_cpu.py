@@ -51,6 +51,7 @@ def test_the_stable_header_holds_no_probe_and_the_drop_in_layers_never_touch_the
     assert "#include \"glim_amd_diag.h\"" not in stable and "#include <glim_amd_diag.h>" not in stable  # (named in a comment only)
     diag = _diag_symbols()
     assert len(diag) >= 20
+    assert "glim_amd_debug_se3_eval" in diag and "glim_amd_debug_se3_eval" not in names  # the window of csrc/ct_se3.hpp is a debug view
     for top in ("adapters", "examples", os.path.join("include", "glim_amd")):
         for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
             for f in files:
