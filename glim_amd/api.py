@@ -2093,6 +2093,15 @@ def debug_sort_pairs(keys, vals=None, bits=64, ctx=None):
     return ko, vo
 
 
+def debug_exclusive_scan(values, ctx=None):
+    """The device's exclusive prefix sum of int32 values (csrc/scan.hpp) behind every stable compaction (parity / debug)."""
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+    out = np.zeros_like(v)
+    check(lib().glim_amd_debug_exclusive_scan(ctx._h, len(v), _ip(v) if len(v) else None, _ip(out) if len(v) else None), "glim_amd_debug_exclusive_scan")
+    return out
+
+
 def expand_compact(compact, T_target_source, flags):
     c = np.ascontiguousarray(compact, dtype=np.float64).reshape(_lib.COMPACT_DOUBLES)
     T = pose12(T_target_source)

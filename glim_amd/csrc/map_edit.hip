@@ -1008,4 +1008,26 @@ int glim_amd_edit_remove_points(const glim_amd_cloud* cloud, int64_t n, const in
   return GLIM_AMD_OK;
 }
 
+// parity / debug only: scan.hpp's exclusive prefix sum of a host array on the device
+int glim_amd_debug_exclusive_scan(glim_amd_ctx* ctx, int64_t n, const int32_t* in, int32_t* out) {
+  using namespace glim_amd;
+  if (!ctx || n < 0 || n > (int64_t)(1 << 28) || (n > 0 && (!in || !out))) return GLIM_AMD_ERR_INVALID;
+  if (n == 0) return GLIM_AMD_OK;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  GA_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream();
+  const unsigned int T = (unsigned int)n;
+  DeviceTemp d_in, d_out, tiles;
+  GA_HIP(pool_malloc(&d_in.p, (size_t)T * sizeof(int)));
+  GA_HIP(pool_malloc(&d_out.p, (size_t)T * sizeof(int)));
+  GA_HIP(pool_malloc(&tiles.p, scan_scratch_ints(T) * sizeof(int)));
+  SyncOnExit in_flight(st);
+  GA_HIP(hipMemcpyAsync(d_in.p, in, (size_t)T * sizeof(int), hipMemcpyHostToDevice, st));
+  GA_HIP(exclusive_scan_int(st, d_in.as<int>(), T, tiles.as<int>(), d_out.as<int>()));
+  GA_HIP(hipMemcpyAsync(out, d_out.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, st));
+  GA_HIP(hipStreamSynchronize(st));
+  in_flight.dismiss();
+  return GLIM_AMD_OK;
+}
+
 }  // extern "C"

@@ -63,6 +63,10 @@ int glim_amd_debug_scratch_poke(glim_amd_ctx* ctx, int32_t word, uint32_t value)
 /* parity / debug only: the stable device radix sort behind the preprocessing (sorts by the low `bits` key bits; vals_in NULL = 0..n-1). */
 int glim_amd_debug_sort_pairs(glim_amd_ctx* ctx, int64_t n, int32_t bits, const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out,
                               uint32_t* vals_out);
+/* parity / debug only: the device's exclusive prefix sum of 32-bit integers (csrc/scan.hpp) behind every stable compaction -- the map editor's
+ * selections and removal, the ball selection, the kNN grid, the preprocessing: out[i] = in[0] + ... + in[i - 1], out[0] = 0, 32-bit wrap-around.
+ * n == 0: GLIM_AMD_OK, nothing is touched.  GLIM_AMD_ERR_INVALID: a NULL context, n < 0, n > 2^28, a NULL array with n > 0. */
+int glim_amd_debug_exclusive_scan(glim_amd_ctx* ctx, int64_t n, const int32_t* in, int32_t* out);
 
 /* The hypotheses [first, first + count) of glim_amd_ransac_align on the same arguments, every one scored, no early stop: samples (count x 3
  * source indices), status (count), poses12 (count x 12; the identity where status != 0), inliers (count; 0 where status != 0); any of them may

@@ -1,7 +1,8 @@
 """NumPy (FP64) restatement of the map editor's device side (include/glim_amd.h "Map editing"; reference:
 src/glim/viewer/editor/points_selector.cpp): the four selection predicates in the device's documented operation order -- every product and
 sum written out term by term, so that each boolean is reproduced bit for bit --, the outlier rule over oracle.find_inliers, region growing as
-a breadth-first search over a brute-force distance matrix, and removal as boolean indexing.
+a breadth-first search over the edge list of a grid-bucketed neighbour search (`neighbor_edges`: the same ordered pairs as the brute-force distance
+matrix `adjacency`, which tests/test_map_scale_cases.py holds it against, without the m x m memory), and removal as boolean indexing.
 
 All comparisons of tests/test_map_edit_gpu.py with this file are equalities.  The one condition on a scene is the outlier test's: the device
 adds the mean neighbour distances d_i in block order and the oracle adds them sequentially, so the two thresholds may differ in their last
@@ -135,6 +136,59 @@ def bfs_levels(adj, seed, max_hops=0):
     return level
 
 
+def neighbor_edges(w, distance_threshold, normals=None, cos_angle=None):
+    """np.nonzero(adjacency(...)) without the m x m matrix: -> (i, j), every ordered pair with an edge (i == j included), ascending in (i, j).
+    The points are bucketed into cells a hair wider than the threshold, so that two points closer than it lie in the same or in adjacent
+    cells; the pairs of the 27 cell neighbourhoods are then tested with adjacency's own expressions, term by term."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1, 3)
+    m = len(w)
+    if m == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    h = np.float64(distance_threshold) * 1.001
+    cell = np.floor((w - w.min(axis=0)) / h).astype(np.int64) + 1  # >= 1: a neighbour's coordinate is never negative
+    dim = cell.max(axis=0) + 2
+    key = (cell[:, 2] * dim[1] + cell[:, 1]) * dim[0] + cell[:, 0]
+    order = np.argsort(key, kind="stable")
+    skey = key[order]
+    thr2 = np.float64(distance_threshold) * np.float64(distance_threshold)
+    src, dst = [], []
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                nk = key + (dz * dim[1] + dy) * dim[0] + dx
+                lo, hi = np.searchsorted(skey, nk, side="left"), np.searchsorted(skey, nk, side="right")
+                cnt = hi - lo
+                i = np.repeat(np.arange(m), cnt)
+                j = order[np.repeat(lo, cnt) + (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt))]
+                ex, ey, ez = (w[i, a] - w[j, a] for a in range(3))
+                keep = ((ex * ex + ey * ey) + ez * ez) < thr2
+                if normals is not None:
+                    n = normals
+                    dot = (n[i, 0] * n[j, 0] + n[i, 1] * n[j, 1]) + n[i, 2] * n[j, 2]
+                    keep &= np.abs(dot) >= cos_angle
+                src.append(i[keep])
+                dst.append(j[keep])
+    src, dst = np.concatenate(src), np.concatenate(dst)
+    o = np.lexsort((dst, src))
+    return src[o], dst[o]
+
+
+def bfs_levels_edges(m, src, dst, seed, max_hops=0):
+    """bfs_levels over the edge list of neighbor_edges"""
+    level = np.full(m, -1, dtype=np.int32)
+    level[seed] = 0
+    rho = 0
+    while max_hops == 0 or rho < max_hops:
+        hit = np.zeros(m, dtype=bool)
+        hit[src[level[dst] == rho]] = True
+        new = (level < 0) & hit
+        if not new.any():
+            break
+        rho += 1
+        level[new] = rho
+    return level
+
+
 def region_grow(clouds, poses, center, distance_threshold=0.5, cos_angle=None, normals=None, dilation_radius=0.5, max_hops=0, resolution=RESOLUTION,
                 window=WINDOW_CELLS):
     """normals: None, or one N x 3 array per cloud (cloud-local; rotated to world here).  -> {pairs, levels, count, num_candidates, seed,
@@ -149,11 +203,13 @@ def region_grow(clouds, poses, center, distance_threshold=0.5, cos_angle=None, n
         nw = np.concatenate([rotate(np.asarray(normals[s])[cand[cand[:, 0] == s, 1]], poses[s]) for s in range(len(clouds))]).reshape(-1, 3)
     qq = center_qq(w, center)
     seed = int(np.lexsort((np.arange(m), qq))[0])  # the smallest qq, ties to the smaller pair
-    level = bfs_levels(adjacency(w, distance_threshold, nw, cos_angle), seed, max_hops)
+    level = bfs_levels_edges(m, *neighbor_edges(w, distance_threshold, nw, cos_angle), seed, max_hops)
     rounds = int(level.max())
     if dilation_radius > 0.0:
-        near = adjacency(w, dilation_radius)
-        level[(level < 0) & near[:, level >= 0].any(axis=1)] = rounds + 1
+        i, j = neighbor_edges(w, dilation_radius)
+        near = np.zeros(m, dtype=bool)
+        near[i[level[j] >= 0]] = True
+        level[(level < 0) & near] = rounds + 1
     keep = level >= 0
     return {"pairs": cand[keep], "levels": level[keep], "count": int(keep.sum()), "num_candidates": m, "seed": (int(cand[seed, 0]), int(cand[seed, 1])),
             "seed_qq": float(qq[seed]), "rounds": rounds, "status": "ok", "all_levels": level, "candidates": cand, "world": w}
