@@ -516,6 +516,10 @@ SYMBOLS = {
     "glim_amd_cloud_download_merged": (_i, [_vp, _dp, _dp]),
     "glim_amd_debug_sort_pairs": (_i, [_vp, _i64, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "glim_amd_debug_exclusive_scan": (_i, [_vp, _i64, _ip, _ip]),
+    "glim_amd_cloud_random_sample": (_i, [_vp, _d, C.c_uint64, _pp]),
+    "glim_amd_cloud_sample": (_i, [_vp, _i64, _ip, _pp]),
+    "glim_amd_cloud_transform": (_i, [_vp, _dp, _pp]),
+    "glim_amd_debug_select_smallest": (_i, [_vp, _i64, C.POINTER(C.c_uint32), _i64, _ip]),
     "glim_amd_cloud_destroy": (_i, [_vp]),
     "glim_amd_cloud_size": (_i, [_vp, _lp]),
     "glim_amd_cloud_memory_usage": (_i, [_vp, C.POINTER(_sz)]),

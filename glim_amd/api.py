@@ -313,6 +313,35 @@ class PointCloudGPU:
         check(lib().glim_amd_cloud_download(self._h, _fp(xyz), _fp(c), _fp(nr), None), "glim_amd_cloud_download")
         return xyz, (c.reshape(n, 3, 3) if covs else None), nr
 
+    def _derived(self, h):
+        """a cloud one of the resampling calls made of this one: neighbours are not carried over, intensities are"""
+        g = PointCloudGPU(h, self.ctx)
+        g._k = 0
+        g._has_intensities = getattr(self, "_has_intensities", False)
+        return g
+
+    def random_sampling(self, rate, seed=0):
+        """gtsam_points::random_sampling on the device: a NEW cloud of int(size * rate) points in their original order, with every per-point
+        array this one holds (rate >= 0.99: a copy of the whole cloud).  The draw is glim_amd_cloud_random_sample's, a function of (seed, size)."""
+        h = C.c_void_p()
+        check(lib().glim_amd_cloud_random_sample(self._h, float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)), "glim_amd_cloud_random_sample")
+        return self._derived(h)
+
+    def sample(self, indices):
+        """gtsam_points::sample on the device: a NEW cloud whose point j is this one's point indices[j] (any order, duplicates allowed)."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        h = C.c_void_p()
+        check(lib().glim_amd_cloud_sample(self._h, len(idx), _ip(idx) if len(idx) else None, C.byref(h)), "glim_amd_cloud_sample")
+        return self._derived(h)
+
+    def transform(self, T):
+        """gtsam_points::transform on the device: a NEW cloud with points, covariances and normals moved by T (4 x 4 or 3 x 4; the linear part
+        need not be a rotation), in FP64 with the operation order include/glim_amd.h states."""
+        T12 = np.ascontiguousarray(np.asarray(T, dtype=np.float64)[:3, :4]).reshape(12)
+        h = C.c_void_p()
+        check(lib().glim_amd_cloud_transform(self._h, _dp(T12), C.byref(h)), "glim_amd_cloud_transform")
+        return self._derived(h)
+
     def close(self):
         if self._h:
             lib().glim_amd_cloud_destroy(self._h)
@@ -2100,6 +2129,17 @@ def debug_exclusive_scan(values, ctx=None):
     out = np.zeros_like(v)
     check(lib().glim_amd_debug_exclusive_scan(ctx._h, len(v), _ip(v) if len(v) else None, _ip(out) if len(v) else None), "glim_amd_debug_exclusive_scan")
     return out
+
+
+def debug_select_smallest(keys, m, ctx=None):
+    """The selection stage of PointCloudGPU.random_sampling on caller-supplied 32-bit keys: keep[i] = 1 iff (keys[i], i) is among the m
+    smallest pairs (parity / debug)."""
+    ctx = ctx or default_context()
+    k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    keep = np.zeros(len(k), dtype=np.int32)
+    check(lib().glim_amd_debug_select_smallest(ctx._h, len(k), k.ctypes.data_as(C.POINTER(C.c_uint32)) if len(k) else None, int(m),
+                                               _ip(keep) if len(k) else None), "glim_amd_debug_select_smallest")
+    return keep
 
 
 def expand_compact(compact, T_target_source, flags):

@@ -11,12 +11,13 @@
 //   edit_round_kernel     one growth round: an unassigned candidate takes level rho iff a neighbour in its 27 cells has a level < rho and an edge to it
 //   edit_mc_*             min-cut: the candidates' neighbour graph -- edge keys from the kNN -> sort.hip -> unique -> capacities, terminal
 //                         capacities; the flow itself is min_cut.hip's
-//   edit_keep_* / edit_gather_kernel   removal: keep flags, prefix sum, gather of every per-point array
+//   edit_keep_*           removal: keep flags, prefix sum, then cloud_gather.hpp's gather of every per-point array
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <memory>
 
+#include "cloud_gather.hpp"
 #include "internal.hpp"
 #include "map_edit.hpp"
 #include "min_cut.hpp"
@@ -341,30 +342,6 @@ static __global__ __launch_bounds__(256) void edit_keep_mark_kernel(const int* _
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < cnt) keep[idx[i]] = 0;
 }
-struct GatherArgs {
-  const float4 *pts, *covA, *normals;
-  const float2* covB;
-  const double4* pts64;
-  const double *times, *intensities, *cov64;
-  float4 *o_pts, *o_covA, *o_normals;
-  float2* o_covB;
-  double4* o_pts64;
-  double *o_times, *o_intensities, *o_cov64;
-};
-static __global__ __launch_bounds__(256) void edit_gather_kernel(int n, const int* __restrict__ keep, const int* __restrict__ pos, GatherArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !keep[i]) return;
-  const int o = pos[i];
-  a.o_pts[o] = a.pts[i];
-  if (a.covA) a.o_covA[o] = a.covA[i];
-  if (a.covB) a.o_covB[o] = a.covB[i];
-  if (a.normals) a.o_normals[o] = a.normals[i];
-  if (a.pts64) a.o_pts64[o] = a.pts64[i];
-  if (a.times) a.o_times[o] = a.times[i];
-  if (a.intensities) a.o_intensities[o] = a.intensities[i];
-  if (a.cov64)
-    for (int c = 0; c < 6; c++) a.o_cov64[6 * (size_t)o + c] = a.cov64[6 * (size_t)i + c];
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
@@ -468,13 +445,6 @@ static int pick_to_host(glim_amd_ctx* ctx, hipStream_t st, const int* flags, int
   *count = n;
   return GLIM_AMD_OK;
 }
-
-struct CloudGuard {
-  glim_amd_cloud* c = nullptr;
-  ~CloudGuard() {
-    if (c) glim_amd_cloud_destroy(c);
-  }
-};
 
 static bool no_device() { return glim_amd_device_count() <= 0; }
 
@@ -971,31 +941,9 @@ int glim_amd_edit_remove_points(const glim_amd_cloud* cloud, int64_t n, const in
   int kept = 0;
   GA_HIP(read_back_sync(ctx, st, &kept, pos.as<int>() + size, sizeof(int)));  // also: the index array has been read
   if (kept < 0 || kept > size) return GLIM_AMD_ERR_HIP;
-  glim_amd_cloud* c = new glim_amd_cloud();
-  result.c = c;
-  c->ctx = ctx;
-  c->n = kept;
-  const size_t nn = (size_t)std::max(kept, 1);
-  GA_HIP(pool_malloc(&c->pts, nn * sizeof(float4)));
-  if (cloud->covA) GA_HIP(pool_malloc(&c->covA, nn * sizeof(float4)));
-  if (cloud->covB) GA_HIP(pool_malloc(&c->covB, nn * sizeof(float2)));
-  if (cloud->normals) GA_HIP(pool_malloc(&c->normals, nn * sizeof(float4)));
-  if (cloud->pts64) GA_HIP(pool_malloc(&c->pts64, nn * sizeof(double4)));
-  if (cloud->times) GA_HIP(pool_malloc(&c->times, nn * sizeof(double)));
-  if (cloud->intensities) GA_HIP(pool_malloc(&c->intensities, nn * sizeof(double)));
-  if (cloud->cov64) GA_HIP(pool_malloc(&c->cov64, nn * 6 * sizeof(double)));
-  c->has_covs = cloud->has_covs;
-  c->has_normals = cloud->has_normals;
-  c->plane_form = cloud->plane_form;
-  if (kept > 0) {
-    GatherArgs a;
-    a.pts = cloud->pts, a.covA = cloud->covA, a.covB = cloud->covB, a.normals = cloud->normals, a.pts64 = cloud->pts64, a.times = cloud->times;
-    a.intensities = cloud->intensities, a.cov64 = cloud->cov64;
-    a.o_pts = c->pts, a.o_covA = c->covA, a.o_covB = c->covB, a.o_normals = c->normals, a.o_pts64 = c->pts64, a.o_times = c->times;
-    a.o_intensities = c->intensities, a.o_cov64 = c->cov64;
-    edit_gather_kernel<<<grid_for(size), 256, 0, st>>>(size, keep.as<int>(), pos.as<int>(), a);
-    GA_HIP(hipGetLastError());
-  }
+  GA_TRY(alloc_cloud_like(cloud, kept, &result));
+  glim_amd_cloud* c = result.c;
+  if (kept > 0) GA_HIP(cloud_gather(st, size, keep.as<int>(), pos.as<int>(), nullptr, gather_args(cloud, c)));
   if (cloud->h_times.size() == (size_t)size) {
     c->h_times.reserve((size_t)kept);
     for (int i = 0; i < size; i++)

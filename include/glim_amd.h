@@ -1279,6 +1279,37 @@ int glim_amd_edit_min_cut(const glim_amd_cloud* const* clouds, int32_t num_cloud
                           const glim_amd_edit_window* window, const glim_amd_edit_min_cut_params* params, int64_t capacity, int32_t* pairs,
                           glim_amd_edit_min_cut_result* out);
 
+/* ---- Resampling a resident cloud ------------------------------------------------------------------------------------------------------
+ * gtsam_points::random_sampling (mapping/sub_mapping.cpp:385, global_mapping.cpp:248 / :734, global_mapping_pose_graph.cpp:263 / :268,
+ * sub_mapping_passthrough.cpp:151, odometry_estimation_cpu.cpp:181), gtsam_points::sample (points_selector.cpp:561,
+ * cloud_preprocessor.cpp:136) and gtsam_points::transform (odometry_estimation_cpu.cpp:184, sub_mapping_passthrough.cpp:75 / :147,
+ * manual_loop_close_modal.cpp:332, loose_initial_state_estimation.cpp:77) on a cloud that is already on the device.  Each call returns a NEW
+ * cloud of the input's context, to be destroyed by the caller; the input is never modified and may be destroyed before the result.
+ *
+ * The result carries every per-point array the input holds: the FP32 points, covariances and normals, the exact FP64 points, times,
+ * intensities and FP64 covariances.  random_sample and sample gather them bit for bit, and "has covariances", "has normals" and the plane
+ * form follow the input.  Neighbour lists are NOT carried over (their indices would be wrong), and whatever a cloud builds on first use is
+ * built again for the result on its first use. */
+/* The m = (int64)((double)size * rate) points with the smallest (sample_hash(seed, i) >> 32, i), compared lexicographically, in
+ * ascending i; sample_hash is splitmix64 of seed + (i + 1) * 0x9E3779B97F4A7C15 (csrc/sample_hash.hpp).  This is the rule of the draw that
+ * ends glim_amd_merge_frames.  rate >= 0.99 returns a copy of the whole cloud: upstream's own
+ * shortcut AS RECALLED (gtsam_points' source is not in the reference tree; the guards at global_mapping.cpp:245 and
+ * global_mapping_pose_graph.cpp:265 show the same constant).  m == 0 and an empty input give an empty cloud.
+ * GLIM_AMD_ERR_INVALID: a NULL cloud or output, a rate that is NaN, infinite or < 0. */
+int glim_amd_cloud_random_sample(const glim_amd_cloud* cloud, double rate, uint64_t seed, glim_amd_cloud** out);
+/* out[j] = in[indices[j]] for j < m: any order, duplicates allowed, m may exceed the input's size (and may be 0, indices NULL).
+ * GLIM_AMD_ERR_INVALID: a NULL cloud or output, m < 0 or m > 2^28, NULL indices with m > 0, an index outside [0, size). */
+int glim_amd_cloud_sample(const glim_amd_cloud* cloud, int64_t m, const int32_t* indices, glim_amd_cloud** out);
+/* T12: row-major 3 x 4 [L | t]; L need not be a rotation.  FP64 throughout, every product and sum rounded on its own, in this order:
+ *   point       out_r = ((T[4r] p0 + T[4r+1] p1) + T[4r+2] p2) + T[4r+3] p3, and p3 is copied
+ *   covariance  (L C) L^T, rows by columns, left to right, the upper triangle only
+ *   normal      out_r = (T[4r] n0 + T[4r+1] n1) + T[4r+2] n2
+ * Where the cloud holds FP64 points / covariances those are transformed and the FP32 arrays of the result are their roundings; where it
+ * holds FP32 only, they are promoted, transformed and rounded.  Times and intensities are copied.  The plane form is decided anew on the
+ * result's arrays, as an upload of them would.  A point that is not finite gives whatever the expressions give.
+ * GLIM_AMD_ERR_INVALID: a NULL argument, an entry of T12 that is not finite. */
+int glim_amd_cloud_transform(const glim_amd_cloud* cloud, const double* T12, glim_amd_cloud** out);
+
 #ifdef __cplusplus
 }
 #endif

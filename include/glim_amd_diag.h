@@ -67,6 +67,11 @@ int glim_amd_debug_sort_pairs(glim_amd_ctx* ctx, int64_t n, int32_t bits, const 
  * selections and removal, the ball selection, the kNN grid, the preprocessing: out[i] = in[0] + ... + in[i - 1], out[0] = 0, 32-bit wrap-around.
  * n == 0: GLIM_AMD_OK, nothing is touched.  GLIM_AMD_ERR_INVALID: a NULL context, n < 0, n > 2^28, a NULL array with n > 0. */
 int glim_amd_debug_exclusive_scan(glim_amd_ctx* ctx, int64_t n, const int32_t* in, int32_t* out);
+/* parity / debug only: the selection stage of the random sampling of a cloud (glim_amd.h; csrc/resample.hip) on a caller's 32-bit keys -- keep_out[i] = 1
+ * iff (keys32[i], i) is among the m lexicographically smallest pairs, else 0.  Keys that tie at the threshold cannot be provoked through the
+ * generator at test sizes; here they can.  n == 0: GLIM_AMD_OK, nothing is touched.  GLIM_AMD_ERR_INVALID: a NULL context, n < 0, n > 2^28,
+ * m < 0, m > n, a NULL array with n > 0. */
+int glim_amd_debug_select_smallest(glim_amd_ctx* ctx, int64_t n, const uint32_t* keys32, int64_t m, int32_t* keep_out);
 
 /* The hypotheses [first, first + count) of glim_amd_ransac_align on the same arguments, every one scored, no early stop: samples (count x 3
  * source indices), status (count), poses12 (count x 12; the identity where status != 0), inliers (count; 0 where status != 0); any of them may
