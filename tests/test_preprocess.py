@@ -322,6 +322,17 @@ def test_hip_preprocess_then_deskew_then_covariances(orc):
     _, ref_covs = orc.covariances(xyz.astype(np.float64), ref["neighbors"])
     # (ill-conditioned neighbourhoods flip the smallest eigenvector: tests/test_gpu_parity.py masks them the same way)
     assert (np.abs(covs - ref_covs).max(axis=(1, 2)) < 1e-4).mean() > 0.9
+    # ... and against what the kernel READS: the exact FP64 deskewed points, every point, no mask (tests/test_ref.py covariance_report) -- the
+    # invariants hold everywhere, and whatever lies beyond 1e-5 has two smallest eigenvalues that coincide to the solver's resolution
+    from test_ref import covariance_report
+
+    p64 = desk.download_points64()
+    np.testing.assert_array_equal(p64, ref_desk)
+    _, covs, normals = desk.download()
+    ref_n64, ref_c64 = orc.covariances(p64, ref["neighbors"])
+    frac, worst_gap = covariance_report(p64, ref["neighbors"], 10, covs, normals, ref_c64, ref_n64)
+    print(f"preprocess -> deskew -> covariances from the FP64 points: fraction beyond 1e-5 = {frac:.2e}, largest relative gap among them = {worst_gap:.2e}")
+    assert frac == 0.0 or worst_gap < 1e-6, (frac, worst_gap)
     # a cloud that did not come from preprocess() cannot be deskewed this way
     with pytest.raises(api.GlimAmdError):
         api.PointCloudGPU.clone(pts[:100], ctx=ctx).deskew(Til)
