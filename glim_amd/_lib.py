@@ -262,6 +262,46 @@ class GraphTerms(C.Structure):
     _fields_ = [("dampings", C.POINTER(GraphDamping)), ("num_dampings", C.c_int32), ("reserved", C.c_int32), ("between_huber_width", C.POINTER(C.c_double))]
 
 
+class NavVectorPrior(C.Structure):
+    """glim_amd_nav_vector_prior (include/glim_amd.h "Graph optimisation with velocity and bias variables")"""
+
+    _fields_ = [("node", C.c_int32), ("reserved", C.c_int32), ("value", C.c_double * 6), ("information", C.c_double * 36)]
+
+
+class NavVectorBetween(C.Structure):
+    """glim_amd_nav_vector_between"""
+
+    _fields_ = [("node_i", C.c_int32), ("node_j", C.c_int32), ("measurement", C.c_double * 6), ("information", C.c_double * 36)]
+
+
+class NavImuTerm(C.Structure):
+    """glim_amd_nav_imu_term"""
+
+    _fields_ = [("pose_i", C.c_int32), ("velocity_i", C.c_int32), ("pose_j", C.c_int32), ("velocity_j", C.c_int32), ("bias", C.c_int32), ("mode", C.c_int32),
+                ("dt", C.c_double), ("gravity", C.c_double * 3), ("bias_hat", C.c_double * 6), ("delta", C.c_double * 9), ("H_bias", C.c_double * 54),
+                ("information", C.c_double * 81)]
+
+
+class NavTerms(C.Structure):
+    """glim_amd_nav_terms"""
+
+    _fields_ = [("kinds", C.POINTER(C.c_int32)), ("vector_priors", C.POINTER(NavVectorPrior)), ("vector_betweens", C.POINTER(NavVectorBetween)),
+                ("imu_terms", C.POINTER(NavImuTerm)), ("num_vector_priors", C.c_int32), ("num_vector_betweens", C.c_int32), ("num_imu_terms", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class NavResult(C.Structure):
+    """glim_amd_nav_result"""
+
+    _fields_ = [("cost", C.c_double), ("factor_cost", C.c_double), ("prior_cost", C.c_double), ("between_cost", C.c_double), ("vector_prior_cost", C.c_double),
+                ("vector_between_cost", C.c_double), ("imu_cost", C.c_double), ("num_inliers", C.c_int64), ("iterations", C.c_int32), ("trials", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32), ("lam", C.c_double)]
+
+
+NODE_POSE, NODE_BIAS, NODE_VELOCITY = 0, 1, 2  # GLIM_AMD_NODE_*
+IMU_TANGENT, IMU_MANIFOLD = 0, 1               # GLIM_AMD_IMU_*
+
+
 class BaParams(C.Structure):
     """glim_amd_ba_params (include/glim_amd.h "Plane / edge bundle-adjustment factors and ball selection")"""
 
@@ -489,6 +529,11 @@ SYMBOLS = {
     "glim_amd_debug_graph_align_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
                                               C.POINTER(LMParams), _dp, _dp, C.POINTER(BundleResult), _i32, _dp, _dp, _dp,
                                               C.POINTER(BundleTraceRound), _i32]),
+    "glim_amd_graph_align_nav": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp, _i32,
+                                      C.POINTER(LMParams), _dp, _dp, C.POINTER(NavResult), C.POINTER(GraphTerms), _dp, C.POINTER(NavTerms)]),
+    "glim_amd_debug_graph_align_nav_trace": (_i, [_vp, _pp, _pp, _ip, _ip, _i32, _u32, C.POINTER(BundlePrior), _i32, C.POINTER(BundleBetween), _i32, _dp,
+                                                  _i32, C.POINTER(LMParams), _dp, _dp, C.POINTER(NavResult), C.POINTER(GraphTerms), _dp, C.POINTER(NavTerms),
+                                                  _i32, _dp, _dp, _dp, C.POINTER(BundleTraceRound), _i32]),
     "glim_amd_debug_graph_solve": (_i, [_vp, _dp, _i32, C.c_double, _dp, C.POINTER(_i32)]),
     "glim_amd_ba_default_params": (_i, [C.POINTER(BaParams)]),
     "glim_amd_ba_ball_select": (_i, [_pp, _i32, _dp, _dp, _d, _i64, _ip, _lp]),

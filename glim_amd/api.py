@@ -916,6 +916,26 @@ class NonlinearFactorSetGPU:
         _lib.GRAPH_MAX_POSES poses and _lib.GRAPH_MAX_FACTORS factors."""
         return self._optimize(graph_align, "optimize_graph", values, priors, betweens, params, dampings)
 
+    def optimize_nav_graph(self, values, kinds, priors=(), betweens=(), vector_priors=(), vector_betweens=(), imu_terms=(), params=None, dampings=()):
+        """optimize_graph() over pose, velocity and bias variables (graph_align_nav; the graphs of sub_mapping.cpp:218-243 and
+        global_mapping.cpp:168-216 with enable_imu = true).  values: {key: 4 x 4 pose, 6 bias values or 3 velocity values}; kinds: {key:
+        NODE_POSE / NODE_BIAS / NODE_VELOCITY}; vector_priors: (key, value, information); vector_betweens: (key_i, key_j, measurement,
+        information); imu_terms: ImuTerm whose five nodes are keys.  The nodes are ordered by sorted key.  Returns ({key: value},
+        NavGraphResult)."""
+        if any(not f.is_binary for f in self.factors):
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize_nav_graph", "a unary factor: the graph is over binary factors")
+        validation = {f.enable_surface_validation for f in self.factors}
+        if len(validation) > 1:
+            raise GlimAmdError(-1, "NonlinearFactorSetGPU.optimize_nav_graph", "surface validation on some factors only")
+        keys = sorted(values)
+        at = {k: i for i, k in enumerate(keys)}
+        terms = [ImuTerm(*[at[k] for k in t.nodes], t.dt, t.gravity, t.bias_hat, t.delta, t.H_bias, t.information, t.mode) for t in imu_terms]
+        res = graph_align_nav([(f.target_voxelmap, f.source, at[f.target_key], at[f.source_key]) for f in self.factors], [(at[k], P, info) for k, P, info in priors],
+                              [(at[b[0]], at[b[1]]) + tuple(b[2:]) for b in betweens], [values[k] for k in keys], [kinds[k] for k in keys],
+                              [(at[k], v, info) for k, v, info in vector_priors], [(at[i], at[j], d, info) for i, j, d, info in vector_betweens], terms,
+                              [(at[k], d) for k, d in dampings], FACTOR_SURFACE_VALIDATION if validation == {True} else 0, params, self.ctx)
+        return {k: res.nodes[i] for i, k in enumerate(keys)}, res
+
     def correspondences(self, index, delta):
         n = self.factors[index].source.size()
         corr = np.zeros((n, 4), dtype=np.int32)
@@ -1839,6 +1859,124 @@ def graph_align_debug_trace(factors, priors, betweens, X_init, flags=0, params=N
     rounds_per_chunk: rounds enqueued between two looks at the status (0: the default); it moves no bit."""
     return _align_poses_trace("glim_amd_debug_graph_align_trace", (int(rounds_per_chunk),), factors, priors, betweens, X_init, flags, params, ctx, one_thread, trace,
                               dampings)
+
+
+NODE_POSE, NODE_BIAS, NODE_VELOCITY = _lib.NODE_POSE, _lib.NODE_BIAS, _lib.NODE_VELOCITY
+IMU_TANGENT, IMU_MANIFOLD = _lib.IMU_TANGENT, _lib.IMU_MANIFOLD
+
+
+class ImuTerm:
+    """One gtsam::ImuFactor(X_i, V_i, X_j, V_j, B) of graph_align_nav (glim_amd_nav_imu_term): the five node indices, dt > 0, gravity (gtsam's
+    n_gravity), bias_hat (acc, gyro), delta = (theta, dp, dv) the preintegrated measurement at bias_hat, H_bias (9 x 6) its derivative by
+    (acc, gyro), information (9 x 9, (rot, pos, vel) order: the inverse of preintMeasCov) and the mode: IMU_TANGENT (gtsam's
+    TangentPreintegration, the build default) or IMU_MANIFOLD."""
+
+    def __init__(self, pose_i, velocity_i, pose_j, velocity_j, bias, dt, gravity, bias_hat, delta, H_bias, information, mode=IMU_TANGENT):
+        self.nodes = (pose_i, velocity_i, pose_j, velocity_j, bias)  # (indices; keys in NonlinearFactorSetGPU.optimize_nav_graph)
+        self.dt, self.mode = float(dt), int(mode)
+        self.gravity = np.asarray(gravity, dtype=np.float64).reshape(3)
+        self.bias_hat = np.asarray(bias_hat, dtype=np.float64).reshape(6)
+        self.delta = np.asarray(delta, dtype=np.float64).reshape(9)
+        self.H_bias = np.asarray(H_bias, dtype=np.float64).reshape(9, 6)
+        self.information = np.asarray(information, dtype=np.float64).reshape(9, 9)
+
+    def _fill(self, c):
+        c.pose_i, c.velocity_i, c.pose_j, c.velocity_j, c.bias = [int(v) for v in self.nodes]
+        c.mode, c.dt = self.mode, self.dt
+        c.gravity[:], c.bias_hat[:], c.delta[:] = list(self.gravity), list(self.bias_hat), list(self.delta)
+        c.H_bias[:], c.information[:] = list(self.H_bias.reshape(-1)), list(self.information.reshape(-1))
+
+
+class NavGraphResult(BundleResult):
+    """glim_amd_graph_align_nav's answer: BundleResult's fields (`poses` is None), `nodes` (per node a 4 x 4 pose, 6 bias values or 3 velocity
+    values), `values12` (the raw N x 12 rows) and the three further parts of the cost."""
+
+    def __init__(self, c, X12, kinds, compact, between_weights=None):
+        BundleResult.__init__(self, c, None, compact, between_weights)
+        self.values12 = X12
+        self.nodes = [_poses44(x[None])[0] if k == NODE_POSE else x[:6].copy() if k == NODE_BIAS else x[:3].copy() for x, k in zip(X12, kinds)]
+        self.vector_prior_cost, self.vector_between_cost, self.imu_cost = c.vector_prior_cost, c.vector_between_cost, c.imu_cost
+
+
+def _padded(v, info, dim):
+    """a vector term's value and information (3 or 6 wide) in the 6-wide form of the C structs"""
+    value, L = np.zeros(6), np.zeros((6, 6))
+    v, info = np.asarray(v, dtype=np.float64).reshape(-1), np.asarray(info, dtype=np.float64)
+    d = len(v)
+    if d not in (dim, 6) or info.shape not in ((d, d), (6, 6)):
+        raise GlimAmdError(-1, "graph_align_nav", "a vector term's value and information must be %d or 6 wide" % dim)
+    value[:d] = v
+    L[:info.shape[0], :info.shape[0]] = info
+    return list(value), list(L.reshape(-1))
+
+
+def _nav_args(nodes_init, kinds, vector_priors, vector_betweens, imu_terms):
+    """-> (the node rows N x 12, glim_amd_nav_terms, what must stay alive)"""
+    kinds = np.ascontiguousarray(kinds, dtype=np.int32).reshape(len(nodes_init))
+    X = np.zeros((len(nodes_init), 12))
+    for k, (x, kind) in enumerate(zip(nodes_init, kinds)):
+        x = np.asarray(x, dtype=np.float64)
+        if kind == NODE_POSE:
+            X[k] = pose12(x)
+        else:
+            X[k, :x.size] = x.reshape(-1)  # (a row that is too long or has entries where none belong is the entry point's to refuse)
+    dim = lambda node: 3 if 0 <= node < len(kinds) and kinds[node] == NODE_VELOCITY else 6
+    VP, VB, I = len(vector_priors), len(vector_betweens), len(imu_terms)
+    cp, cb, ci = (_lib.NavVectorPrior * max(VP, 1))(), (_lib.NavVectorBetween * max(VB, 1))(), (_lib.NavImuTerm * max(I, 1))()
+    for c, (k, v, info) in zip(cp, vector_priors):
+        c.node = int(k)
+        c.value[:], c.information[:] = _padded(v, info, dim(int(k)))
+    for c, (i, j, d, info) in zip(cb, vector_betweens):
+        c.node_i, c.node_j = int(i), int(j)
+        c.measurement[:], c.information[:] = _padded(d, info, dim(int(i)))
+    for c, term in zip(ci, imu_terms):
+        term._fill(c)
+    nav = _lib.NavTerms(_ip(kinds), C.cast(cp, C.POINTER(_lib.NavVectorPrior)), C.cast(cb, C.POINTER(_lib.NavVectorBetween)), C.cast(ci, C.POINTER(_lib.NavImuTerm)),
+                        VP, VB, I, 0)
+    return X, kinds, nav, (cp, cb, ci)
+
+
+def _graph_align_nav(entry, tail, factors, priors, betweens, nodes_init, kinds, vector_priors, vector_betweens, imu_terms, dampings, flags, params, ctx, rounds=0):
+    params = params or bundle_align_params()
+    X, kinds, nav, alive = _nav_args(nodes_init, kinds, list(vector_priors), list(vector_betweens), list(imu_terms))
+    betweens, terms, weights, alive2 = _graph_terms(betweens, dampings)
+    ctx, fa, ta, keep = _bundle_args(factors, priors, betweens, [np.eye(4)] * len(X), ctx)
+    F, N = fa[-1], ta[-1]
+    prm = params._c()
+    X_out, compact, out = np.zeros((N, 12)), np.zeros((F, _lib.COMPACT_DOUBLES)), _lib.NavResult()
+    tX, tTf, trec = np.zeros((rounds, N, 12)), np.zeros((rounds, F, 12)), np.zeros((rounds, F, _lib.COMPACT_DOUBLES))
+    tr = (_lib.BundleTraceRound * max(rounds, 1))()
+    targs = (_dp(tX), _dp(tTf), _dp(trec), tr) if rounds else (None, None, None, None)
+    more = tail(targs) if tail else ()
+    check(getattr(lib(), entry)(*fa, int(flags), *ta[:4], _dp(X), N, C.byref(prm), _dp(X_out), _dp(compact), C.byref(out), *(terms or (None, None)), C.byref(nav),
+                                *more), entry)
+    res = NavGraphResult(out, X_out, kinds, compact, weights)
+    rows = []
+    for k in range(min(rounds, res.trials + 1) if N else 0):
+        rows.append({"X": tX[k].copy(), "Tf": tTf[k].copy(), "compact": trec[k].copy(), "lam": tr[k].lam, "cost": tr[k].cost, "accepted": bool(tr[k].accepted),
+                     "status": tr[k].status})
+    return res, rows, (tX, tTf, trec, tr)
+
+
+def graph_align_nav(factors, priors, betweens, nodes_init, kinds, vector_priors=(), vector_betweens=(), imu_terms=(), dampings=(), flags=0, params=None, ctx=None):
+    """The global-graph optimisation over pose, velocity and bias nodes (glim_amd_graph_align_nav): the graphs GLIM builds with enable_imu = true
+    (sub_mapping.cpp:218-243, global_mapping.cpp:168-216).  factors, priors, betweens, dampings, flags, params: graph_align's, with node
+    indices; factors, priors and betweens must name POSE nodes, a damping may name any node.  nodes_init: per node a 4 x 4 pose, 6 bias values
+    (acc, gyro) or 3 velocity values; kinds: NODE_POSE / NODE_BIAS / NODE_VELOCITY per node.  vector_priors: (node, value, information);
+    vector_betweens: (i, j, measurement of x_j - x_i, information), 3 wide for velocities and 6 wide for biases; imu_terms: ImuTerm.  Returns a
+    NavGraphResult."""
+    return _graph_align_nav("glim_amd_graph_align_nav", None, factors, priors, betweens, nodes_init, kinds, vector_priors, vector_betweens, imu_terms, dampings, flags,
+                            params, ctx)[0]
+
+
+def graph_align_nav_debug_trace(factors, priors, betweens, nodes_init, kinds, vector_priors=(), vector_betweens=(), imu_terms=(), dampings=(), flags=0, params=None,
+                                ctx=None, one_thread=False, trace=True, rounds_per_chunk=0):
+    """Test window (glim_amd_debug_graph_align_nav_trace): graph_align_debug_trace's returns for graph_align_nav; a row's `X` is the N x 12 node
+    values of the round's candidate.  one_thread: every round is bundle_lm_step.hpp's step() in one device thread."""
+    params = params or bundle_align_params()
+    tail = lambda targs: (1 if one_thread else 0, *targs, int(rounds_per_chunk))
+    return _graph_align_nav("glim_amd_debug_graph_align_nav_trace", tail, factors, priors, betweens, nodes_init, kinds, vector_priors, vector_betweens, imu_terms,
+                            dampings, flags, params, ctx, rounds=1 + params.resolved_max_trials() if trace else 0)
 
 
 def graph_solve_debug(S, n, lam, ctx=None):

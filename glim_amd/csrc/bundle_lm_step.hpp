@@ -24,16 +24,21 @@
 //              Hessian factor with G = diag(d), g = 0, f = 0 (the factor's source is not in the reference tree).  It adds d[m]
 //              to entry (6k + m, 6k + m) of H and nothing to any other entry, to b or to the cost.  Several on one pose are allowed; a pose
 //              touched only by dampings has the block diag(sum d) + lambda I, the right-hand side +0.0 and a zero step.
+//   nodes      (the global graph only; Graph::nav, default: none) a block may be a BIAS or a VELOCITY node instead of a pose, and the graph may
+//              hold vector priors, vector betweens and IMU terms (gtsam::ImuFactor): nav_terms.hpp, whose item functions are called here.
+//              The LDS bundle is not extended: 32 blocks hold only ten frames once a frame needs X, V and B.  Still out of scope: ISAM2,
+//              marginals, CombinedImuFactor, IMU terms in the LDS bundle.
 //   system     H dense symmetric 6N x 6N, kept as its lower triangle in packed rows (row i at i (i + 1) / 2), then b as row 6N.  Every entry is a
 //              sum from +0.0 over the items of its pose block in this order: factors by ascending index, then priors, then betweens, then
-//              dampings (assemble_entry, assemble_rhs over the lists build_lists makes).  cost = ((sum_f e_f) + sum priors) + sum betweens,
-//              each ascending from +0.0.  "The cost at a candidate" comes from the LINEARISING evaluation: a trial is one evaluation.
+//              vector priors, vector betweens and IMU terms, then dampings (assemble_entry, assemble_rhs over the lists build_lists makes).
+//              cost = ((((sum_f e_f) + sum priors) + sum betweens) + sum vector priors) + sum vector betweens) + sum IMU terms (total_cost),
+//              each ascending from +0.0; without the last three kinds their sums are +0.0 and the bits are those of the first three.  "The cost at a candidate" comes from the LINEARISING evaluation: a trial is one evaluation.
 //   solve      (H + lambda I) delta = -b.  L[i][j] = (A[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j], the subtractions one at a time in ascending
 //              k (chol_pivot, chol_entry).  -b is carried as row 6N of A, so y = L^-1 (-b) is that row of L.  A pivot that is not > 0 or not
 //              finite is a FAILED solve: the candidate is then the kept poses and the trial is rejected.  Back substitution by columns:
 //              delta[k] = s[k] / L[k][k], then s[i] -= L[k][i] delta[k] for i < k, k descending from 6N - 1.  A pose no factor or term
 //              touches has the block lambda I and a zero step.
-//   retract    X_k' = X_k Exp(delta_k) with lm::retract.  The rotations are re-orthonormalised NEVER.
+//   retract    X_k' = X_k Exp(delta_k) with lm::retract (a BIAS or VELOCITY node: nav::retract_node).  The rotations are re-orthonormalised NEVER.
 //   the rest   round 0, accept / reject, the lambda updates, the statuses and the budgets are lm::decide of lm_step.hpp, CALLED with "the error"
 //              read as the cost above and "inliers" as the sum of the factors' inlier counts.  A graph WITHOUT factors (F = 0) has no inliers
 //              to ask for: the two inlier conditions hold there.  The terms' residuals and Jacobians are ct_se3.hpp's, called too.
@@ -44,6 +49,7 @@
 #pragma once
 #include "ct_se3.hpp"
 #include "lm_step.hpp"
+#include "nav_terms.hpp"
 #include "record_expand.hpp"
 
 // an item function: one definition, never inlined, so that the workgroup form and the one-thread form run the same machine code
@@ -70,7 +76,8 @@ GLIM_AMD_LM_HD inline int system_doubles(int n) { return tri(n) + n; }  // the p
 constexpr int MAX_SYSTEM = MAX_DIM * (MAX_DIM + 1) / 2 + MAX_DIM;
 
 // what an item of a pose block's list adds to the block (rows of pose hi, columns of pose lo, lo <= hi)
-enum { F_TT = 0, F_SS = 1, F_ST = 2, F_TS = 3, PRIOR = 4, B_II = 5, B_JJ = 6, B_JI = 7, B_IJ = 8, DAMP = 9 };
+// (an IMU item's index is 32 * term + 5 * row slot + column slot: the slots of nav_terms.hpp)
+enum { F_TT = 0, F_SS = 1, F_ST = 2, F_TS = 3, PRIOR = 4, B_II = 5, B_JJ = 6, B_JI = 7, B_IJ = 8, DAMP = 9, VPRIOR = 10, VB_II = 11, VB_JJ = 12, VB_JI = 13, VB_IJ = 14, IMU = 15 };
 
 struct Graph {
   int N, F, P, Q;
@@ -84,9 +91,11 @@ struct Graph {
   const int* dk = nullptr;     // D: pose of a damping
   const double* dd = nullptr;  //    its diagonal (6)
   const double* bw = nullptr;  // Q: Huber width of a between (0: Gaussian), or null: every between is Gaussian
+  nav::Terms nav;              // node kinds, vector priors, vector betweens, IMU terms (the global graph only); default: none
 };
 GLIM_AMD_LM_HD inline int list_items(int F, int P, int Q) { return 3 * F + P + 3 * Q; }
 GLIM_AMD_LM_HD inline int list_items(int F, int P, int Q, int D) { return list_items(F, P, Q) + D; }
+GLIM_AMD_LM_HD inline int list_items(int F, int P, int Q, int D, const nav::Terms& t) { return list_items(F, P, Q, D) + t.VP + 3 * t.VB + 15 * t.I; }
 
 // the lists, in the order of the sums.  first: tri(N) + 1 ints, items: list_items ints, cursor: tri(N) ints of workspace.  Host only.
 inline void build_lists(const Graph& g, int* first, int* items, int* cursor) {
@@ -123,6 +132,22 @@ inline void build_lists(const Graph& g, int* first, int* items, int* cursor) {
       if (i < j) put(i, j, q, B_JI);
       else put(j, i, q, B_IJ);
     }
+    for (int p = 0; p < g.nav.VP; p++) put(g.nav.vpk[p], g.nav.vpk[p], p, VPRIOR);
+    for (int q = 0; q < g.nav.VB; q++) {
+      const int i = g.nav.vbi[q], j = g.nav.vbj[q];
+      put(i, i, q, VB_II);
+      put(j, j, q, VB_JJ);
+      if (i < j) put(i, j, q, VB_JI);
+      else put(j, i, q, VB_IJ);
+    }
+    for (int q = 0; q < g.nav.I; q++) {  // the 15 block pairs of the five nodes
+      const int* n = g.nav.imn + nav::IMU_SLOTS * q;
+      for (int a = 0; a < nav::IMU_SLOTS; a++)
+        for (int b = a; b < nav::IMU_SLOTS; b++) {
+          if (n[a] <= n[b]) put(n[a], n[b], 32 * q + 5 * b + a, IMU);
+          else put(n[b], n[a], 32 * q + 5 * a + b, IMU);
+        }
+    }
     for (int d = 0; d < g.D; d++) put(g.dk[d], g.dk[d], d, DAMP);
   }
 }
@@ -133,6 +158,7 @@ struct Scalars {
   double cost, fcost, pcost, bcost;    // at the kept poses
   double inliers;                      // there: the sum of the factors' counts (exact in a double)
   double trial_cost;                   // of the last round's evaluation (kept or not)
+  double vpcost, vbcost, icost;        // at the kept poses: the vector priors', the vector betweens', the IMU terms'
   int solve_ok, started, iterations, trials, status, accepted;  // accepted: of the last round
 };
 
@@ -252,6 +278,23 @@ GLIM_AMD_LM_HD inline double assemble_entry(const Graph& g, const glim_amd_linea
       case B_JJ: v = bc[BETWEEN_STRIDE * k + 12 * (rr + 6) + cc + 6]; break;
       case B_JI: v = bc[BETWEEN_STRIDE * k + 12 * (rr + 6) + cc]; break;
       case B_IJ: v = bc[BETWEEN_STRIDE * k + 12 * rr + cc + 6]; break;
+      case VPRIOR:
+      case VB_II:
+      case VB_JJ:
+      case VB_JI:
+      case VB_IJ: {  // a VELOCITY's rows and columns 3..5: nothing
+        const int d = nav::node_dim(nav::kind_of(g.nav, hi)), kd = it & 15;
+        if (rr >= d || cc >= d) continue;
+        if (kd == VPRIOR) v = g.nav.vpc[nav::VPRIOR_STRIDE * k + 6 * rr + cc];
+        else v = g.nav.vbc[nav::VBETWEEN_STRIDE * k + 12 * (rr + (kd == VB_JJ || kd == VB_JI ? 6 : 0)) + cc + (kd == VB_JJ || kd == VB_IJ ? 6 : 0)];
+        break;
+      }
+      case IMU: {
+        const int q = k >> 5, rs = (k & 31) / 5, cs = (k & 31) % 5;
+        if (rr >= nav::imu_width(rs) || cc >= nav::imu_width(cs)) continue;
+        v = g.nav.ic[(size_t)nav::IMU_STRIDE * q + nav::IMU_W * (nav::imu_offset(rs) + rr) + nav::imu_offset(cs) + cc];
+        break;
+      }
       default:  // DAMP: the diagonal, and no other entry of the block
         if (rr != cc) continue;
         v = g.dd[6 * k + rr];
@@ -276,6 +319,20 @@ GLIM_AMD_LM_HD inline double assemble_rhs(const Graph& g, const glim_amd_lineari
       case PRIOR: v = pc[PRIOR_STRIDE * k + 36 + rr]; break;
       case B_II: v = bc[BETWEEN_STRIDE * k + 144 + rr]; break;
       case B_JJ: v = bc[BETWEEN_STRIDE * k + 144 + 6 + rr]; break;
+      case VPRIOR:
+      case VB_II:
+      case VB_JJ: {
+        const int kd = it & 15;
+        if (rr >= nav::node_dim(nav::kind_of(g.nav, a))) continue;
+        v = kd == VPRIOR ? g.nav.vpc[nav::VPRIOR_STRIDE * k + 36 + rr] : g.nav.vbc[nav::VBETWEEN_STRIDE * k + 144 + (kd == VB_JJ ? 6 : 0) + rr];
+        break;
+      }
+      case IMU: {
+        const int q = k >> 5, rs = (k & 31) / 5;
+        if (rr >= nav::imu_width(rs)) continue;
+        v = g.nav.ic[(size_t)nav::IMU_STRIDE * q + nav::IMU_W * nav::IMU_W + nav::imu_offset(rs) + rr];
+        break;
+      }
       default: continue;  // DAMP: nothing
     }
     s += v;
@@ -334,9 +391,19 @@ GLIM_AMD_LM_HD inline bool solve(double* W, int n, double* delta) {
   return true;
 }
 
+// the cost from its parts: ((((factors + priors) + betweens) + vector priors) + vector betweens) + IMU.  A sum from +0.0 is never -0.0, so a
+// graph without the last three (their sums are +0.0) has the bits of (factors + priors) + betweens
+GLIM_AMD_LM_HD inline double total_cost(double fcost, double pcost, double bcost, double vpcost, double vbcost, double icost) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return ((((fcost + pcost) + bcost) + vpcost) + vbcost) + icost;
+}
+
 // the rule's scalar part: lm::decide on the cost, and the bundle's own bookkeeping.  The evaluation at the candidate gave (cost, fcost, pcost,
 // bcost, inliers).  true: the candidate is kept
-GLIM_AMD_LM_HD inline bool decide(const lm::Params& p, int F, Scalars& s, double cost, double fcost, double pcost, double bcost, double inliers) {
+GLIM_AMD_LM_HD inline bool decide(const lm::Params& p, int F, Scalars& s, double cost, double fcost, double pcost, double bcost, double inliers, double vpcost = 0.0,
+                                  double vbcost = 0.0, double icost = 0.0) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -349,6 +416,9 @@ GLIM_AMD_LM_HD inline bool decide(const lm::Params& p, int F, Scalars& s, double
     s.pcost = pcost;
     s.bcost = bcost;
     s.inliers = inliers;
+    s.vpcost = vpcost;
+    s.vbcost = vbcost;
+    s.icost = icost;
   }
   return keep;
 }
@@ -363,7 +433,7 @@ GLIM_AMD_LM_HD inline void init(const lm::Params& p, const double* X_init, Probl
     for (int q = 0; q < pr.g.Q; q++) pr.wk[q] = 1.0;
   Scalars& s = *pr.s;
   s.lambda = p.lambda_initial;
-  s.cost = s.fcost = s.pcost = s.bcost = s.inliers = s.trial_cost = 0.0;
+  s.cost = s.fcost = s.pcost = s.bcost = s.inliers = s.trial_cost = s.vpcost = s.vbcost = s.icost = 0.0;
   s.solve_ok = 1;
   s.started = s.iterations = s.trials = s.accepted = 0;
   s.status = lm::RUNNING;
@@ -384,9 +454,15 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, Problem& pr, const double* 
   for (int f = 0; f < g.F; f++) expand_factor(recs, pr.Tf, f, pr.lin);
   for (int q = 0; q < g.P; q++) prior_term(g, pr.cand, q, pr.pc);
   for (int q = 0; q < g.Q; q++) between_term(g, pr.cand, q, pr.bc, pr.wt);
+  for (int q = 0; q < g.nav.VP; q++) nav::vector_prior_term(g.nav, pr.cand, q);
+  for (int q = 0; q < g.nav.VB; q++) nav::vector_between_term(g.nav, pr.cand, q);
+  for (int q = 0; q < g.nav.I; q++) nav::imu_term(g.nav, pr.cand, q);
   const double fcost = sum_ascending(recs + 1, g.F, lm::RECORD), inliers = sum_ascending(recs, g.F, lm::RECORD);
   const double pcost = sum_ascending(pr.pc + 42, g.P, PRIOR_STRIDE), bcost = sum_ascending(pr.bc + 156, g.Q, BETWEEN_STRIDE);
-  const double cost = (fcost + pcost) + bcost;
+  const double vpcost = g.nav.VP ? sum_ascending(g.nav.vpc + 42, g.nav.VP, nav::VPRIOR_STRIDE) : 0.0;
+  const double vbcost = g.nav.VB ? sum_ascending(g.nav.vbc + 156, g.nav.VB, nav::VBETWEEN_STRIDE) : 0.0;
+  const double icost = g.nav.I ? sum_ascending(g.nav.ic + nav::IMU_STRIDE - 1, g.nav.I, nav::IMU_STRIDE) : 0.0;
+  const double cost = total_cost(fcost, pcost, bcost, vpcost, vbcost, icost);
   for (int r = 0; r < n; r++)
     for (int c = 0; c <= r; c++) pr.W[tri(r) + c] = assemble_entry(g, pr.lin, pr.pc, pr.bc, r, c);
   for (int r = 0; r < n; r++) pr.W[tri(n) + r] = assemble_rhs(g, pr.lin, pr.pc, pr.bc, r);
@@ -394,7 +470,7 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, Problem& pr, const double* 
     s.status = lm::NUMERIC;
     return;
   }
-  if (decide(p, g.F, s, cost, fcost, pcost, bcost, inliers)) {
+  if (decide(p, g.F, s, cost, fcost, pcost, bcost, inliers, vpcost, vbcost, icost)) {
     for (int i = 0; i < 12 * g.N; i++) pr.X[i] = pr.cand[i];
     for (int i = 0; i < lm::RECORD * g.F; i++) pr.rec[i] = recs[i];
     for (int i = 0; i < nsys; i++) pr.S[i] = pr.W[i];
@@ -407,7 +483,7 @@ GLIM_AMD_LM_HD inline void step(const lm::Params& p, Problem& pr, const double* 
   s.solve_ok = solve(pr.W, n, pr.delta) ? 1 : 0;
   for (int k = 0; k < g.N; k++) {
     if (s.solve_ok) {
-      lm::retract(pr.X + 12 * k, pr.delta + 6 * k, pr.cand + 12 * k);
+      nav::retract_node(nav::kind_of(g.nav, k), pr.X + 12 * k, pr.delta + 6 * k, pr.cand + 12 * k);
     } else {
       for (int i = 0; i < 12; i++) pr.cand[12 * k + i] = pr.X[12 * k + i];
     }

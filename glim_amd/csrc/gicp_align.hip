@@ -652,10 +652,14 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_items_kernel(const bundle
   for (int u = t; u < lm::RECORD * F; u += T) bad = bad || !lm::finite(recs[u]);
   for (int u = t; u < 12 * N; u += T) bad = bad || !lm::finite(pr.cand[u]);
   if (bad) w->bad_in = 1;
-  for (int i = t; i < F + g.P + g.Q; i += T) {
+  const int pose_items = F + g.P + g.Q, items = pose_items + g.nav.VP + g.nav.VB + g.nav.I;
+  for (int i = t; i < items; i += T) {
     if (i < F) expand_factor(recs, pr.Tf, i, pr.lin);
     else if (i < F + g.P) prior_term(g, pr.cand, i - F, pr.pc);
-    else between_term(g, pr.cand, i - F - g.P, pr.bc, pr.wt);
+    else if (i < pose_items) between_term(g, pr.cand, i - F - g.P, pr.bc, pr.wt);
+    else if (i < pose_items + g.nav.VP) nav::vector_prior_term(g.nav, pr.cand, i - pose_items);
+    else if (i < pose_items + g.nav.VP + g.nav.VB) nav::vector_between_term(g.nav, pr.cand, i - pose_items - g.nav.VP);
+    else nav::imu_term(g.nav, pr.cand, i - pose_items - g.nav.VP - g.nav.VB);
   }
 }
 
@@ -670,21 +674,24 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_assemble_kernel(const bun
   if (!lm::finite(v)) w->bad_in = 1;
 }
 
-// One small workgroup: the four ascending sums (a wavefront's first thread each, over values the workgroup stages in LDS chunk by chunk)
-// and bundle_lm::decide.  The decision goes into the problem's Scalars and words, where the later kernels of the round read it
+// One small workgroup: the seven ascending sums (the factors' two, the priors' and the betweens' by a wavefront's first thread each, the
+// vector priors', the vector betweens' and the IMU terms' by the 33rd thread of the first three wavefronts, over values the workgroup stages in
+// LDS chunk by chunk) and bundle_lm::decide.  The decision goes into the problem's Scalars and words, where the later kernels of the round read it
 __global__ __launch_bounds__(GRAPH_THREADS) void graph_decide_kernel(const bundle_lm::Problem pr, const lm::Params prm, GraphWords* w, const double* __restrict__ recs,
                                                                      const BundleTrace tr, int round) {
 #pragma clang fp contract(off)
   using namespace bundle_lm;
-  __shared__ double s_v[4][GRAPH_SUM_CHUNK];
-  __shared__ double s_sums[4];
+  __shared__ double s_v[7][GRAPH_SUM_CHUNK];
+  __shared__ double s_sums[7];
   const int t = threadIdx.x;
   if (pr.s->status != lm::RUNNING) {  // the same for every thread
     if (t == 0) w->keep = 0;
     return;
   }
   const Graph& g = pr.g;
-  const int F = g.F, most = max(F, max(g.P, g.Q));
+  const int F = g.F, most = max(max(F, max(g.P, g.Q)), max(g.nav.VP, max(g.nav.VB, g.nav.I)));
+  const int owns = t % 64 == 0 ? t / 64 : t % 64 == 32 && t < 192 ? 4 + t / 64 : -1;  // the sum this thread owns
+  const int count = owns < 0 ? 0 : owns < 2 ? F : owns == 2 ? g.P : owns == 3 ? g.Q : owns == 4 ? g.nav.VP : owns == 5 ? g.nav.VB : g.nav.I;
   double sum = 0.0;  // of the thread that owns a sum: sum_ascending over the chunks
   for (int base = 0; base < most; base += GRAPH_SUM_CHUNK) {
     for (int u = t; u < GRAPH_SUM_CHUNK; u += GRAPH_THREADS) {
@@ -695,24 +702,27 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_decide_kernel(const bundl
       }
       if (i < g.P) s_v[2][u] = pr.pc[(size_t)PRIOR_STRIDE * i + 42];
       if (i < g.Q) s_v[3][u] = pr.bc[(size_t)BETWEEN_STRIDE * i + 156];
+      if (i < g.nav.VP) s_v[4][u] = g.nav.vpc[(size_t)nav::VPRIOR_STRIDE * i + 42];
+      if (i < g.nav.VB) s_v[5][u] = g.nav.vbc[(size_t)nav::VBETWEEN_STRIDE * i + 156];
+      if (i < g.nav.I) s_v[6][u] = g.nav.ic[(size_t)nav::IMU_STRIDE * i + nav::IMU_STRIDE - 1];
     }
     __syncthreads();
-    if (t % 64 == 0) {
-      const int a = t / 64, count = a < 2 ? F : a == 2 ? g.P : g.Q, end = min(GRAPH_SUM_CHUNK, count - base);
-      for (int u = 0; u < end; u++) sum += s_v[a][u];
+    if (owns >= 0) {
+      const int end = min(GRAPH_SUM_CHUNK, count - base);
+      for (int u = 0; u < end; u++) sum += s_v[owns][u];
     }
     __syncthreads();
   }
-  if (t % 64 == 0) s_sums[t / 64] = sum;
+  if (owns >= 0) s_sums[owns] = sum;
   __syncthreads();
   if (t != 0) return;
   Scalars sc = *pr.s;
   sc.accepted = 0;
   w->lambda_before = sc.lambda;
-  const double cost = (s_sums[0] + s_sums[2]) + s_sums[3];
+  const double cost = total_cost(s_sums[0], s_sums[2], s_sums[3], s_sums[4], s_sums[5], s_sums[6]);
   int keep = 0;
   if (w->bad_in || !lm::finite(cost)) sc.status = lm::NUMERIC;
-  else keep = decide(prm, F, sc, cost, s_sums[0], s_sums[2], s_sums[3], s_sums[1]) ? 1 : 0;
+  else keep = decide(prm, F, sc, cost, s_sums[0], s_sums[2], s_sums[3], s_sums[1], s_sums[4], s_sums[5], s_sums[6]) ? 1 : 0;
   *pr.s = sc;
   w->keep = keep;
   w->bad_in = w->bad_out = 0;
@@ -751,13 +761,13 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_load_kernel(const double*
   graph_load_entry(S, n, lambda, i, j, M);
 }
 
-// the next candidates: a pose each.  After a failed solve they are the kept poses (the solve has left delta at +0.0)
+// the next candidates: a node each, retracted by its kind.  After a failed solve they are the kept poses (the solve has left delta at +0.0)
 __global__ __launch_bounds__(GRAPH_THREADS) void graph_retract_kernel(const bundle_lm::Problem pr, GraphWords* w) {
   if (pr.s->status != lm::RUNNING) return;
   const int k = (int)(blockIdx.x * GRAPH_THREADS + threadIdx.x);
   if (k >= pr.g.N) return;
   if (!w->fail) {
-    lm::retract(pr.X + 12 * k, pr.delta + 6 * k, pr.cand + 12 * k);
+    nav::retract_node(nav::kind_of(pr.g.nav, k), pr.X + 12 * k, pr.delta + 6 * k, pr.cand + 12 * k);
   } else {
     for (int i = 0; i < 12; i++) pr.cand[12 * k + i] = pr.X[12 * k + i];
   }
@@ -806,7 +816,7 @@ int graph_round(const bundle_lm::Problem& pr, const GraphScratch& gs, const lm::
   const int n = 6 * g.N;
   auto blocks = [](int count) { return std::max(1, (count + GRAPH_THREADS - 1) / GRAPH_THREADS); };
   const dim3 square(blocks(n), n + 1);
-  graph_items_kernel<<<blocks(g.F + g.P + g.Q), GRAPH_THREADS, 0, st>>>(pr, gs.words, d_recs, tr, round);
+  graph_items_kernel<<<blocks(g.F + g.P + g.Q + g.nav.VP + g.nav.VB + g.nav.I), GRAPH_THREADS, 0, st>>>(pr, gs.words, d_recs, tr, round);
   graph_assemble_kernel<<<square, GRAPH_THREADS, 0, st>>>(pr, gs.words);
   graph_decide_kernel<<<1, GRAPH_THREADS, 0, st>>>(pr, prm, gs.words, d_recs, tr, round);
   graph_keep_load_kernel<<<square, GRAPH_THREADS, 0, st>>>(pr, gs.words, d_recs, gs.M);
@@ -1225,21 +1235,66 @@ struct GraphCaps {
   int poses, factors, terms;
 };
 
+// the refusals of glim_amd_graph_align_nav's node kinds and new terms (the counts and the arrays have been looked at)
+int check_nav_args(const glim_amd_nav_terms& nav, const int32_t* target_pose, const int32_t* source_pose, int F, const glim_amd_bundle_prior* priors, int P,
+                   const glim_amd_bundle_between* betweens, int Q, const double* X, int N) {
+  auto kind = [&](int k) { return nav.kinds ? nav.kinds[k] : GLIM_AMD_NODE_POSE; };
+  auto is = [&](int k, int want) { return k >= 0 && k < N && kind(k) == want; };
+  auto vector_kind = [&](int k) { return is(k, GLIM_AMD_NODE_BIAS) || is(k, GLIM_AMD_NODE_VELOCITY); };
+  for (int k = 0; k < N; k++) {
+    const int kd = kind(k);
+    if (kd != GLIM_AMD_NODE_POSE && kd != GLIM_AMD_NODE_BIAS && kd != GLIM_AMD_NODE_VELOCITY) return GLIM_AMD_ERR_INVALID;
+    for (int u = kd == GLIM_AMD_NODE_POSE ? 12 : nav::node_dim(kd); u < 12; u++)
+      if (X[12 * k + u] != 0.0 || std::signbit(X[12 * k + u])) return GLIM_AMD_ERR_INVALID;
+  }
+  for (int f = 0; f < F; f++)
+    if (!is(target_pose[f], GLIM_AMD_NODE_POSE) || !is(source_pose[f], GLIM_AMD_NODE_POSE)) return GLIM_AMD_ERR_INVALID;
+  for (int p = 0; p < P; p++)
+    if (!is(priors[p].pose, GLIM_AMD_NODE_POSE)) return GLIM_AMD_ERR_INVALID;
+  for (int q = 0; q < Q; q++)
+    if (!is(betweens[q].pose_i, GLIM_AMD_NODE_POSE) || !is(betweens[q].pose_j, GLIM_AMD_NODE_POSE)) return GLIM_AMD_ERR_INVALID;
+  for (int p = 0; p < nav.num_vector_priors; p++) {
+    const glim_amd_nav_vector_prior& e = nav.vector_priors[p];
+    if (!vector_kind(e.node) || !all_finite_host(e.value, 6) || !all_finite_host(e.information, 36)) return GLIM_AMD_ERR_INVALID;
+  }
+  for (int q = 0; q < nav.num_vector_betweens; q++) {
+    const glim_amd_nav_vector_between& e = nav.vector_betweens[q];
+    if (!vector_kind(e.node_i) || !vector_kind(e.node_j) || e.node_i == e.node_j || kind(e.node_i) != kind(e.node_j)) return GLIM_AMD_ERR_INVALID;
+    if (!all_finite_host(e.measurement, 6) || !all_finite_host(e.information, 36)) return GLIM_AMD_ERR_INVALID;
+  }
+  for (int q = 0; q < nav.num_imu_terms; q++) {
+    const glim_amd_nav_imu_term& e = nav.imu_terms[q];
+    if (e.mode != GLIM_AMD_IMU_TANGENT && e.mode != GLIM_AMD_IMU_MANIFOLD) return GLIM_AMD_ERR_INVALID;
+    if (!is(e.pose_i, GLIM_AMD_NODE_POSE) || !is(e.pose_j, GLIM_AMD_NODE_POSE) || !is(e.velocity_i, GLIM_AMD_NODE_VELOCITY) || !is(e.velocity_j, GLIM_AMD_NODE_VELOCITY) ||
+        !is(e.bias, GLIM_AMD_NODE_BIAS) || e.pose_i == e.pose_j || e.velocity_i == e.velocity_j)
+      return GLIM_AMD_ERR_INVALID;
+    if (!all_finite_host(&e.dt, nav::IMU_DATA) || !(e.dt > 0.0)) return GLIM_AMD_ERR_INVALID;
+  }
+  return GLIM_AMD_OK;
+}
+static_assert(offsetof(glim_amd_nav_imu_term, dt) == 24 && sizeof(glim_amd_nav_imu_term) == 24 + nav::IMU_DATA * sizeof(double), "a term's doubles are nav::IMU_DATA in a row");
+static_assert(GLIM_AMD_NODE_POSE == nav::NODE_POSE && GLIM_AMD_NODE_BIAS == nav::NODE_BIAS && GLIM_AMD_NODE_VELOCITY == nav::NODE_VELOCITY &&
+                  GLIM_AMD_IMU_TANGENT == nav::IMU_TANGENT && GLIM_AMD_IMU_MANIFOLD == nav::IMU_MANIFOLD,
+              "the kinds and the modes");
+
 // the refusals of glim_amd_bundle_align with a loop's caps: everything that is answered before a handle or the context is used, then the pairs.
 // GLIM_AMD_OK with N == 0 is the caller's to answer first
 int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
                      const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
                      int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, const double* X_out12, const glim_amd_bundle_result* result,
-                     const GraphCaps& caps, lm::Params* prm, int* rounds, const glim_amd_graph_terms* more) {
+                     const GraphCaps& caps, lm::Params* prm, int* rounds, const glim_amd_graph_terms* more, const glim_amd_nav_terms* nav = nullptr) {
   if (!ctx || !X_init12 || !X_out12 || !result) return GLIM_AMD_ERR_INVALID;
   if (F > 0 && (!targets || !sources || !target_pose || !source_pose)) return GLIM_AMD_ERR_INVALID;
   if ((P > 0 && !priors) || (Q > 0 && !betweens)) return GLIM_AMD_ERR_INVALID;
   const int D = more ? more->num_dampings : 0;
   if (D < 0 || (D > 0 && !more->dampings)) return GLIM_AMD_ERR_INVALID;
-  if (F + P + Q == 0) return GLIM_AMD_ERR_INVALID;  // (dampings alone too: there is nothing to optimise over)
+  const int VP = nav ? nav->num_vector_priors : 0, VB = nav ? nav->num_vector_betweens : 0, I = nav ? nav->num_imu_terms : 0;
+  if (VP < 0 || VB < 0 || I < 0 || (VP > 0 && !nav->vector_priors) || (VB > 0 && !nav->vector_betweens) || (I > 0 && !nav->imu_terms)) return GLIM_AMD_ERR_INVALID;
+  if (F + P + Q == 0 && VP == 0 && VB == 0 && I == 0) return GLIM_AMD_ERR_INVALID;  // (dampings alone too: there is nothing to optimise over)
   if (flags & ~(uint32_t)GLIM_AMD_FACTOR_SURFACE_VALIDATION) return GLIM_AMD_ERR_INVALID;  // GLIM_AMD_FACTOR_BINARY: every factor here is binary
   GA_TRY(resolve_params(params, bundle_default_params, prm, rounds));
   if (N > caps.poses || F > caps.factors || P > caps.terms || Q > caps.terms || D > caps.terms) return GLIM_AMD_ERR_UNSUPPORTED;
+  if (VP > caps.terms || VB > caps.terms || I > caps.terms) return GLIM_AMD_ERR_UNSUPPORTED;
   if (!one_context(targets, sources, F, ctx)) return GLIM_AMD_ERR_INVALID;
   for (int f = 0; f < F; f++)
     if (target_pose[f] < 0 || target_pose[f] >= N || source_pose[f] < 0 || source_pose[f] >= N || target_pose[f] == source_pose[f]) return GLIM_AMD_ERR_INVALID;
@@ -1262,6 +1317,7 @@ int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
     for (int q = 0; q < Q; q++)
       if (!(more->between_huber_width[q] >= 0.0) || !std::isfinite(more->between_huber_width[q])) return GLIM_AMD_ERR_INVALID;
   if (!all_finite_host(X_init12, 12 * N)) return GLIM_AMD_ERR_INVALID;
+  if (nav) GA_TRY(check_nav_args(*nav, target_pose, source_pose, F, priors, P, betweens, Q, X_init12, N));
   return vgicp_pairs_ok(targets, sources, F);
 }
 
@@ -1270,8 +1326,12 @@ int check_graph_args(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
 // scratch behind the problem's own (o_extra)
 struct GraphBlocks {
   size_t o_X, o_cand, o_delta, o_rec, o_S, o_pT, o_pL, o_bT, o_bL, o_dd, o_bw, o_wk, o_scal, upload_doubles, o_pc, o_bc, o_wt, o_lin, o_Tf0, o_extra, total_doubles;
+  size_t o_vpv, o_vpL, o_vbd, o_vbL, o_imd, o_vpc, o_vbc, o_ic;  // the node kinds' terms (glim_amd_graph_align_nav)
   size_t i_ft, i_fs, i_pk, i_bi, i_bj, i_dk, i_first, i_items, total_ints;
+  size_t i_kind, i_vpk, i_vbi, i_vbj, i_imn, i_imm;
   int N, F, P, Q, D;
+  int VP, VB, I;
+  bool kinds;   // the nodes carry kinds
   bool widths;  // the betweens carry Huber widths
   std::vector<double> hd;
   std::vector<int> hi;
@@ -1281,6 +1341,15 @@ struct GraphBlocks {
     Problem pr{};
     pr.g = Graph{N, F, P, Q, i + i_ft, i + i_fs, i + i_pk, d + o_pT, d + o_pL, i + i_bi, i + i_bj, d + o_bT, d + o_bL, i + i_first, i + i_items,
                  D, i + i_dk, d + o_dd, widths ? d + o_bw : nullptr};
+    if (kinds) {
+      nav::Terms& t = pr.g.nav;
+      t.kind = i + i_kind;
+      t.VP = VP, t.VB = VB, t.I = I;
+      t.vpk = i + i_vpk, t.vpv = d + o_vpv, t.vpL = d + o_vpL;
+      t.vbi = i + i_vbi, t.vbj = i + i_vbj, t.vbd = d + o_vbd, t.vbL = d + o_vbL;
+      t.imn = i + i_imn, t.imm = i + i_imm, t.imd = d + o_imd;
+      t.vpc = d + o_vpc, t.vbc = d + o_vbc, t.ic = d + o_ic;
+    }
     pr.X = d + o_X;
     pr.cand = d + o_cand;
     pr.delta = d + o_delta;
@@ -1298,10 +1367,12 @@ struct GraphBlocks {
   }
 
   GraphBlocks(int N_, int F_, int P_, int Q_, const int32_t* target_pose, const int32_t* source_pose, const glim_amd_bundle_prior* priors,
-              const glim_amd_bundle_between* betweens, const glim_amd_graph_terms* more, const double* X_init12, const lm::Params& prm, size_t extra)
-      : N(N_), F(F_), P(P_), Q(Q_), D(more ? more->num_dampings : 0), widths(more && more->between_huber_width && Q_ > 0) {
+              const glim_amd_bundle_between* betweens, const glim_amd_graph_terms* more, const double* X_init12, const lm::Params& prm, size_t extra,
+              const glim_amd_nav_terms* nav = nullptr)
+      : N(N_), F(F_), P(P_), Q(Q_), D(more ? more->num_dampings : 0), VP(nav ? nav->num_vector_priors : 0), VB(nav ? nav->num_vector_betweens : 0),
+        I(nav ? nav->num_imu_terms : 0), kinds(nav && nav->kinds), widths(more && more->between_huber_width && Q_ > 0) {
     using namespace bundle_lm;
-    const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q, D);
+    const int n = 6 * N, nsys = system_doubles(n), nlist = list_items(F, P, Q, D) + VP + 3 * VB + 15 * I;
     size_t at = 0;
     auto take = [&](size_t count) {
       const size_t o = at;
@@ -1312,12 +1383,15 @@ struct GraphBlocks {
     o_pT = take(12 * (size_t)P), o_pL = take(36 * (size_t)P), o_bT = take(12 * (size_t)Q), o_bL = take(36 * (size_t)Q);
     o_dd = take(6 * (size_t)D), o_bw = take(widths ? (size_t)Q : 0), o_wk = take(Q);
     o_scal = take(sizeof(Scalars) / sizeof(double));
+    o_vpv = take(6 * (size_t)VP), o_vpL = take(36 * (size_t)VP), o_vbd = take(6 * (size_t)VB), o_vbL = take(36 * (size_t)VB), o_imd = take((size_t)nav::IMU_DATA * I);
     upload_doubles = at;  // what the host fills; the scratch below is written before it is read
     o_pc = take((size_t)PRIOR_STRIDE * P), o_bc = take((size_t)BETWEEN_STRIDE * Q), o_wt = take(Q), o_lin = take(122 * (size_t)F), o_Tf0 = take(12 * (size_t)F);
+    o_vpc = take((size_t)nav::VPRIOR_STRIDE * VP), o_vbc = take((size_t)nav::VBETWEEN_STRIDE * VB), o_ic = take((size_t)nav::IMU_STRIDE * I);
     o_extra = take(extra);
     total_doubles = at;
     at = 0;
     i_ft = take(F), i_fs = take(F), i_pk = take(P), i_bi = take(Q), i_bj = take(Q), i_dk = take(D), i_first = take(tri(N) + 1), i_items = take(nlist);
+    i_kind = take(kinds ? N : 0), i_vpk = take(VP), i_vbi = take(VB), i_vbj = take(VB), i_imn = take(nav::IMU_SLOTS * (size_t)I), i_imm = take(I);
     total_ints = at;
     hd.assign(upload_doubles + (size_t)PRIOR_STRIDE * P + (size_t)BETWEEN_STRIDE * Q + (size_t)Q, 0.0);
     hi.assign(total_ints + (size_t)tri(N), 0);  // (the tail: build_lists' cursors)
@@ -1340,6 +1414,25 @@ struct GraphBlocks {
     for (int d = 0; d < D; d++) {
       hi[i_dk + d] = more->dampings[d].pose;
       memcpy(&hd[o_dd + 6 * (size_t)d], more->dampings[d].diagonal, 6 * sizeof(double));
+    }
+    for (int k = 0; kinds && k < N; k++) hi[i_kind + k] = nav->kinds[k];
+    for (int p = 0; p < VP; p++) {
+      hi[i_vpk + p] = nav->vector_priors[p].node;
+      memcpy(&hd[o_vpv + 6 * (size_t)p], nav->vector_priors[p].value, 6 * sizeof(double));
+      memcpy(&hd[o_vpL + 36 * (size_t)p], nav->vector_priors[p].information, 36 * sizeof(double));
+    }
+    for (int q = 0; q < VB; q++) {
+      hi[i_vbi + q] = nav->vector_betweens[q].node_i;
+      hi[i_vbj + q] = nav->vector_betweens[q].node_j;
+      memcpy(&hd[o_vbd + 6 * (size_t)q], nav->vector_betweens[q].measurement, 6 * sizeof(double));
+      memcpy(&hd[o_vbL + 36 * (size_t)q], nav->vector_betweens[q].information, 36 * sizeof(double));
+    }
+    for (int q = 0; q < I; q++) {
+      const glim_amd_nav_imu_term& e = nav->imu_terms[q];
+      const int nodes[nav::IMU_SLOTS] = {e.pose_i, e.velocity_i, e.pose_j, e.velocity_j, e.bias};
+      for (int u = 0; u < nav::IMU_SLOTS; u++) hi[i_imn + nav::IMU_SLOTS * (size_t)q + u] = nodes[u];
+      hi[i_imm + q] = e.mode;
+      memcpy(&hd[o_imd + (size_t)nav::IMU_DATA * q], &e.dt, nav::IMU_DATA * sizeof(double));
     }
     Problem host = problem_at(hd.data(), hi.data(), nullptr);
     build_lists(host.g, hi.data() + i_first, hi.data() + i_items, hi.data() + total_ints);
@@ -1369,7 +1462,8 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
                      const int32_t* source_pose, int32_t F, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t P, const glim_amd_bundle_between* betweens,
                      int32_t Q, const double* X_init12, int32_t N, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
                      glim_amd_bundle_result* result, int one_thread, const BundleTrace& trace_host, bool graph = false, int chunk = 0,
-                     const glim_amd_graph_terms* more = nullptr, double* between_weight_out = nullptr) {
+                     const glim_amd_graph_terms* more = nullptr, double* between_weight_out = nullptr, const glim_amd_nav_terms* nav = nullptr,
+                     glim_amd_nav_result* nav_result = nullptr) {
   using namespace bundle_lm;
   if (N < 0 || F < 0 || P < 0 || Q < 0) return GLIM_AMD_ERR_INVALID;
   if (N == 0) return GLIM_AMD_OK;
@@ -1377,8 +1471,8 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   int rounds;
   const GraphCaps caps = graph ? GraphCaps{GLIM_AMD_GRAPH_MAX_POSES, GLIM_AMD_GRAPH_MAX_FACTORS, GLIM_AMD_GRAPH_MAX_TERMS} : GraphCaps{MAX_POSES, MAX_FACTORS, MAX_TERMS};
   GA_TRY(check_graph_args(ctx, targets, sources, target_pose, source_pose, F, flags, priors, P, betweens, Q, X_init12, N, params, X_out12, result, caps, &prm,
-                          &rounds, more));
-  const GraphBlocks blk(N, F, P, Q, target_pose, source_pose, priors, betweens, more, X_init12, prm, graph ? graph_scratch_doubles(6 * N) : 0);
+                          &rounds, more, nav));
+  const GraphBlocks blk(N, F, P, Q, target_pose, source_pose, priors, betweens, more, X_init12, prm, graph ? graph_scratch_doubles(6 * N) : 0, nav);
 
   std::unique_lock<std::mutex> held(ctx->mu);  // once for the call
   GA_HIP(hipSetDevice(ctx->device));
@@ -1437,6 +1531,14 @@ int run_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets,
   if (F > 0) batch.seen_complete();
   if (compact_out && F > 0) memcpy(compact_out, rec_host.data(), rec_host.size() * sizeof(double));
   graph_result(sc, result);
+  if (nav_result) {
+    memset(nav_result, 0, sizeof(*nav_result));
+    nav_result->cost = sc.cost, nav_result->factor_cost = sc.fcost, nav_result->prior_cost = sc.pcost, nav_result->between_cost = sc.bcost;
+    nav_result->vector_prior_cost = sc.vpcost, nav_result->vector_between_cost = sc.vbcost, nav_result->imu_cost = sc.icost;
+    nav_result->num_inliers = result->num_inliers;
+    nav_result->iterations = sc.iterations, nav_result->trials = sc.trials, nav_result->status = sc.status;
+    nav_result->lambda = sc.lambda;
+  }
   return GLIM_AMD_OK;
 }
 
@@ -1541,6 +1643,36 @@ int glim_amd_debug_graph_align_terms_trace(glim_amd_ctx* ctx, const glim_amd_vox
   return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
                           params, X_out12, compact_out, result, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, true,
                           rounds_per_chunk > 0 ? rounds_per_chunk : GRAPH_ROUNDS_PER_CHUNK, more, between_weight_out);
+}
+
+// the global graph with node kinds, vector priors, vector betweens and IMU terms (sub_mapping.cpp:218-243, global_mapping.cpp:168-216, 976-1042,
+// odometry_estimation_imu.cpp:218-220, 268-283, loose_initial_state_estimation.cpp:105-124, 174): the same scaffold, the terms behind the graph
+int glim_amd_graph_align_nav(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources, const int32_t* target_pose,
+                             const int32_t* source_pose, int32_t num_factors, uint32_t flags, const glim_amd_bundle_prior* priors, int32_t num_priors,
+                             const glim_amd_bundle_between* betweens, int32_t num_betweens, const double* X_init12, int32_t num_poses,
+                             const glim_amd_lm_params* params, double* X_out12, double* compact_out, glim_amd_nav_result* result,
+                             const glim_amd_graph_terms* more, double* between_weight_out, const glim_amd_nav_terms* nav) {
+  if (!result) return GLIM_AMD_ERR_INVALID;
+  glim_amd_bundle_result base;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, &base, 0, BundleTrace{nullptr, nullptr, nullptr, nullptr}, true, GRAPH_ROUNDS_PER_CHUNK, more,
+                          between_weight_out, nav, result);
+}
+
+int glim_amd_debug_graph_align_nav_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                         const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                         const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                         int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                         double* X_out12, double* compact_out, glim_amd_nav_result* result, const glim_amd_graph_terms* more,
+                                         double* between_weight_out, const glim_amd_nav_terms* nav, int32_t one_thread, double* X_trace,
+                                         double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk) {
+  const bool any = X_trace || Tf_trace || compact_trace || rounds;
+  if (any && num_poses > 0 && (!X_trace || !rounds || (num_factors > 0 && (!Tf_trace || !compact_trace)))) return GLIM_AMD_ERR_INVALID;
+  if (rounds_per_chunk < 0 || !result) return GLIM_AMD_ERR_INVALID;
+  glim_amd_bundle_result base;
+  return run_bundle_align(ctx, targets, sources, target_pose, source_pose, num_factors, flags, priors, num_priors, betweens, num_betweens, X_init12, num_poses,
+                          params, X_out12, compact_out, &base, one_thread ? 1 : 0, BundleTrace{X_trace, Tf_trace, compact_trace, rounds}, true,
+                          rounds_per_chunk > 0 ? rounds_per_chunk : GRAPH_ROUNDS_PER_CHUNK, more, between_weight_out, nav, result);
 }
 
 int glim_amd_debug_graph_solve(glim_amd_ctx* ctx, const double* S, int32_t n, double lambda, double* delta_out, int32_t* ok_out) {

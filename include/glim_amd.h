@@ -840,7 +840,8 @@ int glim_amd_ct_align(glim_amd_ct_gicp_factor* factor, const double* X_init12, c
  *              there are none to ask for).  glim_amd_lm_params is reused unchanged.
  * The system lives in one workgroup's LDS (160 KiB on gfx950), which sets GLIM_AMD_BUNDLE_MAX_POSES; the factors' blocks live in device memory.
  * Damping terms and Huber between terms: glim_amd_bundle_align_terms below ("Damping terms and Huber between terms").
- * Out of scope: IMU graphs (V, B variables, ImuFactor), ISAM2, pose marginals, robust priors, M-estimators other than Huber, translating a
+ * Out of scope: IMU terms in this LDS bundle (V, B variables and ImuFactor are glim_amd_graph_align_nav's: 32 blocks hold only ten frames once a
+ * frame needs X, V and B), ISAM2, pose marginals, CombinedImuFactor, robust priors, M-estimators other than Huber, translating a
  * gtsam::NonlinearFactorGraph, several devices.
  * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
  * resident session of the context are not touched. */
@@ -905,13 +906,14 @@ int glim_amd_bundle_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* tar
  *              state lives on the device: the chunk length moves no bit of a result.
  * With the same arguments within the bundle's caps, glim_amd_graph_align returns what glim_amd_bundle_align returns, bit for bit.
  * Damping terms (LinearDampingFactor) and Huber between terms: glim_amd_graph_align_terms below.
- * Out of scope: ISAM2 (GLIM's global mapping is incremental; this is one batch optimisation over the poses), IMU variables, pose marginals,
+ * Velocity and bias variables, vector priors and betweens and IMU terms: glim_amd_graph_align_nav below.
+ * Out of scope: ISAM2 (GLIM's global mapping is incremental; this is one batch optimisation over the poses), pose marginals, CombinedImuFactor,
  * robust priors, M-estimators other than Huber, several devices, translating a gtsam::NonlinearFactorGraph.
  * Deterministic: the same inputs return the same bits, in any context of the same device model.  The caller's factor sets, their plans and a
  * resident session of the context are not touched. */
 #define GLIM_AMD_GRAPH_MAX_POSES 256     /* 1536 x 1536 */
 #define GLIM_AMD_GRAPH_MAX_FACTORS 32768 /* every pair i < j of 256 poses is 32 640 */
-#define GLIM_AMD_GRAPH_MAX_TERMS 1024    /* priors; and betweens; and dampings */
+#define GLIM_AMD_GRAPH_MAX_TERMS 1024    /* priors; and betweens; and dampings; and vector priors; and vector betweens; and IMU terms */
 /* the defaults of glim_amd_bundle_align_default_params */
 int glim_amd_graph_align_default_params(glim_amd_lm_params* params);
 /* The arguments, the results and the refusals of glim_amd_bundle_align, with the caps above.  Nothing is launched when an argument is refused. */
@@ -940,7 +942,7 @@ int glim_amd_graph_align(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targ
  * those of that entry point, and, also before anything is launched: GLIM_AMD_ERR_INVALID: a negative num_dampings, NULL dampings with a
  * positive count, a damping's pose out of range, a diagonal entry or a width that is negative or not finite, a graph with dampings but no
  * factor, prior or between (there is nothing to optimise over); GLIM_AMD_ERR_UNSUPPORTED: more dampings than *_MAX_TERMS.
- * Out of scope: ISAM2, IMU variables, pose marginals, robust priors, other M-estimators, several devices. */
+ * Out of scope: ISAM2, pose marginals, CombinedImuFactor, IMU terms in the LDS bundle, robust priors, other M-estimators, several devices. */
 typedef struct {
   int32_t pose;
   int32_t reserved;
@@ -962,6 +964,102 @@ int glim_amd_graph_align_terms(glim_amd_ctx* ctx, const glim_amd_voxelmap* const
                                const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens, int32_t num_betweens,
                                const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
                                glim_amd_bundle_result* result, const glim_amd_graph_terms* more, double* between_weight_out);
+
+/* ---- Graph optimisation with velocity and bias variables: the global-graph optimisation above over the graphs GLIM builds with enable_imu =
+ *      true (its default).  Sub-mapping (src/glim/mapping/sub_mapping.cpp:218-243): per odometry frame a PriorFactor<Vector3> on V and a
+ *      PriorFactor<ConstantBias> on B (:226-227), per consecutive pair a BetweenFactor<ConstantBias> (:235) and an ImuFactor(X_last, V_last,
+ *      X_cur, V_cur, B_last) (:237) or, with too few IMU samples, a BetweenFactor<Vector3> on the velocities (:240).  Global mapping
+ *      (global_mapping.cpp:168-216, 976-1042): endpoint poses E(2i), E(2i+1) tied to X(i) by pose betweens, bias priors and betweens (:191-192,
+ *      :201), an ImuFactor (:216) or a velocity between (:213) from one sub-map's right endpoint to the next one's left.  The same terms:
+ *      odometry_estimation_imu.cpp:218-220, 268-283, loose_initial_state_estimation.cpp:105-124, 174.  One definition for host and device:
+ *      glim_amd/csrc/nav_terms.hpp, called by glim_amd/csrc/bundle_lm_step.hpp.
+ *   nodes      the N <= GLIM_AMD_GRAPH_MAX_POSES six-wide blocks of the system are nodes with a kind.  GLIM_AMD_NODE_POSE: as above, 12 doubles,
+ *              retraction X Exp(delta).  GLIM_AMD_NODE_BIAS: 6 doubles in gtsam's ConstantBias::vector() order (acc, gyro), retraction
+ *              b + delta.  GLIM_AMD_NODE_VELOCITY: 3 doubles (world frame), retraction v + delta[0..3); its rows 3..5 are touched by nothing and
+ *              carry lambda on the diagonal, +0.0 on the right-hand side and a zero step.  Node values travel as rows of 12 doubles: a vector
+ *              kind uses the leading 6 / 3 entries, the rest is +0.0 going in and coming out.  The tangent order, the packed system, the solve,
+ *              the decision rule, the statuses and the chunked enqueueing are the global-graph optimisation's, unchanged: 6N is the system size.
+ *              Factors, pose priors and pose betweens must name POSE nodes; a damping may name any node (LinearDampingFactor(B(0), 6, 1e6),
+ *              odometry_estimation_imu.cpp:220).
+ *   terms      each adds J^T L J, J^T L r and r^T L r (L r and L J first, sums ascending from +0.0, the upper triangle of L read).
+ *              vector prior (node k of kind BIAS or VELOCITY, value p[6], information 6 x 6): r = x_k - p, J = I; for a VELOCITY the leading
+ *              3 x 3 of the information and 3 of p are read.  vector between (nodes i != j of one vector kind, measurement d[6]):
+ *              r = (x_j - x_i) - d, J = [-I | I].  IMU term (POSE i, VELOCITY vi, POSE j, VELOCITY vj, BIAS b, all distinct): gtsam::ImuFactor.
+ *              gtsam's source is not in the reference tree, so the following is UPSTREAM RECALL (PreintegrationBase::computeError without
+ *              Coriolis term and body_P_sensor).  With db = b - bias_hat: (., dp_c, dv_c) = delta + H_bias db on the position and velocity
+ *              rows in both modes; GLIM_AMD_IMU_TANGENT (gtsam's TangentPreintegration, the build default): theta_c = theta + H_bias[0..3, :]
+ *              db; GLIM_AMD_IMU_MANIFOLD (Forster et al.): theta_c = Log(Exp(theta) Exp(H_bias[0..3, 3..6] db_gyro)).  Prediction:
+ *              R^ = R_i Exp(theta_c), p^ = p_i + v_i dt + g dt^2 / 2 + R_i dp_c, v^ = v_i + g dt + R_i dv_c.  Residual: r = [Log(R_j^T R^);
+ *              R_j^T (p^ - p_j); R_j^T (v^ - v_j)].  J (9 x 24 over the five nodes' used columns) is the exact derivative of r under the
+ *              retractions above; its blocks are written out in glim_amd/csrc/nav_terms.hpp.
+ *   sums       within a block's list: factors, pose priors, pose betweens, vector priors, vector betweens, IMU terms, dampings, each by
+ *              ascending index.  cost = ((((factors + priors) + betweens) + vector priors) + vector betweens) + IMU.
+ * With every node a POSE (or nav == NULL) and no new term, glim_amd_graph_align_nav returns the bits of glim_amd_graph_align_terms.
+ * The sub-map bundle (glim_amd_bundle_align*) is NOT extended: it keeps its system in LDS, and 32 blocks hold only ten frames once a frame needs
+ * X, V and B.
+ * Refusals, all before anything is launched: those of glim_amd_graph_align_terms, and GLIM_AMD_ERR_INVALID: an unknown kind or mode; a term
+ * naming a node of the wrong kind or out of range; repeated nodes in one term; dt <= 0 or not finite; any input that is not finite; a VELOCITY
+ * row whose entries 3..11, or a BIAS row whose entries 6..11, are not +0.0; a negative count or a NULL array with a positive count; a graph with
+ * nothing but dampings.  GLIM_AMD_ERR_UNSUPPORTED: more vector priors, vector betweens or IMU terms than GLIM_AMD_GRAPH_MAX_TERMS each.
+ * Out of scope: ISAM2 and the fixed-lag smoother, marginals, CombinedImuFactor, the Coriolis term, body_P_sensor, IMU terms in the LDS bundle, a
+ * preintegrator for raw IMU samples (the caller's gtsam has one), robust priors, other M-estimators, several devices. */
+#define GLIM_AMD_NODE_POSE 0
+#define GLIM_AMD_NODE_BIAS 1
+#define GLIM_AMD_NODE_VELOCITY 2
+#define GLIM_AMD_IMU_TANGENT 0
+#define GLIM_AMD_IMU_MANIFOLD 1
+typedef struct {
+  int32_t node;            /* of kind BIAS or VELOCITY */
+  int32_t reserved;
+  double value[6];         /* p; a VELOCITY reads 3 */
+  double information[36];  /* row-major 6 x 6; the upper triangle (a VELOCITY: of the leading 3 x 3) is read */
+} glim_amd_nav_vector_prior;
+typedef struct {
+  int32_t node_i, node_j;  /* different, of one vector kind */
+  double measurement[6];   /* d: the measurement of x_j - x_i */
+  double information[36];
+} glim_amd_nav_vector_between;
+typedef struct {
+  int32_t pose_i, velocity_i, pose_j, velocity_j, bias; /* all distinct */
+  int32_t mode;            /* GLIM_AMD_IMU_TANGENT or GLIM_AMD_IMU_MANIFOLD */
+  double dt;               /* > 0 */
+  double gravity[3];       /* gtsam's n_gravity */
+  double bias_hat[6];      /* (acc, gyro) */
+  double delta[9];         /* (theta, dp, dv): the preintegrated measurement at bias_hat */
+  double H_bias[54];       /* row-major 9 x 6: its derivative by (acc, gyro) */
+  double information[81];  /* row-major 9 x 9 in (rot, pos, vel) order: the inverse of preintMeasCov; the upper triangle is read */
+} glim_amd_nav_imu_term;
+typedef struct {
+  const int32_t* kinds;    /* num_poses kinds (GLIM_AMD_NODE_*), or NULL: every node is a POSE */
+  const glim_amd_nav_vector_prior* vector_priors;
+  const glim_amd_nav_vector_between* vector_betweens;
+  const glim_amd_nav_imu_term* imu_terms;
+  int32_t num_vector_priors, num_vector_betweens, num_imu_terms;
+  int32_t reserved;
+} glim_amd_nav_terms;
+typedef struct {
+  double cost;             /* ((((factor + prior) + between) + vector_prior) + vector_between) + imu at the returned nodes */
+  double factor_cost;
+  double prior_cost;
+  double between_cost;
+  double vector_prior_cost;
+  double vector_between_cost;
+  double imu_cost;
+  int64_t num_inliers;
+  int32_t iterations;
+  int32_t trials;
+  int32_t status;          /* GLIM_AMD_ALIGN_* */
+  int32_t reserved;
+  double lambda;
+} glim_amd_nav_result;
+/* The arguments of glim_amd_graph_align_terms with `X` read as node values (num_poses x 12), a result of its own and the node kinds and new
+ * terms in `nav` (NULL: none).  more and between_weight_out may be NULL. */
+int glim_amd_graph_align_nav(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                             const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                             const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens, int32_t num_betweens,
+                             const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params, double* X_out12, double* compact_out,
+                             glim_amd_nav_result* result, const glim_amd_graph_terms* more, double* between_weight_out,
+                             const glim_amd_nav_terms* nav);
 
 /* ---- Scan-to-keyframes VGICP registration: the LiDAR part of GLIM's frame-to-keyframes matching cost
  *      (src/glim/odometry/odometry_estimation_gpu.cpp:150-165, 183-203): one unary IntegratedVGICPFactorGPU(fixed_target_pose, X(current),

@@ -2,8 +2,8 @@
 // sub-map is closed (sub_mapping.cpp:430-452): Levenberg-Marquardt over the keyframe poses on the all-pairs binary VGICP factors, the prior on
 // the first keyframe (:186) and the relative-pose factors (:210/:212) -- graph in, poses out, one call and one host synchronisation.  LMParams
 // is gicp_align.hpp's.  Damping terms (gtsam_points::LinearDampingFactor) and Huber widths on between terms (noiseModel::Robust(Huber)) are
-// add_damping and add_between's last argument; a graph that holds one goes through glim_amd_bundle_align_terms.  Out of scope: IMU graphs,
-// ISAM2, pose marginals, robust priors, other M-estimators, translating a gtsam::NonlinearFactorGraph.
+// add_damping and add_between's last argument; a graph that holds one goes through glim_amd_bundle_align_terms.  Out of scope: IMU terms in
+// this LDS bundle (velocity and bias nodes are graph_align.hpp's NavGraph), ISAM2, pose marginals, CombinedImuFactor, robust priors, other M-estimators, translating a gtsam::NonlinearFactorGraph.
 //
 //   glim_amd::BundleGraph g;
 //   g.add_factor(*voxels[i], *frames[j], i, j);                       // IntegratedVGICPFactorGPU(X(i), X(j), voxels[i], frames[j])

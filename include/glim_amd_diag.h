@@ -330,6 +330,15 @@ int glim_amd_debug_graph_align_terms_trace(glim_amd_ctx* ctx, const glim_amd_vox
                                            double* X_out12, double* compact_out, glim_amd_bundle_result* result, const glim_amd_graph_terms* more,
                                            double* between_weight_out, int32_t one_thread, double* X_trace, double* Tf_trace, double* compact_trace,
                                            glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk);
+/* the same for the entry point of include/glim_amd.h "Graph optimisation with velocity and bias variables": the trace's X rows are node
+ * values.  one_thread: every round is bundle_lm_step.hpp's step() in one device thread, the new terms included */
+int glim_amd_debug_graph_align_nav_trace(glim_amd_ctx* ctx, const glim_amd_voxelmap* const* targets, const glim_amd_cloud* const* sources,
+                                         const int32_t* target_pose, const int32_t* source_pose, int32_t num_factors, uint32_t flags,
+                                         const glim_amd_bundle_prior* priors, int32_t num_priors, const glim_amd_bundle_between* betweens,
+                                         int32_t num_betweens, const double* X_init12, int32_t num_poses, const glim_amd_lm_params* params,
+                                         double* X_out12, double* compact_out, glim_amd_nav_result* result, const glim_amd_graph_terms* more,
+                                         double* between_weight_out, const glim_amd_nav_terms* nav, int32_t one_thread, double* X_trace,
+                                         double* Tf_trace, double* compact_trace, glim_amd_bundle_trace_round* rounds, int32_t rounds_per_chunk);
 /* the device's blocked solve alone (glim_amd/csrc/graph_solve.hpp) on a caller's system: S is the packed lower triangle of H by rows (row i at
  * i (i + 1) / 2), then b; 1 <= n <= 6 GLIM_AMD_GRAPH_MAX_POSES.  Solves (H + lambda I) delta = -b.  delta_out: n doubles, +0.0 after a failed
  * pivot; *ok_out: 1, or 0 after a failed pivot. */

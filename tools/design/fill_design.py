@@ -198,6 +198,21 @@ if os.path.exists(me_path):
             f"the two results are {'equal' if mc['equal'] else 'NOT equal'} (flow and set).  A description of two programs: the issue set no time target, and no round of this solver has been profiled.")
 else:
     vals['MAP_EDIT_MEASURED']="nothing yet.  `tools/map_edit_time.py` writes `profiles/map_edit/map_edit_time.json` (24 sub-maps of 65 536 points: the four selections, the outliers, region growing and the removal beside the NumPy restatement of the same steps, alternating in one process); until that file exists every statement about the speed of this path is UNMEASURED."
+# ---- the graph optimiser over pose, velocity and bias nodes (tools/nav_graph_time.py) ----
+nav_path='profiles/nav_graph/nav_graph_time.json'
+if os.path.exists(nav_path):
+    nav=json.load(open(nav_path))
+    cell=lambda r: f"{r['wall_ms_p50']:.2f} ms for the call, {r['rounds_that_ran']} rounds ran ({r['status']}, {r['iterations']} iterations), {r['round_ms']:.2f} ms a round"
+    s20,g36=nav['submap20'],nav['global36']['terms_only']
+    vals['NAV_MEASURED']=(f"one box, one run (`{nav_path}`, the default parameters).  The sub-mapping-shaped graph over 20 frames ({s20['terms_only']['nodes']} nodes, {s20['terms_only']['rows']} rows, "
+        f"{s20['terms_only']['imu_terms']} IMU terms): terms only {cell(s20['terms_only'])}; with the {s20['with_two_hop_factors']['factors']} two-hop VGICP factors {cell(s20['with_two_hop_factors'])}.  "
+        f"The global-mapping-shaped graph over 36 sub-maps ({g36['nodes']} nodes, {g36['rows']} rows, {g36['imu_terms']} IMU terms), terms only: {cell(g36)}.  "
+        +(f"The trial round of `graph_align` without new terms at N = 64 (`tools/graph_align_time.py`), two processes each, alternating with the parent commit: "
+          f"{nav['graph_align_round_time_n64']['this'][0]:.3f} and {nav['graph_align_round_time_n64']['this'][1]:.3f} ms against the parent's {nav['graph_align_round_time_n64']['parent'][0]:.3f} and {nav['graph_align_round_time_n64']['parent'][1]:.3f} ms, "
+          f"whose own spread is {100*nav['graph_align_round_time_n64']['margin_the_parents_own_spread']:.1f} %.  " if 'graph_align_round_time_n64' in nav else "")
+        +"Nothing was profiled and no speed-up is claimed.")
+else:
+    vals['NAV_MEASURED']="nothing yet.  `tools/nav_graph_time.py` writes `profiles/nav_graph/nav_graph_time.json` (a 20-frame sub-mapping-shaped graph with and without the two-hop VGICP factors, a 36-sub-map global-mapping-shaped graph); until that file exists every statement about the speed of this path is UNMEASURED."
 s=open('tools/design/DESIGN.tpl.md').read()
 missing=set(re.findall(r'@([A-Z0-9_]+)@',s))-set(vals)
 assert not missing, missing
