@@ -1,6 +1,6 @@
 // bundle_lm_step.hpp -- the rule of the on-device sub-map bundle optimisation (include/glim_amd.h "Sub-map bundle optimisation"), ONCE, for host
 // and device: the expansion of a binary factor, the prior and between terms, the assembly of the dense system, the serial Cholesky and the
-// step.  gicp_align.hip's bundle decide kernel runs the ITEM functions below across a workgroup, one owner per item, and runs step() in one
+// step.  bundle_align.hip's bundle decide kernel runs the ITEM functions below across a workgroup, one owner per item, and runs step() in one
 // thread as its cross-check variant; tests/cpp/test_bundle_lm_step.cpp compiles the header with a plain C++ compiler;
 // tests/bundle_lm_restatement.py restates it in NumPy.  Plain C++ apart from the host/device macro.
 //

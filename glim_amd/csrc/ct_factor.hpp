@@ -1,4 +1,4 @@
-// ct_factor.hpp -- the continuous-time GICP factor as the two units that run it see it (gicp.hip: the factor's own entry points; gicp_align.hip:
+// ct_factor.hpp -- the continuous-time GICP factor as the two units that run it see it (gicp.hip: the factor's own entry points; ct_align.hip:
 // the CT frame alignment, which runs the factor's linearising pass inside its rounds): the factor object, the arguments and the bodies of its
 // search pass, bucket pass and ordered sum, the record's layout and its expansion.  Each of them is defined here, once; like gicp_factor.hpp the
 // shared part is in an unnamed namespace and nothing of it is called across units.

@@ -1,5 +1,5 @@
 // ct_lm_step.hpp -- the step rule of the on-device CT frame alignment (include/glim_amd.h "CT-GICP frame alignment"): ONE function, host and
-// device.  gicp_align.hip's CT decide kernel calls it once per round; tests/cpp/test_ct_lm_step.cpp compiles it with a plain C++ compiler and
+// device.  ct_align.hip's decide kernel calls it once per round; tests/cpp/test_ct_lm_step.cpp compiles it with a plain C++ compiler and
 // runs the same statements on the CPU; tests/ct_lm_restatement.py restates it in NumPy.  Plain C++ apart from the host/device macro.
 //
 // The problem is GLIM's continuous-time odometry frame (odometry_estimation_ct.cpp:158-195): 12 DoF, tangent order [X: omega v | Y: omega v],

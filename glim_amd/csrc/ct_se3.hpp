@@ -1,5 +1,5 @@
 // ct_se3.hpp -- SE(3) in FP64 with gtsam::Pose3's conventions, host and device: what the continuous-time GICP factor's bucket pose table
-// (gicp.hip's host table, gicp_align.hip's pose table kernel) and the terms of the CT frame alignment (ct_lm_step.hpp) are made of.  Each routine
+// (gicp.hip's host table, ct_align.hip's pose table kernel) and the terms of the CT frame alignment (ct_lm_step.hpp) are made of.  Each routine
 // is defined here, once.  The header includes nothing of the project, so a plain C++ compiler takes it (tests/cpp/test_ct_lm_step.cpp).
 //
 // gtsam's right-perturbation Jacobians: between(X, Y) = X^-1 Y, H_X = -Ad((X^-1 Y)^-1), H_Y = I; compose(A, B): H_A = Ad(B^-1), H_B = I;

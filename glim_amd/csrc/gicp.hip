@@ -24,7 +24,7 @@
 //
 // Both factors also run over a device iVox (gtsam_points::IncrementalVoxelMap<FlatContainer>, ivox.hip: the container and its insert): the
 // factor kernels take the target kind as a template parameter -- IndexSearch = the exact search above, IvoxSearch = the map's bounded search of
-// the voxels of its neighbour mode -- and share everything behind the correspondence.  What ivox.hip and gicp_align.hip use as well -- the
+// the voxels of its neighbour mode -- and share everything behind the correspondence.  What ivox.hip, gicp_align.hip and ct_align.hip use as well -- the
 // searches, the per-point algebra, the block epilogue, the target description -- is gicp_factor.hpp's; the map object is ivox_map.hpp's.
 //
 // The ICP factors (gtsam_points::IntegratedICPFactor, IntegratedPointToPlaneICPFactor; manual_loop_close_modal.cpp:485-490) are the rigid factor
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void gicp_finalize_kernel(const float* __restr
 }
 
 // ---- the continuous-time factor (IntegratedCT_GICPFactor): the same per-point algebra, one pose per time bucket ----
-// The layout, the arguments and the bodies of the three passes are ct_factor.hpp's (gicp_align.hip runs them inside its rounds as well).
+// The layout, the arguments and the bodies of the three passes are ct_factor.hpp's (ct_align.hip runs them inside its rounds as well).
 template <bool LINEARIZE, class NN>
 __global__ __launch_bounds__(BLOCK) void ct_gicp_kernel(const GicpArgs a, const CtArgs c, float* __restrict__ partials, const NN nn) {
   __shared__ float s_red[4][PARTIAL_STRIDE];

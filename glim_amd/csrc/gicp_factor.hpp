@@ -1,5 +1,5 @@
 // gicp_factor.hpp -- what the translation units of the GICP family share (gicp.hip: the search index, the rigid and the continuous-time factor;
-// ivox.hip: the device iVox; gicp_align.hip: fine registration): the search index object and the factor kernels' arguments, the two searches
+// ivox.hip: the device iVox; gicp_align.hip, ct_align.hip: the loops): the search index object and the factor kernels' arguments, the two searches
 // (IndexSearch, IvoxSearch), the per-point algebra, the block epilogue and the ordered sum that make a record bit-reproducible, and the host's
 // description of a target (GicpTarget).  Each of them is defined here, once.  Like knn_common.hpp the shared part is in an unnamed namespace:
 // device functions are forced inline, the __constant__ tables are static (one copy per unit), the host helpers are a few lines each, and

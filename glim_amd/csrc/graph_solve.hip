@@ -1,4 +1,4 @@
-// graph_align.hip -- the solve of the global-graph optimisation on gfx950 (include/glim_amd.h "Global-graph optimisation"): the blocked,
+// graph_solve.hip -- the solve of the global-graph optimisation on gfx950 (include/glim_amd.h "Global-graph optimisation"): the blocked,
 // left-looking Cholesky factorisation and the back substitution of graph_solve.hpp over a working matrix in device memory, as ordinary
 // launches on one stream.  Per block column, ascending: a panel update (a thread per entry of the panel, its subtractions k < j0), then a
 // panel factor (every workgroup finishes the block's diagonal tile in LDS, redundantly and identically, then its own rows below the tile;
@@ -6,8 +6,8 @@
 // that column's subtractions for its own rows above).  No kernel waits for another workgroup: a kernel boundary is the only ordering.  No
 // kernel declares more than 33 KiB of LDS.  Every value comes from an item function of graph_solve.hpp, one owner per entry.
 //
-// The rule the solve belongs to (records, terms, assembly, decision, retraction) is the bundle's and is run by gicp_align.hip, the one unit
-// that includes the step rules; this unit knows the matrix and nothing else.
+// The rule the solve belongs to (records, terms, assembly, decision, retraction) is the bundle's and is run by bundle_align.hip; this unit
+// knows the matrix and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -19,7 +19,7 @@
 // The working matrix is COLUMN-major with a padded leading dimension: entry (i, k) at W[k * ld + i], i = 0 .. n (row n carries -b and then y).
 // The rows of a column step are neighbours in memory and L[j][k] is one address for all of them.  The layout is not part of the rule.
 // factor_blocked() and back_blocked() below are the launch order on the host: tests/cpp/test_graph_solve.cpp compares them with bundle_lm::solve byte for byte, and
-// graph_align.hip runs the same item functions, one owner per entry.  Plain C++ apart from the host/device macro.
+// graph_solve.hip runs the same item functions, one owner per entry.  Plain C++ apart from the host/device macro.
 #pragma once
 #include <math.h>
 
@@ -181,7 +181,7 @@ inline bool solve_blocked(double* W, int n, int tile, double* delta) {
 }  // namespace graph_solve
 
 #if defined(__HIPCC__)
-// graph_align.hip: the launches of one solve on `st`.  W: matrix_doubles(n) doubles holding the loaded matrix; delta: n; fail: one word, set
+// graph_solve.hip: the launches of one solve on `st`.  W: matrix_doubles(n) doubles holding the loaded matrix; delta: n; fail: one word, set
 // to 1 by a failed pivot and to 0 otherwise.  Every kernel returns at once while *status is not 0 (device memory, lm::RUNNING is 0)
 hipError_t graph_solve_enqueue(hipStream_t st, double* W, int n, double* delta, int* fail, const int* status);
 #endif

@@ -1,5 +1,5 @@
 // ivox_map.hpp -- the device iVox as the other units of the GICP family see it: the map object (ivox.hip creates, fills and sweeps it) and its
-// description as a target of the factor kernels (gicp.hip's factors and gicp_align.hip's batches run over gicp_target(map)).
+// description as a target of the factor kernels (gicp.hip's factors, gicp_align.hip's batches and ct_align.hip's loop run over gicp_target(map)).
 #pragma once
 #include <atomic>
 #include <cstdint>

@@ -1,6 +1,6 @@
 // keyframe_lm_step.hpp -- what the scan-to-keyframes VGICP registration (include/glim_amd.h "Scan-to-keyframes VGICP registration") adds to the
 // step rule of lm_step.hpp, ONCE, for host and device: one pose X per problem, M unary VGICP factors with FIXED target poses P_f, an optional
-// prior on X.  gicp_align.hip's keyframe decide kernel runs the functions below across one wavefront, an owner per value;
+// prior on X.  vgicp_align.hip's keyframe decide kernel runs the functions below across one wavefront, an owner per value;
 // tests/cpp/test_keyframe_lm_step.cpp compiles the header alone with a plain C++ compiler and runs step() on the CPU;
 // tests/keyframe_restatement.py restates it in NumPy.  Plain C++ apart from the host/device macro.  Everything is FP64 with contraction off.
 //
@@ -51,7 +51,7 @@ GLIM_AMD_LM_HD inline double add_prior(double s, const double* c, int t) {
 // One round of one problem in one thread, what the wavefront of the decide kernel does: `recs` are the M records evaluated at `Tf` (= the
 // factor poses of s.cand).  term: the prior, or null.  sum: RECORD doubles, pc: PRIOR doubles (zero without a prior) -- the round's summed
 // record and the prior's contribution, for whoever traces them.  Updates the state and, while the problem runs, the T_f of the next round.
-// keyframe_decide_kernel (gicp_align.hip) spreads THIS sequence over its lanes -- contribution, sums, the non-finite T_f, lm::step, fan-out, in
+// keyframe_decide_kernel (vgicp_align.hip) spreads THIS sequence over its lanes -- contribution, sums, the non-finite T_f, lm::step, fan-out, in
 // this order: the two share the functions above, not the control flow, so a change to the sequence here is a change there.
 GLIM_AMD_LM_HD inline void step(const lm::Params& p, lm::State& s, int M, const double* Pinv, const double* term, const double* recs, double* Tf, double* sum,
                                 double* pc) {

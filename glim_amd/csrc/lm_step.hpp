@@ -1,5 +1,5 @@
 // lm_step.hpp -- the step rule of the on-device GICP fine registration (include/glim_amd.h "GICP fine registration"): ONE function, host and
-// device.  gicp_align.hip's decide kernel calls it once per round and problem; tests/cpp/test_lm_step.cpp compiles it with a plain C++ compiler
+// device.  The decide kernels of gicp_align.hip and vgicp_align.hip call it once per round and problem; tests/cpp/test_lm_step.cpp compiles it with a plain C++ compiler
 // and runs the same statements on the CPU.  The header includes nothing of the project.  The rule's scalar part (decide) and the dense solve
 // (solve_dense<N>) are also what the CT loop (ct_lm_step.hpp) and the sub-map bundle (bundle_lm_step.hpp) call: they exist here, once.
 //

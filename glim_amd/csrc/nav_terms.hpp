@@ -1,6 +1,6 @@
 // nav_terms.hpp -- the velocity and bias variables of the global-graph optimisation and the three terms GLIM's IMU graphs are made of beside
 // the pose terms (include/glim_amd.h "Graph optimisation with velocity and bias variables"), ONCE, for host and device.  bundle_lm_step.hpp's
-// item, assembly and step functions call what is here; gicp_align.hip runs the item functions a thread per term; tests/cpp/test_nav_graph_step.cpp
+// item, assembly and step functions call what is here; bundle_align.hip runs the item functions a thread per term; tests/cpp/test_nav_graph_step.cpp
 // compiles the header with a plain C++ compiler; tests/nav_graph_restatement.py restates it in NumPy.  Plain C++ apart from the host/device macro.
 //
 //   nodes      the N six-wide blocks of the system are nodes with a kind.  POSE: 12 doubles, retraction X Exp(delta) (lm::retract).  BIAS: 6

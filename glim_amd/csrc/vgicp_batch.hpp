@@ -1,4 +1,4 @@
-// vgicp_batch.hpp -- what the VGICP fine registration (gicp_align.hip, include/glim_amd.h "VGICP fine registration") asks of vgicp.hip: the
+// vgicp_batch.hpp -- what the VGICP fine registration (vgicp_align.hip, include/glim_amd.h "VGICP fine registration") asks of vgicp.hip: the
 // evaluation of B independent VGICP factors at poses that live on the device, gated by a status word per factor.
 //
 //   the plan    a TRANSIENT plan over the B (voxel map, cloud) pairs, built by plan_build -- the rule a caller's factor set of the same pairs in the

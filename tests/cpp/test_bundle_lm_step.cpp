@@ -1,4 +1,4 @@
-// glim_amd/csrc/bundle_lm_step.hpp under a plain C++ compiler: the statements gicp_align.hip's bundle decide kernel runs, fed from a file.
+// glim_amd/csrc/bundle_lm_step.hpp under a plain C++ compiler: the statements bundle_align.hip's bundle decide kernel runs, fed from a file.
 // A graph is, in doubles: N, F, P, Q, F x (t, s), P x (pose, 12 of P, 36 of the information), Q x (i, j, 12 of D, 36 of the information).
 //   expand    in : n, then n x (29 of a record, 12 of a pose)
 //             out: n x 122, the bytes of glim_amd_linearized6

@@ -1,4 +1,4 @@
-// glim_amd/csrc/ct_lm_step.hpp and ct_se3.hpp under a plain C++ compiler: the statements gicp_align.hip's CT kernels run, fed from a file.
+// glim_amd/csrc/ct_lm_step.hpp and ct_se3.hpp under a plain C++ compiler: the statements ct_align.hip's kernels run, fed from a file.
 //   step  in  (doubles): 9 parameters in glim_amd_lm_params order (max_trials resolved), 12 + 12 of the initial pair, 26 of the terms
 //                        (T_location, location_precision, T_between, between_precision), N, then N records of 92
 //         out (doubles): per record, the state after the round: kept X, Y (24), next candidate X, Y (24), delta (12), lambda, solve_ok,

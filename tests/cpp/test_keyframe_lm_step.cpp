@@ -1,4 +1,4 @@
-// glim_amd/csrc/keyframe_lm_step.hpp under a plain C++ compiler, as the only include: the statements gicp_align.hip's keyframe decide kernel
+// glim_amd/csrc/keyframe_lm_step.hpp under a plain C++ compiler, as the only include: the statements vgicp_align.hip's keyframe decide kernel
 // runs, fed from a file.
 //   step      in : 9 parameters in glim_amd_lm_params order (max_trials resolved), M, has_prior, M x 12 target poses P_f, [12 of the prior's
 //                  pose, 36 of its information], 12 of X_init, R, then R x M x 29 records (round r's: evaluated at the T_f round r reports)

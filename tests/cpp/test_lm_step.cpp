@@ -1,4 +1,4 @@
-// glim_amd/csrc/lm_step.hpp under a plain C++ compiler: the statements gicp_align.hip's decide kernel runs, fed the records of a file.
+// glim_amd/csrc/lm_step.hpp under a plain C++ compiler: the statements the decide kernels of gicp_align.hip and vgicp_align.hip run, fed the records of a file.
 //   in  (doubles): 9 parameters in glim_amd_lm_params order (max_trials resolved), 12 of the initial pose, N, then N records of 29
 //   out (doubles): per record, the state after the round: 12 kept pose, 12 next candidate, 6 delta, lambda, solve_ok, iterations, trials,
 //                  status, accepted (36 per round)

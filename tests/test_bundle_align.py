@@ -37,10 +37,10 @@ def test_new_symbols_are_declared_once_and_listed():
         assert callable(getattr(api, n))
     assert callable(api.NonlinearFactorSetGPU.optimize)
     assert C.sizeof(_lib.BundlePrior) == 8 + 48 * 8 and C.sizeof(_lib.BundleBetween) == 8 + 48 * 8 and C.sizeof(_lib.BundleResult) == 64
-    # the rule's header stands alone and is included by gicp_align.hip only (tests/test_build_layout.py: lm_step.hpp recompiles that unit alone)
+    # the rule's header stands alone and is included directly by bundle_align.hip only (tests/test_build_layout.py: what a touch of it recompiles)
     csrc = os.path.join(ROOT, "glim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "bundle_lm_step.hpp" in open(os.path.join(csrc, f)).read())
-    assert users == ["gicp_align.hip"]
+    assert users == ["bundle_align.hip"]
 
 
 def test_default_params_are_the_gicp_defaults_with_twenty_iterations():

@@ -1,4 +1,4 @@
-"""CT-GICP frame alignment on the device (include/glim_amd.h "CT-GICP frame alignment", glim_amd/csrc/gicp_align.hip): the device pose table is
+"""CT-GICP frame alignment on the device (include/glim_amd.h "CT-GICP frame alignment", glim_amd/csrc/ct_align.hip): the device pose table is
 the host's, every trial record is the factor's at the trial's pair, the decisions are those of tests/ct_lm_restatement.py, and the call leaves
 the factor's kept state alone.  Cases and scenes: tests/ct_align_cases.py."""
 import ctypes as C

@@ -39,9 +39,9 @@ def test_new_symbols_are_declared_once_and_listed():
     csrc = os.path.join(ROOT, "glim_amd", "csrc")
     solve = open(os.path.join(csrc, "graph_solve.hpp")).read()
     assert re.search(r"constexpr int MAX_DIM = 6 \* (\d+);", solve).group(1) == str(MAX_POSES)
-    assert "static_assert(GLIM_AMD_GRAPH_MAX_POSES * 6 == graph_solve::MAX_DIM" in open(os.path.join(csrc, "gicp_align.hip")).read()
+    assert "static_assert(GLIM_AMD_GRAPH_MAX_POSES * 6 == graph_solve::MAX_DIM" in open(os.path.join(csrc, "bundle_align.hip")).read()
     assert sorted(int(t) for t in re.search(r"TILE == (\d+) \|\| TILE == (\d+) \|\| TILE == (\d+)", solve).groups()) == list(TILES)
-    assert os.path.exists(os.path.join(csrc, "graph_align.hip"))
+    assert os.path.exists(os.path.join(csrc, "graph_solve.hip"))
     for n in ("graph_align", "graph_align_debug_trace", "graph_align_params", "graph_solve_debug"):
         assert callable(getattr(api, n))
     assert callable(api.NonlinearFactorSetGPU.optimize_graph)

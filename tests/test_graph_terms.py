@@ -53,10 +53,10 @@ def test_new_symbols_structs_and_mirrors(tmp_path):
         assert "LinearDampingFactor" in text, n
     for n in ("include/glim_amd.h", "include/glim_amd/graph_align.hpp", "include/glim_amd/bundle_align.hpp", "README.md"):
         assert "pose marginals" in texts[n] and "robust priors" in texts[n], n
-    # the rule's header is still included by gicp_align.hip alone
+    # the rule's header is still included directly by bundle_align.hip alone
     csrc = os.path.join(ROOT, "glim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "bundle_lm_step.hpp" in open(os.path.join(csrc, f)).read())
-    assert users == ["gicp_align.hip"]
+    assert users == ["bundle_align.hip"]
 
 
 # ---- the refusals --------------------------------------------------------------------------------------------------------------------------------

@@ -36,10 +36,10 @@ def test_new_symbols_are_declared_once_and_listed():
     assert "#define GLIM_AMD_KEYFRAME_ALIGN_MAX_TARGETS %d" % MAX_TARGETS in head and api.KEYFRAME_ALIGN_MAX_TARGETS == MAX_TARGETS
     for n in ("vgicp_align_keyframes", "vgicp_align_keyframes_debug_trace"):
         assert callable(getattr(api, n))
-    # the rule's header is included by gicp_align.hip only (tests/test_build_layout.py: lm_step.hpp recompiles that unit alone)
+    # the rule's header is included by vgicp_align.hip only (tests/test_build_layout.py: a touch of it recompiles that unit alone)
     csrc = os.path.join(ROOT, "glim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "keyframe_lm_step.hpp" in open(os.path.join(csrc, f)).read())
-    assert users == ["gicp_align.hip"]
+    assert users == ["vgicp_align.hip"]
 
 
 def test_default_params_are_the_gicp_defaults():

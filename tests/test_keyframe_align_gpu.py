@@ -1,4 +1,4 @@
-"""Scan-to-keyframes VGICP registration on the device (include/glim_amd.h "Scan-to-keyframes VGICP registration"; glim_amd/csrc/gicp_align.hip over
+"""Scan-to-keyframes VGICP registration on the device (include/glim_amd.h "Scan-to-keyframes VGICP registration"; glim_amd/csrc/vgicp_align.hip over
 vgicp_batch.hpp and keyframe_lm_step.hpp): one pose per problem over M factors with fixed target poses.  Every factor record of every round is
 the bits NonlinearFactorSetGPU.linearize_poses returns for the caller's own set of all F pairs at the traced T_f, the problem's record is their
 one-at-a-time sum, the decisions are those of tests/lm_restatement.py on that sum, and the caller's sets, plans and resident session are left

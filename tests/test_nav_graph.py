@@ -74,7 +74,7 @@ def test_new_symbols_structs_and_mirrors(tmp_path):
         assert site in texts["include/glim_amd.h"], site
     csrc = os.path.join(ROOT, "glim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "bundle_lm_step.hpp" in open(os.path.join(csrc, f)).read())
-    assert users == ["gicp_align.hip"]
+    assert users == ["bundle_align.hip"]
 
 
 # ---- the refusals --------------------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""VGICP fine registration on the device (include/glim_amd.h "VGICP fine registration"; glim_amd/csrc/gicp_align.hip over vgicp_batch.hpp): every
+"""VGICP fine registration on the device (include/glim_amd.h "VGICP fine registration"; glim_amd/csrc/vgicp_align.hip over vgicp_batch.hpp): every
 trial record is the bits NonlinearFactorSetGPU.linearize_poses returns for a set of the same pairs at the trial's poses, the decisions are those
 of tests/lm_restatement.py, and the caller's own sets, plans and resident session are left alone.
 

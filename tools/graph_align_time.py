@@ -128,7 +128,7 @@ def main():
     submaps = bench.make_merged_submaps(api, ctx, max(args.sizes), 4, 40, 560)  # bench.py's defaults for global256
     vmaps = [api.GaussianVoxelMapGPU(1.0, ctx=ctx).insert(g) for _, g in submaps]
     out = {"what": __doc__.split("\n")[0], "iters": args.iters, "repeated": "one box, not repeated", "device": ctx.device_info(),
-           "default_chunk_length": "GRAPH_ROUNDS_PER_CHUNK of glim_amd/csrc/gicp_align.hip (rounds_per_chunk = 0)", "scene_seconds": time.time() - t0, "sizes": {}}
+           "default_chunk_length": "GRAPH_ROUNDS_PER_CHUNK of glim_amd/csrc/bundle_align.hip (rounds_per_chunk = 0)", "scene_seconds": time.time() - t0, "sizes": {}}
     for N in args.sizes:
         out["sizes"][str(N)] = measure(api, torch, lmr, ctx, submaps, vmaps, N, args.iters)
         print(f"N = {N} done", file=sys.stderr, flush=True)
